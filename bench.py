@@ -9,27 +9,42 @@ i.e. 10 Gbp of error-free 150-bp reads, 8.0e9 31-mers, L=15 U=40 (reference Make
 For N > 1 every rank holds 10 Gbp of reads sampled from ONE genome of N x 312.5 Mbp (configs[2] at
 N=8: 80 Gbp), so the minimizer exchange is real; scaling is weak.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--scale S]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--scale S] [--dump-outputs DIR] [--full]
 
 `--gpus N` (N > 1) without a launcher starts the N ranks itself (one fresh child:
 python -m torch.distributed.run, one process per GPU); under a launcher (WORLD_SIZE set) this file is a rank.
 
+A plain run sets up, runs the W warm-up steps, times the K steps, writes the outputs (`--dump-outputs`) and prints the line;
+what else the bench measures (the copy-rate yardstick of the roofline block, host_to_host, variants, multi_rank_path,
+large_input, first_calls, cpu_baseline) runs only with `--full`.
+
+`--dump-outputs DIR` writes what the last timed step computed, as float64 .npy files (rank r of several: prefix rank<r>_):
+  kmers.npy             [m, 2 x words] the k-mers of a fixed sample of the entries (those whose key hashes below a threshold set
+                        by the entry count: about 1.4e6 of them for one-word keys), ordered by key; every 64-bit key word as its
+                        high and its low 32 bits
+  counts.npy            [m] their counts
+  histogram.npy         the k-mer histogram of the whole result (histogram[c] = entries with count c)
+  totals.npy            [entries, k-mers counted]
+
 Rank 0 prints ONE JSON line:
   value / ms_per_step   the device-resident rate above (inputs resident in HBM when the timed region starts, as the bench
                         contract asks; `value` never includes PCIe).  The same figure again under `device_resident`.
-  host_to_host          (N = 1) the metric exactly as SURVEY 8(d) and the reference's own timer define it (src/hysortk.cpp:58,91,
+  host_to_host          (--full, N = 1) the metric exactly as SURVEY 8(d) and the reference's own timer define it (src/hysortk.cpp:58,91,
                         "Overall kmer counting (Excluding I/O)"): wall time of hsk_count() from a DnaBuffer in (pinned) host RAM
                         to the KmerListS entries in host RAM, L=15/U=40, with its PCIe shares
   roofline              the TIME-DOMINANT kernel of this run: algorithmic bytes per launch / average launch duration from HIP
-                        events on the launch stream inside the timed region, against the 8 TB/s spec and against the copy rate
-                        measured in this run (hsk_copy_peak: hand-written 16-byte-per-lane copy); .whole_path: the step against
+                        events on the launch stream inside the timed region, against the 8 TB/s spec and (--full) against the copy
+                        rate measured in this run (hsk_copy_peak: hand-written 16-byte-per-lane copy); .whole_path: the step against
                         the PMC-measured traffic of profiles/traffic.json
   kernels               the kernels that make up the step, ms per step and what bounds each
-  variants              (N = 1) short legs of the other record shapes and plans, 3 steps each, device-resident: K=51 (two-word
+  variants              (--full, N = 1) short legs of the other record shapes and plans, 3 steps each, device-resident: K=51 (two-word
                         keys), EXTENSION=1, the same workload without the LDS aggregation, with the reference's own algorithm
                         (LSD over all key bytes + merge-count: the path BASELINE.json's north_star names, against SURVEY 8(d)'s
                         fixed 152.3 B per k-mer), and uniform random reads (every k-mer once, L=1: the worst case for output)
-  cpu_baseline          the CPU path on the host cores on a bounded sample (1/`--cpu-div` of the workload): the real reference
+  multi_rank_path, large_input, first_calls
+                        (--full, N = 1) the several-rank data path on one GPU, BASELINE configs[2]'s whole input on one GPU,
+                        first calls after another kind of input
+  cpu_baseline          (--full) the CPU path on the host cores on a bounded sample (1/`--cpu-div` of the workload): the real reference
                         binary built by oracle/build_ref.sh with the same L=15/U=40 when it travelled ("reference"; best of
                         several ranks x threads layouts), else the C restatement ("port").  The GPU counts the same sample and
                         its histogram must equal the reference's (`sample_check`).
@@ -58,8 +73,11 @@ HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline figure (copy-rate yardstick, host_to_host, "
+                                                        "variants, multi_rank_path, large_input, first_calls, cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float64)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the workload (debug only; 1.0 = BASELINE config)")
     ap.add_argument("--ntasks", type=int, default=0)
     ap.add_argument("--cpu-div", type=int, default=20, help="cpu_baseline sample = workload / this")
@@ -70,7 +88,58 @@ def parse_args():
     ap.add_argument("--error-rate", type=float, default=0.0, help="substitution errors per base in the synthetic reads (informational runs; the headline workload is error-free)")
     ap.add_argument("--ext", type=int, default=0)
     ap.add_argument("--k", type=int, default=31, help="k-mer size (informational runs; the headline metric is K=31)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the last timed step computed
+# ---------------------------------------------------------------------------------------------------------------------
+DUMP_SAMPLE_BYTES = 32 << 20          # the expected size of the entry sample; never more than 1.5 x this (the cap below)
+
+
+def dump_outputs(out_dir, dev, prefix=""):
+    """Writes the k-mer list that `dev` (a DeviceResult: the last timed step's, still in HBM) holds as float64 arrays: a sample of
+    the entries chosen by their keys alone (a multiplicative hash of the key below a threshold that depends only on the entry count),
+    so it does not depend on how the entries are split into tasks or ordered inside them, ordered by key; the whole histogram; totals."""
+    res, nw, n = dev.res, dev.nw, dev.n
+    histo = np.ctypeslib.as_array(res.histo, shape=(int(res.histo_len),)).copy() if res.histo_len else np.zeros(0, np.uint64)
+    per_entry = 8 * (2 * nw + 1)
+    target = DUMP_SAMPLE_BYTES // per_entry
+    cap = target * 3 // 2
+    thr = np.uint64(min(1 << 32, (target << 32) // max(n, 1)))
+    mult = [np.uint64(0x9E3779B97F4A7C15), np.uint64(0xC2B2AE3D27D4EB4F), np.uint64(0x165667B19E3779F9)]
+    keys, cnts, hs = [], [], []
+    with np.errstate(over="ignore"):
+        for t in range(dev.ntasks):
+            d = dev.fetch(t)
+            if not d["n"]:
+                continue
+            k = d["kmers"]
+            h = np.zeros(d["n"], dtype=np.uint64)
+            for w in range(nw):
+                h ^= k[:, w] * mult[w % 3]
+            h >>= np.uint64(32)
+            sel = h < thr
+            keys.append(k[sel]); cnts.append(d["cnt"][sel]); hs.append(h[sel])
+    keys = np.concatenate(keys) if keys else np.zeros((0, nw), np.uint64)
+    cnts = np.concatenate(cnts) if cnts else np.zeros(0, np.uint64)
+    hs = np.concatenate(hs) if hs else np.zeros(0, np.uint64)
+    if len(cnts) > cap:                                    # (a hash threshold is only a bound on the average: keep the smallest hashes)
+        keep = np.lexsort(tuple(keys[:, w] for w in range(nw - 1, -1, -1)) + (hs,))[:cap]
+        keys, cnts = keys[keep], cnts[keep]
+    order = np.lexsort(tuple(keys[:, w] for w in range(nw - 1, -1, -1)))
+    keys, cnts = keys[order], cnts[order]
+    halves = np.empty((len(cnts), 2 * nw), dtype=np.float64)
+    halves[:, 0::2] = (keys >> np.uint64(32)).astype(np.float64)
+    halves[:, 1::2] = (keys & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, prefix + "kmers.npy"), halves)
+    np.save(os.path.join(out_dir, prefix + "counts.npy"), cnts.astype(np.float64))
+    np.save(os.path.join(out_dir, prefix + "histogram.npy"), histo.astype(np.float64))
+    np.save(os.path.join(out_dir, prefix + "totals.npy"), np.array([n, int(res.total_kmers)], dtype=np.float64))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -460,14 +529,26 @@ def main():
     barrier()
     t0 = time.perf_counter()
     phase = {}
-    for _ in range(a.steps):
-        info = ctx.count_device(dp, nb, do, dl, nreads, rid_base=rank * nreads).info
+    last = None
+    for s_ in range(a.steps):
+        if a.dump_outputs and s_ == a.steps - 1:
+            # the same call with its result block kept (the list stays in HBM until it has been written out below)
+            last = H.DeviceDna(ctx, dp, nb, do, dl, nreads).count_resident_device(rid_base=rank * nreads)
+            r_ = last.res
+            info = dict(total_kmers=int(r_.total_kmers), total_supermers=int(r_.total_supermers), total_supermer_bytes=int(r_.total_supermer_bytes),
+                        ntasks=int(r_.ntasks), ms_total=r_.ms_total, ms_parse=r_.ms_parse, ms_exchange=r_.ms_exchange, ms_extract=r_.ms_extract,
+                        ms_sort=r_.ms_sort, ms_count=r_.ms_count, ms_d2h=r_.ms_d2h, n=int(r_.n))
+        else:
+            info = ctx.count_device(dp, nb, do, dl, nreads, rid_base=rank * nreads).info
         for k_, v in info.items():
             if k_.startswith("ms_"):
                 phase[k_] = phase.get(k_, 0.0) + v
     barrier()
     dt = time.perf_counter() - t0
     st = ctx.stats(reset=True)
+    if last is not None:
+        with last:
+            dump_outputs(a.dump_outputs, last, "rank%d_" % rank if world > 1 else "")
     if comm is not None:
         dt = comm.allreduce_max(dt)
     if rank == 0:
@@ -506,7 +587,7 @@ def main():
             return sum(vals) * pmc_scale if vals else None
         path_traffic = (pmc.get("path_hbm_bytes_per_step") or 0) * pmc_scale or None
         rec = 8 * ((KK + 31) // 32)
-        copy_peak = ctx.copy_peak(1 << 32, 3) if world == 1 else None      # hand-written 16-byte-per-lane copy (hsk_copy_peak), measured in this run
+        copy_peak = ctx.copy_peak(1 << 32, 3) if world == 1 and a.full else None      # hand-written 16-byte-per-lane copy (hsk_copy_peak), measured in this run (--full)
         NSIMD, CLK = 256 * 4, 2.4e9
 
         def kern(name, ms, n, alg_bytes, bound, note, pmc_prefix=None, mix_key=None):
@@ -589,7 +670,7 @@ def main():
         out = {
             "metric": "k-mers counted/sec at K=%d" % KK, "value": value, "unit": "k-mers/s", "n_gpus": world, "steps": S, "warmup": a.warmup,
             "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "value_is": "device_resident (inputs already in HBM when the timed region starts, as the bench contract asks); `host_to_host` in this line is the same "
+            "value_is": "device_resident (inputs already in HBM when the timed region starts, as the bench contract asks); `host_to_host` (with --full) is the same "
                         "workload through hsk_count() from host memory to host memory = the metric as SURVEY 8(d) and the reference's timer define it",
             "dtype": ("u64" if KK <= 32 else "u128") + ("" if not a.ext else "+u64 payload"), "data": "synthetic",
             "config": {"workload": "S-reads(G=%d bp x %d GPU, c=%d): %d x %d-bp reads per GPU = %.3g bp, %d k-mers per GPU" % (
@@ -628,13 +709,13 @@ def main():
         }
         ctx.synth_free(dp, do, dl)
         ctx.close()
-        if world == 1 and not a.no_e2e:
+        if a.full and world == 1 and not a.no_e2e:
             try:
                 out["host_to_host"] = e2e_host_leg(H, KK, a.ext, a.ntasks, local, genome_len, nreads, seed, max(a.steps, 3))
             except Exception as e:
                 out["host_to_host"] = {"error": str(e)[:300]}
         only = set(x for x in a.legs.split(",") if x)
-        if world == 1 and not a.no_variants:
+        if a.full and world == 1 and not a.no_variants:
             G = int(GENOME_PER_GPU * a.scale)
             legs = [
                 ("k51", "BASELINE configs[3]'s record shape (two-word keys) on the same reads", 51, 0, None, L, U, G, nreads, 0.0, 464.4),
@@ -657,24 +738,24 @@ def main():
                     out["variants"].append(run_variant(H, local, name, note, vk, vext, plan, Lv, Uv, vg, vn, seed, er, 3, refb))
                 except Exception as e:
                     out["variants"].append({"name": name, "error": str(e)[:300]})
-        if world == 1 and not a.no_variants and (not only or "multi_rank" in only):
+        if a.full and world == 1 and not a.no_variants and (not only or "multi_rank" in only):
             out["multi_rank_path"] = []
             for (mname, mk, mext, mbp) in (("k31_8x5Gbp", 31, 0, 5_000_000_000), ("k51_8x2.5Gbp", 51, 0, 2_500_000_000), ("ext_8x1.25Gbp", 31, 1, 1_250_000_000)):
                 try:
                     out["multi_rank_path"].append(multi_rank_leg(H, local, mname, mk, mext, 8, int(mbp * a.scale), 320, seed + 7))
                 except Exception as e:
                     out["multi_rank_path"].append({"name": mname, "error": str(e)[:300]})
-        if world == 1 and not a.no_variants and a.scale == 1.0 and (not only or "large" in only):
+        if a.full and world == 1 and not a.no_variants and a.scale == 1.0 and (not only or "large" in only):
             try:
                 out["large_input"] = large_input_leg(H, local, 80.0, seed + 200)
             except Exception as e:
                 out["large_input"] = {"error": str(e)[:300]}
-        if world == 1 and not a.no_variants and (not only or "first_calls" in only):
+        if a.full and world == 1 and not a.no_variants and (not only or "first_calls" in only):
             try:
                 out["first_calls"] = first_call_leg(H, local, int(GENOME_PER_GPU * a.scale) // 2, nreads // 2, seed + 100)
             except Exception as e:
                 out["first_calls"] = {"error": str(e)[:300]}
-        if world == 1 and not a.no_cpu:
+        if a.full and world == 1 and not a.no_cpu:
             ncores = os.cpu_count() or 1
             div = max(a.cpu_div, 1)
             g_s = max(int(GENOME_PER_GPU * a.scale) // div, 10000)

@@ -14,7 +14,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$TAG
 P=$OUT/profiles
 mkdir -p $OUT $P
-CMD="python3 $R/bench.py --no-cpu --no-e2e --no-variants"
+CMD="python3 $R/bench.py --full --no-cpu --no-e2e --no-variants"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o $TAG -- $CMD --steps 3 --warmup 1 > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 cp $(find $OUT/stats -name "*kernel_stats.csv" | head -1) $P/${TAG}_kernel_stats.csv
@@ -35,7 +35,7 @@ cat $OUT/pmc_summary.txt
 # the kernels' static mix priced with THIS run's rates, before the bench line that quotes it (30 s of hipcc -S; round 4 computed it beforehand
 # from the previous run's rates: 0.5 % apart)
 python3 tools/valu_floor.py $P/${TAG}_valu_rates.txt profiles/valu_mix.json > $OUT/valu_mix.txt 2>&1 && cp profiles/valu_mix.json $P/valu_mix.json
-timeout 900 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cp $OUT/bench.json $P/${TAG}_bench.json
 python3 tools/bench_summary.py $OUT/bench.json
 head -14 $P/${TAG}_kernel_stats.csv | cut -c1-160

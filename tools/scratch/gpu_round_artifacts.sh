@@ -24,7 +24,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o $TAG -- py
 cd $GRAFT_REPO_ROOT
 cp $(find $OUT/stats -name "*kernel_stats.csv" | head -1) profiles/${TAG}_kernel_stats.csv
 cp $OUT/bench_under_rocprof.json profiles/${TAG}_bench_under_rocprof.json
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cp $OUT/bench.json profiles/${TAG}_bench.json
 python3 tools/bench_summary.py $OUT/bench.json
 head -14 profiles/${TAG}_kernel_stats.csv | cut -c1-160
