@@ -144,6 +144,9 @@ extern "C" int hsk_init(const hsk_config *cfg, hsk_ctx **out)
     g_tune = &c->tune;
     memset(&c->stats, 0, sizeof c->stats);
     c->pool.be_malloc = pool_hip_malloc; c->pool.be_free = pool_hip_free;
+    // (tests) red zones behind every device block, checked at the end of every counting and stage entry point (redzone_end_call)
+    c->pool.redzone = (size_t)std::min<long long>(std::max<long long>(tune("pool_redzone", 0), 0), 1 << 20);
+    c->pool.be_fill = pool_hip_fill; c->pool.be_check = pool_hip_check; c->pool.be_arg = c;
     if (hipSetDevice(cfg->device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking) != hipSuccess) { delete c; return HSK_ERR_HIP; }
@@ -376,6 +379,20 @@ extern "C" void hsk_result_free(hsk_ctx *c, hsk_result *r)
     memset(r, 0, sizeof *r);
 }
 
+// pool_redzone: the end of an entry point that ran kernels -- after its last sync, every zone of a live or quarantined block is compared with
+// the pattern, then the quarantined blocks go back to the pool.  A zone that was written fails the call (its results are dropped).
+static int redzone_end_call(hsk_ctx *c, int rc, hsk_result *outs = nullptr, int nouts = 0)
+{
+    if (!c->pool.redzone) return rc;
+    (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->comm_stream); (void)hipStreamSynchronize(c->d2h_stream);
+    char msg[320];
+    const int hit = c->pool.check(msg, sizeof msg);
+    c->pool.flush();
+    if (hit == 0) return rc;
+    if (rc == HSK_OK) for (int r = 0; r < nouts; ++r) hsk_result_free(c, &outs[r]);
+    return fail(c, HSK_ERR_INTERNAL, "%s", msg);
+}
+
 extern "C" int hsk_result_device_task(const hsk_result *r, int32_t task, const void **entries, uint64_t *n,
                                       const void **payload_off, const void **pos, const void **rid, uint64_t *npay, uint64_t *payload_base)
 {
@@ -545,7 +562,7 @@ extern "C" int hsk_count(hsk_ctx *c, const uint8_t *packed, uint64_t packed_byte
     if (c->roff_check.valid()) (void)c->roff_check.get();          // (the pipeline failed before it collected the verdict)
     c->pool.release(d_given); c->pool.release(d_tsum);
     free_input(c, d);
-    return rc;
+    return redzone_end_call(c, rc, out, 1);
 }
 
 extern "C" int hsk_count_device(hsk_ctx *c, const void *d_packed, uint64_t packed_bytes, const void *d_off, const void *d_len,
@@ -565,7 +582,7 @@ extern "C" int hsk_count_device(hsk_ctx *c, const void *d_packed, uint64_t packe
     if (timing_enabled()) fprintf(stderr, "[hsk] device pool: %.2f GB live, %.2f GB cached (mapped %.2f GB), peak live %.2f GB\n", c->pool.bytes_live / 1e9, c->pool.bytes_cached / 1e9,
                                   c->pool.bytes_mapped() / 1e9, c->pool.peak / 1e9);
     c->pool.release(roff);
-    return rc;
+    return redzone_end_call(c, rc, out, 1);
 }
 
 extern "C" int hsk_count_loopback(hsk_ctx *c, int nranks, const uint8_t *const *packed, const uint64_t *packed_bytes, const uint64_t *const *off,
@@ -598,7 +615,7 @@ extern "C" int hsk_count_loopback(hsk_ctx *c, int nranks, const uint8_t *const *
         c->pool.release_all_but(before);
         (void)hipMemsetAsync(c->d_err, 0, 4, c->stream);
     }
-    return rc;
+    return redzone_end_call(c, rc, outs, nranks);
 }
 
 // the same with every virtual rank's reads already resident in HBM (full-size runs of the multi-rank data path: tests/test_gpu_multirank.py,
@@ -641,7 +658,7 @@ extern "C" int hsk_count_loopback_device(hsk_ctx *c, int nranks, const void *con
     }
     (void)hipStreamSynchronize(c->stream);
     for (u64 *p : roffs) c->pool.release(p);
-    return rc;
+    return redzone_end_call(c, rc, outs, nranks);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -674,7 +691,7 @@ extern "C" int hsk_stage_destinations(hsk_ctx *c, const uint8_t *packed, uint64_
         for (uint64_t i = 0; i < nk; ++i) dest[dest_off[r] + i] = h[off[r] * 4 + i];
     }
     c->pool.release(d_dump); free_input(c, d);
-    return HSK_OK;
+    return redzone_end_call(c, HSK_OK);
 }
 
 template <int NW>
@@ -730,7 +747,7 @@ extern "C" int hsk_stage_task_kmers(hsk_ctx *c, const uint8_t *packed, uint64_t 
     default: rc = stage_task_kmers_impl<3>(c, d, packed_bytes, nreads, rid_base, task, keys, pos, rid, cap, n); break;
     }
     free_input(c, d);
-    return rc;
+    return redzone_end_call(c, rc);
 }
 
 template <int NW>
@@ -762,11 +779,13 @@ extern "C" int hsk_stage_sort(hsk_ctx *c, uint64_t *keys, uint64_t *vals, uint64
     if (n == 0) return HSK_OK;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     enter_ctx(c);
+    int rc;
     switch (nw) {
-    case 1: return stage_sort_impl<1>(c, keys, vals, n);
-    case 2: return stage_sort_impl<2>(c, keys, vals, n);
-    default: return stage_sort_impl<3>(c, keys, vals, n);
+    case 1: rc = stage_sort_impl<1>(c, keys, vals, n); break;
+    case 2: rc = stage_sort_impl<2>(c, keys, vals, n); break;
+    default: rc = stage_sort_impl<3>(c, keys, vals, n); break;
     }
+    return redzone_end_call(c, rc);
 }
 
 template <int NW>
@@ -797,11 +816,13 @@ extern "C" int hsk_stage_count_sorted(hsk_ctx *c, const uint64_t *keys, uint64_t
     if (n == 0) return HSK_OK;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     enter_ctx(c);
+    int rc;
     switch (nw) {
-    case 1: return stage_count_impl<1>(c, keys, n, out_entries, cap, n_out);
-    case 2: return stage_count_impl<2>(c, keys, n, out_entries, cap, n_out);
-    default: return stage_count_impl<3>(c, keys, n, out_entries, cap, n_out);
+    case 1: rc = stage_count_impl<1>(c, keys, n, out_entries, cap, n_out); break;
+    case 2: rc = stage_count_impl<2>(c, keys, n, out_entries, cap, n_out); break;
+    default: rc = stage_count_impl<3>(c, keys, n, out_entries, cap, n_out); break;
     }
+    return redzone_end_call(c, rc);
 }
 
 // ------------------------------------------------------------------------------------------------

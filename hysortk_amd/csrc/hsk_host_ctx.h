@@ -173,7 +173,7 @@ static int fail(hsk_ctx *c, int code, const char *fmt, ...)
 
 #define DALLOC(c, ptr, type, bytes)                                                              \
     do {                                                                                         \
-        ptr = (type)(c)->pool.alloc(bytes);                                                      \
+        ptr = (type)(c)->pool.alloc(bytes, __FILE__, __LINE__);                                  \
         if (!ptr) return fail(c, HSK_ERR_OOM, "device allocation of %zu bytes failed (%s:%d)", (size_t)(bytes), __FILE__, __LINE__); \
     } while (0)
 
@@ -192,6 +192,41 @@ static void tmark(const char *what)
     if (!what) { t0 = last = now; return; }
     fprintf(stderr, "[hsk %8.2f ms  +%7.2f] %s\n", std::chrono::duration<double, std::milli>(now - t0).count(), std::chrono::duration<double, std::milli>(now - last).count(), what);
     last = now;
+}
+
+// pool_redzone (tests): the device side of DevPool's red zones -- the fill on the context's stream, and one kernel that compares every zone
+// with the pattern.  Its result is a word of its own (words 16..31 of d_err are census scratch), in a buffer that is not the pool's.
+static void pool_hip_fill(void *arg, void *p, size_t n) { (void)hipMemsetAsync(p, DevPool::RZ_BYTE, n, ((hsk_ctx *)arg)->stream); }
+
+__global__ void redzone_check_kernel(const unsigned long long *zones, u32 nz, unsigned long long *first_bad)
+{
+    for (u32 z = blockIdx.x; z < nz; z += gridDim.x) {
+        const unsigned char *p = (const unsigned char *)zones[2 * z];
+        const unsigned long long n = zones[2 * z + 1];
+        for (unsigned long long i = threadIdx.x; i < n; i += blockDim.x)
+            if (p[i] != DevPool::RZ_BYTE) { atomicMin(first_bad, ((unsigned long long)z << 32) | i); break; }
+    }
+}
+
+static int pool_hip_check(void *arg, const DevPool::Zone *z, size_t nz, size_t *bad_zone, size_t *bad_off)
+{
+    hsk_ctx *c = (hsk_ctx *)arg;
+    std::vector<unsigned long long> h(2 * nz + 1);
+    for (size_t i = 0; i < nz; ++i) { h[2 * i] = (unsigned long long)(uintptr_t)z[i].p; h[2 * i + 1] = z[i].bytes; }
+    h[2 * nz] = ~0ull;
+    unsigned long long *d = nullptr, res = ~0ull;
+    if (hipMalloc(&d, h.size() * 8) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    bool ok = hipMemcpyAsync(d, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(redzone_check_kernel, dim3((u32)std::min<size_t>(nz, 1024)), dim3(256), 0, c->stream, d, (u32)nz, d + 2 * nz);
+        ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(&res, d + 2 * nz, 8, hipMemcpyDeviceToHost, c->stream) == hipSuccess &&
+             hipStreamSynchronize(c->stream) == hipSuccess;
+    }
+    (void)hipFree(d);
+    if (!ok) return -1;
+    if (res == ~0ull) return 0;
+    *bad_zone = (size_t)(res >> 32); *bad_off = (size_t)(res & 0xffffffffu);
+    return 1;
 }
 
 // every blocking wait of the host on a stream inside the counting path goes through here (hsk_stats.host_syncs)

@@ -365,7 +365,7 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
     u64 rec_cap = max_task;
     if (combine && !fed_combine && c->est.valid && !c->pair_cap_full && tune("pair_cap", 1) != 0)
         rec_cap = std::min<u64>(max_task, std::max<u64>((u64)((double)max_task * std::min(1.0, 4.0 * c->est.distinct_per_kmer * c->est_bias + 0.02)), 1ULL << 22));
-    if (tune("pair_cap_records", 0) > 0 && combine && !fed_combine) rec_cap = std::min<u64>(max_task, (u64)tune("pair_cap_records", 0));      // (tests: stores that run over)
+    if (tune("pair_cap_records", 0) > 0 && combine && !fed_combine && !c->pair_cap_full) rec_cap = std::min<u64>(max_task, (u64)tune("pair_cap_records", 0));      // (tests: stores that run over; the attempt after an overrun is full size)
     auto alloc_sort_buffers = [&]() -> int {
         if (max_task) {
             for (int sl = 0; sl < nslot; ++sl) for (int i = 0; i < nsets; ++i) {
@@ -641,6 +641,17 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
                 if (fed_combine) return fail(c, HSK_ERR_INTERNAL, "pair stores overrun with several ranks");
                 c->pair_cap_full = true;
                 return retry_plan("the pair stores ran over (sized from the estimate)");
+            }
+            // Bit 512 fires only when a task's chunks exceed rec_cap / CH + 257: a task of a few hundred thousand pairs more than rec_cap fills fewer
+            // spare chunks than that, and the sort below would write all its pairs into kA / vA (rec_cap records).  Every count is held to the store.
+            for (int i = 0; i < XCD_BATCH; ++i) {
+                if (mine[pos + i] == EMPTY_TASK || !bt[i].n) continue;
+                if (h_nout[i] > bt[i].n) return fail(c, HSK_ERR_INTERNAL, "task %u: %llu pairs for %llu k-mers", mine[pos + i], (unsigned long long)h_nout[i], (unsigned long long)bt[i].n);
+                if (h_nout[i] > rec_cap) {
+                    if (fed_combine) return fail(c, HSK_ERR_INTERNAL, "pair stores overrun with several ranks");
+                    c->pair_cap_full = true;
+                    return retry_plan("the pair stores ran over (more pairs than records)", (unsigned)std::min<u64>(h_nout[i], 0xffffffffu));
+                }
             }
             u64 bp = 0, bk = 0, pmax = 0;
             for (int i = 0; i < XCD_BATCH; ++i) { if (mine[pos + i] == EMPTY_TASK || !bt[i].n) continue; bk += bt[i].n; bt[i].n = h_nout[i]; bp += h_nout[i]; pmax = std::max<u64>(pmax, h_nout[i]); }

@@ -11,9 +11,17 @@
 // first user on the same stream or behind an event.
 //
 // The backend (hipMalloc / hipFree) is a pair of function pointers so that the segment logic runs on the CPU against malloc (tests/test_pool.py).
+//
+// Red zones (tuning pool_redzone=<bytes>, test-size inputs only): a block is handed out with `redzone` bytes behind its requested size, from the
+// first 16-byte boundary at or after it, filled with RZ_BYTE (be_fill, on the context's stream).  A released block is QUARANTINED -- neither free
+// nor handed out again -- until flush(): a later block of the same call could otherwise legitimately write into the old zone.  check() compares
+// the zones of every live and quarantined block with the pattern (be_check: one kernel) and names the allocation site of the first block whose
+// zone was written; the entry points call it after their final sync, then flush().  A call's memory peak is then the sum of its allocations.
 #pragma once
 #include <algorithm>
 #include <cstddef>
+#include <cstdio>
+#include <cstring>
 #include <map>
 #include <vector>
 
@@ -21,10 +29,22 @@ struct DevPool {
     typedef int (*MallocFn)(void **, size_t);
     typedef int (*FreeFn)(void *);
     MallocFn be_malloc = nullptr; FreeFn be_free = nullptr;          // set by the owner before the first allocation (0: success)
+    struct Zone { char *p; size_t bytes; };
+    typedef void (*FillFn)(void *arg, void *p, size_t bytes);          // fill [p, p + bytes) with RZ_BYTE
+    typedef int (*CheckFn)(void *arg, const Zone *z, size_t n, size_t *bad_zone, size_t *bad_off);   // 0: every zone intact, 1: *bad_zone / *bad_off
+                                                                                                       // name the first byte that is not (lowest zone, lowest offset), else: could not check
+    FillFn be_fill = nullptr; CheckFn be_check = nullptr; void *be_arg = nullptr;                    // red zones (set with `redzone`)
+    size_t redzone = 0;
+    static constexpr unsigned char RZ_BYTE = 0xC5;
     static constexpr size_t ALIGN = 256;
     static constexpr size_t MIN_SPLIT = (size_t)1 << 20;             // a remainder below this stays with the block it was cut from
 
-    struct Seg { size_t size; bool free; char *region; };
+    struct Seg {
+        size_t size; bool free; char *region;
+        size_t req = 0, zoff = 0, zbytes = 0;                        // requested bytes; red zone [zoff, zoff + zbytes) (zbytes = 0: none)
+        const char *file = nullptr; int line = 0;                    // allocation site
+        bool quar = false;                                           // released, quarantined until flush()
+    };
     std::map<char *, Seg> segs;                                      // every segment, live or free, by address
     std::multimap<size_t, char *> free_by_size;
     std::map<char *, size_t> regions;                                // what the backend gave us
@@ -35,7 +55,18 @@ struct DevPool {
         auto r = free_by_size.equal_range(it->second.size);
         for (auto q = r.first; q != r.second; ++q) if (q->second == it->first) { free_by_size.erase(q); break; }
     }
-    void *alloc(size_t bytes)
+    // file / line: the allocation site (DALLOC passes its own; a direct call is tagged with the caller's)
+    void *alloc(size_t bytes, const char *file = __builtin_FILE(), int line = __builtin_LINE())
+    {
+        const size_t req = bytes, zoff = (bytes + 15) & ~(size_t)15;
+        char *p = (char *)alloc_seg(redzone ? zoff + redzone : bytes);
+        if (!p) return nullptr;
+        Seg &s = segs.find(p)->second;
+        s.req = req; s.file = file; s.line = line;
+        if (redzone) { s.zoff = zoff; s.zbytes = redzone; if (be_fill) be_fill(be_arg, p + zoff, redzone); }
+        return p;
+    }
+    void *alloc_seg(size_t bytes)
     {
         if (bytes == 0) bytes = ALIGN;
         bytes = (bytes + ALIGN - 1) & ~(ALIGN - 1);
@@ -53,7 +84,7 @@ struct DevPool {
                 free_by_size.insert({rsz, rest});
                 bytes_cached += rsz;
             }
-            s.free = false;
+            s.free = false; s.zbytes = 0; s.quar = false;
             bytes_live += s.size; peak = std::max(peak, bytes_live);
             return it->first;
         }
@@ -72,7 +103,13 @@ struct DevPool {
     {
         if (!p) return;
         auto it = segs.find((char *)p);
-        if (it == segs.end() || it->second.free) return;
+        if (it == segs.end() || it->second.free || it->second.quar) return;
+        if (redzone) { it->second.quar = true; return; }
+        release_seg(it);
+    }
+    void release_seg(std::map<char *, Seg>::iterator it)
+    {
+        it->second.quar = false; it->second.zbytes = 0;
         bytes_live -= it->second.size;
         it->second.free = true;
         // free neighbours of the same region join
@@ -114,12 +151,40 @@ struct DevPool {
     }
     // Error paths return early (DALLOC / HIPCHK) without releasing what the call had allocated so far: the entry points take
     // a snapshot of the live blocks and, when the call fails, hand everything allocated since back to the pool.
-    std::vector<void *> snapshot() const { std::vector<void *> v; for (auto &kv : segs) if (!kv.second.free) v.push_back(kv.first); return v; }
+    std::vector<void *> snapshot() const { std::vector<void *> v; for (auto &kv : segs) if (!kv.second.free && !kv.second.quar) v.push_back(kv.first); return v; }
     void release_all_but(const std::vector<void *> &keep)        // keep: sorted (map order)
     {
         std::vector<void *> drop;
-        for (auto &kv : segs) if (!kv.second.free && !std::binary_search(keep.begin(), keep.end(), (void *)kv.first)) drop.push_back(kv.first);
+        for (auto &kv : segs) if (!kv.second.free && !kv.second.quar && !std::binary_search(keep.begin(), keep.end(), (void *)kv.first)) drop.push_back(kv.first);
         for (void *p : drop) release(p);
+    }
+    // Red zones: 0 = every zone of a live or quarantined block holds the pattern, 1 = one does not (msg: the block's allocation site and the first
+    // byte written, counted from the block's start), -1 = the check itself failed (msg says so).  The zones of live blocks are filled again after
+    // a hit, so that the next call's check reports only what that call wrote.
+    int check(char *msg, size_t cap)
+    {
+        if (msg && cap) msg[0] = 0;
+        if (!redzone || !be_check) return 0;
+        std::vector<Zone> z; std::vector<const Seg *> owner;
+        for (auto &kv : segs) if (!kv.second.free && kv.second.zbytes) { z.push_back(Zone{kv.first + kv.second.zoff, kv.second.zbytes}); owner.push_back(&kv.second); }
+        if (z.empty()) return 0;
+        size_t bz = 0, bo = 0;
+        const int r = be_check(be_arg, z.data(), z.size(), &bz, &bo);
+        if (r == 0) return 0;
+        if (r != 1 || bz >= z.size()) { if (msg) snprintf(msg, cap, "the red-zone check of %zu blocks could not run", z.size()); return -1; }
+        const Seg &s = *owner[bz];
+        const char *f = s.file ? s.file : "?"; if (const char *sl = strrchr(f, '/')) f = sl + 1;
+        if (msg) snprintf(msg, cap, "a device write past the end of the block allocated at %s:%d (%zu bytes requested): byte %zu of the block was written",
+                          f, s.line, s.req, s.zoff + bo);
+        for (size_t i = 0; i < z.size(); ++i) if (be_fill) be_fill(be_arg, z[i].p, z[i].bytes);
+        return 1;
+    }
+    // the quarantined blocks go back to the free lists (after check(), behind the call's last sync)
+    void flush()
+    {
+        std::vector<char *> q;
+        for (auto &kv : segs) if (kv.second.quar) q.push_back(kv.first);
+        for (char *p : q) release_seg(segs.find(p));
     }
     size_t bytes_mapped() const { size_t s = 0; for (auto &r : regions) s += r.second; return s; }
 };

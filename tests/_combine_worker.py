@@ -64,7 +64,7 @@ def run_spec(spec):
             out.append({"how": how, "digest": h.hexdigest(), "entries": ent, "total_kmers": int(sum(k.info["total_kmers"] for k in res)),
                               "combine_launches": int(st["combine_launches"]), "combine_pairs": int(st["combine_pairs"]), "combine_kmers": int(st["combine_kmers"]),
                               "instance_extractions": int(st["hist_launches"]), "fused_tasks": int(st["fused_tasks"]), "redone_tasks": int(st["redone_tasks"]),
-                              "dropped_kmers": int(st.get("dropped_kmers", 0))})
+                              "dropped_kmers": int(st.get("dropped_kmers", 0)), "parse_fallbacks": int(st["parse_fallbacks"])})
             continue
         if how == "device":
             r = ctx.count_device(dp, nb, do, dl, n)
@@ -79,7 +79,7 @@ def run_spec(spec):
         out.append({"how": how, "digest": digest(r), "entries": len(r), "total_kmers": int(r.info["total_kmers"]),
                           "combine_launches": int(st["combine_launches"]), "combine_pairs": int(st["combine_pairs"]), "combine_kmers": int(st["combine_kmers"]),
                           "instance_extractions": int(st["hist_launches"]), "fused_tasks": int(st["fused_tasks"]), "redone_tasks": int(st["redone_tasks"]),
-                          "dropped_kmers": int(st.get("dropped_kmers", 0))})
+                          "dropped_kmers": int(st.get("dropped_kmers", 0)), "parse_fallbacks": int(st["parse_fallbacks"])})
     if spec.get("dump"):
         np.savez(spec["dump"], kmers=r.kmers, cnt=r.cnt, task_off=r.task_off, packed=packed, off=off, lens=lens)
     if pinned is not None:

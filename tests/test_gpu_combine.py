@@ -247,10 +247,15 @@ def test_two_word_combining_extraction_vs_oracle(tmp_path):
 
 def test_pair_stores_that_run_over_are_enlarged_not_abandoned():
     """The combining extraction's buffers are sized for the pairs the call's sketch promises (four times over), not for the k-mers.  Stores that
-    run over after all (here: forced to 100 000 records per task) set an error bit -- the chunk behind the store takes the overrun -- and the call
-    runs once more with full-sized buffers: still the combining extraction, same list."""
+    run over after all (here: forced to a quarter of the pairs a task has) are caught -- error bit 512 where the chunk behind the store takes the
+    overrun, the host's comparison of every task's pairs with the store where too few chunks ran over for the bit -- and the call runs once more
+    with full-sized buffers: still the combining extraction, same list.  With red zones behind every block (pool_redzone): nothing was written
+    past a store (tests/test_gpu_capacity.py sweeps the cap around the pair count)."""
     ref = run(BASE, {"HSK_COMBINE": "0"})[0]
-    r = run(BASE, {"HSK_COMBINE_MIN_BYTES": "0", "HSK_PAIR_CAP_RECORDS": "100000"})[0]
+    full = run(BASE, {"HSK_COMBINE_MIN_BYTES": "0", "HSK_PAIR_CAP": "0"})[0]
+    cap = full["combine_pairs"] // BASE["ntasks"] // 4
+    assert full["combine_launches"] > 0 and cap > 0
+    r = run(BASE, {"HSK_COMBINE_MIN_BYTES": "0", "HSK_PAIR_CAP_RECORDS": str(cap), "HSK_POOL_REDZONE": "4096"})[0]
     assert r["combine_launches"] > 0 and r["instance_extractions"] == 0
     assert (r["digest"], r["entries"]) == (ref["digest"], ref["entries"])
 

@@ -177,6 +177,29 @@ def test_every_tuning_name_the_library_reads_is_documented():
     assert sorted(n for n in names if "`%s`" % n not in doc and "`%s=" % n not in doc) == []
 
 
+def test_every_tuning_name_the_tests_and_tools_set_is_read_by_the_library():
+    """Tuning::parse ignores names it does not know: a misspelled pool_redzone or pair_cap_records would turn a boundary test into a plain run
+    that passes.  Every name tests/ and tools/ set -- HSK_* dictionary keys and keywords folded by util.tune_env, and "name=value,..." strings
+    (tuning_extra, tuning=) -- must be one the library reads through tune("...") or tune.get("...") in hysortk_amd/csrc."""
+    import glob
+    import re
+    read = set()
+    for f in glob.glob(os.path.join(util.ROOT, "hysortk_amd", "csrc", "*")):
+        read |= set(re.findall(r'tune(?:\.get)?\("([a-z0-9_]+)"', open(f).read()))
+    files = glob.glob(os.path.join(util.ROOT, "tests", "*.py")) + glob.glob(os.path.join(util.ROOT, "tools", "**", "*.py"), recursive=True)
+    used = {}
+    for f in files:
+        text = open(f).read()
+        keys = re.findall(r'"HSK_([A-Z0-9_]+)"\s*:', text) + re.findall(r'\bHSK_([A-Z0-9_]+)\s*=(?!=)', text)
+        names = [k.lower() for k in keys if "HSK_" + k not in util._NOT_TUNING]
+        for s in re.findall(r'["\']([a-z][a-z0-9_]*=[^"\',\s]*(?:,[a-z][a-z0-9_]*=[^"\',\s]*)*)["\']', text):
+            names += [item.split("=")[0] for item in s.split(",")]
+        for n in names:
+            used.setdefault(n, set()).add(os.path.relpath(f, util.ROOT))
+    assert len(used) > 30 and {"pair_cap_records", "pool_redzone", "parse_rec_cap", "bin_cap_pct", "combine_min_bytes"} <= set(used)
+    assert {n: sorted(fs) for n, fs in used.items() if n not in read} == {}
+
+
 def test_scripts_compile():
     """bench.py, __graft_entry__.py and everything under tools/ at least parse (they run on the GPU box only)."""
     files = [os.path.join(util.ROOT, "bench.py"), os.path.join(util.ROOT, "__graft_entry__.py")]
