@@ -23,6 +23,7 @@
 #include <map>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/hsk.h"
@@ -119,6 +120,71 @@ static void backtrace_on_abort(int sig)
     raise(sig);
 }
 
+// ------------------------------------------------------------------------------------------------
+// one scope per call
+// ------------------------------------------------------------------------------------------------
+// A failed call (or a failed attempt of one, dispatch_pipeline) leaves nothing behind: its kernels are drained, its results dropped,
+// every device block handed out since `mark` goes back to the pool (DevPool::rollback) and the device error word is cleared.
+// Returns the number of blocks released.
+static size_t roll_back(hsk_ctx *c, unsigned long long mark, hsk_result *outs, int nouts)
+{
+    (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->comm_stream); (void)hipStreamSynchronize(c->d2h_stream);
+    for (int r = 0; r < nouts; ++r) hsk_result_free(c, &outs[r]);            // (first: their blocks are the rollback's)
+    const size_t n = c->pool.rollback(mark);
+    if (c->d_err) (void)hipMemsetAsync(c->d_err, 0, 4, c->stream);
+    return n;
+}
+
+// What every entry point that takes a context and allocates or launches does first and last.  Open: the context's device, its
+// tuning and plan flags for this thread (enter_ctx), a fresh CallState, a mark of the device pool.  end(): a failed call is rolled
+// back (roll_back); with red zones (tuning pool_redzone), every zone of a live or quarantined block is compared with the pattern
+// after the last sync -- a zone that was written fails the call -- and the quarantined blocks go back to the pool; then the
+// CallState is reset and the thread forgets the context.  An entry point validates its arguments, opens the scope and returns
+// end(impl()) through run(): the impl may return early on any path (it does not run where the device could not be selected).
+// HSK_TIMING: one line per call on stderr.
+struct ApiCall {
+    hsk_ctx *c; const char *name; bool ok; unsigned long long mark; size_t live_open;
+    ApiCall(hsk_ctx *c_, const char *name_) : c(c_), name(name_)
+    {
+        ok = hipSetDevice(c->cfg.device) == hipSuccess;
+        if (!ok) { (void)hipGetLastError(); fail(c, HSK_ERR_HIP, "hipSetDevice(%d) failed", c->cfg.device); }
+        enter_ctx(c);
+        c->call = CallState();
+        mark = c->pool.mark(); live_open = c->pool.bytes_live;
+    }
+    template <typename F> int run(F &&impl, hsk_result *outs = nullptr, int nouts = 0) { return end(ok ? impl() : HSK_ERR_HIP, outs, nouts); }
+    int end(int rc, hsk_result *outs = nullptr, int nouts = 0)
+    {
+        size_t rolled = rc != HSK_OK ? roll_back(c, mark, outs, nouts) : 0;
+        if (c->pool.redzone) {
+            (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->comm_stream); (void)hipStreamSynchronize(c->d2h_stream);
+            char msg[320];
+            if (c->pool.check(msg, sizeof msg) != 0) {
+                if (rc == HSK_OK) rolled = roll_back(c, mark, outs, nouts);
+                rc = fail(c, HSK_ERR_INTERNAL, "%s", msg);
+            }
+            c->pool.flush();
+        }
+        if (timing_enabled())
+            fprintf(stderr, "[hsk] call %s: rc %d, pool live %zu -> %zu bytes, %zu blocks rolled back, cached %zu mapped %zu peak %zu bytes\n", name, rc, live_open,
+                    c->pool.bytes_live, rolled, c->pool.bytes_cached, c->pool.bytes_mapped(), c->pool.peak);
+        if (c->call.roff_check.valid()) (void)c->call.roff_check.get();      // (a call that failed before the pipeline collected the verdict)
+        c->call = CallState();
+        g_tune = nullptr; g_plan_flags = 0;
+        return rc;
+    }
+};
+
+// f(std::integral_constant<int, NW>()) for the key width nw (words: 1, 2, 3)
+template <typename F> static int with_nw(int nw, F &&f)
+{
+    switch (nw) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    default: return f(std::integral_constant<int, 3>());
+    }
+}
+
 extern "C" int hsk_init(const hsk_config *cfg, hsk_ctx **out)
 {
     if (getenv("HSK_BACKTRACE") && atoi(getenv("HSK_BACKTRACE")) != 0) { signal(SIGABRT, backtrace_on_abort); signal(SIGSEGV, backtrace_on_abort); }
@@ -141,27 +207,24 @@ extern "C" int hsk_init(const hsk_config *cfg, hsk_ctx **out)
     c->tune.parse(cfg->tuning);                                   // the client's string first, then the environment's (a name already set stays)
     c->tune.parse(getenv("HSK_TUNING"));
     c->cfg.tuning = nullptr;                                      // (the caller's string is not kept)
-    g_tune = &c->tune;
     memset(&c->stats, 0, sizeof c->stats);
     c->pool.be_malloc = pool_hip_malloc; c->pool.be_free = pool_hip_free;
-    // (tests) red zones behind every device block, checked at the end of every counting and stage entry point (redzone_end_call)
-    c->pool.redzone = (size_t)std::min<long long>(std::max<long long>(tune("pool_redzone", 0), 0), 1 << 20);
     c->pool.be_fill = pool_hip_fill; c->pool.be_check = pool_hip_check; c->pool.be_arg = c;
-    if (hipSetDevice(cfg->device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking) != hipSuccess) { delete c; return HSK_ERR_HIP; }
-    c->pinned_bytes = 1 << 20;
-    if (hipHostMalloc(&c->pinned, c->pinned_bytes, hipHostMallocDefault) != hipSuccess) { delete c; return HSK_ERR_OOM; }
-    c->comm.stage = (char *)c->pinned + (512u << 10); c->comm.stage_bytes = 256u << 10;     // second half of the staging area, 256 KB
-    c->d_err = (u32 *)c->pool.alloc(256);
-    if (!c->d_err) { delete c; return HSK_ERR_OOM; }
-    (void)hipMemsetAsync(c->d_err, 0, 256, c->stream);
-    {   // XCD census: words 16..31 of the error block are scratch here
+    const int rc = ApiCall(c, "hsk_init").run([&]() -> int {
+        // (tests) red zones behind every device block, checked when every entry point's scope ends (ApiCall::end)
+        c->pool.redzone = (size_t)std::min<long long>(std::max<long long>(tune("pool_redzone", 0), 0), 1 << 20);
+        if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking) != hipSuccess ||
+            hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking) != hipSuccess) return HSK_ERR_HIP;
+        c->pinned_bytes = 1 << 20;
+        if (hipHostMalloc(&c->pinned, c->pinned_bytes, hipHostMallocDefault) != hipSuccess) { c->pinned = nullptr; return HSK_ERR_OOM; }
+        c->comm.stage = (char *)c->pinned + (512u << 10); c->comm.stage_bytes = 256u << 10;     // second half of the staging area, 256 KB
+        c->d_err = (u32 *)c->pool.alloc(256);
+        if (!c->d_err) return HSK_ERR_OOM;
+        (void)hipMemsetAsync(c->d_err, 0, 256, c->stream);
+        // XCD census: words 16..31 of the error block are scratch here
         u32 *d_cnt = c->d_err + 16, h_cnt[16] = {0};
         hipLaunchKernelGGL(xcc_census_kernel, dim3(4096), dim3(64), 0, c->stream, d_cnt);
-        if (hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
-            hsk_destroy(c); return HSK_ERR_HIP;
-        }
+        if (hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return HSK_ERR_HIP;
         (void)hipMemsetAsync(d_cnt, 0, sizeof h_cnt, c->stream);
         int seen = 0; u32 lo = ~0u;
         for (int i = 0; i < 8; ++i) { if (h_cnt[i]) ++seen; lo = std::min(lo, h_cnt[i]); }
@@ -169,7 +232,9 @@ extern "C" int hsk_init(const hsk_config *cfg, hsk_ctx **out)
         // every XCD must get a fair share of a round-robin launch (4096 workgroups: 512 each)
         c->xcd_batch_ok = seen == 8 && lo >= 256;
         if (c->tune.get("force_no_xcd", 0)) c->xcd_batch_ok = false;      // test hook
-    }
+        return HSK_OK;
+    });
+    if (rc != HSK_OK) { hsk_destroy(c); return rc; }
     *out = c;
     return HSK_OK;
 }
@@ -247,7 +312,7 @@ extern "C" int hsk_get_stats(hsk_ctx *c, hsk_stats *out, int reset)
 // ------------------------------------------------------------------------------------------------
 static int estimate_plan(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u64 *d_roff, const u32 *d_rlen, u64 nreads, int nranks)
 {
-    c->est = PlanEstimate();
+    c->call.est = PlanEstimate();
     const bool enabled = tune("plan_sample", 1) != 0;
     constexpr u64 MIN_INPUT = 32ULL << 20, MIN_SAMPLE = 4ULL << 20, MAX_SAMPLE = 64ULL << 20;
     // who would use it: one-word keys without payload on one GPU (combining extraction or not, first table, aggregation or not)
@@ -273,7 +338,7 @@ static int estimate_plan(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const
         const u64 s_reads = h_out[8]; s_bytes = h_out[9];
         if (s_reads < 2048 || s_bytes < std::min<u64>(MIN_SAMPLE / 2, (u64)tune("plan_min_input", (long long)MIN_INPUT)) || s_bytes > packed_bytes || s_bytes > want + (1u << 20)) { release(); return HSK_OK; }      // (very long reads, a strange index: no estimate, the context's memory decides)
         // host input: the sample's bytes first (the main run copies them again with its first slab)
-        if (c->h2d_src || c->zc_src) HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed), c->h2d_src ? c->h2d_src : c->zc_src, s_bytes, hipMemcpyDefault, c->stream));
+        if (c->call.h2d_src || c->call.zc_src) HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed), c->call.h2d_src ? c->call.h2d_src : c->call.zc_src, s_bytes, hipMemcpyDefault, c->stream));
         EstimateArgs ea; memset(&ea, 0, sizeof ea);
         ea.packed = d_packed; ea.roff = d_roff; ea.rlen = d_rlen; ea.nreads = s_reads; ea.positions = s_bytes * 4; ea.k = c->cfg.kmer_size;
         ea.keys = d_keys; ea.cnts = d_cnts; ea.cap_mask = cap - 1; ea.out = d_out;
@@ -284,13 +349,13 @@ static int estimate_plan(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const
         HIPCHK(c, hsk_sync(c, c->stream));
         release();                                                          // (stream-ordered reuse: the kernels above are done)
         lost = h_out[0]; n1 = h_out[1]; n2 = h_out[2]; n3 = h_out[3]; ds = h_out[4]; ns = h_out[5];
-        c->est.homo_at = h_out[6]; c->est.homo_cg = h_out[7];
+        c->call.est.homo_at = h_out[6]; c->call.est.homo_cg = h_out[7];
         // shallow data (coverage below ~3): too few tripletons in 1/64 of the reads to tell the depth -- once more on sixteen times as many
         if (round == 0 && !lost && n2 >= 16 && n3 < 256 && want * 16 <= packed_bytes / 2 && want * 16 <= (512ULL << 20)) { want *= 16; continue; }
         break;
     }
     if (lost || ns < (1u << 14) || !plan_wanted) return HSK_OK;            // (no estimate)
-    PlanEstimate &e = c->est;
+    PlanEstimate &e = c->call.est;
     // several ranks: the reads are dealt to the ranks, so this rank's sample is that much thinner a slice of the WHOLE input's depth (a rank of eight
     // that holds 4-fold coverage of its own counts 32-fold k-mers after the exchange)
     e.fraction = (double)s_bytes / ((double)packed_bytes * (double)std::max(nranks, 1)); e.sample_kmers = ns; e.n1 = n1; e.n2 = n2; e.n3 = n3; e.distinct_sample = ds;
@@ -320,51 +385,35 @@ static u32 certain_drop_mask(hsk_ctx *c)
 {
     if (tune("drop_certain", 1) == 0 || c->cfg.kmer_size > 57 || !parse_fast_enabled() || c->cfg.minimizer_size > SCAN_MAX_M) return 0;
     const u64 dmin = std::max<u64>((u64)std::max(c->cfg.upper_freq, 0), 1ULL << 16);
-    return (c->est.homo_at > dmin ? 1u : 0u) | (c->est.homo_cg > dmin ? 2u : 0u);
+    return (c->call.est.homo_at > dmin ? 1u : 0u) | (c->call.est.homo_cg > dmin ? 2u : 0u);
 }
 
 static int dispatch_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u64 *d_roff, const u32 *d_rlen, u64 nreads,
                              int64_t rid_base, hsk_result *out, int attempt = 0)
 {
-    int rc;
-    if (attempt == 0) { c->combine_left_now = false; c->pair_cap_full = false; }
     if (attempt == 0) {
-        rc = estimate_plan(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, c->comm.active() ? c->comm.nranks : 1); if (rc) return rc;
+        int rc = estimate_plan(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, c->comm.active() ? c->comm.nranks : 1); if (rc) return rc;
         // A k-mer with more than U copies inside the sample alone cannot be in the result: the scan leaves the instances of the all-A / all-C k-mer out
         // where they are that many (poly-A, the poly-G reads of two-colour sequencers: one bucket, one bin, one task several times the others' size).
         // From 2^16 copies on (below that nothing is gained).  Several ranks: a rank that is certain is right for all of them -- run_pipeline ORs the
         // ranks' masks in the plan's all-reduce; the general parse kernels honour the mask as well, so a rank whose parse falls back stays consistent.
-        c->drop_mask_now = certain_drop_mask(c);
-        if (c->drop_mask_now && timing_enabled()) fprintf(stderr, "[hsk] certain drops: the sample holds %llu copies of the all-A and %llu of the all-C k-mer (U = %d): mask %u\n",
-                                                           (unsigned long long)c->est.homo_at, (unsigned long long)c->est.homo_cg, c->cfg.upper_freq, c->drop_mask_now);
+        c->call.drop_mask_now = certain_drop_mask(c);
+        if (c->call.drop_mask_now && timing_enabled()) fprintf(stderr, "[hsk] certain drops: the sample holds %llu copies of the all-A and %llu of the all-C k-mer (U = %d): mask %u\n",
+                                                                (unsigned long long)c->call.est.homo_at, (unsigned long long)c->call.est.homo_cg, c->cfg.upper_freq, c->call.drop_mask_now);
     }
-    c->plan_attempt = attempt;                          // (from the third attempt on run_pipeline does not consider the combining extraction at all)
-    const std::vector<void *> before = c->pool.snapshot();
+    c->call.plan_attempt = attempt;                     // (from the third attempt on run_pipeline does not consider the combining extraction at all)
+    const unsigned long long mark = c->pool.mark();
     const hsk_stats stats_before = c->stats;
-    switch (c->nw) {
-    case 1: rc = run_pipeline<1>(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, out); break;
-    case 2: rc = run_pipeline<2>(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, out); break;
-    default: rc = run_pipeline<3>(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, out); break;
-    }
-    c->vt_shift = 0;
-    if (rc != HSK_OK) {
-        // the failed call's kernels are drained, its result is dropped, and every device block it still holds goes back to the pool
-        (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->comm_stream); (void)hipStreamSynchronize(c->d2h_stream);
-        hsk_result_free(c, out);
-        c->pool.release_all_but(before);
-        (void)hipMemsetAsync(c->d_err, 0, 4, c->stream);
-    }
-    if (rc == HSK_RETRY_PLAN) {
-        // the combining extraction gave up (hsk_ctx::combine_off or combine_veto is set): once more, from the reads in HBM, on the instance path;
-        // the statistics describe the attempt that produces the result
-        drain_profile_events(c);
-        c->stats = stats_before;
-        if (attempt >= 3) return fail(c, HSK_ERR_INTERNAL, "the call was started again %d times without settling on a plan", attempt);
-        return dispatch_pipeline(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, out, attempt + 1);
-    }
-    c->plan_attempt = 0; c->est.valid = false;
-    c->drop_mask_now = 0; c->dropped_now = 0;            // (the hsk_stage_* entry points parse without a plan: nothing of this call's may stay behind)
-    return rc;
+    const int rc = with_nw(c->nw, [&](auto w) { return run_pipeline<decltype(w)::value>(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, out); });
+    if (rc != HSK_RETRY_PLAN) return rc;
+    // the combining extraction gave up (hsk_ctx::combine_off or CallState::combine_veto is set): the attempt is rolled back, and the call runs once
+    // more, from the reads in HBM, on the instance path; the statistics describe the attempt that produces the result
+    roll_back(c, mark, out, 1);
+    c->call.vt_shift = 0;
+    drain_profile_events(c);
+    c->stats = stats_before;
+    if (attempt >= 3) return fail(c, HSK_ERR_INTERNAL, "the call was started again %d times without settling on a plan", attempt);
+    return dispatch_pipeline(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, out, attempt + 1);
 }
 
 extern "C" void hsk_result_free(hsk_ctx *c, hsk_result *r)
@@ -377,20 +426,6 @@ extern "C" void hsk_result_free(hsk_ctx *c, hsk_result *r)
         delete rp;
     }
     memset(r, 0, sizeof *r);
-}
-
-// pool_redzone: the end of an entry point that ran kernels -- after its last sync, every zone of a live or quarantined block is compared with
-// the pattern, then the quarantined blocks go back to the pool.  A zone that was written fails the call (its results are dropped).
-static int redzone_end_call(hsk_ctx *c, int rc, hsk_result *outs = nullptr, int nouts = 0)
-{
-    if (!c->pool.redzone) return rc;
-    (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->comm_stream); (void)hipStreamSynchronize(c->d2h_stream);
-    char msg[320];
-    const int hit = c->pool.check(msg, sizeof msg);
-    c->pool.flush();
-    if (hit == 0) return rc;
-    if (rc == HSK_OK) for (int r = 0; r < nouts; ++r) hsk_result_free(c, &outs[r]);
-    return fail(c, HSK_ERR_INTERNAL, "%s", msg);
 }
 
 extern "C" int hsk_result_device_task(const hsk_result *r, int32_t task, const void **entries, uint64_t *n,
@@ -505,15 +540,15 @@ static int derive_input(hsk_ctx *c, uint64_t packed_bytes, const uint64_t *off, 
     // 10 Gbp of 150-bp reads).  A single read of another length sends the call down the same road as a buffer with gaps.
     const bool uniform_enabled = tune("uniform_len", 1) != 0;
     const uint32_t ulen = (uniform_enabled && len[0] != 0 && len[0] == len[nreads / 2] && len[0] == len[nreads - 1]) ? len[0] : 0;
-    if (ulen) { hipLaunchKernelGGL(rlen_fill_kernel, dim3(2048), dim3(256), 0, c->stream, d.rlen, nreads, ulen); c->rlen_host = len; c->stats.h2d_bytes -= nreads * 4; }
+    if (ulen) { hipLaunchKernelGGL(rlen_fill_kernel, dim3(2048), dim3(256), 0, c->stream, d.rlen, nreads, ulen); c->call.rlen_host = len; c->stats.h2d_bytes -= nreads * 4; }
     else HIPCHK(c, hipMemcpyAsync(d.rlen, len, nreads * 4, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(roff_tilesum_kernel, dim3((u32)ntl), dim3(PARSE_THREADS), 0, c->stream, d.rlen, nreads, d_tsum);
     hipLaunchKernelGGL(roff_tilescan_kernel, dim3(1), dim3(PARSE_THREADS), 0, c->stream, d_tsum, ntl);
     hipLaunchKernelGGL(roff_write_kernel, dim3((u32)ntl), dim3(PARSE_THREADS), 0, c->stream, d.rlen, nreads, d_tsum, d.roff);
     HIPCHK(c, hipMemcpyAsync(d.roff + nreads, stage, 8, hipMemcpyHostToDevice, c->stream));
     // the caller's offsets stay on the host: four threads check them against the back-to-back layout while the GPU scans
-    c->roff_given = d_given; c->roff_host = off;
-    c->roff_check = std::async(std::launch::async, offsets_back_to_back, off, len, nreads, packed_bytes, ulen);
+    c->call.roff_given = d_given; c->call.roff_host = off;
+    c->call.roff_check = std::async(std::launch::async, offsets_back_to_back, off, len, nreads, packed_bytes, ulen);
     return HSK_OK;
 }
 
@@ -521,48 +556,47 @@ extern "C" int hsk_count(hsk_ctx *c, const uint8_t *packed, uint64_t packed_byte
                          uint64_t nreads, int64_t rid_base, hsk_result *out)
 {
     if (!c || !out || (nreads && (!off || !len)) || (packed_bytes && !packed)) return HSK_ERR_INVALID_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    enter_ctx(c);
-    tmark(nullptr); tmark("hsk_count enter");
-    const bool device_check = nreads >= (1u << 20);          // a serial host loop over 10^8 reads costs more than the whole count
-    int rc = device_check ? HSK_OK : check_host_index(c, packed_bytes, off, len, nreads); if (rc) return rc;
-    const u8 *zc = nullptr;
-    if (zero_copy_enabled() && packed_bytes >= (16u << 20)) {
-        hipPointerAttribute_t at; memset(&at, 0, sizeof at);
-        if (hipPointerGetAttributes(&at, packed) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) zc = (const u8 *)at.devicePointer;
-        else (void)hipGetLastError();
-    }
-    // pinned input of some size: slab ingest (DMA copies pipelined with the scan, parse_count) instead of reads over PCIe in place;
-    // HSK_H2D_SLABS=0: in place as in round 2, =n: n slabs
-    const int slabs_env = (int)tune("h2d_slabs", 16);
-    const bool slab_ingest = zc != nullptr && slabs_env > 1 && packed_bytes >= (32u << 20);
-    const bool profile = (c->cfg.flags & HSK_FLAG_PROFILE) != 0;
-    const bool derive_enabled = tune("derive_offsets", 1) != 0;
-    // only the read lengths travel ahead of the scan (see roff_tilesum_kernel).  The host threads' verdict on the derived index is read by the
-    // fast parse (parse_count's scan branch, parse_ingest_pipelined): with the general parse kernels from the start (M > SCAN_MAX_M, HSK_PARSE_FAST=0)
-    // the caller's index travels and is checked on the device like a pageable one
-    const bool derive = zc != nullptr && device_check && derive_enabled && parse_fast_enabled() && c->cfg.minimizer_size <= SCAN_MAX_M;
-    DevInput d;
-    u64 *d_given = nullptr, *d_tsum = nullptr;
-    EvPair ep{}; if (profile) { ep.a = ev_get(c); ep.b = ev_get(c); ep.kind = 5; (void)hipEventRecord(ep.a, c->stream); }
-    if (!derive) rc = upload_input(c, zc ? nullptr : packed, packed_bytes, off, len, nreads, d, false);
-    else rc = derive_input(c, packed_bytes, off, len, nreads, d, d_given, d_tsum);
-    if (profile) { (void)hipEventRecord(ep.b, c->stream); c->ev_pending.push_back(ep); }
-    c->stats.h2d_bytes += packed_bytes + nreads * (derive ? 4 : 12);      // (derive: the offsets stay on the host; fixed-length reads: the lengths too, see derive_input)
-    if (rc == HSK_OK && device_check && !derive) {
-        hipLaunchKernelGGL(index_check_kernel, dim3(1024), dim3(256), 0, c->stream, d.roff, d.rlen, nreads, packed_bytes, c->d_err);
-        c->index_unchecked = true;
-    }
-    c->zc_src = slab_ingest ? nullptr : zc;
-    c->h2d_src = slab_ingest ? packed : nullptr; c->h2d_slabs = slabs_env;
-    tmark(zc ? (derive ? "input enqueued (zero-copy packed, offsets derived from the lengths)" : "input enqueued (zero-copy packed)") : "input enqueued (copies)");
-    if (rc == HSK_OK) rc = dispatch_pipeline(c, d.packed, packed_bytes, d.roff, d.rlen, nreads, rid_base, out);
-    tmark("pipeline returned");
-    c->zc_src = nullptr; c->h2d_src = nullptr; c->index_unchecked = false; c->roff_given = nullptr; c->roff_host = nullptr; c->roff_bad = false; c->rlen_host = nullptr;
-    if (c->roff_check.valid()) (void)c->roff_check.get();          // (the pipeline failed before it collected the verdict)
-    c->pool.release(d_given); c->pool.release(d_tsum);
-    free_input(c, d);
-    return redzone_end_call(c, rc, out, 1);
+    memset(out, 0, sizeof *out);
+    return ApiCall(c, "hsk_count").run([&]() -> int {
+        tmark(nullptr); tmark("hsk_count enter");
+        const bool device_check = nreads >= (1u << 20);          // a serial host loop over 10^8 reads costs more than the whole count
+        int rc = device_check ? HSK_OK : check_host_index(c, packed_bytes, off, len, nreads); if (rc) return rc;
+        const u8 *zc = nullptr;
+        if (zero_copy_enabled() && packed_bytes >= (16u << 20)) {
+            hipPointerAttribute_t at; memset(&at, 0, sizeof at);
+            if (hipPointerGetAttributes(&at, packed) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) zc = (const u8 *)at.devicePointer;
+            else (void)hipGetLastError();
+        }
+        // pinned input of some size: slab ingest (DMA copies pipelined with the scan, parse_count) instead of reads over PCIe in place;
+        // HSK_H2D_SLABS=0: in place as in round 2, =n: n slabs
+        const int slabs_env = (int)tune("h2d_slabs", 16);
+        const bool slab_ingest = zc != nullptr && slabs_env > 1 && packed_bytes >= (32u << 20);
+        const bool profile = (c->cfg.flags & HSK_FLAG_PROFILE) != 0;
+        const bool derive_enabled = tune("derive_offsets", 1) != 0;
+        // only the read lengths travel ahead of the scan (see roff_tilesum_kernel).  The host threads' verdict on the derived index is read by the
+        // fast parse (parse_count's scan branch, parse_ingest_pipelined): with the general parse kernels from the start (M > SCAN_MAX_M, HSK_PARSE_FAST=0)
+        // the caller's index travels and is checked on the device like a pageable one
+        const bool derive = zc != nullptr && device_check && derive_enabled && parse_fast_enabled() && c->cfg.minimizer_size <= SCAN_MAX_M;
+        DevInput d;
+        u64 *d_given = nullptr, *d_tsum = nullptr;
+        EvPair ep{}; if (profile) { ep.a = ev_get(c); ep.b = ev_get(c); ep.kind = 5; (void)hipEventRecord(ep.a, c->stream); }
+        if (!derive) rc = upload_input(c, zc ? nullptr : packed, packed_bytes, off, len, nreads, d, false);
+        else rc = derive_input(c, packed_bytes, off, len, nreads, d, d_given, d_tsum);
+        if (profile) { (void)hipEventRecord(ep.b, c->stream); c->ev_pending.push_back(ep); }
+        c->stats.h2d_bytes += packed_bytes + nreads * (derive ? 4 : 12);      // (derive: the offsets stay on the host; fixed-length reads: the lengths too, see derive_input)
+        if (rc) return rc;
+        if (device_check && !derive) {
+            hipLaunchKernelGGL(index_check_kernel, dim3(1024), dim3(256), 0, c->stream, d.roff, d.rlen, nreads, packed_bytes, c->d_err);
+            c->call.index_unchecked = true;
+        }
+        c->call.zc_src = slab_ingest ? nullptr : zc;
+        c->call.h2d_src = slab_ingest ? packed : nullptr; c->call.h2d_slabs = slabs_env;
+        tmark(zc ? (derive ? "input enqueued (zero-copy packed, offsets derived from the lengths)" : "input enqueued (zero-copy packed)") : "input enqueued (copies)");
+        rc = dispatch_pipeline(c, d.packed, packed_bytes, d.roff, d.rlen, nreads, rid_base, out);
+        tmark("pipeline returned");
+        c->pool.release(d_given); c->pool.release(d_tsum); free_input(c, d);
+        return rc;
+    }, out, 1);
 }
 
 extern "C" int hsk_count_device(hsk_ctx *c, const void *d_packed, uint64_t packed_bytes, const void *d_off, const void *d_len,
@@ -570,52 +604,48 @@ extern "C" int hsk_count_device(hsk_ctx *c, const void *d_packed, uint64_t packe
 {
     if (!c || !out || (nreads && (!d_off || !d_len)) || (packed_bytes && !d_packed)) return HSK_ERR_INVALID_ARG;
     if (((uintptr_t)d_packed & 3) != 0) return fail(c, HSK_ERR_INVALID_ARG, "d_packed must be 4-byte aligned");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    enter_ctx(c);
-    // the kernels index roff[r+1]: build the (nreads+1)-entry offset array
-    u64 *roff; DALLOC(c, roff, u64 *, (nreads + 1) * 8);
-    if (nreads) HIPCHK(c, hipMemcpyAsync(roff, d_off, nreads * 8, hipMemcpyDeviceToDevice, c->stream));
-    u64 *stage = (u64 *)((char *)c->pinned + c->pinned_bytes - 256);
-    *stage = packed_bytes;
-    HIPCHK(c, hipMemcpyAsync(roff + nreads, stage, 8, hipMemcpyHostToDevice, c->stream));
-    int rc = dispatch_pipeline(c, (const u8 *)d_packed, packed_bytes, roff, (const u32 *)d_len, nreads, rid_base, out);
-    if (timing_enabled()) fprintf(stderr, "[hsk] device pool: %.2f GB live, %.2f GB cached (mapped %.2f GB), peak live %.2f GB\n", c->pool.bytes_live / 1e9, c->pool.bytes_cached / 1e9,
-                                  c->pool.bytes_mapped() / 1e9, c->pool.peak / 1e9);
-    c->pool.release(roff);
-    return redzone_end_call(c, rc, out, 1);
+    memset(out, 0, sizeof *out);
+    return ApiCall(c, "hsk_count_device").run([&]() -> int {
+        // the kernels index roff[r+1]: build the (nreads+1)-entry offset array
+        u64 *roff; DALLOC(c, roff, u64 *, (nreads + 1) * 8);
+        if (nreads) HIPCHK(c, hipMemcpyAsync(roff, d_off, nreads * 8, hipMemcpyDeviceToDevice, c->stream));
+        u64 *stage = (u64 *)((char *)c->pinned + c->pinned_bytes - 256);
+        *stage = packed_bytes;
+        HIPCHK(c, hipMemcpyAsync(roff + nreads, stage, 8, hipMemcpyHostToDevice, c->stream));
+        const int rc = dispatch_pipeline(c, (const u8 *)d_packed, packed_bytes, roff, (const u32 *)d_len, nreads, rid_base, out);
+        c->pool.release(roff);
+        return rc;
+    }, out, 1);
+}
+
+// virtual ranks on this GPU (run_loopback) over inputs in HBM; the owner table goes to the caller
+static int loopback_impl(hsk_ctx *c, int nranks, const std::vector<DevInput> &in, const uint64_t *packed_bytes, const uint64_t *nreads, hsk_result *outs,
+                         int32_t *owner_out, int32_t owner_capacity)
+{
+    u32 ntasks = 0;
+    std::vector<int32_t> owner(HSK_MAX_TASKS, 0);
+    const int rc = with_nw(c->nw, [&](auto w) { return run_loopback<decltype(w)::value>(c, nranks, in.data(), packed_bytes, nreads, outs, owner.data(), &ntasks); });
+    if (rc || !owner_out) return rc;
+    if ((u32)owner_capacity < ntasks) return fail(c, HSK_ERR_INVALID_ARG, "owner capacity %d < %u tasks", owner_capacity, ntasks);
+    memcpy(owner_out, owner.data(), sizeof(int32_t) * ntasks);
+    return HSK_OK;
 }
 
 extern "C" int hsk_count_loopback(hsk_ctx *c, int nranks, const uint8_t *const *packed, const uint64_t *packed_bytes, const uint64_t *const *off,
                                   const uint32_t *const *len, const uint64_t *nreads, hsk_result *outs, int32_t *owner_out, int32_t owner_capacity)
 {
     if (!c || nranks < 1 || nranks > 64 || !packed || !packed_bytes || !off || !len || !nreads || !outs) return HSK_ERR_INVALID_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    enter_ctx(c);
-    std::vector<DevInput> in(nranks);
-    int rc = HSK_OK;
-    for (int r = 0; r < nranks && rc == HSK_OK; ++r) {
-        rc = check_host_index(c, packed_bytes[r], off[r], len[r], nreads[r]);
-        if (rc == HSK_OK) rc = upload_input(c, packed[r], packed_bytes[r], off[r], len[r], nreads[r], in[r]);
-    }
-    u32 ntasks = 0;
-    std::vector<int32_t> owner(HSK_MAX_TASKS, 0);
-    const std::vector<void *> before = c->pool.snapshot();
-    if (rc == HSK_OK) {
-        switch (c->nw) {
-        case 1: rc = run_loopback<1>(c, nranks, in.data(), packed_bytes, nreads, outs, owner.data(), &ntasks); break;
-        case 2: rc = run_loopback<2>(c, nranks, in.data(), packed_bytes, nreads, outs, owner.data(), &ntasks); break;
-        default: rc = run_loopback<3>(c, nranks, in.data(), packed_bytes, nreads, outs, owner.data(), &ntasks); break;
+    memset(outs, 0, sizeof *outs * nranks);
+    return ApiCall(c, "hsk_count_loopback").run([&]() -> int {
+        std::vector<DevInput> in(nranks);
+        for (int r = 0; r < nranks; ++r) {
+            int rc = check_host_index(c, packed_bytes[r], off[r], len[r], nreads[r]); if (rc) return rc;
+            rc = upload_input(c, packed[r], packed_bytes[r], off[r], len[r], nreads[r], in[r]); if (rc) return rc;
         }
-    }
-    if (rc == HSK_OK && owner_out) { if ((u32)owner_capacity < ntasks) rc = HSK_ERR_INVALID_ARG; else memcpy(owner_out, owner.data(), sizeof(int32_t) * ntasks); }
-    for (auto &d : in) free_input(c, d);
-    if (rc != HSK_OK) {
-        (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->comm_stream); (void)hipStreamSynchronize(c->d2h_stream);
-        for (int r = 0; r < nranks; ++r) hsk_result_free(c, &outs[r]);
-        c->pool.release_all_but(before);
-        (void)hipMemsetAsync(c->d_err, 0, 4, c->stream);
-    }
-    return redzone_end_call(c, rc, outs, nranks);
+        const int rc = loopback_impl(c, nranks, in, packed_bytes, nreads, outs, owner_out, owner_capacity);
+        for (auto &d : in) free_input(c, d);
+        return rc;
+    }, outs, nranks);
 }
 
 // the same with every virtual rank's reads already resident in HBM (full-size runs of the multi-rank data path: tests/test_gpu_multirank.py,
@@ -624,41 +654,23 @@ extern "C" int hsk_count_loopback_device(hsk_ctx *c, int nranks, const void *con
                                          const void *const *d_len, const uint64_t *nreads, hsk_result *outs, int32_t *owner_out, int32_t owner_capacity)
 {
     if (!c || nranks < 1 || nranks > 64 || !d_packed || !packed_bytes || !d_off || !d_len || !nreads || !outs) return HSK_ERR_INVALID_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    enter_ctx(c);
-    std::vector<DevInput> in(nranks);
-    std::vector<u64 *> roffs(nranks, nullptr);
-    u64 *stage = (u64 *)((char *)c->pinned + (256u << 10));                   // (pinned staging: one end offset per rank)
-    int rc = HSK_OK;
-    for (int r = 0; r < nranks && rc == HSK_OK; ++r) {
-        if (((uintptr_t)d_packed[r] & 3) != 0) { rc = fail(c, HSK_ERR_INVALID_ARG, "d_packed must be 4-byte aligned"); break; }
-        roffs[r] = (u64 *)c->pool.alloc((nreads[r] + 1) * 8);
-        if (!roffs[r]) { rc = fail(c, HSK_ERR_OOM, "read offsets of rank %d", r); break; }
-        if (nreads[r]) HIPCHK(c, hipMemcpyAsync(roffs[r], d_off[r], nreads[r] * 8, hipMemcpyDeviceToDevice, c->stream));
-        stage[r] = packed_bytes[r];
-        HIPCHK(c, hipMemcpyAsync(roffs[r] + nreads[r], stage + r, 8, hipMemcpyHostToDevice, c->stream));
-        in[r].packed = (u8 *)const_cast<void *>(d_packed[r]); in[r].roff = roffs[r]; in[r].rlen = (u32 *)const_cast<void *>(d_len[r]);
-    }
-    u32 ntasks = 0;
-    std::vector<int32_t> owner(HSK_MAX_TASKS, 0);
-    const std::vector<void *> before = c->pool.snapshot();
-    if (rc == HSK_OK) {
-        switch (c->nw) {
-        case 1: rc = run_loopback<1>(c, nranks, in.data(), packed_bytes, nreads, outs, owner.data(), &ntasks); break;
-        case 2: rc = run_loopback<2>(c, nranks, in.data(), packed_bytes, nreads, outs, owner.data(), &ntasks); break;
-        default: rc = run_loopback<3>(c, nranks, in.data(), packed_bytes, nreads, outs, owner.data(), &ntasks); break;
+    memset(outs, 0, sizeof *outs * nranks);
+    return ApiCall(c, "hsk_count_loopback_device").run([&]() -> int {
+        std::vector<DevInput> in(nranks);
+        u64 *stage = (u64 *)((char *)c->pinned + (256u << 10));                   // (pinned staging: one end offset per rank)
+        for (int r = 0; r < nranks; ++r) {
+            if (((uintptr_t)d_packed[r] & 3) != 0) return fail(c, HSK_ERR_INVALID_ARG, "d_packed must be 4-byte aligned");
+            DALLOC(c, in[r].roff, u64 *, (nreads[r] + 1) * 8);
+            if (nreads[r]) HIPCHK(c, hipMemcpyAsync(in[r].roff, d_off[r], nreads[r] * 8, hipMemcpyDeviceToDevice, c->stream));
+            stage[r] = packed_bytes[r];
+            HIPCHK(c, hipMemcpyAsync(in[r].roff + nreads[r], stage + r, 8, hipMemcpyHostToDevice, c->stream));
+            in[r].packed = (u8 *)const_cast<void *>(d_packed[r]); in[r].rlen = (u32 *)const_cast<void *>(d_len[r]);
         }
-    }
-    if (rc == HSK_OK && owner_out) { if ((u32)owner_capacity < ntasks) rc = HSK_ERR_INVALID_ARG; else memcpy(owner_out, owner.data(), sizeof(int32_t) * ntasks); }
-    if (rc != HSK_OK) {
-        (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->comm_stream); (void)hipStreamSynchronize(c->d2h_stream);
-        for (int r = 0; r < nranks; ++r) hsk_result_free(c, &outs[r]);
-        c->pool.release_all_but(before);
-        (void)hipMemsetAsync(c->d_err, 0, 4, c->stream);
-    }
-    (void)hipStreamSynchronize(c->stream);
-    for (u64 *p : roffs) c->pool.release(p);
-    return redzone_end_call(c, rc, outs, nranks);
+        const int rc = loopback_impl(c, nranks, in, packed_bytes, nreads, outs, owner_out, owner_capacity);
+        (void)hipStreamSynchronize(c->stream);
+        for (auto &d : in) c->pool.release(d.roff);
+        return rc;
+    }, outs, nranks);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -668,42 +680,45 @@ extern "C" int hsk_stage_destinations(hsk_ctx *c, const uint8_t *packed, uint64_
                                       uint64_t nreads, int32_t *dest, uint64_t cap, uint64_t *dest_off)
 {
     if (!c || !dest_off || (cap && !dest)) return HSK_ERR_INVALID_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    enter_ctx(c);
-    int rc = check_host_index(c, packed_bytes, off, len, nreads); if (rc) return rc;
-    const int K = c->cfg.kmer_size;
-    uint64_t total = 0;
-    for (uint64_t r = 0; r < nreads; ++r) { dest_off[r] = total; total += len[r] >= (uint32_t)K ? len[r] - K + 1 : 0; }
-    dest_off[nreads] = total;
-    if (total > cap) return fail(c, HSK_ERR_INVALID_ARG, "dest capacity %llu < %llu", (unsigned long long)cap, (unsigned long long)total);
-    if (!nreads || !packed_bytes) return HSK_OK;
-    DevInput d; rc = upload_input(c, packed, packed_bytes, off, len, nreads, d); if (rc) return rc;
-    const u32 ntasks = c->cfg.ntasks ? (u32)c->cfg.ntasks : 1;
-    u32 nblocks; ParseArgs a = make_parse_args(c, d.packed, packed_bytes, d.roff, d.rlen, nreads, 0, ntasks, &nblocks);
-    int32_t *d_dump; DALLOC(c, d_dump, int32_t *, packed_bytes * 4 * 4);
-    a.dump_dest = d_dump;
-    hipLaunchKernelGGL((parse_kernel<PARSE_DUMP, false>), dim3(nblocks), dim3(PARSE_THREADS), 64, c->stream, a);
-    std::vector<int32_t> h(packed_bytes * 4);
-    HIPCHK(c, hipMemcpyAsync(h.data(), d_dump, packed_bytes * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (uint64_t r = 0; r < nreads; ++r) {
-        const uint64_t nk = dest_off[r + 1] - dest_off[r];
-        for (uint64_t i = 0; i < nk; ++i) dest[dest_off[r] + i] = h[off[r] * 4 + i];
-    }
-    c->pool.release(d_dump); free_input(c, d);
-    return redzone_end_call(c, HSK_OK);
+    return ApiCall(c, "hsk_stage_destinations").run([&]() -> int {
+        int rc = check_host_index(c, packed_bytes, off, len, nreads); if (rc) return rc;
+        const int K = c->cfg.kmer_size;
+        uint64_t total = 0;
+        for (uint64_t r = 0; r < nreads; ++r) { dest_off[r] = total; total += len[r] >= (uint32_t)K ? len[r] - K + 1 : 0; }
+        dest_off[nreads] = total;
+        if (total > cap) return fail(c, HSK_ERR_INVALID_ARG, "dest capacity %llu < %llu", (unsigned long long)cap, (unsigned long long)total);
+        if (!nreads || !packed_bytes) return HSK_OK;
+        DevInput d; rc = upload_input(c, packed, packed_bytes, off, len, nreads, d); if (rc) return rc;
+        const u32 ntasks = c->cfg.ntasks ? (u32)c->cfg.ntasks : 1;
+        u32 nblocks; ParseArgs a = make_parse_args(c, d.packed, packed_bytes, d.roff, d.rlen, nreads, 0, ntasks, &nblocks);
+        int32_t *d_dump; DALLOC(c, d_dump, int32_t *, packed_bytes * 4 * 4);
+        a.dump_dest = d_dump;
+        hipLaunchKernelGGL((parse_kernel<PARSE_DUMP, false>), dim3(nblocks), dim3(PARSE_THREADS), 64, c->stream, a);
+        std::vector<int32_t> h(packed_bytes * 4);
+        HIPCHK(c, hipMemcpyAsync(h.data(), d_dump, packed_bytes * 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (uint64_t r = 0; r < nreads; ++r) {
+            const uint64_t nk = dest_off[r + 1] - dest_off[r];
+            for (uint64_t i = 0; i < nk; ++i) dest[dest_off[r] + i] = h[off[r] * 4 + i];
+        }
+        c->pool.release(d_dump); free_input(c, d);
+        return HSK_OK;
+    });
 }
 
 template <int NW>
-static int stage_task_kmers_impl(hsk_ctx *c, const DevInput &d, uint64_t packed_bytes, uint64_t nreads, int64_t rid_base, int32_t task,
-                                 uint64_t *keys, uint32_t *pos, int32_t *rid, uint64_t cap, uint64_t *n)
+static int stage_task_kmers_impl(hsk_ctx *c, const uint8_t *packed, uint64_t packed_bytes, const uint64_t *off, const uint32_t *len, uint64_t nreads,
+                                 int64_t rid_base, int32_t task, uint64_t *keys, uint32_t *pos, int32_t *rid, uint64_t cap, uint64_t *n)
 {
+    int rc = check_host_index(c, packed_bytes, off, len, nreads); if (rc) return rc;
+    if (!nreads || !packed_bytes) return HSK_OK;
     const bool ext = c->cfg.extension != 0;
     const u32 ntasks = c->cfg.ntasks ? (u32)c->cfg.ntasks : 1;
     if (task < 0 || (u32)task >= ntasks) return HSK_ERR_INVALID_ARG;
+    DevInput d; rc = upload_input(c, packed, packed_bytes, off, len, nreads, d); if (rc) return rc;
     std::vector<u32> order(ntasks); for (u32 t = 0; t < ntasks; ++t) order[t] = t;
     SupermerStore st;
-    int rc = parse_phase(c, d.packed, packed_bytes, d.roff, d.rlen, nreads, rid_base, ntasks, order, st); if (rc) return rc;
+    rc = parse_phase(c, d.packed, packed_bytes, d.roff, d.rlen, nreads, rid_base, ntasks, order, st); if (rc) return rc;
     TaskSegs ts;
     if (st.task_tot[3 * task]) {
         ExpSeg s; s.sup_off = st.task_base[3 * task]; s.n_sup = st.task_tot[3 * task]; s.byte_off = st.task_base[3 * task + 1]; s.kmer_off = 0; s.tile_start = 0;
@@ -711,23 +726,22 @@ static int stage_task_kmers_impl(hsk_ctx *c, const DevInput &d, uint64_t packed_
     }
     finalize_segs(ts);
     *n = ts.nkmers;
-    if (ts.nkmers > cap) { free_store(c, st); return fail(c, HSK_ERR_INVALID_ARG, "capacity %llu < %llu", (unsigned long long)cap, (unsigned long long)ts.nkmers); }
+    if (ts.nkmers > cap) return fail(c, HSK_ERR_INVALID_ARG, "capacity %llu < %llu", (unsigned long long)cap, (unsigned long long)ts.nkmers);
     if (ts.nkmers) {
         u64 *dk, *dv = nullptr;
         DALLOC(c, dk, u64 *, ts.nkmers * NW * 8 + 64);
         if (ext) DALLOC(c, dv, u64 *, ts.nkmers * 8 + 64);
-        rc = expand_task<NW>(c, ts, st.sm_len, source_from_store(st, d.packed, packed_bytes), st.sm_pos, st.sm_rid, dk, dv);
-        if (rc == HSK_OK) {
-            HIPCHK(c, hipMemcpyAsync(keys, dk, ts.nkmers * NW * 8, hipMemcpyDeviceToHost, c->stream));
-            std::vector<u64> hv;
-            if (ext) { hv.resize(ts.nkmers); HIPCHK(c, hipMemcpyAsync(hv.data(), dv, ts.nkmers * 8, hipMemcpyDeviceToHost, c->stream)); }
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (ext) for (u64 i = 0; i < ts.nkmers; ++i) { if (pos) pos[i] = (uint32_t)hv[i]; if (rid) rid[i] = (int32_t)(hv[i] >> 32); }
-        }
+        rc = expand_task<NW>(c, ts, st.sm_len, source_from_store(st, d.packed, packed_bytes), st.sm_pos, st.sm_rid, dk, dv); if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(keys, dk, ts.nkmers * NW * 8, hipMemcpyDeviceToHost, c->stream));
+        std::vector<u64> hv;
+        if (ext) { hv.resize(ts.nkmers); HIPCHK(c, hipMemcpyAsync(hv.data(), dv, ts.nkmers * 8, hipMemcpyDeviceToHost, c->stream)); }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (ext) for (u64 i = 0; i < ts.nkmers; ++i) { if (pos) pos[i] = (uint32_t)hv[i]; if (rid) rid[i] = (int32_t)(hv[i] >> 32); }
         c->pool.release(dk); c->pool.release(dv);
     }
     free_store(c, st);
-    return rc;
+    free_input(c, d);
+    return HSK_OK;
 }
 
 extern "C" int hsk_stage_task_kmers(hsk_ctx *c, const uint8_t *packed, uint64_t packed_bytes, const uint64_t *off, const uint32_t *len,
@@ -736,18 +750,8 @@ extern "C" int hsk_stage_task_kmers(hsk_ctx *c, const uint8_t *packed, uint64_t 
 {
     if (!c || !n || (cap && !keys)) return HSK_ERR_INVALID_ARG;
     *n = 0;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    enter_ctx(c);
-    int rc = check_host_index(c, packed_bytes, off, len, nreads); if (rc) return rc;
-    if (!nreads || !packed_bytes) return HSK_OK;
-    DevInput d; rc = upload_input(c, packed, packed_bytes, off, len, nreads, d); if (rc) return rc;
-    switch (c->nw) {
-    case 1: rc = stage_task_kmers_impl<1>(c, d, packed_bytes, nreads, rid_base, task, keys, pos, rid, cap, n); break;
-    case 2: rc = stage_task_kmers_impl<2>(c, d, packed_bytes, nreads, rid_base, task, keys, pos, rid, cap, n); break;
-    default: rc = stage_task_kmers_impl<3>(c, d, packed_bytes, nreads, rid_base, task, keys, pos, rid, cap, n); break;
-    }
-    free_input(c, d);
-    return redzone_end_call(c, rc);
+    return ApiCall(c, "hsk_stage_task_kmers").run([&] {
+        return with_nw(c->nw, [&](auto w) { return stage_task_kmers_impl<decltype(w)::value>(c, packed, packed_bytes, off, len, nreads, rid_base, task, keys, pos, rid, cap, n); }); });
 }
 
 template <int NW>
@@ -761,31 +765,21 @@ static int stage_sort_impl(hsk_ctx *c, uint64_t *keys, uint64_t *vals, uint64_t 
     SortScratch sc; int rc = alloc_sort_scratch(c, sc); if (rc) return rc;
     u64 *sk, *sv;
     // all 64 bits of every word take part (K = 32*NW would be the natural name; 32*NW-... use full words)
-    rc = sort_task_device<NW>(c, ka, kb, va, vb, n, 32 * NW, sc, &sk, &sv);
-    if (rc == HSK_OK) rc = check_device_error(c);
-    if (rc == HSK_OK) {
-        HIPCHK(c, hipMemcpyAsync(keys, sk, n * NW * 8, hipMemcpyDeviceToHost, c->stream));
-        if (vals) HIPCHK(c, hipMemcpyAsync(vals, sv, n * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    rc = sort_task_device<NW>(c, ka, kb, va, vb, n, 32 * NW, sc, &sk, &sv); if (rc) return rc;
+    rc = check_device_error(c); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(keys, sk, n * NW * 8, hipMemcpyDeviceToHost, c->stream));
+    if (vals) HIPCHK(c, hipMemcpyAsync(vals, sv, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     free_sort_scratch(c, sc);
     c->pool.release(ka); c->pool.release(kb); c->pool.release(va); c->pool.release(vb);
-    return rc;
+    return HSK_OK;
 }
 
 extern "C" int hsk_stage_sort(hsk_ctx *c, uint64_t *keys, uint64_t *vals, uint64_t n, int32_t nw)
 {
     if (!c || (n && !keys) || nw < 1 || nw > 3) return HSK_ERR_INVALID_ARG;
     if (n == 0) return HSK_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    enter_ctx(c);
-    int rc;
-    switch (nw) {
-    case 1: rc = stage_sort_impl<1>(c, keys, vals, n); break;
-    case 2: rc = stage_sort_impl<2>(c, keys, vals, n); break;
-    default: rc = stage_sort_impl<3>(c, keys, vals, n); break;
-    }
-    return redzone_end_call(c, rc);
+    return ApiCall(c, "hsk_stage_sort").run([&] { return with_nw(nw, [&](auto w) { return stage_sort_impl<decltype(w)::value>(c, keys, vals, n); }); });
 }
 
 template <int NW>
@@ -797,16 +791,14 @@ static int stage_count_impl(hsk_ctx *c, const uint64_t *keys, uint64_t n, uint64
     u64 *d_histo; DALLOC(c, d_histo, u64 *, (size_t)histo_len * 8);
     HIPCHK(c, hipMemsetAsync(d_histo, 0, (size_t)histo_len * 8, c->stream));
     TaskOut to;
-    int rc = count_task_device<NW>(c, dk, nullptr, n, 0, d_histo, histo_len, to);
-    if (rc == HSK_OK) {
-        *n_out = to.n;
-        if (to.n > cap) rc = fail(c, HSK_ERR_INVALID_ARG, "capacity %llu < %llu", (unsigned long long)cap, (unsigned long long)to.n);
-        else if (to.n) HIPCHK(c, hipMemcpyAsync(out_entries, to.entries, to.n * (NW + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    int rc = count_task_device<NW>(c, dk, nullptr, n, 0, d_histo, histo_len, to); if (rc) return rc;
+    *n_out = to.n;
+    if (to.n > cap) return fail(c, HSK_ERR_INVALID_ARG, "capacity %llu < %llu", (unsigned long long)cap, (unsigned long long)to.n);
+    if (to.n) HIPCHK(c, hipMemcpyAsync(out_entries, to.entries, to.n * (NW + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     free_task_out(c, to);
     c->pool.release(dk); c->pool.release(d_histo);
-    return rc;
+    return HSK_OK;
 }
 
 extern "C" int hsk_stage_count_sorted(hsk_ctx *c, const uint64_t *keys, uint64_t n, int32_t nw, uint64_t *out_entries, uint64_t cap, uint64_t *n_out)
@@ -814,15 +806,7 @@ extern "C" int hsk_stage_count_sorted(hsk_ctx *c, const uint64_t *keys, uint64_t
     if (!c || !n_out || (n && !keys) || nw < 1 || nw > 3) return HSK_ERR_INVALID_ARG;
     *n_out = 0;
     if (n == 0) return HSK_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    enter_ctx(c);
-    int rc;
-    switch (nw) {
-    case 1: rc = stage_count_impl<1>(c, keys, n, out_entries, cap, n_out); break;
-    case 2: rc = stage_count_impl<2>(c, keys, n, out_entries, cap, n_out); break;
-    default: rc = stage_count_impl<3>(c, keys, n, out_entries, cap, n_out); break;
-    }
-    return redzone_end_call(c, rc);
+    return ApiCall(c, "hsk_stage_count_sorted").run([&] { return with_nw(nw, [&](auto w) { return stage_count_impl<decltype(w)::value>(c, keys, n, out_entries, cap, n_out); }); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -905,10 +889,10 @@ extern "C" int hsk_comm_get_unique_id(void *id128)
 extern "C" int hsk_comm_init(hsk_ctx *c, int nranks, int rank, const void *id128)
 {
     if (!c || !id128 || nranks < 1 || rank < 0 || rank >= nranks) return HSK_ERR_INVALID_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    int rc = c->comm.init(nranks, rank, id128);
-    if (rc) return fail(c, HSK_ERR_COMM, "RCCL init failed: %s", c->comm.last_error.c_str());
-    return HSK_OK;
+    return ApiCall(c, "hsk_comm_init").run([&]() -> int {
+        if (c->comm.init(nranks, rank, id128)) return fail(c, HSK_ERR_COMM, "RCCL init failed: %s", c->comm.last_error.c_str());
+        return HSK_OK;
+    });
 }
 // One-rank communicator on this ctx's GPU: every RCCL entry point the exchange uses (unique id, init, all-reduce
 // sum/max of u64, grouped send/recv of bytes to self on the second stream, destroy) with checked results.  This is
@@ -916,51 +900,52 @@ extern "C" int hsk_comm_init(hsk_ctx *c, int nranks, int rank, const void *id128
 extern "C" int hsk_comm_selftest(hsk_ctx *c)
 {
     if (!c) return HSK_ERR_INVALID_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    char id[HSK_UNIQUE_ID_BYTES];
-    if (Comm::get_unique_id(id) != 0) return fail(c, HSK_ERR_COMM, "ncclGetUniqueId failed (librccl not loadable?)");
-    Comm cm;
-    int rc = cm.init(1, 0, id, true);
-    if (rc) return fail(c, HSK_ERR_COMM, "RCCL init failed: %s", cm.last_error.c_str());
-    const size_t n = 1 << 20;
-    u64 *d_a; u8 *d_src, *d_dst;
-    DALLOC(c, d_a, u64 *, 4096 * 8); DALLOC(c, d_src, u8 *, n); DALLOC(c, d_dst, u8 *, n);
-    std::vector<u64> h(4096), h2(4096);
-    for (size_t i = 0; i < h.size(); ++i) h[i] = splitmix64(i);
-    std::vector<u8> hs(n), hd(n, 0);
-    for (size_t i = 0; i < n; ++i) hs[i] = (u8)(splitmix64(i) >> 13);
-    int out = HSK_OK;
-    do {
-        if (hipMemcpyAsync(d_a, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipMemcpyAsync(d_src, hs.data(), n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipMemsetAsync(d_dst, 0, n, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { out = fail(c, HSK_ERR_HIP, "selftest upload"); break; }
-        if ((rc = cm.check(cm.api->AllReduce(d_a, d_a, h.size(), RCCL_UINT64, RCCL_SUM, cm.comm, c->stream), "ncclAllReduce(sum)")) ||
-            (rc = cm.check(cm.api->AllReduce(d_a, d_a, h.size(), RCCL_UINT64, RCCL_MAX, cm.comm, c->stream), "ncclAllReduce(max)"))) { out = fail(c, HSK_ERR_COMM, "%s", cm.last_error.c_str()); break; }
-        if (hipMemcpyAsync(h2.data(), d_a, h.size() * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { out = fail(c, HSK_ERR_HIP, "selftest download"); break; }
-        if (h2 != h) { out = fail(c, HSK_ERR_COMM, "one-rank all-reduce changed the data"); break; }
-        // the host-vector all-reduce the pipeline uses (pinned staging, one wait) and its status element
-        cm.solo = true; cm.stage = c->comm.stage; cm.stage_bytes = c->comm.stage_bytes;
-        std::vector<u64> v(h.begin(), h.begin() + 1000);
-        if (cm.allreduce_with_status(v, RCCL_SUM, false, c->stream, c->pool) != 0 || v.size() != 1000 || !std::equal(v.begin(), v.end(), h.begin())) { out = fail(c, HSK_ERR_COMM, "staged all-reduce with status (sum) failed: %s", cm.last_error.c_str()); break; }
-        if (cm.allreduce_with_status(v, RCCL_MAX, true, c->stream, c->pool) != 1 || v.size() != 1000 || !std::equal(v.begin(), v.end(), h.begin())) { out = fail(c, HSK_ERR_COMM, "staged all-reduce with status (max, failed rank) failed: %s", cm.last_error.c_str()); break; }
-        std::vector<u64> big(h); big.resize(40000, 7);                       // larger than the staging area: unstaged path
-        std::vector<u64> big0(big);
-        if (cm.allreduce_with_status(big, RCCL_SUM, false, c->stream, c->pool) != 0 || big != big0) { out = fail(c, HSK_ERR_COMM, "unstaged all-reduce with status failed"); break; }
-        cm.solo = false;
-        // two messages to self inside one group, on the second stream (as post_exchange does per peer and array)
-        hipStream_t s = c->comm_stream;
-        if ((rc = cm.check(cm.api->GroupStart(), "ncclGroupStart")) ||
-            (rc = cm.check(cm.api->Send(d_src, n / 2, RCCL_UINT8, 0, cm.comm, s), "ncclSend")) ||
-            (rc = cm.check(cm.api->Send(d_src + n / 2, n - n / 2, RCCL_UINT8, 0, cm.comm, s), "ncclSend")) ||
-            (rc = cm.check(cm.api->Recv(d_dst, n / 2, RCCL_UINT8, 0, cm.comm, s), "ncclRecv")) ||
-            (rc = cm.check(cm.api->Recv(d_dst + n / 2, n - n / 2, RCCL_UINT8, 0, cm.comm, s), "ncclRecv")) ||
-            (rc = cm.check(cm.api->GroupEnd(), "ncclGroupEnd"))) { out = fail(c, HSK_ERR_COMM, "%s", cm.last_error.c_str()); break; }
-        if (hipMemcpyAsync(hd.data(), d_dst, n, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { out = fail(c, HSK_ERR_HIP, "selftest download"); break; }
-        if (hd != hs) { out = fail(c, HSK_ERR_COMM, "grouped send/recv to self delivered different bytes"); break; }
-    } while (0);
-    cm.destroy();
-    c->pool.release(d_a); c->pool.release(d_src); c->pool.release(d_dst);
-    return out;
+    return ApiCall(c, "hsk_comm_selftest").run([&]() -> int {
+        char id[HSK_UNIQUE_ID_BYTES];
+        if (Comm::get_unique_id(id) != 0) return fail(c, HSK_ERR_COMM, "ncclGetUniqueId failed (librccl not loadable?)");
+        const size_t n = 1 << 20;
+        u64 *d_a; u8 *d_src, *d_dst;
+        DALLOC(c, d_a, u64 *, 4096 * 8); DALLOC(c, d_src, u8 *, n); DALLOC(c, d_dst, u8 *, n);
+        Comm cm;
+        int rc = cm.init(1, 0, id, true);
+        if (rc) return fail(c, HSK_ERR_COMM, "RCCL init failed: %s", cm.last_error.c_str());
+        std::vector<u64> h(4096), h2(4096);
+        for (size_t i = 0; i < h.size(); ++i) h[i] = splitmix64(i);
+        std::vector<u8> hs(n), hd(n, 0);
+        for (size_t i = 0; i < n; ++i) hs[i] = (u8)(splitmix64(i) >> 13);
+        int out = HSK_OK;
+        do {
+            if (hipMemcpyAsync(d_a, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                hipMemcpyAsync(d_src, hs.data(), n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                hipMemsetAsync(d_dst, 0, n, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { out = fail(c, HSK_ERR_HIP, "selftest upload"); break; }
+            if ((rc = cm.check(cm.api->AllReduce(d_a, d_a, h.size(), RCCL_UINT64, RCCL_SUM, cm.comm, c->stream), "ncclAllReduce(sum)")) ||
+                (rc = cm.check(cm.api->AllReduce(d_a, d_a, h.size(), RCCL_UINT64, RCCL_MAX, cm.comm, c->stream), "ncclAllReduce(max)"))) { out = fail(c, HSK_ERR_COMM, "%s", cm.last_error.c_str()); break; }
+            if (hipMemcpyAsync(h2.data(), d_a, h.size() * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { out = fail(c, HSK_ERR_HIP, "selftest download"); break; }
+            if (h2 != h) { out = fail(c, HSK_ERR_COMM, "one-rank all-reduce changed the data"); break; }
+            // the host-vector all-reduce the pipeline uses (pinned staging, one wait) and its status element
+            cm.solo = true; cm.stage = c->comm.stage; cm.stage_bytes = c->comm.stage_bytes;
+            std::vector<u64> v(h.begin(), h.begin() + 1000);
+            if (cm.allreduce_with_status(v, RCCL_SUM, false, c->stream, c->pool) != 0 || v.size() != 1000 || !std::equal(v.begin(), v.end(), h.begin())) { out = fail(c, HSK_ERR_COMM, "staged all-reduce with status (sum) failed: %s", cm.last_error.c_str()); break; }
+            if (cm.allreduce_with_status(v, RCCL_MAX, true, c->stream, c->pool) != 1 || v.size() != 1000 || !std::equal(v.begin(), v.end(), h.begin())) { out = fail(c, HSK_ERR_COMM, "staged all-reduce with status (max, failed rank) failed: %s", cm.last_error.c_str()); break; }
+            std::vector<u64> big(h); big.resize(40000, 7);                       // larger than the staging area: unstaged path
+            std::vector<u64> big0(big);
+            if (cm.allreduce_with_status(big, RCCL_SUM, false, c->stream, c->pool) != 0 || big != big0) { out = fail(c, HSK_ERR_COMM, "unstaged all-reduce with status failed"); break; }
+            cm.solo = false;
+            // two messages to self inside one group, on the second stream (as post_exchange does per peer and array)
+            hipStream_t s = c->comm_stream;
+            if ((rc = cm.check(cm.api->GroupStart(), "ncclGroupStart")) ||
+                (rc = cm.check(cm.api->Send(d_src, n / 2, RCCL_UINT8, 0, cm.comm, s), "ncclSend")) ||
+                (rc = cm.check(cm.api->Send(d_src + n / 2, n - n / 2, RCCL_UINT8, 0, cm.comm, s), "ncclSend")) ||
+                (rc = cm.check(cm.api->Recv(d_dst, n / 2, RCCL_UINT8, 0, cm.comm, s), "ncclRecv")) ||
+                (rc = cm.check(cm.api->Recv(d_dst + n / 2, n - n / 2, RCCL_UINT8, 0, cm.comm, s), "ncclRecv")) ||
+                (rc = cm.check(cm.api->GroupEnd(), "ncclGroupEnd"))) { out = fail(c, HSK_ERR_COMM, "%s", cm.last_error.c_str()); break; }
+            if (hipMemcpyAsync(hd.data(), d_dst, n, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { out = fail(c, HSK_ERR_HIP, "selftest download"); break; }
+            if (hd != hs) { out = fail(c, HSK_ERR_COMM, "grouped send/recv to self delivered different bytes"); break; }
+        } while (0);
+        cm.destroy();
+        c->pool.release(d_a); c->pool.release(d_src); c->pool.release(d_dst);
+        return out;
+    });
 }
 
 extern "C" int hsk_comm_destroy(hsk_ctx *c)
@@ -978,19 +963,19 @@ static int synth_reads_impl(hsk_ctx *c, uint64_t genome_len, uint32_t read_len, 
 extern "C" int hsk_synth_reads(hsk_ctx *c, uint64_t genome_len, uint32_t read_len, uint64_t nreads, uint64_t seed, uint64_t first_read,
                                void **d_packed, uint64_t *packed_bytes, void **d_off, void **d_len)
 {
-    return synth_reads_impl(c, genome_len, read_len, nreads, seed, first_read, 0.0, d_packed, packed_bytes, d_off, d_len);
+    if (!c) return HSK_ERR_INVALID_ARG;
+    return ApiCall(c, "hsk_synth_reads").run([&] { return synth_reads_impl(c, genome_len, read_len, nreads, seed, first_read, 0.0, d_packed, packed_bytes, d_off, d_len); });
 }
 extern "C" int hsk_synth_reads_err(hsk_ctx *c, uint64_t genome_len, uint32_t read_len, uint64_t nreads, uint64_t seed, uint64_t first_read, double error_rate,
                                    void **d_packed, uint64_t *packed_bytes, void **d_off, void **d_len)
 {
-    if (!(error_rate >= 0.0 && error_rate <= 0.75)) return HSK_ERR_INVALID_ARG;      // 0.75: every base uniform over ACGT whatever the genome says
-    return synth_reads_impl(c, genome_len, read_len, nreads, seed, first_read, error_rate, d_packed, packed_bytes, d_off, d_len);
+    if (!c || !(error_rate >= 0.0 && error_rate <= 0.75)) return HSK_ERR_INVALID_ARG;      // 0.75: every base uniform over ACGT whatever the genome says
+    return ApiCall(c, "hsk_synth_reads_err").run([&] { return synth_reads_impl(c, genome_len, read_len, nreads, seed, first_read, error_rate, d_packed, packed_bytes, d_off, d_len); });
 }
 static int synth_reads_impl(hsk_ctx *c, uint64_t genome_len, uint32_t read_len, uint64_t nreads, uint64_t seed, uint64_t first_read, double error_rate,
                             void **d_packed, uint64_t *packed_bytes, void **d_off, void **d_len)
 {
-    if (!c || !d_packed || !packed_bytes || !d_off || !d_len || read_len == 0 || genome_len < read_len) return HSK_ERR_INVALID_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (!d_packed || !packed_bytes || !d_off || !d_len || read_len == 0 || genome_len < read_len) return HSK_ERR_INVALID_ARG;
     const u64 nwords = (genome_len + 31) / 32;
     const u32 nb = (read_len + 3) / 4;
     const u64 bytes = nreads * nb;
@@ -1016,37 +1001,38 @@ extern "C" int hsk_pack_fasta(hsk_ctx *c, const char *text, uint64_t text_bytes,
                               void **d_packed, uint64_t *packed_bytes, void **d_off, void **d_len)
 {
     if (!c || !d_packed || !packed_bytes || !d_off || !d_len || (nrec && (!text || !rec_pos || !rec_len || !line_bases || !line_width))) return HSK_ERR_INVALID_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
     *d_packed = nullptr; *d_off = nullptr; *d_len = nullptr; *packed_bytes = 0;
-    uint64_t total = 0;
-    for (uint64_t r = 0; r < nrec; ++r) {
-        const uint64_t nl = line_bases[r] ? ((uint64_t)rec_len[r] + line_bases[r] - 1) / line_bases[r] : 0;
-        const uint64_t last = rec_len[r] ? rec_pos[r] + (line_bases[r] ? (nl - 1) * (uint64_t)line_width[r] + ((uint64_t)rec_len[r] - (nl - 1) * line_bases[r]) : rec_len[r]) : rec_pos[r];
-        if (last > text_bytes) return fail(c, HSK_ERR_INVALID_ARG, "record %llu extends past the text", (unsigned long long)r);
-        if (line_bases[r] && line_width[r] < line_bases[r]) return fail(c, HSK_ERR_INVALID_ARG, "record %llu: line width < bases per line", (unsigned long long)r);
-        total += ((uint64_t)rec_len[r] + 3) / 4;
-    }
-    u8 *d_text, *pk; u64 *d_pos, *roff; u32 *rlen, *d_lb, *d_lw;
-    DALLOC(c, pk, u8 *, total + 64);
-    DALLOC(c, roff, u64 *, (nrec + 1) * 8);
-    DALLOC(c, rlen, u32 *, (nrec + 1) * 4);
-    if (nrec) {
-        DALLOC(c, d_text, u8 *, text_bytes + 64);
-        DALLOC(c, d_pos, u64 *, nrec * 8); DALLOC(c, d_lb, u32 *, nrec * 4); DALLOC(c, d_lw, u32 *, nrec * 4);
-        HIPCHK(c, hipMemcpyAsync(d_text, text, text_bytes, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_pos, rec_pos, nrec * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(rlen, rec_len, nrec * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_lb, line_bases, nrec * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_lw, line_width, nrec * 4, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(pack_fasta_offsets_kernel, dim3(1), dim3(256), 0, c->stream, rlen, nrec, roff);
-        if (total) hipLaunchKernelGGL(pack_fasta_kernel, dim3((u32)std::min<u64>((total + 255) / 256, 1u << 20)), dim3(256), 0, c->stream,
-                                      d_text, text_bytes, d_pos, rlen, d_lb, d_lw, roff, nrec, total, pk);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->pool.release(d_text); c->pool.release(d_pos); c->pool.release(d_lb); c->pool.release(d_lw);
-    }
-    *d_packed = pk; *packed_bytes = total; *d_off = roff; *d_len = rlen;
-    return HSK_OK;
+    return ApiCall(c, "hsk_pack_fasta").run([&]() -> int {
+        uint64_t total = 0;
+        for (uint64_t r = 0; r < nrec; ++r) {
+            const uint64_t nl = line_bases[r] ? ((uint64_t)rec_len[r] + line_bases[r] - 1) / line_bases[r] : 0;
+            const uint64_t last = rec_len[r] ? rec_pos[r] + (line_bases[r] ? (nl - 1) * (uint64_t)line_width[r] + ((uint64_t)rec_len[r] - (nl - 1) * line_bases[r]) : rec_len[r]) : rec_pos[r];
+            if (last > text_bytes) return fail(c, HSK_ERR_INVALID_ARG, "record %llu extends past the text", (unsigned long long)r);
+            if (line_bases[r] && line_width[r] < line_bases[r]) return fail(c, HSK_ERR_INVALID_ARG, "record %llu: line width < bases per line", (unsigned long long)r);
+            total += ((uint64_t)rec_len[r] + 3) / 4;
+        }
+        u8 *d_text, *pk; u64 *d_pos, *roff; u32 *rlen, *d_lb, *d_lw;
+        DALLOC(c, pk, u8 *, total + 64);
+        DALLOC(c, roff, u64 *, (nrec + 1) * 8);
+        DALLOC(c, rlen, u32 *, (nrec + 1) * 4);
+        if (nrec) {
+            DALLOC(c, d_text, u8 *, text_bytes + 64);
+            DALLOC(c, d_pos, u64 *, nrec * 8); DALLOC(c, d_lb, u32 *, nrec * 4); DALLOC(c, d_lw, u32 *, nrec * 4);
+            HIPCHK(c, hipMemcpyAsync(d_text, text, text_bytes, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(d_pos, rec_pos, nrec * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(rlen, rec_len, nrec * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(d_lb, line_bases, nrec * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(d_lw, line_width, nrec * 4, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(pack_fasta_offsets_kernel, dim3(1), dim3(256), 0, c->stream, rlen, nrec, roff);
+            if (total) hipLaunchKernelGGL(pack_fasta_kernel, dim3((u32)std::min<u64>((total + 255) / 256, 1u << 20)), dim3(256), 0, c->stream,
+                                          d_text, text_bytes, d_pos, rlen, d_lb, d_lw, roff, nrec, total, pk);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            c->pool.release(d_text); c->pool.release(d_pos); c->pool.release(d_lb); c->pool.release(d_lw);
+        }
+        *d_packed = pk; *packed_bytes = total; *d_off = roff; *d_len = rlen;
+        return HSK_OK;
+    });
 }
 
 extern "C" int hsk_format_entries(hsk_ctx *c, const void *entries, uint64_t n, int32_t nw, int32_t on_device, char *text, uint64_t capacity, uint64_t *nbytes)
@@ -1054,30 +1040,30 @@ extern "C" int hsk_format_entries(hsk_ctx *c, const void *entries, uint64_t n, i
     if (!c || !nbytes || (n && !entries) || nw < 1 || nw > 3 || nw != c->nw) return HSK_ERR_INVALID_ARG;
     *nbytes = 0;
     if (n == 0) return HSK_OK;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    const size_t eb = (size_t)n * (nw + 1) * 8;
-    u64 *d_e = (u64 *)entries, *d_own = nullptr;
-    if (!on_device) { DALLOC(c, d_own, u64 *, eb); HIPCHK(c, hipMemcpyAsync(d_own, entries, eb, hipMemcpyHostToDevice, c->stream)); d_e = d_own; }
-    const u64 ntiles = (n + FMT_THREADS - 1) / FMT_THREADS;
-    u64 *d_tile, *d_total;
-    DALLOC(c, d_tile, u64 *, ntiles * 8 + 64); DALLOC(c, d_total, u64 *, 256);
-    hipLaunchKernelGGL(format_entries_kernel<false>, dim3((u32)ntiles), dim3(FMT_THREADS), 0, c->stream, d_e, n, nw, c->cfg.kmer_size, d_tile, (char *)nullptr);
-    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_tile, ntiles, d_total);
-    u64 *tot = (u64 *)((char *)c->pinned + c->pinned_bytes - 128);
-    HIPCHK(c, hipMemcpyAsync(tot, d_total, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *nbytes = tot[0];
-    int rc = HSK_OK;
-    if (text && capacity >= tot[0]) {
-        char *d_text; DALLOC(c, d_text, char *, tot[0] + 64);
-        hipLaunchKernelGGL(format_entries_kernel<true>, dim3((u32)ntiles), dim3(FMT_THREADS), 0, c->stream, d_e, n, nw, c->cfg.kmer_size, d_tile, d_text);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(text, d_text, tot[0], hipMemcpyDeviceToHost, c->stream));
+    return ApiCall(c, "hsk_format_entries").run([&]() -> int {
+        const size_t eb = (size_t)n * (nw + 1) * 8;
+        u64 *d_e = (u64 *)entries, *d_own = nullptr;
+        if (!on_device) { DALLOC(c, d_own, u64 *, eb); HIPCHK(c, hipMemcpyAsync(d_own, entries, eb, hipMemcpyHostToDevice, c->stream)); d_e = d_own; }
+        const u64 ntiles = (n + FMT_THREADS - 1) / FMT_THREADS;
+        u64 *d_tile, *d_total;
+        DALLOC(c, d_tile, u64 *, ntiles * 8 + 64); DALLOC(c, d_total, u64 *, 256);
+        hipLaunchKernelGGL(format_entries_kernel<false>, dim3((u32)ntiles), dim3(FMT_THREADS), 0, c->stream, d_e, n, nw, c->cfg.kmer_size, d_tile, (char *)nullptr);
+        hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_tile, ntiles, d_total);
+        u64 *tot = (u64 *)((char *)c->pinned + c->pinned_bytes - 128);
+        HIPCHK(c, hipMemcpyAsync(tot, d_total, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->pool.release(d_text);
-    } else if (text || capacity) rc = fail(c, HSK_ERR_INVALID_ARG, "text capacity %llu < %llu", (unsigned long long)capacity, (unsigned long long)tot[0]);
-    c->pool.release(d_tile); c->pool.release(d_total); c->pool.release(d_own);
-    return rc;
+        *nbytes = tot[0];
+        if (text && capacity >= tot[0]) {
+            char *d_text; DALLOC(c, d_text, char *, tot[0] + 64);
+            hipLaunchKernelGGL(format_entries_kernel<true>, dim3((u32)ntiles), dim3(FMT_THREADS), 0, c->stream, d_e, n, nw, c->cfg.kmer_size, d_tile, d_text);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(text, d_text, tot[0], hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            c->pool.release(d_text);
+        } else if (text || capacity) return fail(c, HSK_ERR_INVALID_ARG, "text capacity %llu < %llu", (unsigned long long)capacity, (unsigned long long)tot[0]);
+        c->pool.release(d_tile); c->pool.release(d_total); c->pool.release(d_own);
+        return HSK_OK;
+    });
 }
 
 extern "C" int hsk_synth_free(hsk_ctx *c, void *d_packed, void *d_off, void *d_len)
@@ -1090,9 +1076,11 @@ extern "C" int hsk_synth_free(hsk_ctx *c, void *d_packed, void *d_off, void *d_l
 extern "C" int hsk_memcpy_d2h(hsk_ctx *c, void *dst, const void *d_src, uint64_t bytes)
 {
     if (!c || !dst || !d_src) return HSK_ERR_INVALID_ARG;
-    HIPCHK(c, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return HSK_OK;
+    return ApiCall(c, "hsk_memcpy_d2h").run([&]() -> int {
+        HIPCHK(c, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return HSK_OK;
+    });
 }
 
 // The yardstick for "fraction of what HBM delivers": a plain copy, 16 bytes per lane, every workgroup streaming its own
@@ -1113,30 +1101,31 @@ __global__ __launch_bounds__(256) void copy_peak_kernel(const uint4 *__restrict_
 extern "C" int hsk_copy_peak(hsk_ctx *c, uint64_t bytes, int iters, double *gbs)
 {
     if (!c || !gbs || bytes < (1u << 20) || iters < 1) return HSK_ERR_INVALID_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
     *gbs = 0;
-    const u64 n16 = bytes / 16;
-    uint4 *a, *b;
-    DALLOC(c, a, uint4 *, n16 * 16); DALLOC(c, b, uint4 *, n16 * 16);
-    HIPCHK(c, hipMemsetAsync(a, 0x5a, n16 * 16, c->stream));
-    HIPCHK(c, hipMemsetAsync(b, 0, n16 * 16, c->stream));
-    hipEvent_t e0 = ev_get(c), e1 = ev_get(c);
-    double best = 0;
-    for (int grid : {2048, 4096, 8192, 16384}) {
-        for (int it = 0; it < iters; ++it) {
-            (void)hipEventRecord(e0, c->stream);
-            hipLaunchKernelGGL(copy_peak_kernel, dim3(grid), dim3(256), 0, c->stream, a, b, n16);
-            (void)hipEventRecord(e1, c->stream);
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess && ms > 0) best = std::max(best, 2.0 * (double)n16 * 16 / (ms * 1e-3) / 1e9);
+    return ApiCall(c, "hsk_copy_peak").run([&]() -> int {
+        const u64 n16 = bytes / 16;
+        uint4 *a, *b;
+        DALLOC(c, a, uint4 *, n16 * 16); DALLOC(c, b, uint4 *, n16 * 16);
+        HIPCHK(c, hipMemsetAsync(a, 0x5a, n16 * 16, c->stream));
+        HIPCHK(c, hipMemsetAsync(b, 0, n16 * 16, c->stream));
+        EvList ev(c);
+        hipEvent_t e0 = ev.get(), e1 = ev.get();
+        double best = 0;
+        for (int grid : {2048, 4096, 8192, 16384}) {
+            for (int it = 0; it < iters; ++it) {
+                (void)hipEventRecord(e0, c->stream);
+                hipLaunchKernelGGL(copy_peak_kernel, dim3(grid), dim3(256), 0, c->stream, a, b, n16);
+                (void)hipEventRecord(e1, c->stream);
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                float ms = 0;
+                if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess && ms > 0) best = std::max(best, 2.0 * (double)n16 * 16 / (ms * 1e-3) / 1e9);
+            }
         }
-    }
-    ev_put(c, e0); ev_put(c, e1);
-    HIPCHK(c, hipGetLastError());
-    c->pool.release(a); c->pool.release(b);
-    *gbs = best;
-    return HSK_OK;
+        HIPCHK(c, hipGetLastError());
+        c->pool.release(a); c->pool.release(b);
+        *gbs = best;
+        return HSK_OK;
+    });
 }
 
 // Experiment (tools/parse_overlap.py; not part of include/hsk.h): can the placement of one set of reads run BESIDE the minimizer scan of
@@ -1146,53 +1135,52 @@ extern "C" int hsk_debug_parse_overlap(hsk_ctx *c, const void *d_packed, uint64_
                                        uint32_t blocks, double *out_ms)
 {
     if (!c || !out_ms) return HSK_ERR_INVALID_ARG;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    enter_ctx(c);
-    u64 *roff; DALLOC(c, roff, u64 *, (nreads + 1) * 8);
-    HIPCHK(c, hipMemcpyAsync(roff, d_off, nreads * 8, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(roff + nreads, &packed_bytes, 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const u32 ntasks = c->cfg.ntasks ? (u32)c->cfg.ntasks : 40;
-    std::vector<u32> order(ntasks); for (u32 t = 0; t < ntasks; ++t) order[t] = t;
-    hipEvent_t e[6]; for (auto &x : e) x = ev_get(c);
-    auto ms = [&](hipEvent_t a, hipEvent_t b) { float f = 0; (void)hipEventElapsedTime(&f, a, b); return (double)f; };
-    int rc;
-    ParseJob j1, j2, j3; SupermerStore st1, st2;
-    (void)hipEventRecord(e[0], c->stream);
-    rc = parse_count(c, (const u8 *)d_packed, packed_bytes, roff, (const u32 *)d_len, nreads, 0, ntasks, j1); if (rc) return rc;
-    (void)hipEventRecord(e[1], c->stream);
-    rc = parse_place(c, j1, order, st1); if (rc) return rc;
-    (void)hipEventRecord(e[2], c->stream);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    out_ms[0] = ms(e[0], e[1]); out_ms[2] = ms(e[1], e[2]);
-    c->scan_blocks = blocks;
-    (void)hipEventRecord(e[0], c->stream);
-    rc = parse_count(c, (const u8 *)d_packed, packed_bytes, roff, (const u32 *)d_len, nreads, 0, ntasks, j2);
-    (void)hipEventRecord(e[1], c->stream);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (rc) { c->scan_blocks = 0; return rc; }
-    out_ms[1] = ms(e[0], e[1]);
-    // both at once: the placement of j1's records (again, into a second store) on the second stream, the scan of j3 on the main stream
-    (void)hipEventRecord(e[0], c->stream);
-    HIPCHK(c, hipStreamWaitEvent(c->comm_stream, e[0], 0));
-    hipStream_t main_s = c->stream;
-    c->stream = c->comm_stream;
-    (void)hipEventRecord(e[3], c->stream);
-    rc = parse_place(c, j1, order, st2);
-    (void)hipEventRecord(e[4], c->stream);
-    c->stream = main_s;
-    if (rc) { c->scan_blocks = 0; return rc; }
-    rc = parse_count(c, (const u8 *)d_packed, packed_bytes, roff, (const u32 *)d_len, nreads, 0, ntasks, j3);
-    (void)hipEventRecord(e[1], c->stream);
-    c->scan_blocks = 0;
-    HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->comm_stream));
-    if (rc) return rc;
-    out_ms[4] = ms(e[0], e[1]); out_ms[5] = ms(e[3], e[4]);
-    out_ms[3] = std::max(ms(e[0], e[1]), ms(e[0], e[4]));
-    parse_release(c, j1); parse_release(c, j2); parse_release(c, j3); free_store(c, st1); free_store(c, st2);
-    c->pool.release(roff);
-    for (auto x : e) ev_put(c, x);
-    return HSK_OK;
+    return ApiCall(c, "hsk_debug_parse_overlap").run([&]() -> int {
+        u64 *roff; DALLOC(c, roff, u64 *, (nreads + 1) * 8);
+        HIPCHK(c, hipMemcpyAsync(roff, d_off, nreads * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(roff + nreads, &packed_bytes, 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        const u32 ntasks = c->cfg.ntasks ? (u32)c->cfg.ntasks : 40;
+        std::vector<u32> order(ntasks); for (u32 t = 0; t < ntasks; ++t) order[t] = t;
+        EvList ev(c);
+        hipEvent_t e[6]; for (auto &x : e) x = ev.get();
+        auto ms = [&](hipEvent_t a, hipEvent_t b) { float f = 0; (void)hipEventElapsedTime(&f, a, b); return (double)f; };
+        int rc;
+        ParseJob j1, j2, j3; SupermerStore st1, st2;
+        (void)hipEventRecord(e[0], c->stream);
+        rc = parse_count(c, (const u8 *)d_packed, packed_bytes, roff, (const u32 *)d_len, nreads, 0, ntasks, j1); if (rc) return rc;
+        (void)hipEventRecord(e[1], c->stream);
+        rc = parse_place(c, j1, order, st1); if (rc) return rc;
+        (void)hipEventRecord(e[2], c->stream);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        out_ms[0] = ms(e[0], e[1]); out_ms[2] = ms(e[1], e[2]);
+        c->call.scan_blocks = blocks;
+        (void)hipEventRecord(e[0], c->stream);
+        rc = parse_count(c, (const u8 *)d_packed, packed_bytes, roff, (const u32 *)d_len, nreads, 0, ntasks, j2);
+        (void)hipEventRecord(e[1], c->stream);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (rc) return rc;
+        out_ms[1] = ms(e[0], e[1]);
+        // both at once: the placement of j1's records (again, into a second store) on the second stream, the scan of j3 on the main stream
+        (void)hipEventRecord(e[0], c->stream);
+        HIPCHK(c, hipStreamWaitEvent(c->comm_stream, e[0], 0));
+        hipStream_t main_s = c->stream;
+        c->stream = c->comm_stream;
+        (void)hipEventRecord(e[3], c->stream);
+        rc = parse_place(c, j1, order, st2);
+        (void)hipEventRecord(e[4], c->stream);
+        c->stream = main_s;
+        if (rc) return rc;
+        rc = parse_count(c, (const u8 *)d_packed, packed_bytes, roff, (const u32 *)d_len, nreads, 0, ntasks, j3);
+        (void)hipEventRecord(e[1], c->stream);
+        HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, hipStreamSynchronize(c->comm_stream));
+        if (rc) return rc;
+        out_ms[4] = ms(e[0], e[1]); out_ms[5] = ms(e[3], e[4]);
+        out_ms[3] = std::max(ms(e[0], e[1]), ms(e[0], e[4]));
+        parse_release(c, j1); parse_release(c, j2); parse_release(c, j3); free_store(c, st1); free_store(c, st2);
+        c->pool.release(roff);
+        return HSK_OK;
+    });
 }
 
 // diagnostic build only: phase clock sums of the onesweep kernel (zeros in the product build)

@@ -83,6 +83,38 @@ struct Tuning {
     long long get(const char *name, long long dflt) const { auto it = v.find(name); return it == v.end() ? dflt : it->second; }
 };
 
+// What describes only the call that is running: reset by value when an entry point opens its scope and when it closes it (ApiCall,
+// hsk_api.hip), so that nothing of one call reaches the next.  What a call learns for the calls after it stays in hsk_ctx.
+struct CallState {
+    // the plan
+    PlanEstimate est;                  // this call's estimate (estimate_plan); est.valid decides instead of combine_off / agg_off / agg_first_cap
+    int plan_attempt = 0;              // dispatch_pipeline: how often this call has been started again (HSK_RETRY_PLAN); bounded there
+    // combining extraction (hsk_combine.h): combine_now = this call lays the store out for it (one GPU, one-word keys, no payload)
+    bool combine_now = false;
+    bool item_mode_now = false;        // ... on ONE GPU: the store holds items (several ranks: byte runs + minimizer bits, items built by the owners)
+    u32 vt_shift = 0;                  // this call's parse splits every task into 1 << vt_shift virtual tasks (combining extraction)
+    bool combine_left_now = false;     // this call has left the combining extraction (binding for the attempts that follow, whatever the estimate said)
+    bool combine_veto = false;         // this attempt's store turned out to be no use to the combining extraction (too few tasks for a batch ...): the next attempt goes without it
+    bool pair_cap_full = false;        // this call's pair buffers ran over once: full size for the attempts that follow
+    u32 drop_mask_now = 0;             // bit 0 / 1 = the all-A / all-C k-mer has more than U copies inside the sample alone, the scan leaves its instances out
+    u64 dropped_now = 0;               // ... and how many it left out (they count as k-mers of the input: hsk_result::total_kmers)
+    // the input
+    const u8 *zc_src = nullptr;        // hsk_count() with pinned input: device view of the caller's packed reads (scan_kernel reads them in place)
+    const u8 *h2d_src = nullptr;       // hsk_count() with pinned input, slab ingest: the caller's packed reads (host pointer); parse_count copies them slab by
+    int h2d_slabs = 0;                 // slab (DMA, d2h_stream) and hashes slab s while slab s + 2 is on the link
+    // hsk_count() with derived read offsets: host threads compare the caller's offsets with the back-to-back layout while the GPU
+    // scans (result collected with the task totals); roff_host / roff_given: the caller's array and a device buffer for it, used
+    // only when the comparison fails (a buffer with gaps)
+    std::future<bool> roff_check;
+    bool roff_bad = false;             // ... its verdict, when somebody other than parse_count collected it (parse_ingest_pipelined)
+    const uint32_t *rlen_host = nullptr;   // the read lengths were generated on the device from a sample (all reads equally long): the caller's array,
+                                           // copied after all if the host threads find a read of another length (same fallback as a buffer with gaps)
+    const uint64_t *roff_host = nullptr;
+    u64 *roff_given = nullptr;
+    bool index_unchecked = false;      // hsk_count(): the read index is validated on the device (index_check_kernel), the verdict is read with the task totals
+    u32 scan_blocks = 0;               // experiments (hsk_debug_parse_overlap): workgroups of the parse kernels instead of 1024
+};
+
 struct hsk_ctx {
     hsk_config cfg;
     Tuning tune;
@@ -100,20 +132,7 @@ struct hsk_ctx {
     void *pinned = nullptr; size_t pinned_bytes = 0;     // small staging area (histograms, totals)
     u32 *d_err = nullptr;
     Comm comm;
-    const u8 *zc_src = nullptr;        // hsk_count() with pinned input: device view of the caller's packed reads (scan_kernel reads them in place)
-    const u8 *h2d_src = nullptr;       // hsk_count() with pinned input, slab ingest: the caller's packed reads (host pointer); parse_count copies them slab by
-    int h2d_slabs = 0;
-    u32 scan_blocks = 0;               // experiments (hsk_debug_parse_overlap): workgroups of the parse kernels instead of 1024                 // slab (DMA, d2h_stream) and hashes slab s while slab s + 2 is on the link
-    // hsk_count() with derived read offsets: host threads compare the caller's offsets with the back-to-back layout while the GPU
-    // scans (result collected with the task totals); roff_host / roff_given: the caller's array and a device buffer for it, used
-    // only when the comparison fails (a buffer with gaps)
-    std::future<bool> roff_check;
-    bool roff_bad = false;
-    const uint32_t *rlen_host = nullptr;   // the read lengths were generated on the device from a sample (all reads equally long): the caller's array,
-                                           // copied after all if the host threads find a read of another length (same fallback as a buffer with gaps)             // ... its verdict, when somebody other than parse_count collected it (parse_ingest_pipelined)
-    const uint64_t *roff_host = nullptr;
-    u64 *roff_given = nullptr;
-    bool index_unchecked = false;      // hsk_count(): the read index is validated on the device (index_check_kernel), the verdict is read with the task totals
+    CallState call;                    // the running call's
     int agg_first_cap = 10;            // log2 of the hash table the next aggregation starts with (AG_LOG2CAP_*): follows the fullest bin of the
                                        // previous batch, so that reads with errors / low coverage do not pay for a table they overflow anyway
     bool xcd_batch_ok = true;          // hsk_init's census saw workgroups on all eight XCC ids (see xcc_census_kernel)
@@ -122,34 +141,24 @@ struct hsk_ctx {
     bool agg_off_wide = false;         // the same for multi-word keys and EXTENSION: no prefix passes + tables, the full-width passes and the two-pass counter
     bool agg_off = false;              // one-word keys without payload: the input has too few copies per k-mer for the LDS aggregation (most bins of a
                                        // batch overflowed the 2048-slot table): batches take four prefix passes + the tile finish from here on
-    // combining extraction (hsk_combine.h): combine_now = this call lays the store out for it (one GPU, one-word keys, no payload);
     // combine_off = the input kept too many pairs per k-mer (or a bin beat the weighted finish): the instance path until another look
-    bool combine_now = false, combine_off = false; int combine_off_calls = 0;
+    bool combine_off = false; int combine_off_calls = 0;
     // ... another look after combine_off_period calls: 8, and twice as many every time the look finds the same kind of input again (up
     // to 64: a look costs the call ~2 x, reads with errors should not pay that every eighth call); back to 8 once a call has gone through
     int combine_off_period = 8, combine_good_calls = 0;
-    bool combine_left_now = false;     // ... during THIS call (binding for the attempts that follow, whatever the estimate said)
-    u32 drop_mask_now = 0;             // this call: bit 0 / 1 = the all-A / all-C k-mer has more than U copies inside the sample alone, the scan leaves its instances out
-    u64 dropped_now = 0;               // ... and how many it left out (they count as k-mers of the input: hsk_result::total_kmers)
-    void leave_combine() { combine_left_now = true; combine_off_period = combine_good_calls ? 8 : std::min(combine_off_period * 2, 64); combine_good_calls = 0; combine_off = true; combine_off_calls = 0; }
-    bool item_mode_now = false;        // ... on ONE GPU: the store holds items (several ranks: byte runs + minimizer bits, items built by the owners)
-    u32 vt_shift = 0;                  // this call's parse splits every task into 1 << vt_shift virtual tasks (combining extraction)
+    void leave_combine() { call.combine_left_now = true; combine_off_period = combine_good_calls ? 8 : std::min(combine_off_period * 2, 64); combine_good_calls = 0; combine_off = true; combine_off_calls = 0; }
     int combine_prefix_floor = 0;      // ... never below this again (set when a bin beat the last table with fewer bits)
     int combine_prefix = 0;            // key bits of the weighted finish's bins the next batch is planned with (0: the default; follows the pairs per task)
-    bool combine_veto = false;         // this call's store turned out to be no use to the combining extraction (too few tasks for a batch ...): the call again, without it
-    bool pair_cap_full = false;        // this call's pair buffers ran over once: full size for the attempt that follows (dispatch_pipeline clears it with the call)
-    PlanEstimate est;                  // this call's estimate (estimate_plan); est.valid decides instead of combine_off / agg_off / agg_first_cap
     double est_bias = 1.0;             // pairs per k-mer the combining extraction really produced / what the estimate promised, when a call had to leave the plan after all
     // a call that followed its estimate into the combining extraction and had to start again: estimates like this one are not believed again on this context
-    void distrust_estimate(double ratio) { if (est.valid && est.distinct_per_kmer > 0) est_bias = std::max(est_bias, 1.05 / (est.distinct_per_kmer * ratio)); }
-    int plan_attempt = 0;              // dispatch_pipeline: how often this call has been started again (HSK_RETRY_PLAN); bounded there
+    void distrust_estimate(double ratio) { const PlanEstimate &est = call.est; if (est.valid && est.distinct_per_kmer > 0) est_bias = std::max(est_bias, 1.05 / (est.distinct_per_kmer * ratio)); }
     bool forbid_long_way = false;      // heavy-hitter pre-aggregation: a task the aggregating finish cannot handle is reported, not redone
 };
 
 // HSK_FLAG_NO_AGGREGATION / HSK_FLAG_FULL_SORT of the context whose call is running on this thread (set by the counting entry
 // points): the plan switches below (agg_enabled, hybrid_enabled, finish_enabled) are asked in places that have no context at hand
 static thread_local int g_plan_flags = 0;
-// ... and its tuning table (same lifetime: set by every entry point that takes a context)
+// ... and its tuning table (same lifetime: set when an entry point opens its scope, cleared when it closes it)
 static thread_local const Tuning *g_tune = nullptr;
 static long long tune(const char *name, long long dflt) { return g_tune ? g_tune->get(name, dflt) : dflt; }
 static void enter_ctx(hsk_ctx *c) { g_plan_flags = c->cfg.flags; g_tune = &c->tune; }

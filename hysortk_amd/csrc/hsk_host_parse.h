@@ -78,10 +78,10 @@ static ParseArgs make_parse_args(hsk_ctx *c, const u8 *d_packed, u64 packed_byte
 {
     ParseArgs a; memset(&a, 0, sizeof a);
     a.packed = d_packed; a.packed_bytes = packed_bytes; a.roff = d_roff; a.rlen = d_rlen; a.nreads = nreads;
-    a.k = c->cfg.kmer_size; a.m = c->cfg.minimizer_size; a.ntasks = ntasks; a.fm = make_fastmod(ntasks >> c->vt_shift); a.vt_shift = c->vt_shift;      // (virtual tasks: `ntasks` counts them)
+    a.k = c->cfg.kmer_size; a.m = c->cfg.minimizer_size; a.ntasks = ntasks; a.fm = make_fastmod(ntasks >> c->call.vt_shift); a.vt_shift = c->call.vt_shift;      // (virtual tasks: `ntasks` counts them)
     a.item_maxk = (u32)std::max(1, std::min(16, 61 - c->cfg.kmer_size));
     a.ntiles = (packed_bytes * 4 + PARSE_TILE - 1) / PARSE_TILE;
-    u32 nblocks = (u32)std::min<u64>(a.ntiles, c->scan_blocks ? c->scan_blocks : 1024);
+    u32 nblocks = (u32)std::min<u64>(a.ntiles, c->call.scan_blocks ? c->call.scan_blocks : 1024);
     a.rid_base = rid_base;
     if (nslabs > 1 && a.ntiles >= (u64)nblocks * nslabs) {
         const u64 per_slab = (a.ntiles + nslabs - 1) / nslabs;
@@ -164,7 +164,7 @@ struct ParseJob {
     u64 *d_blk_cnt = nullptr; u16 *d_dest_cache = nullptr; u32 *d_tile_rec = nullptr, *d_tile_nrec = nullptr, *d_overflow = nullptr;
     u32 *d_tile_r0 = nullptr;     // EXTENSION: first read of every tile (hint for the (pos, rid) lookup)
     u32 *d_tile_sub = nullptr;    // combining extraction: minimizer bits of every record
-    unsigned long long *d_dropped = nullptr;      // scan_kernel<.., DROP>: positions left out (hsk_ctx::drop_mask_now)
+    unsigned long long *d_dropped = nullptr;      // scan_kernel<.., DROP>: positions left out (CallState::drop_mask_now)
     ScanBins bins;                // ... or no records at all: scan_kernel places the items itself
     std::vector<u64> task_tot;    // [ntasks][3] supermers, bytes, kmers of this rank
 };
@@ -229,9 +229,9 @@ static int parse_count(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u
     j.empty = false;
     j.fast = parse_fast_enabled() && c->cfg.minimizer_size <= SCAN_MAX_M;
     // slab ingest (hsk_count() from pinned memory): only the fast path hashes slab by slab; everything else wants the reads in HBM first
-    const u8 *h2d_src = c->h2d_src; c->h2d_src = nullptr;
+    const u8 *h2d_src = c->call.h2d_src; c->call.h2d_src = nullptr;
     if (h2d_src && !j.fast) { HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed), h2d_src, packed_bytes, hipMemcpyHostToDevice, c->stream)); h2d_src = nullptr; }
-    j.a = make_parse_args(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, ntasks, &j.nblocks, h2d_src ? (u32)c->h2d_slabs : 1);
+    j.a = make_parse_args(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, ntasks, &j.nblocks, h2d_src ? (u32)c->call.h2d_slabs : 1);
     ParseArgs &a = j.a;
     if (h2d_src && a.nslabs <= 1) { HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed), h2d_src, packed_bytes, hipMemcpyHostToDevice, c->stream)); h2d_src = nullptr; }   // (too small for slabs)
     DALLOC(c, j.d_blk_cnt, u64 *, (size_t)1024 * ntasks * 3 * 8);
@@ -242,7 +242,7 @@ static int parse_count(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u
     if (j.fast) {
         a.rec_cap = parse_rec_cap(c->cfg.kmer_size - c->cfg.minimizer_size + 1);
         a.place_group = std::max<u32>(1, std::min<u32>(16, PLACE_MAX_REC / a.rec_cap));
-        const bool bins = c->item_mode_now && c->combine_now && scan_place_enabled() && a.rec_cap <= PLACE_ITEM_REC;
+        const bool bins = c->call.item_mode_now && c->call.combine_now && scan_place_enabled() && a.rec_cap <= PLACE_ITEM_REC;
         DALLOC(c, j.d_overflow, u32 *, 256);
         HIPCHK(c, hipMemsetAsync(j.d_overflow, 0, 4, c->stream));
         a.overflow = j.d_overflow;
@@ -255,13 +255,13 @@ static int parse_count(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u
             a.tile_rec = j.d_tile_rec; a.tile_nrec = j.d_tile_nrec;
         }
         if (c->cfg.extension && nreads < (1ULL << 32)) { DALLOC(c, j.d_tile_r0, u32 *, (size_t)a.ntiles * 4 + 64); a.tile_r0 = j.d_tile_r0; }
-        if (!bins && c->combine_now && a.rec_cap <= PLACE_ITEM_REC) { DALLOC(c, j.d_tile_sub, u32 *, (size_t)a.ntiles * a.rec_cap * 4 + 64); a.tile_sub = j.d_tile_sub; }
+        if (!bins && c->call.combine_now && a.rec_cap <= PLACE_ITEM_REC) { DALLOC(c, j.d_tile_sub, u32 *, (size_t)a.ntiles * a.rec_cap * 4 + 64); a.tile_sub = j.d_tile_sub; }
         const bool profile = (c->cfg.flags & HSK_FLAG_PROFILE) != 0;
-        if (c->zc_src) { a.packed = c->zc_src; a.packed_copy = (u32 *)const_cast<u8 *>(d_packed); }      // ingest fused into the scan
+        if (c->call.zc_src) { a.packed = c->call.zc_src; a.packed_copy = (u32 *)const_cast<u8 *>(d_packed); }      // ingest fused into the scan
         EvPair ep{}; if (profile) { ep.a = ev_get(c); ep.b = ev_get(c); ep.kind = 3; ep.bytes = packed_bytes; (void)hipEventRecord(ep.a, c->stream); }
         const bool scan_generic = tune("scan_generic", 0) != 0;      // (tests: the default (k, m) through the generic instance)
-        c->dropped_now = 0;
-        a.drop_mask = bins ? 0u : c->drop_mask_now;
+        c->call.dropped_now = 0;
+        a.drop_mask = bins ? 0u : c->call.drop_mask_now;
         if (a.drop_mask) { DALLOC(c, j.d_dropped, unsigned long long *, 256); HIPCHK(c, hipMemsetAsync(j.d_dropped, 0, 8, c->stream)); a.dropped = j.d_dropped; }
         auto launch_scan = [&]() {
             if (a.drop_mask) hipLaunchKernelGGL((scan_kernel<0, 0, false, true>), dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, c->stream, a);
@@ -301,7 +301,7 @@ static int parse_count(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u
             a.slab = 0;
         } else launch_scan();
         if (profile) { (void)hipEventRecord(ep.b, c->stream); c->ev_pending.push_back(ep); }
-        a.packed = d_packed; a.packed_copy = nullptr; c->zc_src = nullptr;                                  // everything after the scan reads the copy in HBM
+        a.packed = d_packed; a.packed_copy = nullptr; c->call.zc_src = nullptr;                                  // everything after the scan reads the copy in HBM
         hipLaunchKernelGGL(task_totals_kernel, dim3(1), dim3(HSK_MAX_TASKS), 0, c->stream, j.d_blk_cnt, j.nblocks, ntasks, d_task_tot);
         HIPCHK(c, hipMemcpyAsync(h_ovf, j.d_overflow, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(h_ovf + 1, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
@@ -309,38 +309,38 @@ static int parse_count(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u
         if (j.d_dropped) HIPCHK(c, hipMemcpyAsync(h_ovf + 4, j.d_dropped, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(j.task_tot.data(), d_task_tot, (size_t)ntasks * 3 * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hsk_sync(c, c->stream));
-        if (j.d_dropped) c->dropped_now = *(const unsigned long long *)(h_ovf + 4);
+        if (j.d_dropped) c->call.dropped_now = *(const unsigned long long *)(h_ovf + 4);
         if (j.bins.items) j.bins.nchunks = std::min(h_ovf[2], j.bins.cap);
-        bool gaps = c->roff_bad; c->roff_bad = false;
-        if (c->roff_check.valid() && !c->roff_check.get()) gaps = true;
+        bool gaps = c->call.roff_bad; c->call.roff_bad = false;
+        if (c->call.roff_check.valid() && !c->call.roff_check.get()) gaps = true;
         if (gaps) {
             // the buffer's reads do not lie back to back (the host threads found a gap while the GPU scanned): everything again
             // with the caller's offsets, copied now and validated on the device
-            u64 *given = c->roff_given;
+            u64 *given = c->call.roff_given;
             c->pool.release(d_task_tot);
             parse_release(c, j);
-            if (c->rlen_host) {                                    // (the lengths were a guess from a sample: the real ones now)
-                HIPCHK(c, hipMemcpyAsync(const_cast<u32 *>(d_rlen), c->rlen_host, nreads * 4, hipMemcpyHostToDevice, c->stream));
-                c->stats.h2d_bytes += nreads * 4; c->rlen_host = nullptr;
+            if (c->call.rlen_host) {                                    // (the lengths were a guess from a sample: the real ones now)
+                HIPCHK(c, hipMemcpyAsync(const_cast<u32 *>(d_rlen), c->call.rlen_host, nreads * 4, hipMemcpyHostToDevice, c->stream));
+                c->stats.h2d_bytes += nreads * 4; c->call.rlen_host = nullptr;
             }
-            HIPCHK(c, hipMemcpyAsync(given, c->roff_host, nreads * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(given, c->call.roff_host, nreads * 8, hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipMemcpyAsync(given + nreads, d_roff + nreads, 8, hipMemcpyDeviceToDevice, c->stream));
             hipLaunchKernelGGL(index_check_kernel, dim3(1024), dim3(256), 0, c->stream, given, d_rlen, nreads, packed_bytes, c->d_err);
-            c->index_unchecked = true;
+            c->call.index_unchecked = true;
             c->stats.h2d_bytes += nreads * 8;
             return parse_count(c, d_packed, packed_bytes, given, d_rlen, nreads, rid_base, ntasks, j);
         }
-        if (c->index_unchecked) {
-            c->index_unchecked = false;
+        if (c->call.index_unchecked) {
+            c->call.index_unchecked = false;
             if (h_ovf[1] & 32u) { (void)hipMemsetAsync(c->d_err, 0, 4, c->stream); c->pool.release(d_task_tot); return fail(c, HSK_ERR_INVALID_ARG, "the read index is not ascending / overlaps / leaves the packed buffer"); }
         }
         if (j.bins.items && (h_ovf[1] & (2u | 128u | 256u))) {          // the chunk store or a bin's map ran out: the call again, without the combining extraction
-            (void)hipMemsetAsync(c->d_err, 0, 4, c->stream); c->pool.release(d_task_tot); c->combine_veto = true; return retry_plan("the scan-placed items' chunk store or a bin's map ran out (error word)", h_ovf[1]);
+            (void)hipMemsetAsync(c->d_err, 0, 4, c->stream); c->pool.release(d_task_tot); c->call.combine_veto = true; return retry_plan("the scan-placed items' chunk store or a bin's map ran out (error word)", h_ovf[1]);
         }
-        if (*h_ovf && c->vt_shift) { c->pool.release(d_task_tot); c->combine_veto = true; return retry_plan("a tile beyond the record capacity"); }      // (the general kernels know no virtual tasks: the call again, without them)
+        if (*h_ovf && c->call.vt_shift) { c->pool.release(d_task_tot); c->call.combine_veto = true; return retry_plan("a tile beyond the record capacity"); }      // (the general kernels know no virtual tasks: the call again, without them)
         if (*h_ovf) {                                                // a tile with more supermers than the record capacity
             j.fast = false; c->stats.parse_fallbacks++;
-            c->dropped_now = 0;                                       // (the general kernels count again; they honour the same mask: several ranks stay consistent)
+            c->call.dropped_now = 0;                                       // (the general kernels count again; they honour the same mask: several ranks stay consistent)
             if (a.nslabs > 1) {                                       // the general kernels know one tile range per workgroup
                 ParseArgs b = make_parse_args(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, ntasks, &j.nblocks);
                 b.blk_cnt = a.blk_cnt; b.rec_cap = a.rec_cap; b.place_group = a.place_group;
@@ -352,15 +352,15 @@ static int parse_count(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u
             c->pool.release(j.d_tile_sub); j.d_tile_sub = nullptr; a.tile_sub = nullptr;
         }
     }
-    if (c->zc_src) {                                                  // the general kernels read the reads more than once: plain copy first
-        HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed), c->zc_src, packed_bytes, hipMemcpyDefault, c->stream));
-        c->zc_src = nullptr;
+    if (c->call.zc_src) {                                                  // the general kernels read the reads more than once: plain copy first
+        HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed), c->call.zc_src, packed_bytes, hipMemcpyDefault, c->stream));
+        c->call.zc_src = nullptr;
     }
     if (!j.fast) {
         // task id per base position, kept from COUNT to EMIT (2 B x 4 x packed_bytes); optional: without it EMIT re-hashes
         j.d_dest_cache = (u16 *)c->pool.alloc((size_t)a.ntiles * PARSE_TILE * 2);
         a.dest_cache = j.d_dest_cache;
-        a.drop_mask = c->drop_mask_now;                               // (a fresh ParseArgs after a slab fallback has lost it)
+        a.drop_mask = c->call.drop_mask_now;                               // (a fresh ParseArgs after a slab fallback has lost it)
         if (a.drop_mask) {
             if (!j.d_dropped) DALLOC(c, j.d_dropped, unsigned long long *, 256);
             HIPCHK(c, hipMemsetAsync(j.d_dropped, 0, 8, c->stream)); a.dropped = j.d_dropped;
@@ -372,12 +372,12 @@ static int parse_count(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u
         if (a.drop_mask) HIPCHK(c, hipMemcpyAsync(h_ovf + 4, j.d_dropped, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(j.task_tot.data(), d_task_tot, (size_t)ntasks * 3 * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hsk_sync(c, c->stream));
-        if (a.drop_mask) c->dropped_now = *(const unsigned long long *)(h_ovf + 4);
+        if (a.drop_mask) c->call.dropped_now = *(const unsigned long long *)(h_ovf + 4);
         // (hsk_count derives the read index only for the fast parse; should a derived index ever arrive here with its verdict still open, a
         //  wrong guess must not be counted: the call fails instead of trusting lengths and offsets nobody has confirmed)
-        if (c->roff_check.valid() && !c->roff_check.get()) { c->pool.release(d_task_tot); return fail(c, HSK_ERR_INTERNAL, "derived read index reached the general parse unverified and does not match the caller's"); }
-        if (c->index_unchecked) {
-            c->index_unchecked = false;
+        if (c->call.roff_check.valid() && !c->call.roff_check.get()) { c->pool.release(d_task_tot); return fail(c, HSK_ERR_INTERNAL, "derived read index reached the general parse unverified and does not match the caller's"); }
+        if (c->call.index_unchecked) {
+            c->call.index_unchecked = false;
             if (h_ovf[1] & 32u) { (void)hipMemsetAsync(c->d_err, 0, 4, c->stream); c->pool.release(d_task_tot); return fail(c, HSK_ERR_INVALID_ARG, "the read index is not ascending / overlaps / leaves the packed buffer"); }
         }
     }
@@ -424,8 +424,8 @@ static int parse_place(hsk_ctx *c, ParseJob &j, const std::vector<u32> &order, S
     // place_bytes_kernel once; positions are kept only where something still needs them (EXTENSION: pos / rid lookup)
     bool bytes_mode = !item_mode && j.fast && place_bytes_enabled(supermers_travel) && a.rec_cap <= PLACE_BYTES_REC;
     for (u32 t = 0; t < ntasks && bytes_mode; ++t) if (st.task_tot[3 * t + 1] >= (1ULL << 32)) bytes_mode = false;     // 32-bit offsets inside a task's run
-    // several ranks with the combining extraction planned (c->combine_now): the supermers' minimizer bits go into the store as well
-    const bool with_sub16 = bytes_mode && supermers_travel && c->combine_now && a.tile_sub && !ext;      // (heavy-hitter tasks are skipped by the kernel itself: their k-mers travel as lists)
+    // several ranks with the combining extraction planned (c->call.combine_now): the supermers' minimizer bits go into the store as well
+    const bool with_sub16 = bytes_mode && supermers_travel && c->call.combine_now && a.tile_sub && !ext;      // (heavy-hitter tasks are skipped by the kernel itself: their k-mers travel as lists)
     a.sm_sub16 = nullptr;
     if (with_sub16) { DALLOC(c, st.sm_sub16, unsigned short *, st.tot_sup * 2 + 64); a.sm_sub16 = st.sm_sub16; }
     if (bytes_mode) {
@@ -438,7 +438,7 @@ static int parse_place(hsk_ctx *c, ParseJob &j, const std::vector<u32> &order, S
     if (ext) { DALLOC(c, st.sm_pos, u32 *, st.tot_sup * 4 + 64); DALLOC(c, st.sm_rid, int32_t *, st.tot_sup * 4 + 64); }
     a.sm_sub = nullptr; a.sm_item = nullptr;
     if (from_bins) {
-        int brc = bins_to_store(c, j.bins, st, ntasks, c->vt_shift, c->stream);
+        int brc = bins_to_store(c, j.bins, st, ntasks, c->call.vt_shift, c->stream);
         c->pool.release(d_blk_base); c->pool.release(d_task_tot); c->pool.release(d_task_base); c->pool.release(d_order); c->pool.release(d_skip);
         a.task_skip = nullptr;
         return brc;
@@ -492,14 +492,14 @@ static int parse_ingest_pipelined(hsk_ctx *c, const u8 *h2d_src, const u8 *d_pac
                                   int64_t rid_base, u32 ntasks, SupermerStore &st, std::vector<TaskSegs> &segs)
 {
     u32 nblocks = 0;
-    ParseArgs a = make_parse_args(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, ntasks, &nblocks, (u32)c->h2d_slabs);
+    ParseArgs a = make_parse_args(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, ntasks, &nblocks, (u32)c->call.h2d_slabs);
     if (a.nslabs <= 1) return PARSE_FALLBACK;
     const u32 nsl = a.nslabs;
     const bool profile = (c->cfg.flags & HSK_FLAG_PROFILE) != 0;
     a.rec_cap = parse_rec_cap(c->cfg.kmer_size - c->cfg.minimizer_size + 1);
     a.place_group = std::max<u32>(1, std::min<u32>(16, PLACE_MAX_REC / a.rec_cap));
     a.place_one = 1;
-    const bool bins = c->item_mode_now && c->combine_now && scan_place_enabled() && a.rec_cap <= PLACE_ITEM_REC;      // scan_kernel places the items itself: no records, no placement kernel
+    const bool bins = c->call.item_mode_now && c->call.combine_now && scan_place_enabled() && a.rec_cap <= PLACE_ITEM_REC;      // scan_kernel places the items itself: no records, no placement kernel
     ScanBins sbins;
     u64 *d_blk_cnt, *d_blk_base, *d_tot, *d_task_base, *d_run; u32 *d_order, *d_tile_rec = nullptr, *d_tile_nrec = nullptr, *d_overflow, *d_tile_sub = nullptr;
     const size_t mat = (size_t)nblocks * ntasks;
@@ -511,10 +511,10 @@ static int parse_ingest_pipelined(hsk_ctx *c, const u8 *h2d_src, const u8 *d_pac
     DALLOC(c, d_order, u32 *, (size_t)ntasks * 4);
     if (!bins) { DALLOC(c, d_tile_rec, u32 *, (size_t)a.ntiles * a.rec_cap * 4 + 64); DALLOC(c, d_tile_nrec, u32 *, (size_t)a.ntiles * 4 + 64); }
     DALLOC(c, d_overflow, u32 *, 256);
-    if (!bins && c->combine_now && a.rec_cap <= PLACE_ITEM_REC) DALLOC(c, d_tile_sub, u32 *, (size_t)a.ntiles * a.rec_cap * 4 + 64);
+    if (!bins && c->call.combine_now && a.rec_cap <= PLACE_ITEM_REC) DALLOC(c, d_tile_sub, u32 *, (size_t)a.ntiles * a.rec_cap * 4 + 64);
     if (bins) { int brc = bins_alloc(c, sbins, ntasks, packed_bytes, nreads, c->cfg.kmer_size - c->cfg.minimizer_size + 1, c->stream); if (brc) return brc; }
     u64 *d_ps; DALLOC(c, d_ps, u64 *, (size_t)PS_SEGS * ntasks * 3 * 8);
-    unsigned long long *d_dropped = nullptr;                                // scan_kernel<.., DROP>: positions left out (hsk_ctx::drop_mask_now)
+    unsigned long long *d_dropped = nullptr;                                // scan_kernel<.., DROP>: positions left out (CallState::drop_mask_now)
     // the store holds at most rec_cap supermers per tile (a tile beyond that falls back); its real size is known when the last slab is in
     const u64 cap_sup = a.ntiles * (u64)a.rec_cap;
     st = SupermerStore();
@@ -541,8 +541,8 @@ static int parse_ingest_pipelined(hsk_ctx *c, const u8 *h2d_src, const u8 *d_pac
     a.tile_sub = d_tile_sub; a.sm_sub = st.sm_sub; a.sm_item = st.sm_item;
     if (d_tile_sub) a.place_group = std::max<u32>(1, std::min<u32>(PLACE_ITEM_TILES, PLACE_ITEM_REC / a.rec_cap));
     if (bins) bins_args(c, a, sbins);
-    c->dropped_now = 0;
-    a.drop_mask = bins ? 0u : c->drop_mask_now;
+    c->call.dropped_now = 0;
+    a.drop_mask = bins ? 0u : c->call.drop_mask_now;
     if (a.drop_mask) { DALLOC(c, d_dropped, unsigned long long *, 256); HIPCHK(c, hipMemsetAsync(d_dropped, 0, 8, sA)); a.dropped = d_dropped; }
     EvList evs(c);
     hipEvent_t ready = evs.get();                                          // the small buffers above are set up; the second stream may start
@@ -608,16 +608,16 @@ static int parse_ingest_pipelined(hsk_ctx *c, const u8 *h2d_src, const u8 *d_pac
     if (profile) { pp.keys = 0; c->ev_pending.push_back(pp); }
     if (staged) memcpy(tot.data(), h_tot, (size_t)nsl * ntasks * 24);
     bool fallback = *h_flags != 0;                                          // a tile with more supermers than the record capacity
-    if (c->roff_check.valid() && !c->roff_check.get()) { fallback = true; c->roff_bad = true; }     // the reads do not lie back to back: the caller's offsets are needed
-    if (c->index_unchecked && (h_flags[1] & 32u)) fallback = true;          // (parse_count reports it)
+    if (c->call.roff_check.valid() && !c->call.roff_check.get()) { fallback = true; c->call.roff_bad = true; }     // the reads do not lie back to back: the caller's offsets are needed
+    if (c->call.index_unchecked && (h_flags[1] & 32u)) fallback = true;          // (parse_count reports it)
     if (bins && (h_flags[1] & (2u | 128u | 256u))) { fallback = true; (void)hipMemsetAsync(c->d_err, 0, 4, sA); }      // the chunk store or a bin's map ran out (run_pipeline: the call again, without virtual tasks)
     if (fallback) { HIPCHK(c, hsk_sync(c, sA)); release_all(); free_store(c, st); return PARSE_FALLBACK; }
-    if (d_dropped) c->dropped_now = *(const unsigned long long *)(h_flags + 4);
+    if (d_dropped) c->call.dropped_now = *(const unsigned long long *)(h_flags + 4);
     if (bins) {
         sbins.nchunks = std::min(h_flags[2], sbins.cap);
-        int brc = bins_to_store(c, sbins, st, ntasks, c->vt_shift, sA); if (brc) { release_all(); return brc; }      // (main stream: behind the `placed` wait above)
+        int brc = bins_to_store(c, sbins, st, ntasks, c->call.vt_shift, sA); if (brc) { release_all(); return brc; }      // (main stream: behind the `placed` wait above)
     }
-    c->index_unchecked = false;
+    c->call.index_unchecked = false;
     // segments: slab by slab, tasks in storage order inside a slab (what parse_scan_kernel laid out on the device)
     st.task_tot.assign((size_t)ntasks * 3, 0); st.task_base.assign((size_t)ntasks * 3, 0);
     segs.assign(ntasks, TaskSegs());

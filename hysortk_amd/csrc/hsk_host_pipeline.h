@@ -127,17 +127,17 @@ struct GroupFeeder {
     // This rank's count has failed after the exchange began (RCCL only).  Its peers still expect its supermers and still send
     // it theirs: a rank that simply returned would leave them blocked in ncclRecv for ever (the reference dies together there:
     // MPI_Abort, src/kmerops.cpp:1477).  So the rank drains its own work, hands every device block the failed count allocated
-    // (`keep`: the live blocks before it, i.e. the supermer store stays) back to the pool -- a failed allocation is the usual
-    // reason to be here -- and posts the remaining groups one by one, receiving into buffers it drops at once.  The ranks then
-    // agree on the outcome (run_pipeline) and all return an error.
+    // (since `mark`: the supermer store stays) back to the pool -- a failed allocation is the usual reason to be here -- and posts
+    // the remaining groups one by one, receiving into buffers it drops at once.  The ranks then agree on the outcome (run_pipeline)
+    // and all return an error.
     bool draining = false;
-    int drain_after_failure(const std::vector<void *> &keep)
+    int drain_after_failure(unsigned long long mark)
     {
         draining = true;
         (void)hipStreamSynchronize(c->stream); (void)hipStreamSynchronize(c->comm_stream); (void)hipStreamSynchronize(c->d2h_stream);
         for (int g = 0; g < ngroups; ++g) { xb[g] = ExchangeBuffers(); packs[g].clear(); if (arrived[g]) { ev_put(c, arrived[g]); arrived[g] = nullptr; } }
         released = posted;
-        c->pool.release_all_but(keep);
+        c->pool.rollback(mark);
         for (; posted < ngroups; ++posted) {
             const int g = posted;
             int rc = post(g); if (rc) return rc;
@@ -276,10 +276,10 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
     u64 max_task = 0, total_kmers = 0;
     for (u32 t = 0; t < ntasks; ++t) { finalize_segs(segs[t]); max_task = std::max(max_task, segs[t].nkmers); total_kmers += segs[t].nkmers; }
     out->total_kmers = total_kmers;
-    if (c->est.valid && NW == 1 && !ext && !c->forbid_long_way && max_task) {
+    if (c->call.est.valid && NW == 1 && !ext && !c->forbid_long_way && max_task) {
         // distinct keys per 16-bit prefix bin of the largest task, from this call's estimate: the first table of the ladder, or no tables at all
         // (most bins beyond 2048 slots: four prefix passes + the tile finish; what a batch used to find out the hard way, agg_stage2)
-        const double d = c->est.distinct_per_kmer * (double)max_task / 65536.0;
+        const double d = c->call.est.distinct_per_kmer * (double)max_task / 65536.0;
         c->agg_first_cap = d <= 600.0 ? AG_LOG2CAP_SMALL : d <= 1250.0 ? AG_LOG2CAP_MEDIUM : AG_LOG2CAP_LARGE;
         if (d > 1450.0 && !(ex && ex->vt_shift) && !x_src.item) { c->agg_off = true; c->agg_off_calls = 0; }
     }
@@ -300,7 +300,7 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
     TaskSegs empty_segs;
     std::vector<TaskOut> touts(ntasks);
     // several ranks, the supermers arrived with their minimizer bits: the owner builds the items, batch by batch (hsk_combine.h, 1b)
-    const bool fed_wanted = NW <= 2 && feeder && feeder->with_sub && c->combine_now && !ext;
+    const bool fed_wanted = NW <= 2 && feeder && feeder->with_sub && c->call.combine_now && !ext;
     const bool forced = ((ex && ex->force_batch) || x_src.item != nullptr || fed_wanted) && batch_enabled;      // (item-mode store: every task goes through whole batches)
     // a caller's task count below eight (the reference's default for one rank is five): three to seven tasks of some size still
     // go faster as one padded batch (5/8 of the batch path's rate) than one by one on the single-task path (about 1/3 of it)
@@ -347,7 +347,7 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
         fed_combine = fed_wanted && !item_mode && xs && agg && !(NW == 1 ? c->agg_off : c->agg_off_wide) && batch && mine.size() % XCD_BATCH == 0;
         combine = combine || fed_combine;
     }
-    if (item_mode && !combine) { c->combine_veto = true; return retry_plan("an item-mode store, but no batch to combine (xs / agg / batch)", (xs ? 1u : 0u) | (agg ? 2u : 0u) | (batch ? 4u : 0u) | ((mine.size() % XCD_BATCH == 0) ? 8u : 0u)); }
+    if (item_mode && !combine) { c->call.combine_veto = true; return retry_plan("an item-mode store, but no batch to combine (xs / agg / batch)", (xs ? 1u : 0u) | (agg ? 2u : 0u) | (batch ? 4u : 0u) | ((mine.size() % XCD_BATCH == 0) ? 8u : 0u)); }
     BucketOrder border;
     BucketOrder border_fed[2]; FedItems fed_items[2];      // per slot: the items and the bucket order of the batch in flight (several ranks)
     bool slot_combine[2] = {false, false};
@@ -363,9 +363,9 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
     // whose pairs do not fit after all (error bit 512: the last chunk takes what runs over) starts again with full-sized buffers.  Several ranks: full
     // size (nobody starts again while peers wait).
     u64 rec_cap = max_task;
-    if (combine && !fed_combine && c->est.valid && !c->pair_cap_full && tune("pair_cap", 1) != 0)
-        rec_cap = std::min<u64>(max_task, std::max<u64>((u64)((double)max_task * std::min(1.0, 4.0 * c->est.distinct_per_kmer * c->est_bias + 0.02)), 1ULL << 22));
-    if (tune("pair_cap_records", 0) > 0 && combine && !fed_combine && !c->pair_cap_full) rec_cap = std::min<u64>(max_task, (u64)tune("pair_cap_records", 0));      // (tests: stores that run over; the attempt after an overrun is full size)
+    if (combine && !fed_combine && c->call.est.valid && !c->call.pair_cap_full && tune("pair_cap", 1) != 0)
+        rec_cap = std::min<u64>(max_task, std::max<u64>((u64)((double)max_task * std::min(1.0, 4.0 * c->call.est.distinct_per_kmer * c->est_bias + 0.02)), 1ULL << 22));
+    if (tune("pair_cap_records", 0) > 0 && combine && !fed_combine && !c->call.pair_cap_full) rec_cap = std::min<u64>(max_task, (u64)tune("pair_cap_records", 0));      // (tests: stores that run over; the attempt after an overrun is full size)
     auto alloc_sort_buffers = [&]() -> int {
         if (max_task) {
             for (int sl = 0; sl < nslot; ++sl) for (int i = 0; i < nsets; ++i) {
@@ -386,7 +386,7 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
         pt.begin(PH_EXTRACT);
         int rc = bucket_order_tasks(c, ntasks, segs, mine, x_src, ex ? ex->vt_shift : 0, border); if (rc) return rc;
         pt.end(PH_EXTRACT);
-        if (!border.active) { c->combine_veto = true; return retry_plan("no bucket order"); }
+        if (!border.active) { c->call.combine_veto = true; return retry_plan("no bucket order"); }
         if (ex && ex->items_store) {                      // (stream-ordered reuse: every later user of these blocks is enqueued behind the scatter)
             SupermerStore &is = *ex->items_store;
             c->pool.release(is.sm_item); is.sm_item = nullptr; c->pool.release(is.sm_sub); is.sm_sub = nullptr;
@@ -536,7 +536,7 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
         slot_fext[sl] = fused_ext && !c->agg_off_wide;
         slot_follow[sl] = slot_agg[sl] || slot_fext[sl] || (NW == 1 && fused);
         const bool will_combine = combine && (fed_combine || border.active) && slot_agg[sl];
-        if (combine && !will_combine && !fed_combine) { c->combine_veto = true; return retry_plan("a batch that cannot take the combining extraction"); }      // (several ranks: the batch simply takes the instance path -- nobody starts a call again while peers wait)
+        if (combine && !will_combine && !fed_combine) { c->call.combine_veto = true; return retry_plan("a batch that cannot take the combining extraction"); }      // (several ranks: the batch simply takes the instance path -- nobody starts a call again while peers wait)
         // (two-word keys: the finish orders a bin's keys by the bits below a 16-bit prefix, agg_order_many -- their pairs take bins of 16 bits)
         const int prefix_bits = will_combine ? (NW == 1 ? combine_prefix_bits(c) : AG_PREFIX_BITS) : (slot_agg[sl] || slot_fext[sl]) ? AG_PREFIX_BITS : 64 - HYBRID_SHIFT;
         slot_prefix[sl] = prefix_bits;
@@ -639,7 +639,7 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
             if ((u32)h_nout[XCD_BATCH] & 512u) {                   // the pair stores ran over (they were sized from the estimate): once more, sized for the k-mers
                 (void)hipMemsetAsync(c->d_err, 0, 4, c->stream);
                 if (fed_combine) return fail(c, HSK_ERR_INTERNAL, "pair stores overrun with several ranks");
-                c->pair_cap_full = true;
+                c->call.pair_cap_full = true;
                 return retry_plan("the pair stores ran over (sized from the estimate)");
             }
             // Bit 512 fires only when a task's chunks exceed rec_cap / CH + 257: a task of a few hundred thousand pairs more than rec_cap fills fewer
@@ -649,7 +649,7 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
                 if (h_nout[i] > bt[i].n) return fail(c, HSK_ERR_INTERNAL, "task %u: %llu pairs for %llu k-mers", mine[pos + i], (unsigned long long)h_nout[i], (unsigned long long)bt[i].n);
                 if (h_nout[i] > rec_cap) {
                     if (fed_combine) return fail(c, HSK_ERR_INTERNAL, "pair stores overrun with several ranks");
-                    c->pair_cap_full = true;
+                    c->call.pair_cap_full = true;
                     return retry_plan("the pair stores ran over (more pairs than records)", (unsigned)std::min<u64>(h_nout[i], 0xffffffffu));
                 }
             }
@@ -665,7 +665,7 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
             const u64 ratio_env = combine_ratio();
             if (bk && bp * ratio_env > bk && !c->combine_off) {
                 c->leave_combine();
-                if (c->est.valid) c->est_bias = std::min(8.0, std::max(1.0, ((double)bp / (double)bk) / c->est.distinct_per_kmer));      // (the estimate promised fewer pairs: later estimates on this context are scaled)
+                if (c->call.est.valid) c->est_bias = std::min(8.0, std::max(1.0, ((double)bp / (double)bk) / c->call.est.distinct_per_kmer));      // (the estimate promised fewer pairs: later estimates on this context are scaled)
             }
         }
         pt.begin(PH_SORT);
@@ -890,20 +890,20 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
     // moves the limit (tests: 0)
     const u64 combine_min = (u64)tune("combine_min_bytes", 64LL << 20);
     // this call's own estimate of the input (estimate_plan) decides where there is one; the context's memory of earlier calls (combine_off, agg_off) where there is none
-    const bool est = c->est.valid;
-    const bool combine_pays = !c->combine_left_now && (est ? c->est.distinct_per_kmer * c->est_bias * (double)combine_ratio() <= 1.0 : !c->combine_off);
-    if (est && c->agg_off && c->plan_attempt == 0) { c->agg_off = false; c->agg_off_calls = 0; }      // (process_rank decides again, from the estimate and the task sizes)
+    const bool est = c->call.est.valid;
+    const bool combine_pays = !c->call.combine_left_now && (est ? c->call.est.distinct_per_kmer * c->est_bias * (double)combine_ratio() <= 1.0 : !c->combine_off);
+    if (est && c->agg_off && c->call.plan_attempt == 0) { c->agg_off = false; c->agg_off_calls = 0; }      // (process_rank decides again, from the estimate and the task sizes)
     // several ranks (round 4): the supermers travel as byte runs with 16 of their minimizer bits, the OWNER of a task builds the items (hsk_combine.h, 1b);
     // needs the grouped exchange and the byte-store placement, and every rank's consent (below)
     // (two-word keys: 40 <= K <= 55 -- the prefix bits sit in the most significant word, an item of 64 bases holds six k-mers and more: shorter
     //  items would be more records per tile than the parse keeps, for 16 bytes that stand for very few k-mers)
-    c->combine_now = (NW == 1 || (NW == 2 && K >= 40 && K <= 55)) && !ext && combine_pays && !c->combine_veto && c->plan_attempt < 2 && !(NW == 1 ? c->agg_off : c->agg_off_wide) && combine_enabled() && parse_fast_enabled() &&
+    c->call.combine_now = (NW == 1 || (NW == 2 && K >= 40 && K <= 55)) && !ext && combine_pays && !c->call.combine_veto && c->call.plan_attempt < 2 && !(NW == 1 ? c->agg_off : c->agg_off_wide) && combine_enabled() && parse_fast_enabled() &&
                      c->cfg.minimizer_size <= SCAN_MAX_M && packed_bytes >= combine_min && c->xcd_batch_ok &&
                      (nranks == 1 || (overlap_enabled() && place_bytes_enabled(true)));
-    c->combine_veto = false;
+    c->call.combine_veto = false;
     // the combining extraction wants buckets of ~12 k k-mers: the parse itself splits every task by the top minimizer bits (virtual
     // tasks, up to 16 per task and HSK_MAX_TASKS in all: ParseArgs::vt_shift), the bucket order does the rest (hsk_combine.h)
-    c->vt_shift = 0;
+    c->call.vt_shift = 0;
     PhaseTimer pt(c);
     pt.begin(PH_TOTAL);
 
@@ -912,25 +912,25 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
         // every rank must use the same task count (the maximum of the local proposals) and the same plan (the combining extraction only if
         // every rank's own estimate says its input pays for it: the minimizer bits either travel from all ranks or from none)
         // ... and the certain drops: a rank whose own sample holds more than U copies of a homopolymer k-mer is right for all ranks (OR of the masks)
-        u64 v[4] = {c->cfg.ntasks ? 0ULL : (u64)ntasks, c->combine_now ? 0ULL : 1ULL, (u64)(c->drop_mask_now & 1u), (u64)((c->drop_mask_now >> 1) & 1u)};
+        u64 v[4] = {c->cfg.ntasks ? 0ULL : (u64)ntasks, c->call.combine_now ? 0ULL : 1ULL, (u64)(c->call.drop_mask_now & 1u), (u64)((c->call.drop_mask_now >> 1) & 1u)};
         int rc = c->comm.allreduce_max_u64(v, 4, c->stream, c->pool); if (rc) return fail(c, HSK_ERR_COMM, "allreduce(ntasks, plan) failed: %d", rc);
         if (!c->cfg.ntasks) ntasks = (u32)v[0];
-        if (v[1]) c->combine_now = false;
-        c->drop_mask_now = (v[2] ? 1u : 0u) | (v[3] ? 2u : 0u);
+        if (v[1]) c->call.combine_now = false;
+        c->call.drop_mask_now = (v[2] ? 1u : 0u) | (v[3] ? 2u : 0u);
     }
     out->ntasks = (int32_t)ntasks;
     // (at most 768 virtual tasks: the item placement's LDS holds 16 bytes for each beside its 16384 records; more real tasks than that: the instance path)
-    if (ntasks > 768 && nranks == 1) c->combine_now = false;
-    if (c->combine_now && nranks == 1) { u32 sh = 0; while (sh < 4 && ((u64)ntasks << (sh + 1)) <= 768) ++sh; c->vt_shift = sh; }
-    if (c->combine_now && est && nranks == 1) {
+    if (ntasks > 768 && nranks == 1) c->call.combine_now = false;
+    if (c->call.combine_now && nranks == 1) { u32 sh = 0; while (sh < 4 && ((u64)ntasks << (sh + 1)) <= 768) ++sh; c->call.vt_shift = sh; }
+    if (c->call.combine_now && est && nranks == 1) {
         // a task has at most 2^14 buckets (CS_MAX_LOG2NB; 2^(10 + virtual-task bits)): few, large tasks make buckets whose distinct k-mers overflow the
         // 2048-slot tables again and again (partial pairs: the detour stops paying) -- predicted from the estimate instead of found out by a batch
-        const u32 lg = (u32)std::min<int>(CS_MAX_LOG2NB, CS_MAX_LOCAL + (int)c->vt_shift);
+        const u32 lg = (u32)std::min<int>(CS_MAX_LOG2NB, CS_MAX_LOCAL + (int)c->call.vt_shift);
         const double per_bucket = (double)packed_bytes * 4.0 / (double)ntasks / (double)(1u << lg);
-        if (per_bucket > (double)combine_bucket_kmers() && c->est.distinct_per_kmer * per_bucket > 1400.0) { c->combine_now = false; c->vt_shift = 0; }
+        if (per_bucket > (double)combine_bucket_kmers() && c->call.est.distinct_per_kmer * per_bucket > 1400.0) { c->call.combine_now = false; c->call.vt_shift = 0; }
     }
-    c->item_mode_now = c->combine_now && nranks == 1;      // one GPU: the store holds items (several ranks: byte runs + minimizer bits, the owners build the items)
-    const u32 vts = c->vt_shift, nvt = ntasks << vts;       // what the parse calls tasks
+    c->call.item_mode_now = c->call.combine_now && nranks == 1;      // one GPU: the store holds items (several ranks: byte runs + minimizer bits, the owners build the items)
+    const u32 vts = c->call.vt_shift, nvt = ntasks << vts;       // what the parse calls tasks
     std::vector<int32_t> owner(ntasks, 0);
     std::vector<u32> order(ntasks);
     for (u32 t = 0; t < ntasks; ++t) order[t] = t;
@@ -948,8 +948,8 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
     pt.begin(PH_PARSE);
     // one GPU, reads arriving from pinned host memory, no payload: ingest, scan and placement as one pipeline over slabs
     const bool pipe_enabled = tune("ingest_pipeline", 1) != 0;
-    if (nranks == 1 && !ext && c->h2d_src && pipe_enabled && parse_fast_enabled() && c->cfg.minimizer_size <= SCAN_MAX_M) {
-        const u8 *src = c->h2d_src; c->h2d_src = nullptr;
+    if (nranks == 1 && !ext && c->call.h2d_src && pipe_enabled && parse_fast_enabled() && c->cfg.minimizer_size <= SCAN_MAX_M) {
+        const u8 *src = c->call.h2d_src; c->call.h2d_src = nullptr;
         std::vector<TaskSegs> segs_v;
         const int prc = parse_ingest_pipelined(c, src, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, nvt, st, vts ? segs_v : segs);
         if (prc == HSK_OK) {
@@ -962,8 +962,8 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
                 }
             }
         }
-        else if (prc == PARSE_FALLBACK && vts) { c->vt_shift = 0; c->combine_veto = true; return retry_plan("the pipelined ingest fell back"); }      // (the fallback parse knows no virtual tasks: the call again, without them)
-        else if (prc != PARSE_FALLBACK) { c->vt_shift = 0; return prc; }
+        else if (prc == PARSE_FALLBACK && vts) { c->call.vt_shift = 0; c->call.combine_veto = true; return retry_plan("the pipelined ingest fell back"); }      // (the fallback parse knows no virtual tasks: the call again, without them)
+        else if (prc != PARSE_FALLBACK) { c->call.vt_shift = 0; return prc; }
         else c->stats.parse_fallbacks++;                        // (the packed reads are in HBM now: the two-step parse below takes it from there)
     }
     if (!pipelined) {
@@ -971,8 +971,8 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
         // before the storage order (tasks grouped by owner rank) is known, then parse_place lays the supermers out
         ParseJob job;
         int rc = parse_count(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, nvt, job);
-        if (rc && nranks == 1) { parse_release(c, job); c->vt_shift = 0; return rc; }
-        if (vts && !job.d_tile_sub && !job.bins.items && !job.empty) { parse_release(c, job); c->vt_shift = 0; c->combine_veto = true; return retry_plan("the parse left its fast path: no items"); }   // (the parse left its fast path: no items)
+        if (rc && nranks == 1) { parse_release(c, job); c->call.vt_shift = 0; return rc; }
+        if (vts && !job.d_tile_sub && !job.bins.items && !job.empty) { parse_release(c, job); c->call.vt_shift = 0; c->call.combine_veto = true; return retry_plan("the parse left its fast path: no items"); }   // (the parse left its fast path: no items)
         if (nranks > 1) {
             // Several ranks: a rank that fails must not return alone (its peers would wait for it in the next collective for
             // ever).  Every all-reduce below carries the ranks' status as one more element; a failed rank keeps taking part
@@ -1023,7 +1023,7 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
         place_rc = rc;                                           // several ranks: carried into the size-matrix all-reduce below
     }
     pt.end(PH_PARSE);
-    c->vt_shift = 0;
+    c->call.vt_shift = 0;
     tmark("parse enqueued (task totals read)");
     out->total_supermers = st.tot_sup; out->total_supermer_bytes = st.tot_bytes + st.tot_sup * (ext ? 9 : 1);
 
@@ -1046,7 +1046,7 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
             const int st_ = c->comm.allreduce_with_status(M, RCCL_SUM, local_rc != 0, c->stream, c->pool);
             if (st_ < 0) return fail(c, HSK_ERR_COMM, "allreduce(size matrix) failed: %d (%s)", st_, c->comm.last_error.c_str());
             if (st_ > 0) return local_rc ? local_rc : fail(c, HSK_ERR_COMM, "another rank failed before the supermer exchange");
-            const bool all_sub = M.back() == (u64)nranks && c->combine_now;
+            const bool all_sub = M.back() == (u64)nranks && c->call.combine_now;
             M.pop_back();
             rc = feeder.plan(c, nranks, rank, ntasks, owner, order, M, st.task_base, segs); if (rc) return rc;
             feeder.st = &st; feeder.lazy_pack = true; feeder.with_sub = all_sub; fed = true;
@@ -1131,9 +1131,9 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
     }
     pt.end(PH_EXCH);
     ProcExtra ex; ex.heavy_in = &hin; ex.vt_shift = vts; if (nranks == 1 && st.sm_item) ex.items_store = &st;
-    const std::vector<void *> before_rank = (fed && c->comm.active()) ? c->pool.snapshot() : std::vector<void *>();
+    const unsigned long long before_rank = c->pool.mark();
     int rc = process_rank<NW>(c, ntasks, owner, rank, segs, x_len, x_src, x_pos, x_rid, out, rp, pt, true, fed ? &feeder : nullptr, &ex);
-    if (rc == HSK_OK && c->dropped_now) { out->total_kmers += c->dropped_now; c->stats.dropped_kmers += (int64_t)c->dropped_now; }      // (the instances the scan left out are k-mers of the input all the same)
+    if (rc == HSK_OK && c->call.dropped_now) { out->total_kmers += c->call.dropped_now; c->stats.dropped_kmers += (int64_t)c->call.dropped_now; }      // (the instances the scan left out are k-mers of the input all the same)
     if (rc == HSK_OK && nranks > 1) for (u32 t = 0; t < ntasks; ++t) if (is_heavy[t] && owner[t] == rank) out->total_kmers += heavy_kmers[t];      // (they arrived as lists, not as supermers)
     if (fed && feeder.live) {
         // Leaving together, part two (part one: the all-reduces with status up to the first task group).  A rank whose count failed
@@ -1141,6 +1141,7 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
         // other how it went, and if one of them failed they all return an error -- the failed rank its own, the others HSK_ERR_COMM.
         if (rc != HSK_OK) {
             char keep_msg[sizeof c->err]; memcpy(keep_msg, c->err, sizeof keep_msg);
+            hsk_result_free(c, out);                                               // (its blocks are the rollback's: dropped first)
             const int drc = feeder.drain_after_failure(before_rank);
             if (drc) return drc;                                                   // the transport itself is broken: nothing more to agree on
             memcpy(c->err, keep_msg, sizeof keep_msg);
@@ -1173,24 +1174,21 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
     for (int r = 1; r < R; ++r) rid_base[r] = rid_base[r - 1] + (int64_t)nreads[r - 1];      // MPI_Exscan of the read counts
     std::vector<u32> order(ntasks); for (u32 t = 0; t < ntasks; ++t) order[t] = t;
     // the plan, as run_pipeline chooses it with several ranks: the sketch of a rank's reads (here: of the first virtual rank that has some)
-    c->combine_now = false; c->item_mode_now = false; c->vt_shift = 0; c->combine_left_now = false; c->drop_mask_now = 0; c->dropped_now = 0;
     const bool scan_ok = parse_fast_enabled() && c->cfg.minimizer_size <= SCAN_MAX_M;
     const bool plan_cond = (NW == 1 || (NW == 2 && c->cfg.kmer_size >= 40 && c->cfg.kmer_size <= 55)) && R > 1 && !ext && combine_enabled() && scan_ok && c->xcd_batch_ok && overlap_enabled() && place_bytes_enabled(true);
     if (R > 1 && (plan_cond || (scan_ok && c->cfg.kmer_size <= 57))) {          // (without a plan to choose, the sketch still says which k-mers are certain to be dropped)
         const u64 combine_min = (u64)tune("combine_min_bytes", 64LL << 20);
         int r0 = 0; while (r0 + 1 < R && nreads[r0] == 0) ++r0;
         int erc = estimate_plan(c, in[r0].packed, packed_bytes[r0], in[r0].roff, in[r0].rlen, nreads[r0], R); if (erc) return erc;
-        c->drop_mask_now = certain_drop_mask(c);              // (a rank that is certain is right for all: the virtual ranks share the first one's)
+        c->call.drop_mask_now = certain_drop_mask(c);              // (a rank that is certain is right for all: the virtual ranks share the first one's)
         if (plan_cond) {
-            const bool pays = c->est.valid ? c->est.distinct_per_kmer * c->est_bias * (double)combine_ratio() <= 1.0 : !c->combine_off;
-            c->combine_now = pays && tot_bytes / (u64)R >= combine_min && !(NW == 1 ? c->agg_off : c->agg_off_wide);
+            const bool pays = c->call.est.valid ? c->call.est.distinct_per_kmer * c->est_bias * (double)combine_ratio() <= 1.0 : !c->combine_off;
+            c->call.combine_now = pays && tot_bytes / (u64)R >= combine_min && !(NW == 1 ? c->agg_off : c->agg_off_wide);
         }
     }
-    struct PlanReset { hsk_ctx *c; ~PlanReset() { c->combine_now = false; c->est.valid = false; c->drop_mask_now = 0; } } plan_reset{c};
     // 1. hash every rank's reads once (parse_count), sum the task sizes, dispatch
     std::vector<u64> bytes(ntasks, 0), dropped(R, 0);
     std::vector<ParseJob> jobs(R);
-    auto release_jobs = [&]() { for (auto &j : jobs) parse_release(c, j); };
     // per-rank device time of the parse (hash + count, then placement + byte store): outs[r].ms_parse
     EvList tev(c);
     std::vector<hipEvent_t> e0(R), e1(R), e2(R), e3(R);
@@ -1199,16 +1197,15 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
     for (int r = 0; r < R; ++r) {
         (void)hipEventRecord(e0[r], c->stream);
         int rc = parse_count(c, in[r].packed, packed_bytes[r], in[r].roff, in[r].rlen, nreads[r], rid_base[r], ntasks, jobs[r]);
-        dropped[r] = c->dropped_now;
+        dropped[r] = c->call.dropped_now;
         (void)hipEventRecord(e1[r], c->stream);
-        if (rc) { release_jobs(); return rc; }
+        if (rc) return rc;
         for (u32 t = 0; t < ntasks; ++t) bytes[t] += jobs[r].task_tot[3 * t + 1] + jobs[r].task_tot[3 * t] * (ext ? 9 : 1);
     }
     // 1b. heavy-hitter tasks: classify on the global k-mer counts, every rank pre-aggregates its share
     std::vector<u8> is_heavy(ntasks, 0);
     std::vector<u64> heavy_kmers(ntasks, 0);             // k-mer instances of a heavy task over all ranks: its owner counts them into total_kmers
     std::vector<std::vector<TaskOut>> hlists(R);
-    auto free_hlists = [&]() { for (auto &v : hlists) for (auto &to : v) free_task_out(c, to); };
     bool any_heavy = false;
     if (heavy_enabled(c, NW, R)) {
         std::vector<u64> kg(ntasks, 0); std::vector<int32_t> types(ntasks, 0);
@@ -1221,7 +1218,7 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
         for (int r = 0; r < R; ++r) {
             std::vector<u8> failed;
             int rc = heavy_preaggregate<NW>(c, jobs[r], in[r].packed, packed_bytes[r], is_heavy, hlists[r], failed);
-            if (rc) { release_jobs(); free_hlists(); return rc; }
+            if (rc) return rc;
             for (u32 t = 0; t < ntasks; ++t) bad[t] |= failed[t];
         }
         any_heavy = false;
@@ -1234,10 +1231,8 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
         }
     }
     std::vector<int32_t> owner(ntasks, 0);
-    if (plan_dispatch(bytes.data(), (int)ntasks, R, c->cfg.plain_dispatcher != 0, c->cfg.dispatch_upper_coe, c->cfg.dispatch_step, owner.data())) {
-        release_jobs(); free_hlists();
-        return fail(c, HSK_ERR_DISPATCH, "%s", hsk_strerror(HSK_ERR_DISPATCH));
-    }
+    if (plan_dispatch(bytes.data(), (int)ntasks, R, c->cfg.plain_dispatcher != 0, c->cfg.dispatch_upper_coe, c->cfg.dispatch_step, owner.data()))
+        return fail(c, HSK_ERR_DISPATCH, "%s", hsk_strerror(HSK_ERR_DISPATCH));      // (a failed call's blocks go back with its scope: ApiCall)
     if (owner_out) memcpy(owner_out, owner.data(), sizeof(int32_t) * ntasks);
     std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) { return owner[x] < owner[y]; });
     // 2. owner-grouped placement + byte materialisation on every rank
@@ -1247,8 +1242,8 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
         (void)hipEventRecord(e2[r], c->stream);
         int rc = parse_place(c, jobs[r], order, st[r], any_heavy ? &is_heavy : nullptr, R > 1);
         parse_release(c, jobs[r]);
-        if (rc) { release_jobs(); return rc; }
-        rc = pack_store_bytes(c, st[r], source_from_packed(in[r].packed, packed_bytes[r], st[r].sm_gpos), !overlap_enabled()); if (rc) { release_jobs(); return rc; }
+        if (rc) return rc;
+        rc = pack_store_bytes(c, st[r], source_from_packed(in[r].packed, packed_bytes[r], st[r].sm_gpos), !overlap_enabled()); if (rc) return rc;
         (void)hipEventRecord(e3[r], c->stream);
         for (size_t i = 0; i < (size_t)ntasks * 3; ++i) M[(size_t)r * ntasks * 3 + i] = st[r].task_tot[i];
     }
@@ -1270,7 +1265,7 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
             hin[owner[t]].push_back(hv);
         }
         HIPCHK(c, hsk_sync(c, c->stream));
-        free_hlists();
+        for (auto &v : hlists) for (auto &to : v) free_task_out(c, to);
     }
     auto free_hin = [&]() { for (auto &v : hin) for (auto &hv : v) c->pool.release(hv.d_entries); };
     // 3. the exchange: same plans as the RCCL path (hsk_comm.h), device copies instead of send/recv
@@ -1279,7 +1274,7 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
         std::vector<GroupFeeder> fd(R);
         std::vector<std::vector<ExchangePlan>> pl_all(R);
         std::vector<std::vector<TaskSegs>> segs(R);
-        bool all_sub = c->combine_now;
+        bool all_sub = c->call.combine_now;
         for (int r = 0; r < R; ++r) if (st[r].tot_sup && !st[r].sm_sub16) all_sub = false;
         for (int d = 0; d < R; ++d) { int rc = fd[d].plan(c, R, d, ntasks, owner, order, M, st[d].task_base, segs[d]); if (rc) return rc; pl_all[d] = fd[d].pl; fd[d].with_sub = all_sub; }
         int rc_all = HSK_OK;
@@ -1330,7 +1325,7 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
         ProcExtra ex; ex.heavy_in = &hin[r];
         int rc = process_rank<NW>(c, ntasks, owner, r, segs[r], xb[r].len, source_from_bytes(xb[r].bytes, xb[r].nbytes), xb[r].pos, xb[r].rid, &outs[r], rp, pt, false, nullptr, &ex);
         xb[r].release(c->pool);
-        if (rc) { free_hin(); return rc; }
+        if (rc) return rc;
         outs[r].ms_parse = parse_ms(r); outs[r].ms_total = outs[r].ms_parse + outs[r].ms_exchange + outs[r].ms_extract + outs[r].ms_sort + outs[r].ms_count + outs[r].ms_d2h;
     }
     free_hin();

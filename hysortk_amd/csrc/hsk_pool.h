@@ -44,11 +44,13 @@ struct DevPool {
         size_t req = 0, zoff = 0, zbytes = 0;                        // requested bytes; red zone [zoff, zoff + zbytes) (zbytes = 0: none)
         const char *file = nullptr; int line = 0;                    // allocation site
         bool quar = false;                                           // released, quarantined until flush()
+        unsigned long long serial = 0;                               // when it was handed out (mark / rollback)
     };
     std::map<char *, Seg> segs;                                      // every segment, live or free, by address
     std::multimap<size_t, char *> free_by_size;
     std::map<char *, size_t> regions;                                // what the backend gave us
     size_t bytes_live = 0, bytes_cached = 0, peak = 0;
+    unsigned long long serial = 0;                                   // blocks handed out so far
 
     void unlist(std::map<char *, Seg>::iterator it)
     {
@@ -84,7 +86,7 @@ struct DevPool {
                 free_by_size.insert({rsz, rest});
                 bytes_cached += rsz;
             }
-            s.free = false; s.zbytes = 0; s.quar = false;
+            s.free = false; s.zbytes = 0; s.quar = false; s.serial = ++serial;
             bytes_live += s.size; peak = std::max(peak, bytes_live);
             return it->first;
         }
@@ -95,7 +97,7 @@ struct DevPool {
             if (be_malloc(&p, bytes) != 0 || !p) return nullptr;
         }
         regions[(char *)p] = bytes;
-        segs[(char *)p] = Seg{bytes, false, (char *)p};
+        (segs[(char *)p] = Seg{bytes, false, (char *)p}).serial = ++serial;
         bytes_live += bytes; peak = std::max(peak, bytes_live);
         return p;
     }
@@ -149,14 +151,17 @@ struct DevPool {
         for (auto &r : regions) (void)be_free(r.first);
         regions.clear(); segs.clear(); free_by_size.clear(); bytes_live = bytes_cached = 0;
     }
-    // Error paths return early (DALLOC / HIPCHK) without releasing what the call had allocated so far: the entry points take
-    // a snapshot of the live blocks and, when the call fails, hand everything allocated since back to the pool.
-    std::vector<void *> snapshot() const { std::vector<void *> v; for (auto &kv : segs) if (!kv.second.free && !kv.second.quar) v.push_back(kv.first); return v; }
-    void release_all_but(const std::vector<void *> &keep)        // keep: sorted (map order)
+    // Error paths return early (DALLOC / HIPCHK) without releasing what they had allocated so far.  A call takes a mark when it
+    // opens (ApiCall, hsk_api.hip); when it fails, rollback(mark) releases every block handed out since -- a block released and
+    // handed out again at the same address included.  The blocks are free at once: whoever still holds a pointer into one (the
+    // call's results) drops it before the rollback and never releases it afterwards.  Returns the number of blocks released.
+    unsigned long long mark() const { return serial; }
+    size_t rollback(unsigned long long m)
     {
-        std::vector<void *> drop;
-        for (auto &kv : segs) if (!kv.second.free && !kv.second.quar && !std::binary_search(keep.begin(), keep.end(), (void *)kv.first)) drop.push_back(kv.first);
-        for (void *p : drop) release(p);
+        std::vector<char *> drop;
+        for (auto &kv : segs) if (!kv.second.free && !kv.second.quar && kv.second.serial > m) drop.push_back(kv.first);
+        for (char *p : drop) release(p);
+        return drop.size();
     }
     // Red zones: 0 = every zone of a live or quarantined block holds the pattern, 1 = one does not (msg: the block's allocation site and the first
     // byte written, counted from the block's start), -1 = the check itself failed (msg says so).  The zones of live blocks are filled again after

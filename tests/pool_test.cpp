@@ -1,6 +1,7 @@
 // CPU exerciser of hysortk_amd/csrc/hsk_pool.h (the device pool's segment logic against malloc): random allocate / write / check / release
 // sequences; every live block keeps its pattern, live blocks never overlap, bytes_live + bytes_cached == bytes mapped, trim returns all.
-// The same with red zones on (pool_redzone: quarantine, periodic check + flush), and the red zones' own cases (redzone_cases).
+// The same with red zones on (pool_redzone: quarantine, periodic check + flush), the red zones' own cases (redzone_cases) and a failed
+// call's rollback to its mark (rollback_cases).
 #include "../hysortk_amd/csrc/hsk_pool.h"
 #include <cstdio>
 #include <cstdlib>
@@ -20,6 +21,7 @@ static int be_check(void *, const DevPool::Zone *z, size_t n, size_t *bz, size_t
     return 0;
 }
 static void with_redzone(DevPool &pool, size_t rz) { pool.redzone = rz; pool.be_fill = be_fill; pool.be_check = be_check; }
+static size_t live_blocks(const DevPool &pool) { size_t n = 0; for (auto &kv : pool.segs) n += !kv.second.free && !kv.second.quar; return n; }
 #define EXPECT(cond, ...) do { if (!(cond)) { std::printf("FAIL " __VA_ARGS__); std::printf(" (line %d)\n", __LINE__); return 1; } } while (0)
 
 static int redzone_cases()
@@ -68,7 +70,7 @@ static int redzone_cases()
         std::vector<void *> first;
         for (int i = 0; i < 8; ++i) first.push_back(pool.alloc(((size_t)1 + i) << 20));
         for (void *p : first) pool.release(p);
-        EXPECT(pool.snapshot().empty(), "quarantined blocks are not live for release_all_but");
+        EXPECT(live_blocks(pool) == 0 && pool.rollback(0) == 0, "quarantined blocks are not live for rollback");
         EXPECT(pool.bytes_live > live0, "quarantined blocks still occupy their memory");
         std::vector<void *> second;
         for (int i = 0; i < 16; ++i) {
@@ -90,6 +92,56 @@ static int redzone_cases()
         EXPECT(again == warm, "the first region did not coalesce after the flush");
         pool.release(again); pool.flush(); pool.trim(); EXPECT(g_mapped == 0 && pool.bytes_cached == 0, "trim");
     }
+    return 0;
+}
+
+// a failed call hands back what it allocated after its mark (DevPool::rollback), with and without red zones
+static int rollback_cases(size_t rz)
+{
+    DevPool pool; pool.be_malloc = be_malloc; pool.be_free = be_free;
+    if (rz) with_redzone(pool, rz);
+    auto settle = [&]() { if (rz) pool.flush(); };              // (red zones: released blocks are quarantined until the call's end)
+    auto accounting = [&]() { return pool.bytes_live + pool.bytes_cached == pool.bytes_mapped() && pool.bytes_mapped() == g_mapped; };
+    {   // blocks older than the mark survive, newer ones are released; live bytes return to their value at the mark
+        void *old1 = pool.alloc(3u << 20), *old2 = pool.alloc(1000);
+        const size_t live0 = pool.bytes_live;
+        const unsigned long long m = pool.mark();
+        void *n1 = pool.alloc(5u << 20), *n2 = pool.alloc(77), *n3 = pool.alloc(2u << 20);
+        EXPECT(n1 && n2 && n3 && pool.bytes_live > live0, "alloc");
+        pool.release(n2);                                        // released inside the call: not the rollback's to release again
+        EXPECT(pool.rollback(m) == 2, "rollback released the wrong number of blocks");
+        settle();
+        EXPECT(live_blocks(pool) == 2 && pool.bytes_live == live0, "live %zu blocks / %zu bytes after the rollback, %zu bytes at the mark", live_blocks(pool), pool.bytes_live, live0);
+        EXPECT(!pool.segs.at((char *)old1).free && !pool.segs.at((char *)old2).free, "a block older than the mark was released");
+        EXPECT(pool.rollback(m) == 0, "a second rollback released something");
+        EXPECT(accounting(), "accounting after the rollback");
+        pool.release(old1); pool.release(old2); settle();
+    }
+    {   // a block released after the mark and handed out again at the same address is newer than the mark (a list of the live
+        // addresses at the mark would keep it)
+        char *a = (char *)pool.alloc(1u << 20);
+        const unsigned long long m = pool.mark();
+        pool.release(a); settle();
+        char *b = (char *)pool.alloc(1u << 20);
+        EXPECT(b == a, "the released block was not handed out again at its address (test premise)");
+        EXPECT(pool.rollback(m) == 1, "the block re-allocated at an old address survived the rollback");
+        settle();
+        EXPECT(live_blocks(pool) == 0 && pool.bytes_live == 0 && accounting(), "after the rollback");
+    }
+    if (rz) {   // quarantined blocks are left alone: released once, not twice; the flush hands them back
+        const unsigned long long m = pool.mark();
+        void *q = pool.alloc(4096), *l = pool.alloc(8192);
+        pool.release(q);
+        const size_t live1 = pool.bytes_live;
+        EXPECT(pool.rollback(m) == 1 && pool.segs.at((char *)q).quar && pool.segs.at((char *)l).quar, "rollback and the quarantine");
+        EXPECT(pool.bytes_live == live1, "a quarantined block's bytes changed at the rollback");
+        char msg[320];
+        EXPECT(pool.check(msg, sizeof msg) == 0, "clean zones reported: %s", msg);
+        pool.flush();
+        EXPECT(live_blocks(pool) == 0 && pool.bytes_live == 0 && accounting(), "after the flush");
+    }
+    pool.trim();
+    EXPECT(g_mapped == 0 && pool.bytes_cached == 0, "trim");
     return 0;
 }
 
@@ -134,14 +186,19 @@ static int random_sequence(unsigned seed, size_t redzone)
             }
             // no two adjacent free segments of one region (they must have joined)
             for (auto it = pool.segs.begin(); it != pool.segs.end(); ++it) { auto nx = std::next(it); if (nx != pool.segs.end() && it->second.free && nx->second.free && it->second.region == nx->second.region) { std::printf("FAIL uncoalesced\n"); return 1; } }
-            if (pool.snapshot().size() != live.size()) { std::printf("FAIL snapshot\n"); return 1; }
+            if (live_blocks(pool) != live.size()) { std::printf("FAIL live blocks\n"); return 1; }
         }
     }
-    // release_all_but keeps exactly the named blocks
-    std::vector<void *> keep; for (size_t i = 0; i < live.size(); i += 2) keep.push_back(live[i].p);
+    // rollback to a mark releases exactly the blocks handed out after it
+    const unsigned long long m = pool.mark();
+    std::vector<void *> keep; for (auto &b : live) keep.push_back(b.p);
     std::sort(keep.begin(), keep.end());
-    pool.release_all_but(keep);
-    if (pool.snapshot() != keep) { std::printf("FAIL release_all_but\n"); return 1; }
+    size_t added = 0;
+    for (int i = 0; i < 50; ++i) added += pool.alloc(1 + rng() % (4u << 20)) != nullptr;
+    if (pool.rollback(m) != added) { std::printf("FAIL rollback count\n"); return 1; }
+    pool.flush();
+    if (pool.bytes_live + pool.bytes_cached != pool.bytes_mapped()) { std::printf("FAIL accounting after the rollback\n"); return 1; }
+    { std::vector<void *> now; for (auto &kv : pool.segs) if (!kv.second.free && !kv.second.quar) now.push_back(kv.first); if (now != keep) { std::printf("FAIL rollback\n"); return 1; } }
     for (void *p : keep) pool.release(p);
     pool.flush();
     pool.trim();
@@ -153,7 +210,7 @@ static int random_sequence(unsigned seed, size_t redzone)
 int main(int argc, char **argv)
 {
     const unsigned seed = argc > 1 ? (unsigned)atoi(argv[1]) : 1;
-    if (random_sequence(seed, 0) || random_sequence(seed, 64) || redzone_cases()) return 1;
+    if (random_sequence(seed, 0) || random_sequence(seed, 64) || redzone_cases() || rollback_cases(0) || rollback_cases(64)) return 1;
     std::printf("OK seed %u\n", seed);
     return 0;
 }

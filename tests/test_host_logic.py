@@ -207,3 +207,42 @@ def test_scripts_compile():
         files += [os.path.join(d, f) for f in fs if f.endswith(".py")]
     for f in files:
         compile(open(f).read(), f, "exec")
+
+
+def test_every_entry_point_that_takes_a_context_opens_a_call_scope():
+    """hsk_api.hip: an extern "C" function that takes an hsk_ctx * opens an ApiCall (device, tuning and plan flags for the thread, a fresh
+    CallState, a pool mark; at its end the rollback of a failed call and the red-zone check) unless it only reads or releases.  Nothing else
+    selects the context's device or enters it: enter_ctx( and hipSetDevice(c->cfg.device) appear only inside ApiCall, hsk_init and hsk_destroy."""
+    import glob
+    import re
+    exempt = {"hsk_last_error", "hsk_get_stats", "hsk_result_free", "hsk_synth_free", "hsk_comm_destroy", "hsk_destroy"}
+    src_dir = os.path.join(util.ROOT, "hysortk_amd", "csrc")
+    api = open(os.path.join(src_dir, "hsk_api.hip")).read()
+
+    def body(text, start):
+        """the braces' contents of the function or struct whose header starts at `start`"""
+        i = text.index("{", start)
+        depth = 0
+        for j in range(i, len(text)):
+            depth += {"{": 1, "}": -1}.get(text[j], 0)
+            if depth == 0:
+                return text[i:j + 1]
+        raise AssertionError("unbalanced braces")
+
+    entries = {}
+    for m in re.finditer(r'extern "C" [\w\s\*]+?\b(hsk_\w+)\(([^)]*)\)\s*\{', api):
+        if re.search(r"hsk_ctx\s*\*", m.group(2)):
+            entries[m.group(1)] = body(api, m.start())
+    assert len(entries) > 20 and {"hsk_count", "hsk_init", "hsk_stage_sort", "hsk_copy_peak"} <= set(entries)
+    unscoped = sorted(n for n, b in entries.items() if n not in exempt and not re.search(r'ApiCall\(c, "%s"\)\.run\(' % n, b))
+    assert unscoped == []
+    assert sorted(n for n in exempt if n in entries and "ApiCall" in entries[n]) == []
+
+    allowed = [body(api, api.index("struct ApiCall {")), entries["hsk_init"], entries["hsk_destroy"]]
+    for f in glob.glob(os.path.join(src_dir, "*")):
+        text = open(f).read()
+        for a in allowed:
+            text = text.replace(a, "")
+        text = text.replace("static void enter_ctx(hsk_ctx *c)", "")
+        assert not re.search(r"\benter_ctx\(|hipSetDevice\(c->cfg\.device\)", text), os.path.basename(f)
+        assert not re.search(r"\b(snapshot|release_all_but|redzone_end_call)\(|PlanReset", text), os.path.basename(f)
