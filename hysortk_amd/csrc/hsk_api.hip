@@ -292,6 +292,7 @@ extern "C" int hsk_get_stats(hsk_ctx *c, hsk_stats *out, int reset)
 #include "hsk_host_scatter.h"
 #include "hsk_host_combine.h"
 #include "hsk_host_finish.h"
+#include "hsk_host_result.h"
 #include "hsk_host_pipeline.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -323,7 +324,7 @@ static int estimate_plan(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const
     const auto t0 = std::chrono::steady_clock::now();
     u64 want = std::min<u64>(std::max<u64>(packed_bytes / 64, MIN_SAMPLE), MAX_SAMPLE);      // (10 Gbp: 40 MB of reads, ~4 M chosen k-mer instances: 1.2 ms of kernels)
     u64 lost = 0, n1 = 0, n2 = 0, n3 = 0, ds = 0, ns = 0, s_bytes = 0;
-    unsigned long long *h_out = (unsigned long long *)((char *)c->pinned + c->pinned_bytes - 512);
+    unsigned long long *h_out = (unsigned long long *)staging(c)->estimate;
     for (int round = 0; round < 2; ++round) {
         const u64 exp_ins = want * 4 / (1ULL << EST_SELECT_BITS) + 1024;
         u64 cap = 1ULL << 16; while (cap < exp_ins * 4) cap <<= 1;
@@ -463,7 +464,7 @@ static int upload_input(hsk_ctx *c, const uint8_t *packed, uint64_t packed_bytes
         HIPCHK(c, hipStreamSynchronize(c->stream));     // host buffers (and &packed_bytes) may go away after return
     } else {
         // hsk_count returns after the pipeline's final wait: the caller's buffers outlive the copies, only the stack value needs a home
-        u64 *stage = (u64 *)((char *)c->pinned + c->pinned_bytes - 256);
+        u64 *stage = &staging(c)->packed_bytes;
         *stage = packed_bytes;
         HIPCHK(c, hipMemcpyAsync(d.roff + nreads, stage, 8, hipMemcpyHostToDevice, c->stream));
     }
@@ -533,7 +534,7 @@ static int derive_input(hsk_ctx *c, uint64_t packed_bytes, const uint64_t *off, 
     DALLOC(c, d.rlen, u32 *, (nreads + 1) * 4);
     DALLOC(c, d_given, u64 *, (nreads + 1) * 8);
     DALLOC(c, d_tsum, u64 *, ntl * 8 + 64);
-    u64 *stage = (u64 *)((char *)c->pinned + c->pinned_bytes - 256);
+    u64 *stage = &staging(c)->packed_bytes;
     *stage = packed_bytes;
     // Fixed-length reads (sequencer output): three samples say so, the device fills in the lengths, and the host threads that
     // compare the offsets anyway verify EVERY length while the GPU scans -- 4 bytes per read less on the link (267 MB of 2.8 GB at
@@ -609,7 +610,7 @@ extern "C" int hsk_count_device(hsk_ctx *c, const void *d_packed, uint64_t packe
         // the kernels index roff[r+1]: build the (nreads+1)-entry offset array
         u64 *roff; DALLOC(c, roff, u64 *, (nreads + 1) * 8);
         if (nreads) HIPCHK(c, hipMemcpyAsync(roff, d_off, nreads * 8, hipMemcpyDeviceToDevice, c->stream));
-        u64 *stage = (u64 *)((char *)c->pinned + c->pinned_bytes - 256);
+        u64 *stage = &staging(c)->packed_bytes;
         *stage = packed_bytes;
         HIPCHK(c, hipMemcpyAsync(roff + nreads, stage, 8, hipMemcpyHostToDevice, c->stream));
         const int rc = dispatch_pipeline(c, (const u8 *)d_packed, packed_bytes, roff, (const u32 *)d_len, nreads, rid_base, out);
@@ -1049,7 +1050,7 @@ extern "C" int hsk_format_entries(hsk_ctx *c, const void *entries, uint64_t n, i
         DALLOC(c, d_tile, u64 *, ntiles * 8 + 64); DALLOC(c, d_total, u64 *, 256);
         hipLaunchKernelGGL(format_entries_kernel<false>, dim3((u32)ntiles), dim3(FMT_THREADS), 0, c->stream, d_e, n, nw, c->cfg.kmer_size, d_tile, (char *)nullptr);
         hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_tile, ntiles, d_total);
-        u64 *tot = (u64 *)((char *)c->pinned + c->pinned_bytes - 128);
+        u64 *tot = &staging(c)->total;
         HIPCHK(c, hipMemcpyAsync(tot, d_total, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         *nbytes = tot[0];

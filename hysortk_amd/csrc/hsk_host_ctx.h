@@ -155,6 +155,29 @@ struct hsk_ctx {
     bool forbid_long_way = false;      // heavy-hitter pre-aggregation: a task the aggregating finish cannot handle is reported, not redone
 };
 
+// The staging words at the end of hsk_ctx::pinned: small device results the host waits for, and host words a copy reads.  One field per
+// user, at the offset the user has always had (the kernels and copies see the same addresses); a field with several users says why
+// they are never live together.
+struct PinnedTail {
+    unsigned char agg[2][512];         // agg_stage1 / agg_stage2: the AggHostRead of the batch in slot 0 / 1
+    unsigned char free0[1024];
+    u64 pairs[2][16];                  // combining extraction: pairs per task + error word of the batch in slot 0 / 1 (combine_batch -> process_rank)
+    unsigned char free1[1280];
+    u64 estimate[16];                  // estimate_plan: the sample's counters
+    unsigned char free2[64];
+    u32 parse_flags[16];               // parse_count, parse_ingest_pipelined: overflow, error word, chunks, dropped k-mers.  One parse per attempt: the
+                                       // pipelined ingest has read its words before it falls back to parse_count
+    alignas(64) u64 packed_bytes;      // the last read offset on its way to the device: one entry point per call writes it, and every call ends with a wait
+    alignas(64) u32 sort_flag;         // sort_task_device: a long bin with several keys
+    alignas(64) u64 total;             // count_task_device, merge_sorted_pairs, hsk_format: entries kept -- copied, waited for and read on the spot
+    alignas(64) u32 err;               // the sticky device error word: check_device_error and the end of process_rank, each copy, wait and read in one go
+};
+static_assert(sizeof(PinnedTail) == 4096, "the staging words are the last 4096 bytes of the pinned block");
+static_assert(offsetof(PinnedTail, agg) == 4096 - 4096 && offsetof(PinnedTail, pairs) == 4096 - 2048 && offsetof(PinnedTail, estimate) == 4096 - 512, "staging offsets");
+static_assert(offsetof(PinnedTail, parse_flags) == 4096 - 320 && offsetof(PinnedTail, packed_bytes) == 4096 - 256 && offsetof(PinnedTail, sort_flag) == 4096 - 192, "staging offsets");
+static_assert(offsetof(PinnedTail, total) == 4096 - 128 && offsetof(PinnedTail, err) == 4096 - 64, "staging offsets");
+static PinnedTail *staging(hsk_ctx *c) { return (PinnedTail *)((char *)c->pinned + c->pinned_bytes - sizeof(PinnedTail)); }
+
 // HSK_FLAG_NO_AGGREGATION / HSK_FLAG_FULL_SORT of the context whose call is running on this thread (set by the counting entry
 // points): the plan switches below (agg_enabled, hybrid_enabled, finish_enabled) are asked in places that have no context at hand
 static thread_local int g_plan_flags = 0;

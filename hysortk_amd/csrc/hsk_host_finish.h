@@ -22,7 +22,7 @@ static int count_task_device(hsk_ctx *c, const u64 *keys, const u64 *vals, u64 n
     a.tile_cnt = d_tile_cnt; a.histo = d_histo; a.histo_len = histo_len; a.payoff_add = payoff_add;
     hipLaunchKernelGGL((count_kernel<NW, false, false>), dim3((u32)ntiles), dim3(CNT_THREADS), 0, c->stream, a);
     hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_tile_cnt, ntiles, d_total);
-    u64 *tot = (u64 *)((char *)c->pinned + c->pinned_bytes - 128);
+    u64 *tot = &staging(c)->total;
     HIPCHK(c, hipMemcpyAsync(tot, d_total, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hsk_sync(c, c->stream));
     out.n = tot[0]; out.npay = ext ? n : 0;
@@ -190,6 +190,7 @@ static bool agg_enabled()
 //               compaction and sends tasks the tables cannot take the long way.
 // prefix_bits = 16: bins of the top 16 bits (two scatter passes), small tables with a retry ladder and the long way.
 struct AggHostRead { u32 flags[AG_BATCH]; u32 maxd[AG_BATCH]; u32 ovf[2][AG_BATCH]; u64 total[AG_BATCH]; };   // mirrors the device control block (+ totals)
+static_assert(sizeof(AggHostRead) <= sizeof PinnedTail().agg[0], "a slot of the pinned staging words holds one AggHostRead");
 struct AggPending {
     bool active = false;
     BatchTask bt[AG_BATCH];
@@ -287,7 +288,7 @@ static int agg_stage1(hsk_ctx *c, const BatchTask *bt, int K, int prefix_bits, i
     p.slot_shift = (L >= 2 && !weighted) ? 1 : 0;       // a bin of n records keeps at most n / L entries (pairs: every record may be an entry)
     p.big = false;                                      // (8-bit bins: the one-pass experiment of rounds 1-2, removed)
     p.nbins = 1u << prefix_bits; p.K = K;
-    p.h = (AggHostRead *)((char *)c->pinned + c->pinned_bytes - 4096 + (size_t)slot * 512);
+    p.h = (AggHostRead *)staging(c)->agg[slot];
     memset(p.h, 0, sizeof *p.h);
     const u32 nbins = p.nbins;
     const size_t per = (size_t)nbins + 8;
@@ -373,7 +374,7 @@ static int merge_sorted_pairs(hsk_ctx *c, const u64 *sk, const u64 *sv, u64 n, u
     a.keys = sk; a.cnts = sv; a.n = n; a.lower = (u64)c->cfg.lower_freq; a.upper = (u64)c->cfg.upper_freq; a.tile_cnt = d_tile; a.histo = d_histo; a.histo_len = histo_len;
     hipLaunchKernelGGL((heavy_merge_kernel<NW, false>), dim3((u32)ntiles), dim3(HV_THREADS), 0, c->stream, a);
     hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_tile, ntiles, d_total);
-    u64 *tot = (u64 *)((char *)c->pinned + c->pinned_bytes - 128);
+    u64 *tot = &staging(c)->total;
     HIPCHK(c, hipMemcpyAsync(tot, d_total, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hsk_sync(c, c->stream));
     out.n = tot[0];

@@ -237,7 +237,7 @@ static int parse_count(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u
     DALLOC(c, j.d_blk_cnt, u64 *, (size_t)1024 * ntasks * 3 * 8);
     a.blk_cnt = j.d_blk_cnt;
     u64 *d_task_tot; DALLOC(c, d_task_tot, u64 *, (size_t)ntasks * 3 * 8 + 64);
-    u32 *h_ovf = (u32 *)((char *)c->pinned + c->pinned_bytes - 320);
+    u32 *h_ovf = staging(c)->parse_flags;
     *h_ovf = 0;
     if (j.fast) {
         a.rec_cap = parse_rec_cap(c->cfg.kmer_size - c->cfg.minimizer_size + 1);
@@ -592,7 +592,7 @@ static int parse_ingest_pipelined(hsk_ctx *c, const u8 *h2d_src, const u8 *d_pac
     }
     if (profile) { (void)hipEventRecord(sp.b, sA); c->ev_pending.push_back(sp); (void)hipEventRecord(pp.b, sB); }
     // the verdicts and the totals
-    u32 *h_flags = (u32 *)((char *)c->pinned + c->pinned_bytes - 320);
+    u32 *h_flags = staging(c)->parse_flags;
     std::vector<u64> tot((size_t)nsl * ntasks * 3);
     u64 *h_tot = (u64 *)((char *)c->pinned + (192u << 10));
     const bool staged = (size_t)nsl * ntasks * 24 <= (64u << 10);

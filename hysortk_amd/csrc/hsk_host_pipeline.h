@@ -193,68 +193,6 @@ static int heavy_merge_task(hsk_ctx *c, const u64 *d_entries, u64 n, u64 *d_hist
     return HSK_OK;
 }
 
-// Host threads that widen compact result batches (pack_entries_kernel's k-mer words + 16-bit counts, copied into pinned staging)
-// into the caller-visible entries while the GPU counts the next batches.  Every thread of a batch waits for the batch's copy
-// event, then takes its slice.  The destructor joins: no thread outlives the call that started it.
-struct WidenPiece {                                                 // one task's share of a batch
-    hipEvent_t copied; const u64 *keys; const unsigned short *cnts; u64 *dst; u64 n;
-    // prefix form (one-word keys): low 48 key bits as u32 + u16, counts of cw bytes, dir[p] = first entry of prefix p (dir[65536] = n)
-    const u32 *lo32 = nullptr; const unsigned short *mid16 = nullptr; const u8 *cnt8 = nullptr; const u32 *dir = nullptr; int cw = 0;
-};
-struct WidenPool {
-    hsk_ctx *c;
-    std::vector<std::thread> th;
-    std::vector<hipEvent_t> evs;
-    explicit WidenPool(hsk_ctx *c_) : c(c_) {}
-    static int nthreads()
-    {
-        { const int v = (int)tune("widen_threads", 0); if (v > 0) return std::min(v, 64); }
-        static const int n = []() { const unsigned hc = std::thread::hardware_concurrency(); return (int)std::min<unsigned>(32, std::max<unsigned>(2, hc / 2)); }();
-        return n;
-    }
-    // A batch arrives task by task (one copy + one event per piece): thread t widens slice t of every piece in turn, so that all
-    // threads are done shortly after the LAST piece has landed -- the tail of the call is one piece's widening, not one batch's.
-    void add(const std::vector<WidenPiece> &pieces, int nw)
-    {
-        for (auto &p : pieces) evs.push_back(p.copied);
-        const int nt = nthreads(), dev = c->cfg.device;
-        for (int t = 0; t < nt; ++t) {
-            th.emplace_back([=]() {
-                (void)hipSetDevice(dev);
-                for (const WidenPiece &p : pieces) {
-                    (void)hipEventSynchronize(p.copied);
-                    const u64 lo = p.n * (u64)t / nt, hi = p.n * (u64)(t + 1) / nt;
-                    const u64 *keys = p.keys; const unsigned short *cnts = p.cnts; u64 *dst = p.dst;
-                    if (p.dir) {                                       // prefix form: the top 16 key bits come from the directory
-                        if (lo >= hi) continue;
-                        typedef unsigned long long v2u64p __attribute__((vector_size(16)));
-                        u32 pl = 0, ph = 65536;                        // last prefix that starts at or before entry lo
-                        while (ph - pl > 1) { const u32 mid = (pl + ph) >> 1; if ((u64)p.dir[mid] <= lo) pl = mid; else ph = mid; }
-                        u32 pre = pl; u64 next = p.dir[pre + 1];
-                        const bool nt = ((uintptr_t)dst & 15) == 0;
-                        for (u64 i = lo; i < hi; ++i) {
-                            while (i >= next) { ++pre; next = p.dir[pre + 1]; }
-                            const unsigned long long key = ((unsigned long long)pre << 48) | ((unsigned long long)p.mid16[i] << 32) | p.lo32[i];
-                            const unsigned long long cv = p.cw == 1 ? (unsigned long long)p.cnt8[i] : (unsigned long long)reinterpret_cast<const unsigned short *>(p.cnt8)[i];
-                            if (nt) { const v2u64p e = {key, cv}; __builtin_nontemporal_store(e, (v2u64p *)dst + i); }
-                            else { dst[2 * i] = key; dst[2 * i + 1] = cv; }
-                        }
-                        continue;
-                    }
-                    // one-word keys: an entry is one aligned 16-byte store that nobody reads back soon -- non-temporal (no read for
-                    // ownership: a plain store loop is bound by the cache lines it first has to fetch)
-                    typedef unsigned long long v2u64 __attribute__((vector_size(16)));
-                    if (nw == 1 && ((uintptr_t)dst & 15) == 0) for (u64 i = lo; i < hi; ++i) { const v2u64 e = {keys[i], (unsigned long long)cnts[i]}; __builtin_nontemporal_store(e, (v2u64 *)dst + i); }
-                    else if (nw == 1) for (u64 i = lo; i < hi; ++i) { dst[2 * i] = keys[i]; dst[2 * i + 1] = cnts[i]; }
-                    else for (u64 i = lo; i < hi; ++i) { for (int w = 0; w < nw; ++w) dst[i * (nw + 1) + w] = keys[i * nw + w]; dst[i * (nw + 1) + nw] = cnts[i]; }
-                }
-            });
-        }
-    }
-    void join() { for (auto &t : th) if (t.joinable()) t.join(); th.clear(); for (auto e : evs) ev_put(c, e); evs.clear(); }
-    ~WidenPool() { join(); }
-};
-
 struct HeavyIn { u32 task; u64 *d_entries; u64 n; };       // a heavy task this rank owns: concatenated lists of all ranks
 struct ProcExtra {
     bool force_batch = false;                              // every task through the batch kernels (partial batches padded)
@@ -263,58 +201,78 @@ struct ProcExtra {
     SupermerStore *items_store = nullptr;                  // item-mode store of one GPU: its items go back to the pool as soon as the bucket order has read them
 };
 
-// Everything after the supermers of the owned tasks are in place: per task expand, sort, count; then the
-// result of this rank.  `segs[t]` lists where the supermers of task t live (x_len / x_src / x_pos / x_rid).
-template <int NW>
-static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owner, int rank, std::vector<TaskSegs> &segs,
-                        const u8 *x_len, const BaseSource &x_src, const u32 *x_pos, const int32_t *x_rid,
-                        hsk_result *out, ResultPriv *rp, PhaseTimer &pt, bool pt_total_open, GroupFeeder *feeder = nullptr,
-                        const ProcExtra *ex = nullptr)
-{
-    const bool ext = c->cfg.extension != 0;
-    const int K = c->cfg.kmer_size;
-    u64 max_task = 0, total_kmers = 0;
-    for (u32 t = 0; t < ntasks; ++t) { finalize_segs(segs[t]); max_task = std::max(max_task, segs[t].nkmers); total_kmers += segs[t].nkmers; }
-    out->total_kmers = total_kmers;
-    if (c->call.est.valid && NW == 1 && !ext && !c->forbid_long_way && max_task) {
-        // distinct keys per 16-bit prefix bin of the largest task, from this call's estimate: the first table of the ladder, or no tables at all
-        // (most bins beyond 2048 slots: four prefix passes + the tile finish; what a batch used to find out the hard way, agg_stage2)
-        const double d = c->call.est.distinct_per_kmer * (double)max_task / 65536.0;
-        c->agg_first_cap = d <= 600.0 ? AG_LOG2CAP_SMALL : d <= 1250.0 ? AG_LOG2CAP_MEDIUM : AG_LOG2CAP_LARGE;
-        if (d > 1450.0 && !(ex && ex->vt_shift) && !x_src.item) { c->agg_off = true; c->agg_off_calls = 0; }
-    }
+static bool agg_is_off(const hsk_ctx *c, int nw) { return nw == 1 ? c->agg_off : c->agg_off_wide; }      // (run-time state: may change in the middle of a call)
 
-    // ---- per task: expand, sort, count ---------------------------------------------------------------
-    const u32 histo_len = (u32)std::min<int64_t>((int64_t)c->cfg.upper_freq + 1, 65536);    // (U <= 65535 except in the unfiltered pre-aggregation)
-    u64 *d_histo; DALLOC(c, d_histo, u64 *, (size_t)histo_len * 8);
-    HIPCHK(c, hipMemsetAsync(d_histo, 0, (size_t)histo_len * 8, c->stream));
+// Result of an all-reduce with status (Comm::allreduce_with_status) -> return code of this rank: 0 everybody is fine; the transport failed; this
+// rank (local_rc) or another one (peer_msg, may name `what` as %s) has failed since the last collective and all ranks leave together.
+static int left_together(hsk_ctx *c, int st, const char *what, int local_rc, const char *peer_msg)
+{
+    if (st == 0) return HSK_OK;
+    if (st < 0) return fail(c, HSK_ERR_COMM, "allreduce(%s) failed: %d (%s)", what, st, c->comm.last_error.c_str());
+    return local_rc ? local_rc : fail(c, HSK_ERR_COMM, peer_msg, what);
+}
+
+// Step of its own, before the plan reads hsk_ctx::agg_off: this call's estimate says how many distinct keys a 16-bit prefix bin of the largest
+// task holds -- the first table of the ladder, or no tables at all (most bins beyond 2048 slots: four prefix passes + the tile finish; what a batch
+// used to find out the hard way, agg_stage2).  `items`: the store holds items (or virtual tasks), which only the aggregating finish can take.
+static void first_table_from_estimate(hsk_ctx *c, int nw, u64 max_task, bool items)
+{
+    if (!c->call.est.valid || nw != 1 || c->cfg.extension || c->forbid_long_way || !max_task) return;
+    const double d = c->call.est.distinct_per_kmer * (double)max_task / 65536.0;
+    c->agg_first_cap = d <= 600.0 ? AG_LOG2CAP_SMALL : d <= 1250.0 ? AG_LOG2CAP_MEDIUM : AG_LOG2CAP_LARGE;
+    if (d > 1450.0 && !items) { c->agg_off = true; c->agg_off_calls = 0; }
+}
+
+// What a rank's count will do, decided once (plan_rank) from the context's flags and tuning, the owned tasks' sizes, the feeder, the kind of
+// store and ProcExtra; const afterwards.  What may change while the batches run (hsk_ctx::agg_off, agg_off_wide, combine_off, the result
+// copier giving up its early copies) is not here: it is read where a batch needs it.
+template <int NW>
+struct RankPlan {
+    static constexpr int XS_CH = XsCfg<(NW <= 2 ? NW : 1)>::CHUNK;
+    bool ext = false; int K = 0; u64 max_task = 0;
+    std::vector<u32> mine;             // the owned, non-empty tasks in ascending id; padded with EMPTY_TASK to whole batches where that pays
+    bool batch = false;                // eight tasks at a time, one per XCD (a remainder: the single-task kernels)
+    bool fused = false, agg = false, fused_ext = false;      // the finish a batch may take
+    bool lag = false;                  // two batches in flight (two slots)
+    bool xs = false;                   // expand fused with the first scatter pass
+    bool item_mode = false, combine = false, fed_combine = false;      // the combining extraction: at all / on items the owner builds (several ranks)
+    u64 rec_cap = 0;                   // records a task's sort buffers hold
+    bool early = false; int compact_mode = 0;      // the result's way to the host (ResultCopier)
+    int retry = HSK_OK;                // HSK_RETRY_PLAN: this store is no use to this plan, the call starts again
+    int nslot() const { return lag ? 2 : 1; }
+    int nsets() const { return batch ? XCD_BATCH : 1; }
+    bool own_items() const { return combine && !fed_combine; }      // one GPU: the store holds the items, one bucket order for all tasks
+};
+
+template <int NW>
+static RankPlan<NW> plan_rank(const hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owner, int rank, const std::vector<TaskSegs> &segs, u64 max_task, const GroupFeeder *feeder, bool item_mode, const ProcExtra *ex)
+{
+    RankPlan<NW> p; p.max_task = max_task; p.item_mode = item_mode;
+    const bool ext = p.ext = c->cfg.extension != 0;
+    const int K = p.K = c->cfg.kmer_size;
     // Tasks are sorted eight at a time, one per XCD (sort_batch_device); a remainder of fewer than eight
     // tasks goes through the single-task kernel.  HSK_XCD_BATCH=0 forces the single-task path.
-    const bool batch_env = tune("xcd_batch", 1) != 0;
-    const bool batch_enabled = batch_env && c->xcd_batch_ok;          // the one-task-per-XCD kernels need all eight XCDs (hsk_init's census)
-    std::vector<u32> mine;
+    const bool batch_enabled = tune("xcd_batch", 1) != 0 && c->xcd_batch_ok;          // the one-task-per-XCD kernels need all eight XCDs (hsk_init's census)
+    std::vector<u32> &mine = p.mine;
     for (u32 t = 0; t < ntasks; ++t) if (owner[t] == rank && segs[t].nkmers) mine.push_back(t);
-    // A remainder of three or more tasks is padded to a full batch with empty slots (an XCD without a task idles, which
-    // still beats eight full-width passes per task on the single-task path); ex->force_batch pads any remainder.
-    const u32 EMPTY_TASK = ~0u;
-    TaskSegs empty_segs;
-    std::vector<TaskOut> touts(ntasks);
     // several ranks, the supermers arrived with their minimizer bits: the owner builds the items, batch by batch (hsk_combine.h, 1b)
     const bool fed_wanted = NW <= 2 && feeder && feeder->with_sub && c->call.combine_now && !ext;
-    const bool forced = ((ex && ex->force_batch) || x_src.item != nullptr || fed_wanted) && batch_enabled;      // (item-mode store: every task goes through whole batches)
+    const bool forced = ((ex && ex->force_batch) || item_mode || fed_wanted) && batch_enabled;      // (item-mode store: every task goes through whole batches)
     // a caller's task count below eight (the reference's default for one rank is five): three to seven tasks of some size still
     // go faster as one padded batch (5/8 of the batch path's rate) than one by one on the single-task path (about 1/3 of it)
     u64 mine_kmers = 0; for (u32 t : mine) mine_kmers += segs[t].nkmers;
     const bool small_batch = batch_enabled && mine.size() >= 3 && mine.size() < (size_t)XCD_BATCH && mine_kmers >= (1ULL << 25);
+    // A remainder of three or more tasks is padded to a full batch with empty slots (an XCD without a task idles, which
+    // still beats eight full-width passes per task on the single-task path); ex->force_batch pads any remainder.
     if ((batch_enabled && mine.size() >= (size_t)XCD_BATCH && mine.size() % XCD_BATCH >= 3) || (forced && !mine.empty()) || small_batch)
         while (mine.size() % XCD_BATCH) mine.push_back(EMPTY_TASK);
-    const bool batch = batch_enabled && mine.size() >= (size_t)XCD_BATCH;
-    const int nsets = batch ? XCD_BATCH : 1;
+    const bool whole = mine.size() % XCD_BATCH == 0;
+    p.batch = batch_enabled && mine.size() >= (size_t)XCD_BATCH;
     // fused finish: one-word keys (aggregating or tile finish), two-word keys with K >= 40 (aggregating finish only)
-    const bool fused = !ext && finish_enabled() && (NW == 1 ? hybrid_enabled() : (NW <= 3 && agg_enabled() && prefix_plan_ok<NW>(K, true)));
-    const bool agg = fused && agg_enabled();
+    p.fused = !ext && finish_enabled() && (NW == 1 ? hybrid_enabled() : (NW <= 3 && agg_enabled() && prefix_plan_ok<NW>(K, true)));
+    p.agg = p.fused && agg_enabled();
     // EXTENSION with one-word keys: two passes on the top 16 bits (payload carried) + grouping aggregation
-    const bool fused_ext = ext && NW <= 3 && hybrid_enabled() && finish_enabled() && agg_enabled() && prefix_plan_ok<NW>(K, true);
+    p.fused_ext = ext && NW <= 3 && hybrid_enabled() && finish_enabled() && agg_enabled() && prefix_plan_ok<NW>(K, true);
     // Two batches in flight on ONE stream (two sets of sort buffers): the host enqueues expand / scatter / aggregation of
     // batch b + 1 BEFORE it waits for the aggregation totals of batch b, sizes batch b's outputs and enqueues its
     // compaction.  The GPU therefore never runs dry while the host waits (HSK_LAG=0: one batch at a time, every wait drains
@@ -327,64 +285,289 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
     const bool keep_dev = (c->cfg.flags & HSK_FLAG_KEEP_DEVICE) != 0;
     const int lag_env = (int)tune("lag", -1);
     const bool lag_enabled = lag_env < 0 ? keep_dev : lag_env != 0;
-    const bool lag = batch && agg && NW <= 2 && lag_enabled && mine.size() >= 2 * (size_t)XCD_BATCH;
-    const int nslot = lag ? 2 : 1;
+    p.lag = p.batch && p.agg && NW <= 2 && lag_enabled && mine.size() >= 2 * (size_t)XCD_BATCH;
     // expand fused with the first scatter pass (hsk_scatter.h): one-word keys, aggregating finish, whole batches
     // (EXTENSION: payload chunks beside the key chunks, HSK_FUSED_SCATTER_EXT=0 turns that variant off)
     const bool xs_ext_enabled = tune("fused_scatter_ext", 1) != 0;
     const bool xs_wide_enabled = tune("fused_scatter_wide", 1) != 0;      // two-word keys
-    constexpr int XS_CH = XsCfg<(NW <= 2 ? NW : 1)>::CHUNK;
-    const bool xs = batch && (NW == 1 ? (!ext || xs_ext_enabled) : (NW == 2 && !ext && xs_wide_enabled && prefix_top_bits(K, NW) == 16)) && scatter_enabled() &&
-                    scatter_store_keys(max_task, XS_CH) < (1ULL << 32) && finish_enabled() && hybrid_enabled() && agg_enabled() && prefix_plan_ok<NW>(K, true);
+    p.xs = p.batch && (NW == 1 ? (!ext || xs_ext_enabled) : (NW == 2 && !ext && xs_wide_enabled && prefix_top_bits(K, NW) == 16)) && scatter_enabled() &&
+           scatter_store_keys(max_task, p.XS_CH) < (1ULL << 32) && finish_enabled() && hybrid_enabled() && agg_enabled() && prefix_plan_ok<NW>(K, true);
     // the combining extraction (hsk_combine.h): the store carries the supermers' minimizer bits, whole batches, the aggregating finish
-    bool combine = false;
-    // (an item-mode store -- x_src.item -- holds nothing the instance path could read: every batch takes the combining extraction, or the
-    //  call starts again without it)
-    const bool item_mode = x_src.item != nullptr;
-    bool fed_combine = false;
+    // (an item-mode store holds nothing the instance path could read: every batch takes the combining extraction, or the call starts again
+    //  without it)
     if constexpr (NW <= 2) {
-        combine = item_mode && xs && agg && !(NW == 1 ? c->agg_off : c->agg_off_wide) && !ext && !feeder && mine.size() % XCD_BATCH == 0;
-        fed_combine = fed_wanted && !item_mode && xs && agg && !(NW == 1 ? c->agg_off : c->agg_off_wide) && batch && mine.size() % XCD_BATCH == 0;
-        combine = combine || fed_combine;
+        const bool can = p.xs && p.agg && !agg_is_off(c, NW) && whole;
+        p.fed_combine = fed_wanted && !item_mode && can && p.batch;
+        p.combine = (item_mode && can && !ext && !feeder) || p.fed_combine;
     }
-    if (item_mode && !combine) { c->call.combine_veto = true; return retry_plan("an item-mode store, but no batch to combine (xs / agg / batch)", (xs ? 1u : 0u) | (agg ? 2u : 0u) | (batch ? 4u : 0u) | ((mine.size() % XCD_BATCH == 0) ? 8u : 0u)); }
-    BucketOrder border;
-    BucketOrder border_fed[2]; FedItems fed_items[2];      // per slot: the items and the bucket order of the batch in flight (several ranks)
-    bool slot_combine[2] = {false, false};
-    ScatterBatch sbatch[2];                               // per slot
-    PassDesc xs_plan[MAX_PASSES];
-    u64 *kAs[2][XCD_BATCH] = {{nullptr}}, *kBs[2][XCD_BATCH] = {{nullptr}}, *vAs[2][XCD_BATCH] = {{nullptr}}, *vBs[2][XCD_BATCH] = {{nullptr}};
-    u64 **kA = kAs[0], **kB = kBs[0], **vA = vAs[0], **vB = vBs[0];          // slot 0: also the single-task path
-    SortScratch sc;
-    u64 *d_ghist_slot[2] = {nullptr, nullptr};
+    if (item_mode && !p.combine)
+        p.retry = retry_plan("an item-mode store, but no batch to combine (xs / agg / batch)", (p.xs ? 1u : 0u) | (p.agg ? 2u : 0u) | (p.batch ? 4u : 0u) | (whole ? 8u : 0u));
     // The combining extraction's buffers hold {k-mer, count} PAIRS, not k-mers: with the call's own estimate of the input (estimate_plan: distinct k-mers
     // per k-mer) they are sized for four times the pairs it promises (+ 2 % of the k-mers) instead of one record per k-mer -- 20 GB instead of 102 at
     // 10 Gbp, and device memory is what a process's FIRST call pays for (~20-60 ms per GB mapped for the first time, tools/exp/malloc_cost.hip).  A call
     // whose pairs do not fit after all (error bit 512: the last chunk takes what runs over) starts again with full-sized buffers.  Several ranks: full
     // size (nobody starts again while peers wait).
-    u64 rec_cap = max_task;
-    if (combine && !fed_combine && c->call.est.valid && !c->call.pair_cap_full && tune("pair_cap", 1) != 0)
-        rec_cap = std::min<u64>(max_task, std::max<u64>((u64)((double)max_task * std::min(1.0, 4.0 * c->call.est.distinct_per_kmer * c->est_bias + 0.02)), 1ULL << 22));
-    if (tune("pair_cap_records", 0) > 0 && combine && !fed_combine && !c->call.pair_cap_full) rec_cap = std::min<u64>(max_task, (u64)tune("pair_cap_records", 0));      // (tests: stores that run over; the attempt after an overrun is full size)
-    auto alloc_sort_buffers = [&]() -> int {
-        if (max_task) {
-            for (int sl = 0; sl < nslot; ++sl) for (int i = 0; i < nsets; ++i) {
-                DALLOC(c, kAs[sl][i], u64 *, rec_cap * NW * 8 + 64);
-                DALLOC(c, kBs[sl][i], u64 *, (xs ? scatter_store_keys(rec_cap, XS_CH) + XS_CH : rec_cap) * NW * 8 + 64);   // xs: the chunk store of the first pass (+ the chunk that takes what runs over)
-                if (ext || combine) { DALLOC(c, vAs[sl][i], u64 *, rec_cap * 8 + 64); DALLOC(c, vBs[sl][i], u64 *, (xs ? scatter_store_keys(rec_cap, XS_CH) + XS_CH : rec_cap) * 8 + 64); }
-            }
-            int rc = alloc_sort_scratch(c, sc); if (rc) return rc;
+    p.rec_cap = max_task;
+    if (p.own_items() && !c->call.pair_cap_full) {
+        if (c->call.est.valid && tune("pair_cap", 1) != 0)
+            p.rec_cap = std::min<u64>(max_task, std::max<u64>((u64)((double)max_task * std::min(1.0, 4.0 * c->call.est.distinct_per_kmer * c->est_bias + 0.02)), 1ULL << 22));
+        if (tune("pair_cap_records", 0) > 0) p.rec_cap = std::min<u64>(max_task, (u64)tune("pair_cap_records", 0));      // (tests: stores that run over; the attempt after an overrun is full size)
+    }
+    // result copies that overlap the kernels: host result, no payload, tasks finished in ascending id (heavy tasks finish last, out of order)
+    p.early = p.batch && p.agg && NW <= 2 && !keep_dev && !ext && tune("early_d2h", 1) != 0 && !(ex && ex->heavy_in && !ex->heavy_in->empty());
+    p.compact_mode = (int)tune("compact_d2h", 2);
+    return p;
+}
+
+// The batch in flight in one slot: its buffers, what was decided for it when it was expanded, and the aggregation that waits for its totals.
+struct BatchSlot {
+    int index = 0;
+    u64 *kA[XCD_BATCH] = {nullptr}, *kB[XCD_BATCH] = {nullptr}, *vA[XCD_BATCH] = {nullptr}, *vB[XCD_BATCH] = {nullptr};      // sort buffers (slot 0's first: also the single-task path)
+    u64 *d_ghist = nullptr;                // [XCD_BATCH][MAX_PASSES][256]
+    const u32 *tk = nullptr;               // the eight tasks (RankPlan::mine)
+    BatchTask bt[XCD_BATCH];
+    BucketOrder border_fed; FedItems fed_items;      // several ranks: the items and the bucket order of the batch
+    ScatterBatch sbatch; PassDesc xs_plan[MAX_PASSES];
+    bool combine = false;                  // the batch went through the combining extraction: its records are pairs
+    int prefix = 0;                        // the digit plan the batch was expanded for
+    // ... and which finish follows it: the aggregation (agg), the grouping aggregation of EXTENSION (fext), or -- once hsk_ctx::agg_off /
+    // agg_off_wide have found the input to hold (nearly) only unique k-mers, possibly in the middle of a call -- the tile finish (one-word
+    // keys) / full-width passes and the two-pass counter (everything else); follow: a finish that wants prefix passes only
+    bool agg = false, fext = false, follow = false;
+    AggPending pend;                       // the aggregation's second stage is still to come
+};
+
+template <int NW>
+static int alloc_batch_buffers(hsk_ctx *c, const RankPlan<NW> &P, BatchSlot *slots, SortScratch &sc)
+{
+    // xs: the chunk store of the first pass (+ the chunk that takes what runs over)
+    const u64 chunked = P.xs ? scatter_store_keys(P.rec_cap, P.XS_CH) + P.XS_CH : P.rec_cap;
+    if (P.max_task) {
+        for (int sl = 0; sl < P.nslot(); ++sl) for (int i = 0; i < P.nsets(); ++i) {
+            BatchSlot &s = slots[sl];
+            DALLOC(c, s.kA[i], u64 *, P.rec_cap * NW * 8 + 64); DALLOC(c, s.kB[i], u64 *, chunked * NW * 8 + 64);
+            if (P.ext || P.combine) { DALLOC(c, s.vA[i], u64 *, P.rec_cap * 8 + 64); DALLOC(c, s.vB[i], u64 *, chunked * 8 + 64); }
         }
-        if (batch) for (int sl = 0; sl < nslot; ++sl) DALLOC(c, d_ghist_slot[sl], u64 *, (size_t)XCD_BATCH * MAX_PASSES * 256 * 8);
-        return HSK_OK;
+        int rc = alloc_sort_scratch(c, sc); if (rc) return rc;
+    }
+    if (P.batch) for (int sl = 0; sl < P.nslot(); ++sl) DALLOC(c, slots[sl].d_ghist, u64 *, (size_t)XCD_BATCH * MAX_PASSES * 256 * 8);
+    return HSK_OK;
+}
+static void release_batch_buffers(hsk_ctx *c, BatchSlot *slots, SortScratch &sc)
+{
+    for (int sl = 0; sl < 2; ++sl) for (int i = 0; i < XCD_BATCH; ++i) { BatchSlot &s = slots[sl]; c->pool.release(s.kA[i]); c->pool.release(s.kB[i]); c->pool.release(s.vA[i]); c->pool.release(s.vB[i]); }
+    free_sort_scratch(c, sc);
+    c->pool.release(slots[0].d_ghist); c->pool.release(slots[1].d_ghist);
+}
+
+// one launch expands the eight tasks tk[] into the slot's buffers and counts the digits of the passes that follow
+template <int NW>
+static int expand_slot(hsk_ctx *c, const RankPlan<NW> &P, BatchSlot &s, const u32 *tk, u32 ntasks, const std::vector<TaskSegs> &segs, const GroupFeeder *feeder, const TaskInput &dflt, const BucketOrder &border, PhaseTimer &pt)
+{
+    s.tk = tk;
+    s.agg = P.agg && !agg_is_off(c, NW);
+    s.fext = P.fused_ext && !c->agg_off_wide;
+    s.follow = s.agg || s.fext || (NW == 1 && P.fused);
+    const bool will_combine = P.combine && (P.fed_combine || border.active) && s.agg;
+    // (several ranks: the batch simply takes the instance path -- nobody starts a call again while peers wait)
+    if (P.own_items() && !will_combine) { c->call.combine_veto = true; return retry_plan("a batch that cannot take the combining extraction"); }
+    // (two-word keys: the finish orders a bin's keys by the bits below a 16-bit prefix, agg_order_many -- their pairs take bins of 16 bits)
+    const int prefix_bits = will_combine ? (NW == 1 ? combine_prefix_bits(c) : AG_PREFIX_BITS) : (s.agg || s.fext) ? AG_PREFIX_BITS : 64 - HYBRID_SHIFT;
+    s.prefix = prefix_bits;
+    PassDesc plan[MAX_PASSES];
+    int npass = batch_pass_plan<NW>(c, P.K, s.follow, will_combine ? AG_PREFIX_BITS : prefix_bits, plan);
+    // the pairs' two digits (most significant word): the low prefix bits, then the top 8
+    if (will_combine) { npass = 2; plan[0] = PassDesc{NW - 1, 64 - prefix_bits, prefix_bits - 8}; plan[1] = PassDesc{NW - 1, 56, 8}; }
+    pt.begin(PH_EXTRACT);
+    HIPCHK(c, hipMemsetAsync(s.d_ghist, 0, (size_t)XCD_BATCH * MAX_PASSES * 256 * 8, c->stream));
+    TaskSegs empty_segs;
+    ExpandJob jobs[XCD_BATCH]; const unsigned short *s16[XCD_BATCH]; u64 *gh[XCD_BATCH];
+    for (int i = 0; i < XCD_BATCH; ++i) {
+        const u32 t = tk[i];
+        BatchTask &b = s.bt[i];
+        b = BatchTask();
+        b.kA = s.kA[i]; b.kB = s.kB[i];
+        if (P.ext || will_combine) { b.vA = s.vA[i]; b.vB = s.vB[i]; }      // (the payload buffers mean "records carry a payload" to everything downstream)
+        gh[i] = s.d_ghist + (size_t)i * MAX_PASSES * 256; s16[i] = nullptr;
+        if (t == EMPTY_TASK) { jobs[i] = ExpandJob(); jobs[i].ts = &empty_segs; continue; }
+        b.n = segs[t].nkmers;
+        const TaskInput in = feeder ? feeder->input(t) : dflt;
+        jobs[i].ts = &segs[t]; jobs[i].sm_len = in.len; jobs[i].src = in.src; jobs[i].sm_pos = in.pos; jobs[i].sm_rid = in.rid; s16[i] = in.sub16;
+        jobs[i].keys = b.kA; jobs[i].vals = b.vA; jobs[i].ghist = gh[i];
+    }
+    int rc;
+    s.combine = false;
+    if (will_combine) {
+        if constexpr (NW <= 2) {
+            memcpy(s.xs_plan, plan, sizeof(PassDesc) * 2);
+            u64 *h_nout = staging(c)->pairs[s.index];
+            if (P.fed_combine) {
+                std::vector<TaskSegs> gsegs; BaseSource gsrc;
+                rc = build_items_batch(c, ntasks, tk, jobs, s16, gsegs, gsrc, s.fed_items, c->stream); if (rc) return rc;
+                rc = bucket_order_tasks(c, ntasks, gsegs, std::vector<u32>(tk, tk + XCD_BATCH), gsrc, FED_VT_SHIFT, s.border_fed); if (rc) return rc;
+                if (!s.border_fed.active) return fail(c, HSK_ERR_UNSUPPORTED, "a task of 2^32 supermers and more");
+                rc = combine_batch<NW>(c, tk, s.bt, gh, plan, s.border_fed, h_nout, s.sbatch, c->stream, P.rec_cap); if (rc) return rc;
+                fed_release(c, s.fed_items); bucket_release(c, s.border_fed);      // (stream-ordered reuse: their readers are enqueued)
+            } else { rc = combine_batch<NW>(c, tk, s.bt, gh, plan, border, h_nout, s.sbatch, c->stream, P.rec_cap); if (rc) return rc; }
+            s.combine = s.sbatch.active;
+        }
+    } else if (P.xs && (s.agg || s.fext) && npass == 2 && plan[0].bits == 8 && plan[1].bits == 8) {
+        if constexpr (NW <= 2) {
+            for (int i = 0; i < XCD_BATCH; ++i) { jobs[i].keys = s.bt[i].kB; jobs[i].vals = s.bt[i].vB; }
+            memcpy(s.xs_plan, plan, sizeof(PassDesc) * 2);
+            rc = scatter_expand_batch<NW>(c, jobs, s.bt, plan, s.sbatch, c->stream); if (rc) return rc;
+        }
+    } else { rc = expand_batch<NW>(c, jobs, XCD_BATCH, npass, plan, c->stream, nullptr); if (rc) return rc; }
+    pt.end(PH_EXTRACT);
+    return HSK_OK;
+}
+
+// The pairs of every task of a combined batch are known on the device only: one wait per batch (the kernels behind it are sized from the answer).
+// Every count is held to the pair stores; then the context learns from the batch (bin width, whether the detour pays).
+template <int NW>
+static int read_pair_counts(hsk_ctx *c, const RankPlan<NW> &P, BatchSlot &s)
+{
+    c->stats.host_syncs++;
+    HIPCHK(c, hsk_sync(c, c->stream));
+    const u64 *h_nout = staging(c)->pairs[s.index];
+    // the pair stores ran over (they were sized from the estimate): once more, sized for the k-mers
+    auto ran_over = [&](const char *why, unsigned info) -> int {
+        if (P.fed_combine) return fail(c, HSK_ERR_INTERNAL, "pair stores overrun with several ranks");
+        c->call.pair_cap_full = true; return retry_plan(why, info);
     };
+    if ((u32)h_nout[XCD_BATCH] & 512u) { (void)hipMemsetAsync(c->d_err, 0, 4, c->stream); return ran_over("the pair stores ran over (sized from the estimate)", 0); }
+    // Bit 512 fires only when a task's chunks exceed rec_cap / CH + 257: a task of a few hundred thousand pairs more than rec_cap fills fewer
+    // spare chunks than that, and the sort below would write all its pairs into kA / vA (rec_cap records).  Every count is held to the store.
+    u64 bp = 0, bk = 0, pmax = 0;
+    for (int i = 0; i < XCD_BATCH; ++i) {
+        BatchTask &b = s.bt[i];
+        if (s.tk[i] == EMPTY_TASK || !b.n) continue;
+        if (h_nout[i] > b.n) return fail(c, HSK_ERR_INTERNAL, "task %u: %llu pairs for %llu k-mers", s.tk[i], (unsigned long long)h_nout[i], (unsigned long long)b.n);
+        if (h_nout[i] > P.rec_cap) return ran_over("the pair stores ran over (more pairs than records)", (unsigned)std::min<u64>(h_nout[i], 0xffffffffu));
+    }
+    for (int i = 0; i < XCD_BATCH; ++i) { BatchTask &b = s.bt[i]; if (s.tk[i] == EMPTY_TASK || !b.n) continue; bk += b.n; b.n = h_nout[i]; bp += h_nout[i]; pmax = std::max<u64>(pmax, h_nout[i]); }
+    c->combine_prefix = std::max(c->combine_prefix_floor, combine_prefix_for(pmax));      // (the batches and calls after this one)
+    c->stats.combine_pairs += bp;
+    if (timing_enabled()) fprintf(stderr, "[hsk] combining extraction: %llu pairs for %llu k-mers\n", (unsigned long long)bp, (unsigned long long)bk);
+    // More than one pair per sixteen k-mers: this input has too few copies per k-mer for the detour to pay (measured on 10 Gbp, DESIGN.md 3.2d:
+    // one pair per 25.6 k-mers 102 against 126 ms, one per 6.6 -- reads with 0.3 % errors -- 171 against 138: the tables overflow inside
+    // the buckets and the parse side's extra 20 ms buy nothing; at one per sixteen a bucket's table is already 37 % full); the batches of this
+    // call finish on the pairs, the next calls take the instance path
+    if (bk && bp * combine_ratio() > bk && !c->combine_off) {
+        c->leave_combine();
+        // (the estimate promised fewer pairs: later estimates on this context are scaled)
+        if (c->call.est.valid) c->est_bias = std::min(8.0, std::max(1.0, ((double)bp / (double)bk) / c->call.est.distinct_per_kmer));
+    }
+    return HSK_OK;
+}
+
+// second stage of the aggregating finish of the batch in the slot: totals -> outputs -> compaction -> result copy
+template <int NW>
+static int finish_slot(hsk_ctx *c, const RankPlan<NW> &P, BatchSlot &s, bool covered, ResultCopier<NW> &R, PhaseTimer &pt)
+{
+    if constexpr (NW <= 3) {
+        TaskOut fo[XCD_BATCH];
+        pt.begin(PH_COUNT);
+        int rc = agg_stage2<NW>(c, s.pend, R.d_histo, R.histo_len, fo, covered);
+        pt.end(PH_COUNT);
+        tmark("batch stage 2 done (totals waited for, compaction enqueued)");
+        if (rc) return rc;
+        R.take(s.tk, fo);
+        for (int i = 0; i < XCD_BATCH; ++i) if (s.tk[i] != EMPTY_TASK && fo[i].failed) {
+            R.early = false;
+            // a bin of pairs beyond the last table of the weighted finish: this call again, on the instance path (dispatch_pipeline)
+            if (P.combine) {
+                if (!combine_prefix_forced() && s.prefix < COMBINE_PREFIX_MAX) c->combine_prefix = c->combine_prefix_floor = COMBINE_PREFIX_MAX;      // once more with the narrowest bins
+                else if (!c->combine_off) c->leave_combine();
+                c->distrust_estimate((double)combine_ratio());
+                return retry_plan("a bin beyond the weighted finish");
+            }
+        }
+        return R.copy_batch(s.tk, XCD_BATCH);
+    }
+    return HSK_OK;
+}
+
+// The sorted batch of slot s is counted by the finish that was chosen when it was expanded.  `ahead`: with two batches in flight, the slot whose
+// batch was sorted before this one and still waits for its aggregation totals.
+template <int NW>
+static int count_slot(hsk_ctx *c, const RankPlan<NW> &P, BatchSlot &s, BatchSlot *ahead, const std::vector<u64> &pay_before, ResultCopier<NW> &R, PhaseTimer &pt)
+{
+    BatchTask *bt = s.bt;
+    if (s.agg) {
+        if constexpr (NW <= 3) {
+            // the previous batch first: this batch's expand and scatter pass are queued behind its aggregation, so the
+            // wait for its totals does not idle the GPU, and its compaction (and result copy) starts one kernel earlier
+            // (stage 2 of the previous batch BEFORE this batch's stage 1 would start its result copy one kernel earlier, but a
+            // device-to-host copy running beside agg_finish_kernel stretches a batch from 19 to 32 ms: measured in round 2, gone)
+            pt.begin(PH_COUNT);
+            int rc = agg_stage1<NW>(c, bt, P.K, s.prefix, s.index, s.pend, s.combine);
+            pt.end(PH_COUNT);
+            if (rc) return rc;
+            if (ahead && ahead->pend.active) { rc = finish_slot<NW>(c, P, *ahead, true, R, pt); if (rc) return rc; }
+            if (!P.lag) { rc = finish_slot<NW>(c, P, s, false, R, pt); if (rc) return rc; }
+        }
+        return HSK_OK;
+    }
+    pt.begin(PH_COUNT);
+    TaskOut fo[XCD_BATCH];
+    if (s.fext) {
+        if constexpr (NW <= 3) {
+            u64 pb[XCD_BATCH];
+            for (int i = 0; i < XCD_BATCH; ++i) pb[i] = s.tk[i] != EMPTY_TASK ? pay_before[s.tk[i]] : 0;
+            int rc = agg_ext_finish_batch_device<NW>(c, bt, P.K, pb, R.d_histo, R.histo_len, fo); if (rc) return rc;
+            R.take(s.tk, fo);
+        }
+    } else if (P.fused && NW == 1 && !P.ext) {
+        if constexpr (NW == 1) {
+            int rc = finish_batch_device<1>(c, bt, P.K, P.max_task, R.d_histo, R.histo_len, fo); if (rc) return rc;
+            R.take(s.tk, fo);
+        }
+    } else {
+        for (int i = 0; i < XCD_BATCH; ++i) {
+            const u32 t = s.tk[i];
+            if (t == EMPTY_TASK) continue;
+            int rc = count_task_device<NW>(c, bt[i].out_k, bt[i].out_v, bt[i].n, pay_before[t], R.d_histo, R.histo_len, R.touts[t]); if (rc) return rc;
+        }
+    }
+    pt.end(PH_COUNT);
+    return HSK_OK;
+}
+
+// Everything after the supermers of the owned tasks are in place: per task expand, sort, count; then the
+// result of this rank.  `segs[t]` lists where the supermers of task t live (x_len / x_src / x_pos / x_rid).
+template <int NW>
+static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owner, int rank, std::vector<TaskSegs> &segs, const u8 *x_len, const BaseSource &x_src, const u32 *x_pos,
+                        const int32_t *x_rid, hsk_result *out, ResultPriv *rp, PhaseTimer &pt, bool pt_total_open, GroupFeeder *feeder = nullptr, const ProcExtra *ex = nullptr)
+{
+    u64 max_task = 0, total_kmers = 0;
+    for (u32 t = 0; t < ntasks; ++t) { finalize_segs(segs[t]); max_task = std::max(max_task, segs[t].nkmers); total_kmers += segs[t].nkmers; }
+    out->total_kmers = total_kmers;
+    const bool item_mode = x_src.item != nullptr;
+    const u32 vt_shift = ex ? ex->vt_shift : 0;
+    first_table_from_estimate(c, NW, max_task, vt_shift || item_mode);
+    const u32 histo_len = (u32)std::min<int64_t>((int64_t)c->cfg.upper_freq + 1, 65536);    // (U <= 65535 except in the unfiltered pre-aggregation)
+    u64 *d_histo; DALLOC(c, d_histo, u64 *, (size_t)histo_len * 8);
+    HIPCHK(c, hipMemsetAsync(d_histo, 0, (size_t)histo_len * 8, c->stream));
+
+    // ---- the plan ---------------------------------------------------------------------------------------
+    const RankPlan<NW> P = plan_rank<NW>(c, ntasks, owner, rank, segs, max_task, feeder, item_mode, ex);
+    if (P.retry) { c->call.combine_veto = true; return P.retry; }
+    const std::vector<u32> &mine = P.mine;
+    const bool ext = P.ext;
+    ResultCopier<NW> R(c, rp, segs, ntasks, total_kmers, P.early, P.compact_mode);
+    R.d_histo = d_histo; R.histo_len = histo_len;
+    std::vector<TaskOut> &touts = R.touts;
+
+    // ---- bucket order (one GPU) -------------------------------------------------------------------------
     // The bucket order of ALL owned tasks comes before the sort buffers are allocated: once its scatter is enqueued nobody reads the item store
     // again, and its 21 GB (10 Gbp) go back to the pool: the call's peak of live device memory 68 -> 46 GB (HSK_TIMING prints the pool's state;
     // what the pool has MAPPED stays at 89 GB -- it hands a cached block only to requests of nearly its size -- and that, mapped for the first
     // time, is what a process's first call pays for).
-    if (combine && !fed_combine) {
+    BucketOrder border;
+    if (P.own_items()) {
         pt.begin(PH_EXTRACT);
-        int rc = bucket_order_tasks(c, ntasks, segs, mine, x_src, ex ? ex->vt_shift : 0, border); if (rc) return rc;
+        int rc = bucket_order_tasks(c, ntasks, segs, mine, x_src, vt_shift, border); if (rc) return rc;
         pt.end(PH_EXTRACT);
         if (!border.active) { c->call.combine_veto = true; return retry_plan("no bucket order"); }
         if (ex && ex->items_store) {                      // (stream-ordered reuse: every later user of these blocks is enqueued behind the scatter)
@@ -393,426 +576,97 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
             c->pool.release(is.d_bitems); is.d_bitems = nullptr; is.n_bitems = 0; for (void *&q : is.bin_aux) { c->pool.release(q); q = nullptr; }
         }
     }
+
+    // ---- buffers ----------------------------------------------------------------------------------------
+    BatchSlot slots[2]; slots[1].index = 1;
+    SortScratch sc;
     {
-        int arc = alloc_sort_buffers();
+        int arc = alloc_batch_buffers<NW>(c, P, slots, sc);
         if (!arc && feeder && test_fail(c, "sortbuf")) arc = fail(c, HSK_ERR_OOM, "sort buffers (injected)");
         if (feeder && !feeder->st_all && c->comm.active()) {
             // the largest allocations of the call are behind us: make sure EVERY rank got them before the first task group
             // travels (a rank that gave up here alone would leave its peers blocked in their first send / receive)
             std::vector<u64> none;
             const int st_ = c->comm.allreduce_with_status(none, RCCL_MAX, arc != 0, c->stream, c->pool);
-            if (st_ < 0) return fail(c, HSK_ERR_COMM, "allreduce(status) failed: %d (%s)", st_, c->comm.last_error.c_str());
-            if (st_ > 0) return arc ? arc : fail(c, HSK_ERR_COMM, "another rank ran out of memory before the supermer exchange");
+            if (st_) return left_together(c, st_, "status", arc, "another rank ran out of memory before the supermer exchange");
             feeder->live = true;                          // from here on a failing rank drains the exchange and the ranks agree at the end (run_pipeline)
         } else if (arc) return arc;
     }
-    u64 n_total = 0, pay_total = 0;
     // payload offsets are global over the owned tasks in ascending id: prefix of k-mer counts
     std::vector<u64> pay_before(ntasks, 0);
     { u64 acc = 0; for (u32 t : mine) { if (t == EMPTY_TASK) continue; pay_before[t] = acc; if (ext) acc += segs[t].nkmers; } }
     TaskInput dflt; dflt.len = x_len; dflt.src = x_src; dflt.pos = x_pos; dflt.rid = x_rid;
-    // ---- result copies that overlap the kernels (host result, no payload, tasks finished in ascending id) ------------
-    // The pinned block is sized from the entries-per-k-mer ratio of the previous call (or of this call's first batch);
-    // should the list outgrow it, the early copies are abandoned and everything is copied again at the end.
-    const bool keep = keep_dev;
-    const bool early_enabled = tune("early_d2h", 1) != 0;
-    bool early = batch && agg && NW <= 2 && !keep && !ext && early_enabled && !(ex && ex->heavy_in && !ex->heavy_in->empty());
-    u64 *early_buf = nullptr; u64 early_cap = 0, early_used = 0, early_kmers = 0;
-    // compact copies (HSK_COMPACT_D2H=0: entries travel as they are): counts fit 16 bits whenever the filter's upper bound does
-    // HSK_COMPACT_D2H: 0 entries as they are (16 bytes), 1 k-mer words + 16-bit counts (10 bytes), 2 (default) the prefix form for
-    // one-word keys (7 bytes with U <= 255, else 8; + 256 KB of directory per task)
-    const int compact_mode = (int)tune("compact_d2h", 2);
-    const bool compact = compact_mode > 0 && c->cfg.upper_freq <= 65535;
-    WidenPool widen(c);
-    u64 compact_bytes = 0, compact_entries = 0;
-    std::vector<void *> pk_dev, pk_host;                  // device / pinned staging of the compact batches (handed back when the call ends)
-    std::vector<u8> copied(ntasks, 0);
-    std::vector<EvPair> d2h_ev;
-    const bool profile_ev = (c->cfg.flags & HSK_FLAG_PROFILE) != 0;
-    auto early_copy = [&](const u32 *tasks, int ntk) -> int {
-        if (!early) return HSK_OK;
-        u64 nb = 0, kb = 0;
-        for (int i = 0; i < ntk; ++i) if (tasks[i] != EMPTY_TASK) { nb += touts[tasks[i]].n; kb += segs[tasks[i]].nkmers; }
-        if (!early_buf) {
-            const double ratio = c->entries_per_kmer > 0 ? c->entries_per_kmer : (kb ? (double)nb / (double)kb : 1.0);
-            early_cap = (u64)(ratio * 1.08 * (double)total_kmers) + (1u << 16);
-            if (early_cap * (NW + 1) * 8 > (64ULL << 30)) { early = false; return HSK_OK; }      // not worth pinning that much on a guess
-            early_buf = (u64 *)host_alloc(c, rp, early_cap * (NW + 1) * 8);
-            if (!early_buf) { early = false; return HSK_OK; }
-        }
-        if (early_used + nb > early_cap) { early = false; return HSK_OK; }                       // the guess was too small: copy at the end
-        // compact: every task's entries are packed on the main stream ([k-mer words][16-bit counts], 16-byte aligned per task), copied
-        // task by task into pinned staging and widened into early_buf by host threads while the next batch is counted
-        u8 *d_pk = nullptr, *h_pk = nullptr;
-        size_t pk_off[XCD_BATCH + 1] = {0}, pk_len[XCD_BATCH] = {0};
-        // one-word keys: the prefix form (7 or 8 bytes per entry + a 256 KB directory per task); otherwise k-mer words + 16-bit counts
-        const bool prefix_form = NW == 1 && compact_mode >= 2;
-        const int cw = c->cfg.upper_freq <= 255 ? 1 : 2;
-        constexpr size_t DIR_BYTES = (size_t)65537 * 4 + 12;            // (padded to 16 bytes)
-        if (compact && nb) {
-            bool fits = true;
-            for (int i = 0; i < ntk; ++i) {
-                const u64 n_i = (tasks[i] == EMPTY_TASK) ? 0 : touts[tasks[i]].n;
-                if (n_i >= 0xFFFFFFF0ULL) fits = false;
-                pk_len[i] = prefix_form ? (n_i ? (((size_t)n_i * 4 + 15) & ~(size_t)15) + (((size_t)n_i * 2 + 15) & ~(size_t)15) + (((size_t)n_i * cw + 15) & ~(size_t)15) + DIR_BYTES : 0)
-                                        : (size_t)n_i * (NW * 8 + 2);
-                pk_off[i + 1] = pk_off[i] + ((pk_len[i] + 15) & ~(size_t)15);
-            }
-            const size_t pk_bytes = pk_off[ntk] + 64;
-            if (fits) { d_pk = (u8 *)c->pool.alloc(pk_bytes); h_pk = (u8 *)host_alloc(c, rp, pk_bytes); }
-            if (!d_pk || !h_pk) { c->pool.release(d_pk); if (h_pk) host_release(c, rp, h_pk); d_pk = nullptr; h_pk = nullptr; }      // (no room: this batch travels as it is)
-            else {
-                pk_dev.push_back(d_pk); pk_host.push_back(h_pk);
-                for (int i = 0; i < ntk; ++i) {
-                    if (tasks[i] == EMPTY_TASK || !touts[tasks[i]].n) continue;
-                    const TaskOut &to = touts[tasks[i]];
-                    const u32 grid = (u32)std::min<u64>((to.n + 255) / 256, 2048);
-                    if (prefix_form) {
-                        if constexpr (NW == 1) {
-                            u8 *b = d_pk + pk_off[i];
-                            u32 *lo32 = (u32 *)b; unsigned short *mid16 = (unsigned short *)(b + (((size_t)to.n * 4 + 15) & ~(size_t)15));
-                            u8 *cnt = (u8 *)mid16 + (((size_t)to.n * 2 + 15) & ~(size_t)15);
-                            u32 *dir = (u32 *)(cnt + (((size_t)to.n * cw + 15) & ~(size_t)15));
-                            HIPCHK(c, hipMemsetAsync(dir, 0xFF, (size_t)65537 * 4, c->stream));
-                            if (cw == 1) hipLaunchKernelGGL((pack_entries_prefix_kernel<u8>), dim3(grid), dim3(256), 0, c->stream, to.entries, to.n, lo32, mid16, cnt, dir);
-                            else hipLaunchKernelGGL((pack_entries_prefix_kernel<unsigned short>), dim3(grid), dim3(256), 0, c->stream, to.entries, to.n, lo32, mid16, (unsigned short *)cnt, dir);
-                            hipLaunchKernelGGL(pack_dir_close_kernel, dim3(1), dim3(1024), 0, c->stream, dir, (u32)to.n);
-                        }
-                    } else hipLaunchKernelGGL(pack_entries_kernel, dim3(grid), dim3(256), 0, c->stream, to.entries, to.n, NW,
-                                              (u64 *)(d_pk + pk_off[i]), (unsigned short *)(d_pk + pk_off[i] + (size_t)to.n * NW * 8));
-                }
-            }
-        }
-        hipEvent_t done = ev_get(c);
-        HIPCHK(c, hipEventRecord(done, c->stream));
-        HIPCHK(c, hipStreamWaitEvent(c->d2h_stream, done, 0));
-        ev_put(c, done);
-        EvPair ep{}; if (profile_ev) { ep.a = ev_get(c); ep.b = ev_get(c); ep.kind = 6; (void)hipEventRecord(ep.a, c->d2h_stream); }
-        if (d_pk) {
-            std::vector<WidenPiece> pieces;
-            u64 o = 0;
-            for (int i = 0; i < ntk; ++i) {
-                if (tasks[i] == EMPTY_TASK || !touts[tasks[i]].n) continue;
-                const u64 n_i = touts[tasks[i]].n;
-                HIPCHK(c, hipMemcpyAsync(h_pk + pk_off[i], d_pk + pk_off[i], pk_len[i], hipMemcpyDeviceToHost, c->d2h_stream));
-                WidenPiece wp; wp.copied = ev_get(c);
-                HIPCHK(c, hipEventRecord(wp.copied, c->d2h_stream));
-                wp.keys = nullptr; wp.cnts = nullptr;
-                if (prefix_form) {
-                    const u8 *b = h_pk + pk_off[i];
-                    wp.lo32 = (const u32 *)b; wp.mid16 = (const unsigned short *)(b + (((size_t)n_i * 4 + 15) & ~(size_t)15));
-                    wp.cnt8 = (const u8 *)wp.mid16 + (((size_t)n_i * 2 + 15) & ~(size_t)15);
-                    wp.dir = (const u32 *)(wp.cnt8 + (((size_t)n_i * cw + 15) & ~(size_t)15)); wp.cw = cw;
-                } else { wp.keys = (const u64 *)(h_pk + pk_off[i]); wp.cnts = (const unsigned short *)(h_pk + pk_off[i] + (size_t)n_i * NW * 8); }
-                wp.dst = early_buf + (early_used + o) * (NW + 1); wp.n = n_i;
-                pieces.push_back(wp);
-                o += n_i;
-                compact_bytes += pk_len[i];
-            }
-            widen.add(pieces, NW);
-            compact_entries += nb;
-        }
-        for (int i = 0; i < ntk; ++i) {
-            const u32 t = tasks[i];
-            if (t == EMPTY_TASK) continue;
-            TaskOut &to = touts[t];
-            if (to.n && !d_pk) HIPCHK(c, hipMemcpyAsync(early_buf + early_used * (NW + 1), to.entries, to.n * (NW + 1) * 8, hipMemcpyDeviceToHost, c->d2h_stream));
-            early_used += to.n; copied[t] = 1;
-        }
-        if (profile_ev) { (void)hipEventRecord(ep.b, c->d2h_stream); d2h_ev.push_back(ep); }
-        early_kmers += kb;
-        return HSK_OK;
-    };
-    int slot_prefix[2] = {0, 0};                          // the digit plan a slot's batch was expanded for
-    // ... and which finish follows it: the aggregation (slot_agg), the grouping aggregation of EXTENSION (slot_fext), or -- once
-    // hsk_ctx::agg_off / agg_off_wide have found the input to hold (nearly) only unique k-mers, possibly in the middle of a call --
-    // the tile finish (one-word keys) / full-width passes and the two-pass counter (everything else); slot_follow: a finish that
-    // wants prefix passes only
-    bool slot_agg[2] = {false, false}, slot_fext[2] = {false, false}, slot_follow[2] = {false, false};
-    BatchTask bts[2][XCD_BATCH];
-    // one launch expands the eight tasks mine[bpos ..] into the slot's buffers and counts the digits of the passes that follow
-    auto issue_expand = [&](size_t bpos, int sl) -> int {
-        slot_agg[sl] = agg && !(NW == 1 ? c->agg_off : c->agg_off_wide);
-        slot_fext[sl] = fused_ext && !c->agg_off_wide;
-        slot_follow[sl] = slot_agg[sl] || slot_fext[sl] || (NW == 1 && fused);
-        const bool will_combine = combine && (fed_combine || border.active) && slot_agg[sl];
-        if (combine && !will_combine && !fed_combine) { c->call.combine_veto = true; return retry_plan("a batch that cannot take the combining extraction"); }      // (several ranks: the batch simply takes the instance path -- nobody starts a call again while peers wait)
-        // (two-word keys: the finish orders a bin's keys by the bits below a 16-bit prefix, agg_order_many -- their pairs take bins of 16 bits)
-        const int prefix_bits = will_combine ? (NW == 1 ? combine_prefix_bits(c) : AG_PREFIX_BITS) : (slot_agg[sl] || slot_fext[sl]) ? AG_PREFIX_BITS : 64 - HYBRID_SHIFT;
-        slot_prefix[sl] = prefix_bits;
-        PassDesc plan[MAX_PASSES];
-        int npass = batch_pass_plan<NW>(c, K, slot_follow[sl], will_combine ? AG_PREFIX_BITS : prefix_bits, plan);
-        if (will_combine) { npass = 2; plan[0] = PassDesc{NW - 1, 64 - prefix_bits, prefix_bits - 8}; plan[1] = PassDesc{NW - 1, 56, 8}; }      // the pairs' two digits (most significant word): the low prefix bits, then the top 8
-        pt.begin(PH_EXTRACT);
-        HIPCHK(c, hipMemsetAsync(d_ghist_slot[sl], 0, (size_t)XCD_BATCH * MAX_PASSES * 256 * 8, c->stream));
-        ExpandJob jobs[XCD_BATCH];
-        for (int i = 0; i < XCD_BATCH; ++i) {
-            const u32 t = mine[bpos + i];
-            BatchTask &b = bts[sl][i];
-            b = BatchTask();
-            b.kA = kAs[sl][i]; b.kB = kBs[sl][i];
-            if (ext || will_combine) { b.vA = vAs[sl][i]; b.vB = vBs[sl][i]; }      // (the payload buffers mean "records carry a payload" to everything downstream)
-            if (t == EMPTY_TASK) { jobs[i] = ExpandJob(); jobs[i].ts = &empty_segs; continue; }
-            b.n = segs[t].nkmers;
-            const TaskInput in = feeder ? feeder->input(t) : dflt;
-            jobs[i].ts = &segs[t]; jobs[i].sm_len = in.len; jobs[i].src = in.src; jobs[i].sm_pos = in.pos; jobs[i].sm_rid = in.rid;
-            jobs[i].keys = b.kA; jobs[i].vals = b.vA; jobs[i].ghist = d_ghist_slot[sl] + (size_t)i * MAX_PASSES * 256;
-        }
-        int rc;
-        slot_combine[sl] = false;
-        if (will_combine) {
-            if constexpr (NW <= 2) {
-                u32 tk[XCD_BATCH]; u64 *gh[XCD_BATCH];
-                for (int i = 0; i < XCD_BATCH; ++i) { tk[i] = mine[bpos + i]; gh[i] = d_ghist_slot[sl] + (size_t)i * MAX_PASSES * 256; }
-                memcpy(xs_plan, plan, sizeof(PassDesc) * 2);
-                u64 *h_nout = (u64 *)((char *)c->pinned + c->pinned_bytes - 2048 + (size_t)sl * 128);
-                if (fed_combine) {
-                    const unsigned short *s16[XCD_BATCH];
-                    for (int i = 0; i < XCD_BATCH; ++i) s16[i] = tk[i] == EMPTY_TASK ? nullptr : feeder->input(tk[i]).sub16;
-                    std::vector<TaskSegs> gsegs; BaseSource gsrc;
-                    rc = build_items_batch(c, ntasks, tk, jobs, s16, gsegs, gsrc, fed_items[sl], c->stream); if (rc) return rc;
-                    rc = bucket_order_tasks(c, ntasks, gsegs, std::vector<u32>(tk, tk + XCD_BATCH), gsrc, FED_VT_SHIFT, border_fed[sl]); if (rc) return rc;
-                    if (!border_fed[sl].active) return fail(c, HSK_ERR_UNSUPPORTED, "a task of 2^32 supermers and more");
-                    rc = combine_batch<NW>(c, tk, bts[sl], gh, plan, border_fed[sl], h_nout, sbatch[sl], c->stream, rec_cap); if (rc) return rc;
-                    fed_release(c, fed_items[sl]); bucket_release(c, border_fed[sl]);      // (stream-ordered reuse: their readers are enqueued)
-                } else { rc = combine_batch<NW>(c, tk, bts[sl], gh, plan, border, h_nout, sbatch[sl], c->stream, rec_cap); if (rc) return rc; }
-                slot_combine[sl] = sbatch[sl].active;
-            }
-        } else
-        if (xs && (slot_agg[sl] || slot_fext[sl]) && npass == 2 && plan[0].bits == 8 && plan[1].bits == 8) {
-            if constexpr (NW <= 2) {
-                for (int i = 0; i < XCD_BATCH; ++i) { jobs[i].keys = bts[sl][i].kB; jobs[i].vals = bts[sl][i].vB; }
-                memcpy(xs_plan, plan, sizeof(PassDesc) * 2);
-                rc = scatter_expand_batch<NW>(c, jobs, bts[sl], plan, sbatch[sl], c->stream); if (rc) return rc;
-            }
-        } else { rc = expand_batch<NW>(c, jobs, XCD_BATCH, npass, plan, c->stream, nullptr); if (rc) return rc; }
-        pt.end(PH_EXTRACT);
-        return HSK_OK;
-    };
-    AggPending pend[2]; size_t pend_pos[2] = {0, 0};
-    // second stage of the aggregating finish of the batch in slot sl: totals -> outputs -> compaction -> result copy
-    auto finish_stage2 = [&](int sl, bool covered) -> int {
-        if constexpr (NW <= 3) {
-            TaskOut fo[XCD_BATCH];
-            pt.begin(PH_COUNT);
-            int rc = agg_stage2<NW>(c, pend[sl], d_histo, histo_len, fo, covered);
-            pt.end(PH_COUNT);
-            tmark("batch stage 2 done (totals waited for, compaction enqueued)");
-            if (rc) return rc;
-            u32 tk[XCD_BATCH];
-            for (int i = 0; i < XCD_BATCH; ++i) { tk[i] = mine[pend_pos[sl] + i]; if (tk[i] != EMPTY_TASK) touts[tk[i]] = fo[i]; }
-            for (int i = 0; i < XCD_BATCH; ++i) if (tk[i] != EMPTY_TASK && fo[i].failed) {
-                early = false;
-                // a bin of pairs beyond the last table of the weighted finish: this call again, on the instance path (dispatch_pipeline)
-                if (combine) {
-                    if (!combine_prefix_forced() && slot_prefix[sl] < COMBINE_PREFIX_MAX) c->combine_prefix = c->combine_prefix_floor = COMBINE_PREFIX_MAX;      // once more with the narrowest bins
-                    else if (!c->combine_off) c->leave_combine();
-                    c->distrust_estimate((double)combine_ratio());
-                    return retry_plan("a bin beyond the weighted finish");
-                }
-            }
-            return early_copy(tk, XCD_BATCH);
-        }
-        return HSK_OK;
-    };
-    u64 comb_pairs = 0, comb_kmers = 0;                   // pairs the combining extraction has written / k-mers they stand for (this call)
+
+    // ---- batches ----------------------------------------------------------------------------------------
     size_t pos = 0;
-    const size_t nbatch = batch ? mine.size() / XCD_BATCH : 0;
+    const size_t nbatch = P.batch ? mine.size() / XCD_BATCH : 0;
     for (size_t b = 0; b < nbatch; ++b, pos += XCD_BATCH) {
-        const int sl = lag ? (int)(b & 1) : 0;
+        BatchSlot &s = slots[P.lag ? (b & 1) : 0];
+        const u32 *tk = &mine[pos];
         if (b == 1 && feeder && test_fail(c, "late")) return fail(c, HSK_ERR_OOM, "second batch (injected)");
-        if (pend[sl].active) { int rc = finish_stage2(sl, false); if (rc) return rc; }       // (only after hsk_ctx::agg_off ended the aggregation in the middle of the call: the slot's buffers are about to be reused)
+        // (only after hsk_ctx::agg_off ended the aggregation in the middle of the call: the slot's buffers are about to be reused)
+        if (s.pend.active) { int rc = finish_slot<NW>(c, P, s, false, R, pt); if (rc) return rc; }
         if (feeder) {                                   // exposed (not overlapped) part of the exchange
             pt.begin(PH_EXCH);
-            for (int i = 0; i < XCD_BATCH; ++i) { if (mine[pos + i] == EMPTY_TASK) continue; int rc = feeder->need(feeder->group_of[mine[pos + i]]); if (rc) return rc; }
+            for (int i = 0; i < XCD_BATCH; ++i) { if (tk[i] == EMPTY_TASK) continue; int rc = feeder->need(feeder->group_of[tk[i]]); if (rc) return rc; }
             pt.end(PH_EXCH);
         }
-        { int rc = issue_expand(pos, sl); if (rc) return rc; }
-        BatchTask *bt = bts[sl];
+        { int rc = expand_slot<NW>(c, P, s, tk, ntasks, segs, feeder, dflt, border, pt); if (rc) return rc; }
         if (feeder) feeder->release_below((pos + XCD_BATCH < mine.size() && mine[pos + XCD_BATCH] != EMPTY_TASK) ? feeder->group_of[mine[pos + XCD_BATCH]] : feeder->ngroups);
-        const int prefix_bits = slot_prefix[sl];
-        if (slot_combine[sl]) {
-            // the pairs of every task are known on the device only: one wait per batch (the kernels behind it are sized from the answer)
-            c->stats.host_syncs++;
-            HIPCHK(c, hsk_sync(c, c->stream));
-            const u64 *h_nout = (const u64 *)((char *)c->pinned + c->pinned_bytes - 2048 + (size_t)sl * 128);
-            if ((u32)h_nout[XCD_BATCH] & 512u) {                   // the pair stores ran over (they were sized from the estimate): once more, sized for the k-mers
-                (void)hipMemsetAsync(c->d_err, 0, 4, c->stream);
-                if (fed_combine) return fail(c, HSK_ERR_INTERNAL, "pair stores overrun with several ranks");
-                c->call.pair_cap_full = true;
-                return retry_plan("the pair stores ran over (sized from the estimate)");
-            }
-            // Bit 512 fires only when a task's chunks exceed rec_cap / CH + 257: a task of a few hundred thousand pairs more than rec_cap fills fewer
-            // spare chunks than that, and the sort below would write all its pairs into kA / vA (rec_cap records).  Every count is held to the store.
-            for (int i = 0; i < XCD_BATCH; ++i) {
-                if (mine[pos + i] == EMPTY_TASK || !bt[i].n) continue;
-                if (h_nout[i] > bt[i].n) return fail(c, HSK_ERR_INTERNAL, "task %u: %llu pairs for %llu k-mers", mine[pos + i], (unsigned long long)h_nout[i], (unsigned long long)bt[i].n);
-                if (h_nout[i] > rec_cap) {
-                    if (fed_combine) return fail(c, HSK_ERR_INTERNAL, "pair stores overrun with several ranks");
-                    c->call.pair_cap_full = true;
-                    return retry_plan("the pair stores ran over (more pairs than records)", (unsigned)std::min<u64>(h_nout[i], 0xffffffffu));
-                }
-            }
-            u64 bp = 0, bk = 0, pmax = 0;
-            for (int i = 0; i < XCD_BATCH; ++i) { if (mine[pos + i] == EMPTY_TASK || !bt[i].n) continue; bk += bt[i].n; bt[i].n = h_nout[i]; bp += h_nout[i]; pmax = std::max<u64>(pmax, h_nout[i]); }
-            c->combine_prefix = std::max(c->combine_prefix_floor, combine_prefix_for(pmax));      // (the batches and calls after this one)
-            comb_pairs += bp; comb_kmers += bk; c->stats.combine_pairs += bp;
-            if (timing_enabled()) fprintf(stderr, "[hsk] combining extraction: %llu pairs for %llu k-mers\n", (unsigned long long)bp, (unsigned long long)bk);
-            // More than one pair per sixteen k-mers: this input has too few copies per k-mer for the detour to pay (measured on 10 Gbp, DESIGN.md 3.2d:
-            // one pair per 25.6 k-mers 102 against 126 ms, one per 6.6 -- reads with 0.3 % errors -- 171 against 138: the tables overflow inside
-            // the buckets and the parse side's extra 20 ms buy nothing; at one per sixteen a bucket's table is already 37 % full); the batches of this call finish on the pairs, the next calls take the
-            // instance path
-            const u64 ratio_env = combine_ratio();
-            if (bk && bp * ratio_env > bk && !c->combine_off) {
-                c->leave_combine();
-                if (c->call.est.valid) c->est_bias = std::min(8.0, std::max(1.0, ((double)bp / (double)bk) / c->call.est.distinct_per_kmer));      // (the estimate promised fewer pairs: later estimates on this context are scaled)
-            }
-        }
+        if (s.combine) { int rc = read_pair_counts<NW>(c, P, s); if (rc) return rc; }
         pt.begin(PH_SORT);
-        if (sbatch[sl].active) { if constexpr (NW <= 2) { int rc = sort_batch_prescattered<NW>(c, bt, xs_plan, d_ghist_slot[sl], sbatch[sl]); if (rc) return rc; } }
-        else { int rc = sort_batch_device<NW>(c, bt, K, slot_follow[sl], prefix_bits, d_ghist_slot[sl]); if (rc) return rc; }
+        if (s.sbatch.active) { if constexpr (NW <= 2) { int rc = sort_batch_prescattered<NW>(c, s.bt, s.xs_plan, s.d_ghist, s.sbatch); if (rc) return rc; } }
+        else { int rc = sort_batch_device<NW>(c, s.bt, P.K, s.follow, s.prefix, s.d_ghist); if (rc) return rc; }
         pt.end(PH_SORT);
-        if (slot_fext[sl]) {
-            if constexpr (NW <= 3) {
-                pt.begin(PH_COUNT);
-                TaskOut fo[XCD_BATCH]; u64 pb[XCD_BATCH];
-                for (int i = 0; i < XCD_BATCH; ++i) pb[i] = mine[pos + i] != EMPTY_TASK ? pay_before[mine[pos + i]] : 0;
-                int rc = agg_ext_finish_batch_device<NW>(c, bt, K, pb, d_histo, histo_len, fo); if (rc) return rc;
-                for (int i = 0; i < XCD_BATCH; ++i) if (mine[pos + i] != EMPTY_TASK) touts[mine[pos + i]] = fo[i];
-                pt.end(PH_COUNT);
-            }
-        } else if (agg && slot_agg[sl]) {
-            if constexpr (NW <= 3) {
-                // the previous batch first: this batch's expand and scatter pass are queued behind its aggregation, so the
-                // wait for its totals does not idle the GPU, and its compaction (and result copy) starts one kernel earlier
-                // (stage 2 of the previous batch BEFORE this batch's stage 1 would start its result copy one kernel earlier, but a
-                // device-to-host copy running beside agg_finish_kernel stretches a batch from 19 to 32 ms: measured in round 2, gone)
-                pt.begin(PH_COUNT);
-                int rc = agg_stage1<NW>(c, bt, K, prefix_bits, sl, pend[sl], slot_combine[sl]);
-                pt.end(PH_COUNT);
-                if (rc) return rc;
-                pend_pos[sl] = pos;
-                if (lag && b > 0 && pend[sl ^ 1].active) { rc = finish_stage2(sl ^ 1, true); if (rc) return rc; }
-                if (!lag) { rc = finish_stage2(sl, false); if (rc) return rc; }
-            }
-        } else if (fused && NW == 1 && !ext) {
-            if constexpr (NW == 1) {
-                pt.begin(PH_COUNT);
-                TaskOut fo[XCD_BATCH];
-                int rc = finish_batch_device<1>(c, bt, K, max_task, d_histo, histo_len, fo); if (rc) return rc;
-                for (int i = 0; i < XCD_BATCH; ++i) if (mine[pos + i] != EMPTY_TASK) touts[mine[pos + i]] = fo[i];
-                pt.end(PH_COUNT);
-            }
-        } else {
-            pt.begin(PH_COUNT);
-            for (int i = 0; i < XCD_BATCH; ++i) {
-                const u32 t = mine[pos + i];
-                if (t == EMPTY_TASK) continue;
-                int rc = count_task_device<NW>(c, bt[i].out_k, bt[i].out_v, bt[i].n, pay_before[t], d_histo, histo_len, touts[t]); if (rc) return rc;
-            }
-            pt.end(PH_COUNT);
-        }
+        { int rc = count_slot<NW>(c, P, s, (P.lag && b > 0) ? &slots[s.index ^ 1] : nullptr, pay_before, R, pt); if (rc) return rc; }
     }
-    if (lag && agg && nbatch > 0) for (int sl = 0; sl < 2; ++sl) if (pend[sl].active) { int rc = finish_stage2(sl, false); if (rc) return rc; }
+    if (P.lag && nbatch > 0) for (BatchSlot &s : slots) if (s.pend.active) { int rc = finish_slot<NW>(c, P, s, false, R, pt); if (rc) return rc; }
+
+    // ---- single tasks (slot 0's first buffers) ----------------------------------------------------------
     for (; pos < mine.size(); ++pos) {
         const u32 t = mine[pos];
         const u64 n = segs[t].nkmers;
+        u64 *kA = slots[0].kA[0], *kB = slots[0].kB[0], *vA = ext ? slots[0].vA[0] : nullptr, *vB = ext ? slots[0].vB[0] : nullptr;
         int rc;
         if (feeder) { pt.begin(PH_EXCH); rc = feeder->need(feeder->group_of[t]); pt.end(PH_EXCH); if (rc) return rc; }
         pt.begin(PH_EXTRACT);
         const TaskInput in = feeder ? feeder->input(t) : dflt;
-        rc = expand_task<NW>(c, segs[t], in.len, in.src, in.pos, in.rid, kA[0], ext ? vA[0] : nullptr); if (rc) return rc;
+        rc = expand_task<NW>(c, segs[t], in.len, in.src, in.pos, in.rid, kA, vA); if (rc) return rc;
         pt.end(PH_EXTRACT);
         if (feeder) feeder->release_below(pos + 1 < mine.size() ? feeder->group_of[mine[pos + 1]] : feeder->ngroups);
         pt.begin(PH_SORT);
         u64 *sk, *sv;
-        rc = sort_task_device<NW>(c, kA[0], kB[0], ext ? vA[0] : nullptr, ext ? vB[0] : nullptr, n, K, sc, &sk, &sv); if (rc) return rc;
+        rc = sort_task_device<NW>(c, kA, kB, vA, vB, n, P.K, sc, &sk, &sv); if (rc) return rc;
         pt.end(PH_SORT);
         pt.begin(PH_COUNT);
         rc = count_task_device<NW>(c, sk, sv, n, pay_before[t], d_histo, histo_len, touts[t]); if (rc) return rc;
         pt.end(PH_COUNT);
     }
-    // heavy-hitter tasks this rank owns arrive as k-mer lists: order, sum, filter
+
+    // ---- heavy lists: the heavy-hitter tasks this rank owns arrive as k-mer lists: order, sum, filter ----
     if (ex && ex->heavy_in) {
         pt.begin(PH_COUNT);
-        for (const HeavyIn &hv : *ex->heavy_in) {
-            { int rc = heavy_merge_task<NW>(c, hv.d_entries, hv.n, d_histo, histo_len, touts[hv.task]); if (rc) return rc; }
-            mine.push_back(hv.task);
-        }
+        for (const HeavyIn &hv : *ex->heavy_in) { int rc = heavy_merge_task<NW>(c, hv.d_entries, hv.n, d_histo, histo_len, touts[hv.task]); if (rc) return rc; }
         pt.end(PH_COUNT);
     }
-    for (u32 t : mine) { if (t == EMPTY_TASK) continue; touts[t].pay_base = pay_before[t]; n_total += touts[t].n; pay_total += touts[t].npay; }
+    u64 n_total = 0, pay_total = 0;
+    for (u32 t = 0; t < ntasks; ++t) { touts[t].pay_base = pay_before[t]; n_total += touts[t].n; pay_total += touts[t].npay; }      // (a task of another rank: all zero)
     if (feeder) { int rc = feeder->finish(); if (rc) return rc; }
-    for (int sl = 0; sl < nslot; ++sl) for (int i = 0; i < nsets; ++i) { c->pool.release(kAs[sl][i]); c->pool.release(kBs[sl][i]); c->pool.release(vAs[sl][i]); c->pool.release(vBs[sl][i]); }
-    free_sort_scratch(c, sc);
-    if (combine && !c->combine_off) c->combine_good_calls++;
+    release_batch_buffers(c, slots, sc);
+    if (P.combine && !c->combine_off) c->combine_good_calls++;
     bucket_release(c, border);
-    c->pool.release(d_ghist_slot[0]); c->pool.release(d_ghist_slot[1]);
 
     // ---- result ----------------------------------------------------------------------------------------
     pt.begin(PH_D2H);
-    out->n = n_total;
-    out->task_off = (uint64_t *)host_alloc(c, rp, (size_t)(ntasks + 1) * 8);
-    out->histo = (uint64_t *)host_alloc(c, rp, (size_t)histo_len * 8);
-    out->histo_len = histo_len;
-    if (!out->task_off || !out->histo) return fail(c, HSK_ERR_OOM, "pinned host allocation failed");
-    HIPCHK(c, hipMemcpyAsync(out->histo, d_histo, (size_t)histo_len * 8, hipMemcpyDeviceToHost, c->stream));
-    u32 *h_err = (u32 *)((char *)c->pinned + c->pinned_bytes - 64);        // the sticky device error word travels with the result
-    HIPCHK(c, hipMemcpyAsync(h_err, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
-    if (!keep) {
-        // the early copies are good if they stayed inside the block and cover a prefix of the list (tasks in ascending id)
-        bool early_ok = early_buf != nullptr && early && n_total <= early_cap;
-        if (early_ok) { bool gap = false; for (u32 t = 0; t < ntasks && early_ok; ++t) { if (!touts[t].n) continue; if (!copied[t]) gap = true; else if (gap) early_ok = false; } }
-        if (early_buf && !early_ok) { HIPCHK(c, hsk_sync(c, c->d2h_stream)); widen.join(); host_release(c, rp, early_buf); early_buf = nullptr; std::fill(copied.begin(), copied.end(), 0); compact_bytes = compact_entries = 0; }
-        out->entries = early_buf ? early_buf : (uint64_t *)host_alloc(c, rp, n_total * (NW + 1) * 8);
-        if (!out->entries) return fail(c, HSK_ERR_OOM, "pinned host allocation of %llu bytes failed", (unsigned long long)(n_total * (NW + 1) * 8));
-        if (ext) {
-            out->payload_off = (uint64_t *)host_alloc(c, rp, (n_total + 1) * 8);
-            out->pos = (uint32_t *)host_alloc(c, rp, pay_total * 4);
-            out->rid = (int32_t *)host_alloc(c, rp, pay_total * 4);
-            if (!out->payload_off || !out->pos || !out->rid) return fail(c, HSK_ERR_OOM, "pinned host allocation failed");
-        }
-    }
-    EvPair d2h_tail{}; if (profile_ev && !keep) { d2h_tail.a = ev_get(c); d2h_tail.b = ev_get(c); d2h_tail.kind = 6; (void)hipEventRecord(d2h_tail.a, c->stream); }
-    u64 o = 0, po = 0;
-    for (u32 t = 0; t < ntasks; ++t) {
-        out->task_off[t] = o;
-        TaskOut &to = touts[t];
-        if (!keep) {
-            if (to.n && !copied[t]) { HIPCHK(c, hipMemcpyAsync(out->entries + o * (NW + 1), to.entries, to.n * (NW + 1) * 8, hipMemcpyDeviceToHost, c->stream)); c->stats.d2h_bytes += 0; }
-            if (ext && to.n) HIPCHK(c, hipMemcpyAsync(out->payload_off + o, to.payoff, to.n * 8, hipMemcpyDeviceToHost, c->stream));
-            if (ext && to.npay) {
-                HIPCHK(c, hipMemcpyAsync(out->pos + po, to.pos, to.npay * 4, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipMemcpyAsync(out->rid + po, to.rid, to.npay * 4, hipMemcpyDeviceToHost, c->stream));
-            }
-        }
-        o += to.n; po += to.npay;
-    }
-    out->task_off[ntasks] = o;
-    if (profile_ev && !keep) { (void)hipEventRecord(d2h_tail.b, c->stream); d2h_ev.push_back(d2h_tail); }
-    if (!keep) c->stats.d2h_bytes += (n_total - compact_entries) * (NW + 1) * 8 + compact_bytes + (ext ? (n_total + 1) * 8 + pay_total * 8 : 0);
+    { int rc = R.finish_list(out, n_total, pay_total); if (rc) return rc; }
     pt.end(PH_D2H);
     if (pt_total_open) pt.end(PH_TOTAL);
     tmark("result copies enqueued");
-    HIPCHK(c, hsk_sync(c, c->stream));
-    tmark("main stream drained");
-    if (early_buf) HIPCHK(c, hsk_sync(c, c->d2h_stream));
-    tmark("copy stream drained");
-    widen.join();                                         // the last batch's entries are being widened
-    for (void *p : pk_dev) c->pool.release(p);
-    for (void *p : pk_host) host_release(c, rp, p);
-    tmark("entries widened");
-    for (auto &e : d2h_ev) c->ev_pending.push_back(e);
-    if (*h_err) {
-        const u32 w = *h_err;
-        (void)hipMemsetAsync(c->d_err, 0, 4, c->stream);
-        return fail(c, HSK_ERR_INTERNAL, "device-side check failed (error word %u:%s%s%s%s%s)", w, (w & 1) ? " radix look-back timed out;" : "",
-                    (w & 2) ? " chunk map wait timed out;" : "", (w & 4) ? " foreign supermer;" : "",
-                    (w & 8) ? " an XCD did not expand its task (cursors / histogram do not add up);" : "", (w & 16) ? " an XCD did not drain its sort task;" : "");
-    }
+    { int rc = R.drain(); if (rc) return rc; }
+    if (const u32 w = staging(c)->err) return device_check_failed(c, w);
     if (!ext && total_kmers && !c->forbid_long_way) c->entries_per_kmer = (double)n_total / (double)total_kmers;
-    if (ext && !keep) out->payload_off[n_total] = pay_total;
-    if (keep) { rp->dev_tasks = touts; out->entries_dev = nullptr; }
+    if (ext && !R.keep) out->payload_off[n_total] = pay_total;
+    if (R.keep) { rp->dev_tasks = touts; out->entries_dev = nullptr; }
     else for (auto &to : touts) free_task_out(c, to);
     c->pool.release(d_histo);
     if (pt_total_open) out->ms_total = pt.collect(PH_TOTAL);
@@ -822,11 +676,40 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
     return HSK_OK;
 }
 
+// ---- what run_pipeline and run_loopback both say around process_rank ---------------------------------------------
+// May a call over `nranks` ranks with about `bytes` of packed reads per rank take the combining extraction?  The part both drivers share; what only
+// one of them knows (the attempt's history, the task count and bucket sizes of one GPU) stays there.
+// The combining extraction pays from a few hundred million k-mers on (a bucket order of the supermers comes first); HSK_COMBINE_MIN_BYTES moves
+// the limit (tests: 0).  This call's own estimate of the input (estimate_plan) decides where there is one; the context's memory of earlier calls
+// (combine_off, agg_off) where there is none.
+// (two-word keys: 40 <= K <= 55 -- the prefix bits sit in the most significant word, an item of 64 bases holds six k-mers and more: shorter
+//  items would be more records per tile than the parse keeps, for 16 bytes that stand for very few k-mers)
+// Several ranks (round 4): the supermers travel as byte runs with 16 of their minimizer bits, the OWNER of a task builds the items (hsk_combine.h,
+// 1b); needs the grouped exchange and the byte-store placement, and every rank's consent (run_pipeline)
+template <int NW>
+static bool combine_allowed(const hsk_ctx *c, int nranks, u64 bytes)
+{
+    const int K = c->cfg.kmer_size;
+    const bool pays = c->call.est.valid ? c->call.est.distinct_per_kmer * c->est_bias * (double)combine_ratio() <= 1.0 : !c->combine_off;
+    return (NW == 1 || (NW == 2 && K >= 40 && K <= 55)) && !c->cfg.extension && pays && !agg_is_off(c, NW) && combine_enabled() && parse_fast_enabled() &&
+           c->cfg.minimizer_size <= SCAN_MAX_M && bytes >= (u64)tune("combine_min_bytes", 64LL << 20) && c->xcd_batch_ok &&
+           (nranks == 1 || (overlap_enabled() && place_bytes_enabled(true)));
+}
+static ResultPriv *begin_result(hsk_result *out, int nw) { memset(out, 0, sizeof *out); ResultPriv *rp = new ResultPriv(); out->priv = rp; out->nw = nw; return rp; }
+// the k-mers of the input that did not arrive as supermers: the instances the scan left out, and the heavy tasks this rank owns (they arrived as lists)
+static void add_unsent_kmers(hsk_ctx *c, hsk_result *out, u64 dropped, const std::vector<u8> &is_heavy, const std::vector<u64> &heavy_kmers, const std::vector<int32_t> &owner, int rank)
+{
+    out->total_kmers += dropped; c->stats.dropped_kmers += (int64_t)dropped;
+    for (size_t t = 0; t < is_heavy.size(); ++t) if (is_heavy[t] && owner[t] == rank) out->total_kmers += heavy_kmers[t];
+}
+// virtual ranks: a rank's parse was timed on its own, its total is the sum of its phases
+static void sum_phases(hsk_result &o, double ms_parse) { o.ms_parse = ms_parse; o.ms_total = o.ms_parse + o.ms_exchange + o.ms_extract + o.ms_sort + o.ms_count + o.ms_d2h; }
+
 // ---- heavy-hitter tasks (a8): the sending side ----------------------------------------------------------------
 // HeavyHitterClassifier (reference src/kmerops.cpp:1157-1199) on the GLOBAL k-mer counts, for every key width (the
 // reference's ScatteredKmerList is generic over TKmer, kmerops.cpp:363-401); forced plain with EXTENSION or
 // PLAIN_CLASSIFIER (kmerops.cpp:109-113).
-static bool heavy_enabled(hsk_ctx *c, int /*nw*/, int nranks)
+static bool heavy_enabled(hsk_ctx *c, int nranks)
 {
     return nranks > 1 && c->cfg.extension == 0 && (c->cfg.flags & HSK_FLAG_PLAIN_CLASSIFIER) == 0;
 }
@@ -881,25 +764,11 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
     const int K = c->cfg.kmer_size;
     const int nranks = c->comm.active() ? c->comm.nranks : 1;
     const int rank = c->comm.active() ? c->comm.rank : 0;
-    memset(out, 0, sizeof *out);
-    ResultPriv *rp = new ResultPriv();
-    out->priv = rp; out->nw = NW;
+    ResultPriv *rp = begin_result(out, NW);
     if ((c->agg_off || c->agg_off_wide) && ++c->agg_off_calls >= 8) { c->agg_off = c->agg_off_wide = false; c->agg_off_calls = 0; }      // (another look every eighth call: the input may have changed)
     if (c->combine_off && ++c->combine_off_calls >= c->combine_off_period) { c->combine_off = false; c->combine_off_calls = 0; c->combine_prefix_floor = 0; }      // (another look: the bin width starts from the default again as well)
-    // the combining extraction pays from a few hundred million k-mers on (a bucket order of the supermers comes first); HSK_COMBINE_MIN_BYTES
-    // moves the limit (tests: 0)
-    const u64 combine_min = (u64)tune("combine_min_bytes", 64LL << 20);
-    // this call's own estimate of the input (estimate_plan) decides where there is one; the context's memory of earlier calls (combine_off, agg_off) where there is none
-    const bool est = c->call.est.valid;
-    const bool combine_pays = !c->call.combine_left_now && (est ? c->call.est.distinct_per_kmer * c->est_bias * (double)combine_ratio() <= 1.0 : !c->combine_off);
-    if (est && c->agg_off && c->call.plan_attempt == 0) { c->agg_off = false; c->agg_off_calls = 0; }      // (process_rank decides again, from the estimate and the task sizes)
-    // several ranks (round 4): the supermers travel as byte runs with 16 of their minimizer bits, the OWNER of a task builds the items (hsk_combine.h, 1b);
-    // needs the grouped exchange and the byte-store placement, and every rank's consent (below)
-    // (two-word keys: 40 <= K <= 55 -- the prefix bits sit in the most significant word, an item of 64 bases holds six k-mers and more: shorter
-    //  items would be more records per tile than the parse keeps, for 16 bytes that stand for very few k-mers)
-    c->call.combine_now = (NW == 1 || (NW == 2 && K >= 40 && K <= 55)) && !ext && combine_pays && !c->call.combine_veto && c->call.plan_attempt < 2 && !(NW == 1 ? c->agg_off : c->agg_off_wide) && combine_enabled() && parse_fast_enabled() &&
-                     c->cfg.minimizer_size <= SCAN_MAX_M && packed_bytes >= combine_min && c->xcd_batch_ok &&
-                     (nranks == 1 || (overlap_enabled() && place_bytes_enabled(true)));
+    if (c->call.est.valid && c->agg_off && c->call.plan_attempt == 0) { c->agg_off = false; c->agg_off_calls = 0; }      // (process_rank decides again, from the estimate and the task sizes)
+    c->call.combine_now = combine_allowed<NW>(c, nranks, packed_bytes) && !c->call.combine_left_now && !c->call.combine_veto && c->call.plan_attempt < 2;
     c->call.combine_veto = false;
     // the combining extraction wants buckets of ~12 k k-mers: the parse itself splits every task by the top minimizer bits (virtual
     // tasks, up to 16 per task and HSK_MAX_TASKS in all: ParseArgs::vt_shift), the bucket order does the rest (hsk_combine.h)
@@ -922,7 +791,7 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
     // (at most 768 virtual tasks: the item placement's LDS holds 16 bytes for each beside its 16384 records; more real tasks than that: the instance path)
     if (ntasks > 768 && nranks == 1) c->call.combine_now = false;
     if (c->call.combine_now && nranks == 1) { u32 sh = 0; while (sh < 4 && ((u64)ntasks << (sh + 1)) <= 768) ++sh; c->call.vt_shift = sh; }
-    if (c->call.combine_now && est && nranks == 1) {
+    if (c->call.combine_now && c->call.est.valid && nranks == 1) {
         // a task has at most 2^14 buckets (CS_MAX_LOG2NB; 2^(10 + virtual-task bits)): few, large tasks make buckets whose distinct k-mers overflow the
         // 2048-slot tables again and again (partial pairs: the detour stops paying) -- predicted from the estimate instead of found out by a batch
         const u32 lg = (u32)std::min<int>(CS_MAX_LOG2NB, CS_MAX_LOCAL + (int)c->call.vt_shift);
@@ -979,15 +848,11 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
             // (with zeros) until the next one, then all ranks return together.
             Comm &cm = c->comm;
             int local_rc = rc;                                   // first local failure since the last collective
-            auto together = [&](int st_, const char *what) -> int {      // result of an all-reduce with status -> return code of this rank
-                if (st_ == 0) return HSK_OK;
-                if (st_ < 0) return fail(c, HSK_ERR_COMM, "allreduce(%s) failed: %d (%s)", what, st_, cm.last_error.c_str());
-                return local_rc ? local_rc : fail(c, HSK_ERR_COMM, "another rank failed before the all-reduce of %s", what);
-            };
+            auto together = [&](int st_, const char *what) { return left_together(c, st_, what, local_rc, "another rank failed before the all-reduce of %s"); };
             std::vector<u64> bytes(ntasks, 0);
             if (!local_rc) for (u32 t = 0; t < ntasks; ++t) bytes[t] = job.task_tot[3 * t + 1] + job.task_tot[3 * t] * (ext ? 9 : 1);
             // heavy-hitter tasks (a8): classified on the global k-mer counts; every rank pre-aggregates its own share
-            if (heavy_enabled(c, NW, nranks)) {
+            if (heavy_enabled(c, nranks)) {
                 std::vector<u64> kg(ntasks, 0); std::vector<int32_t> types(ntasks, 0);
                 if (!local_rc) for (u32 t = 0; t < ntasks; ++t) kg[t] = job.task_tot[3 * t + 2];
                 rc = together(cm.allreduce_with_status(kg, RCCL_SUM, local_rc != 0, c->stream, c->pool), "task k-mers");
@@ -1044,8 +909,7 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
             if (!local_rc) for (size_t i = 0; i < (size_t)ntasks * 3; ++i) M[(size_t)rank * ntasks * 3 + i] = st.task_tot[i];
             M.push_back((!local_rc && (st.sm_sub16 != nullptr || st.tot_sup == 0)) ? 1 : 0);      // this rank's supermers carry their minimizer bits (or it has none to send)
             const int st_ = c->comm.allreduce_with_status(M, RCCL_SUM, local_rc != 0, c->stream, c->pool);
-            if (st_ < 0) return fail(c, HSK_ERR_COMM, "allreduce(size matrix) failed: %d (%s)", st_, c->comm.last_error.c_str());
-            if (st_ > 0) return local_rc ? local_rc : fail(c, HSK_ERR_COMM, "another rank failed before the supermer exchange");
+            if (st_) return left_together(c, st_, "size matrix", local_rc, "another rank failed before the supermer exchange");
             const bool all_sub = M.back() == (u64)nranks && c->call.combine_now;
             M.pop_back();
             rc = feeder.plan(c, nranks, rank, ntasks, owner, order, M, st.task_base, segs); if (rc) return rc;
@@ -1095,8 +959,8 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
         {   // every owner must have its receive buffers before anybody sends
             std::vector<u64> none;
             const int st_ = c->comm.allreduce_with_status(none, RCCL_MAX, oom, c->stream, c->pool);
-            if (st_ < 0) return fail(c, HSK_ERR_COMM, "allreduce(status) failed: %d (%s)", st_, c->comm.last_error.c_str());
-            if (st_ > 0) { for (auto &hv : hin) c->pool.release(hv.d_entries); hin.clear(); return oom ? fail(c, HSK_ERR_OOM, "heavy-hitter receive buffers") : fail(c, HSK_ERR_COMM, "another rank ran out of memory before the heavy-hitter exchange"); }
+            if (st_ > 0) { for (auto &hv : hin) c->pool.release(hv.d_entries); hin.clear(); }
+            if (st_) return left_together(c, st_, "status", oom ? fail(c, HSK_ERR_OOM, "heavy-hitter receive buffers") : 0, "another rank ran out of memory before the heavy-hitter exchange");
         }
         Comm &cm = c->comm;
         size_t hi = 0;
@@ -1133,8 +997,7 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
     ProcExtra ex; ex.heavy_in = &hin; ex.vt_shift = vts; if (nranks == 1 && st.sm_item) ex.items_store = &st;
     const unsigned long long before_rank = c->pool.mark();
     int rc = process_rank<NW>(c, ntasks, owner, rank, segs, x_len, x_src, x_pos, x_rid, out, rp, pt, true, fed ? &feeder : nullptr, &ex);
-    if (rc == HSK_OK && c->call.dropped_now) { out->total_kmers += c->call.dropped_now; c->stats.dropped_kmers += (int64_t)c->call.dropped_now; }      // (the instances the scan left out are k-mers of the input all the same)
-    if (rc == HSK_OK && nranks > 1) for (u32 t = 0; t < ntasks; ++t) if (is_heavy[t] && owner[t] == rank) out->total_kmers += heavy_kmers[t];      // (they arrived as lists, not as supermers)
+    if (rc == HSK_OK) add_unsent_kmers(c, out, c->call.dropped_now, is_heavy, heavy_kmers, owner, rank);      // (one GPU: no task is heavy)
     if (fed && feeder.live) {
         // Leaving together, part two (part one: the all-reduces with status up to the first task group).  A rank whose count failed
         // while the groups were travelling has kept its side of the exchange going (drain_after_failure); now the ranks tell each
@@ -1148,8 +1011,9 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
         }
         std::vector<u64> none;
         const int st_ = c->comm.allreduce_with_status(none, RCCL_MAX, rc != HSK_OK, c->stream, c->pool);
-        if (st_ < 0) return fail(c, HSK_ERR_COMM, "allreduce(final status) failed: %d (%s)", st_, c->comm.last_error.c_str());
-        if (st_ > 0 && rc == HSK_OK) rc = fail(c, HSK_ERR_COMM, "another rank failed while the supermers were travelling; this rank's result is dropped");
+        const int trc = left_together(c, st_, "final status", rc, "another rank failed while the supermers were travelling; this rank's result is dropped");
+        if (st_ < 0) return trc;
+        if (st_ > 0) rc = trc;
     }
     for (auto &hv : hin) c->pool.release(hv.d_entries);
     if (nranks > 1 && !fed) xb.release(c->pool); else free_store(c, st);
@@ -1175,16 +1039,11 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
     std::vector<u32> order(ntasks); for (u32 t = 0; t < ntasks; ++t) order[t] = t;
     // the plan, as run_pipeline chooses it with several ranks: the sketch of a rank's reads (here: of the first virtual rank that has some)
     const bool scan_ok = parse_fast_enabled() && c->cfg.minimizer_size <= SCAN_MAX_M;
-    const bool plan_cond = (NW == 1 || (NW == 2 && c->cfg.kmer_size >= 40 && c->cfg.kmer_size <= 55)) && R > 1 && !ext && combine_enabled() && scan_ok && c->xcd_batch_ok && overlap_enabled() && place_bytes_enabled(true);
-    if (R > 1 && (plan_cond || (scan_ok && c->cfg.kmer_size <= 57))) {          // (without a plan to choose, the sketch still says which k-mers are certain to be dropped)
-        const u64 combine_min = (u64)tune("combine_min_bytes", 64LL << 20);
+    if (R > 1 && scan_ok && c->cfg.kmer_size <= 57) {          // (without a plan to choose, the sketch still says which k-mers are certain to be dropped)
         int r0 = 0; while (r0 + 1 < R && nreads[r0] == 0) ++r0;
         int erc = estimate_plan(c, in[r0].packed, packed_bytes[r0], in[r0].roff, in[r0].rlen, nreads[r0], R); if (erc) return erc;
         c->call.drop_mask_now = certain_drop_mask(c);              // (a rank that is certain is right for all: the virtual ranks share the first one's)
-        if (plan_cond) {
-            const bool pays = c->call.est.valid ? c->call.est.distinct_per_kmer * c->est_bias * (double)combine_ratio() <= 1.0 : !c->combine_off;
-            c->call.combine_now = pays && tot_bytes / (u64)R >= combine_min && !(NW == 1 ? c->agg_off : c->agg_off_wide);
-        }
+        c->call.combine_now = combine_allowed<NW>(c, R, tot_bytes / (u64)R);
     }
     // 1. hash every rank's reads once (parse_count), sum the task sizes, dispatch
     std::vector<u64> bytes(ntasks, 0), dropped(R, 0);
@@ -1207,7 +1066,7 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
     std::vector<u64> heavy_kmers(ntasks, 0);             // k-mer instances of a heavy task over all ranks: its owner counts them into total_kmers
     std::vector<std::vector<TaskOut>> hlists(R);
     bool any_heavy = false;
-    if (heavy_enabled(c, NW, R)) {
+    if (heavy_enabled(c, R)) {
         std::vector<u64> kg(ntasks, 0); std::vector<int32_t> types(ntasks, 0);
         for (int r = 0; r < R; ++r) for (u32 t = 0; t < ntasks; ++t) kg[t] += jobs[r].task_tot[3 * t + 2];
         plan_classify(kg.data(), (int)ntasks, c->cfg.unbalanced_ratio, types.data());
@@ -1280,15 +1139,11 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
         int rc_all = HSK_OK;
         for (int r = 0; r < R && rc_all == HSK_OK; ++r) {
             fd[r].st_all = &st; fd[r].pl_all = &pl_all; fd[r].lazy_pack = true;
-            memset(&outs[r], 0, sizeof(hsk_result));
-            ResultPriv *rp = new ResultPriv();
-            outs[r].priv = rp; outs[r].nw = NW; outs[r].ntasks = (int32_t)ntasks;
+            ResultPriv *rp = begin_result(&outs[r], NW); outs[r].ntasks = (int32_t)ntasks;
             PhaseTimer pt(c);
             ProcExtra ex; ex.heavy_in = &hin[r];
             rc_all = process_rank<NW>(c, ntasks, owner, r, segs[r], nullptr, BaseSource(), nullptr, nullptr, &outs[r], rp, pt, false, &fd[r], &ex);
-            if (rc_all == HSK_OK) { outs[r].total_kmers += dropped[r]; c->stats.dropped_kmers += (int64_t)dropped[r]; }
-            if (rc_all == HSK_OK) for (u32 t = 0; t < ntasks; ++t) if (is_heavy[t] && owner[t] == r) outs[r].total_kmers += heavy_kmers[t];      // (they arrived as lists, not as supermers)
-            if (rc_all == HSK_OK) { outs[r].ms_parse = parse_ms(r); outs[r].ms_total = outs[r].ms_parse + outs[r].ms_exchange + outs[r].ms_extract + outs[r].ms_sort + outs[r].ms_count + outs[r].ms_d2h; }
+            if (rc_all == HSK_OK) { add_unsent_kmers(c, &outs[r], dropped[r], is_heavy, heavy_kmers, owner, r); sum_phases(outs[r], parse_ms(r)); }
         }
         for (int r = 0; r < R; ++r) free_store(c, st[r]);
         free_hin();
@@ -1318,15 +1173,13 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
     for (int r = 0; r < R; ++r) free_store(c, st[r]);
     // 4. every rank finishes its own tasks
     for (int r = 0; r < R; ++r) {
-        memset(&outs[r], 0, sizeof(hsk_result));
-        ResultPriv *rp = new ResultPriv();
-        outs[r].priv = rp; outs[r].nw = NW; outs[r].ntasks = (int32_t)ntasks;
+        ResultPriv *rp = begin_result(&outs[r], NW); outs[r].ntasks = (int32_t)ntasks;
         PhaseTimer pt(c);
         ProcExtra ex; ex.heavy_in = &hin[r];
         int rc = process_rank<NW>(c, ntasks, owner, r, segs[r], xb[r].len, source_from_bytes(xb[r].bytes, xb[r].nbytes), xb[r].pos, xb[r].rid, &outs[r], rp, pt, false, nullptr, &ex);
         xb[r].release(c->pool);
         if (rc) return rc;
-        outs[r].ms_parse = parse_ms(r); outs[r].ms_total = outs[r].ms_parse + outs[r].ms_exchange + outs[r].ms_extract + outs[r].ms_sort + outs[r].ms_count + outs[r].ms_d2h;
+        sum_phases(outs[r], parse_ms(r));
     }
     free_hin();
     return HSK_OK;

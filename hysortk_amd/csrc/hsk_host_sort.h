@@ -149,7 +149,7 @@ static int sort_task_device(hsk_ctx *c, u64 *keysA, u64 *keysB, u64 *valsA, u64 
         hipLaunchKernelGGL(binsort_kernel, dim3((u32)((n + BS_TILE - 1) / BS_TILE)), dim3(BS_THREADS), 0, c->stream, b);
         HIPCHK(c, hipGetLastError());
         std::swap(kin, kout); std::swap(vin, vout);
-        u32 *hf = (u32 *)((char *)c->pinned + c->pinned_bytes - 192);
+        u32 *hf = &staging(c)->sort_flag;
         HIPCHK(c, hipMemcpyAsync(hf, d_flag, 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hsk_sync(c, c->stream));
         if (*hf) {                                             // a long bin with several keys: finish with the full-width passes
@@ -320,17 +320,18 @@ static void free_sort_scratch(hsk_ctx *c, SortScratch &sc)
     sc = SortScratch();
 }
 
-static int check_device_error(hsk_ctx *c)
+// the sticky device error word was not zero: cleared, and named
+static int device_check_failed(hsk_ctx *c, u32 w)
 {
-    u32 *e = (u32 *)((char *)c->pinned + c->pinned_bytes - 64);
-    HIPCHK(c, hipMemcpyAsync(e, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hsk_sync(c, c->stream));
-    if (*e) {
-        (void)hipMemsetAsync(c->d_err, 0, 4, c->stream);
-        const u32 w = *e;
-        return fail(c, HSK_ERR_INTERNAL, "device-side check failed (error word %u:%s%s%s%s%s)", w, (w & 1) ? " radix look-back timed out;" : "",
+    (void)hipMemsetAsync(c->d_err, 0, 4, c->stream);
+    return fail(c, HSK_ERR_INTERNAL, "device-side check failed (error word %u:%s%s%s%s%s)", w, (w & 1) ? " radix look-back timed out;" : "",
                     (w & 2) ? " chunk map wait timed out;" : "", (w & 4) ? " foreign supermer;" : "",
                     (w & 8) ? " an XCD did not expand its task (cursors / histogram do not add up);" : "", (w & 16) ? " an XCD did not drain its sort task;" : "");
-    }
-    return HSK_OK;
+}
+static int check_device_error(hsk_ctx *c)
+{
+    u32 *e = &staging(c)->err;
+    HIPCHK(c, hipMemcpyAsync(e, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hsk_sync(c, c->stream));
+    return *e ? device_check_failed(c, *e) : HSK_OK;
 }
