@@ -2,8 +2,8 @@
 //
 // Replaces the tail of sort_task + count_sorted_kmers (reference src/kmerops.cpp:1382-1445).  Kernels by key width and
 // payload: agg_finish_kernel (one word; described below), agg2_finish_kernel / agg3_finish_kernel (two / three words),
-// agg_ext_kernel<cap, NW> (EXTENSION: the payloads grouped by key), agg_big_kernel (8-bit bins, HSK_ONEPASS
-// and the last rung of the ladder).  The probe loops of the tables are hand-written assembly (agg_count_keys,
+// agg_ext_kernel<cap, NW> (EXTENSION: the payloads grouped by key), agg_big_kernel (one word, 8192 slots: the last
+// rung of the ladder, on the listed bins).  The probe loops of the tables are hand-written assembly (agg_count_keys,
 // agg2_count_keys, agg3_count_keys): as loops of the WAVE they cost 6 scalar instructions per probe instead of the ~25 the
 // compiler spends on execution masks -- the scalar unit was what agg_finish_kernel ran out of --, and for multi-word keys
 // the order "claimers publish, then the others wait" must not be left to the compiler's choice of which branch runs first.
@@ -1340,20 +1340,20 @@ __global__ __launch_bounds__(AG_THREADS) void agg_ext_compact_kernel(AggExtCompa
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// One scatter pass, then aggregate: bins of the top 8 key bits.  With tasks of ~2^24 k-mers a bin holds ~65 000
-// records and ~2 500 distinct keys (32 x coverage): too many records for LDS, but the hash table only has to hold
-// the DISTINCT keys.  One workgroup of 1024 threads per bin, 8192 slots (96 KB of the CU's 160 KB LDS): the bin
-// is streamed once from HBM, the distinct keys are compacted and ordered with a bitonic network in LDS, filtered
-// and written in key order.  The per-bin fixed work (table init, compaction, ordering, output) is spread over
-// ~65 000 records instead of ~3 000, and the second scatter pass (16 B of HBM traffic per k-mer) is not needed.
-// More distinct keys than the table takes (low coverage, or a skewed bin) raise AG_FLAG_OVERFLOW: the host sorts
-// that task on the next 8 bits as well and finishes it with agg_finish_kernel.
+// The last rung of the table ladder for one-word keys (hsk_host_finish.h: AG_LOG2CAP_HUGE): the bins that the
+// 4096-slot table of agg_finish_kernel could not hold, taken from the task's bin list.  The hash table only has to
+// hold the DISTINCT keys of a bin.  One workgroup of 1024 threads per bin, 8192 slots (96 KB of the CU's 160 KB
+// LDS): the bin is streamed once from HBM, the distinct keys are compacted and ordered in LDS (counting sort on
+// the 12 bits below the bin prefix, a bitonic network beyond half the table), filtered and written in key order.
+// (Written for bins of the top 8 key bits after ONE scatter pass; that plan was removed, the kernel takes its
+// bin prefix from AggArgs::shift.)  More distinct keys than the table takes (a skewed bin) raise the task's
+// AG_FLAG_OVERFLOW: there is no list to append to on the last rung, the host sends the task the long way.
 // ------------------------------------------------------------------------------------------------------------
 constexpr int AGB_THREADS = 1024;
 constexpr int AGB_LOG2CAP = 13;
 constexpr int AGB_CAP = 1 << AGB_LOG2CAP;
 constexpr int AGB_MAX_LOAD = AGB_CAP * 3 / 4;      // distinct keys accepted (beyond that probes get long: overflow)
-constexpr int AGB_NBKT = 4096;                     // buckets of the in-LDS counting sort: the 12 key bits below the 8-bit bin prefix
+constexpr int AGB_NBKT = 4096;                     // buckets of the in-LDS counting sort: the 12 key bits below the bin prefix
 
 template <typename T>
 __device__ __forceinline__ T block_excl_scan_1024(T v, T *scratch /* >= 16 */, T *total)

@@ -160,7 +160,7 @@ struct hsk_ctx {
 // they are never live together.
 struct PinnedTail {
     unsigned char agg[2][512];         // agg_stage1 / agg_stage2: the AggHostRead of the batch in slot 0 / 1
-    unsigned char free0[1024];
+    unsigned char agg_large[2][512];   // agg_stage1: host copy of the batch's eight AggLarge structs (slot 0 / 1) until the copy to the device has run
     u64 pairs[2][16];                  // combining extraction: pairs per task + error word of the batch in slot 0 / 1 (combine_batch -> process_rank)
     unsigned char free1[1280];
     u64 estimate[16];                  // estimate_plan: the sample's counters
@@ -173,7 +173,7 @@ struct PinnedTail {
     alignas(64) u32 err;               // the sticky device error word: check_device_error and the end of process_rank, each copy, wait and read in one go
 };
 static_assert(sizeof(PinnedTail) == 4096, "the staging words are the last 4096 bytes of the pinned block");
-static_assert(offsetof(PinnedTail, agg) == 4096 - 4096 && offsetof(PinnedTail, pairs) == 4096 - 2048 && offsetof(PinnedTail, estimate) == 4096 - 512, "staging offsets");
+static_assert(offsetof(PinnedTail, agg) == 4096 - 4096 && offsetof(PinnedTail, agg_large) == 4096 - 3072 && offsetof(PinnedTail, pairs) == 4096 - 2048 && offsetof(PinnedTail, estimate) == 4096 - 512, "staging offsets");
 static_assert(offsetof(PinnedTail, parse_flags) == 4096 - 320 && offsetof(PinnedTail, packed_bytes) == 4096 - 256 && offsetof(PinnedTail, sort_flag) == 4096 - 192, "staging offsets");
 static_assert(offsetof(PinnedTail, total) == 4096 - 128 && offsetof(PinnedTail, err) == 4096 - 64, "staging offsets");
 static PinnedTail *staging(hsk_ctx *c) { return (PinnedTail *)((char *)c->pinned + c->pinned_bytes - sizeof(PinnedTail)); }

@@ -45,7 +45,6 @@ static int count_task_device(hsk_ctx *c, const u64 *keys, const u64 *vals, u64 n
                                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, count_kernel<NW, true, false>, CNT_THREADS, 0);
             occ = (e == hipSuccess && nb > 0) ? nb : 4;
         }
-        hipDeviceProp_t *pr = nullptr; (void)pr;
         const u32 egrid = (u32)std::min<u64>(ntiles, (u64)occ * 256);
         if (ext) hipLaunchKernelGGL((count_kernel<NW, true, true>), dim3(egrid), dim3(CNT_THREADS), 0, c->stream, a);
         else hipLaunchKernelGGL((count_kernel<NW, true, false>), dim3(egrid), dim3(CNT_THREADS), 0, c->stream, a);
@@ -81,8 +80,8 @@ static void host_release(hsk_ctx *c, ResultPriv *rp, void *p)
     c->hpool.release(p);
 }
 
-static bool finish_enabled();
-static bool agg_enabled();
+static bool finish_enabled() { return !(g_plan_flags & HSK_FLAG_FULL_SORT); }
+static bool agg_enabled() { return !(g_plan_flags & (HSK_FLAG_NO_AGGREGATION | HSK_FLAG_FULL_SORT)); }
 static u32 auto_ntasks(hsk_ctx *c, u64 packed_bytes, int nranks)
 {
     // one task per ~2^28 k-mers (2 GB of 8-byte keys): large enough to saturate the chip, small
@@ -102,11 +101,6 @@ static u32 auto_ntasks(hsk_ctx *c, u64 packed_bytes, int nranks)
 // Fused finish of a batch (hybrid sort, one-word keys, no payload): one finish_multi_kernel launch turns the
 // prefix-ordered keys of eight tasks into their (k-mer, count) lists.  Tasks the kernel could not finish (a
 // long bin with several keys, see hsk_finish.h) are redone with the full-width passes and the two-pass counter.
-static bool finish_enabled()
-{
-    return !(g_plan_flags & HSK_FLAG_FULL_SORT);
-}
-
 template <int NW>
 static int finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, u64 max_task, u64 *d_histo, u32 histo_len, TaskOut *outs)
 {
@@ -125,9 +119,8 @@ static int finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, u64 max_task, u
     u64 *scratch[XCD_BATCH] = {nullptr}; bool own_scratch[XCD_BATCH] = {false};
     for (int i = 0; i < XCD_BATCH; ++i) {
         if (bt[i].n == 0) continue;
-        u64 *other = (bt[i].out_k == bt[i].kA) ? bt[i].kB : bt[i].kA;
         const u64 need = ntiles[i] * (u64)cap_t * 16;
-        if (need <= max_task * 8) scratch[i] = other;
+        if (need <= max_task * 8) scratch[i] = other_side(bt[i]);
         else { scratch[i] = (u64 *)c->pool.alloc(need + 64); own_scratch[i] = true; if (!scratch[i]) return fail(c, HSK_ERR_OOM, "finish scratch of %llu bytes", (unsigned long long)need); }
         FinishArgs a; memset(&a, 0, sizeof a);
         a.keys = bt[i].out_k; a.n = bt[i].n; a.scratch = scratch[i]; a.cap_t = cap_t; a.tile_cnt = d_cnt + cnt_off[i]; a.flags = d_flags + i;
@@ -149,13 +142,8 @@ static int finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, u64 max_task, u
         if (h.flags[i] && c->forbid_long_way) { outs[i].failed = true; continue; }
         if (h.flags[i]) {
             // the long way for this task: full-width passes from the current order, then the two-pass counter
-            c->stats.redone_tasks++;
             if (own_scratch[i]) { c->pool.release(scratch[i]); scratch[i] = nullptr; own_scratch[i] = false; }
-            SortScratch sc1; rc = alloc_sort_scratch(c, sc1); if (rc) break;
-            u64 *cur = bt[i].out_k, *other = (cur == bt[i].kA) ? bt[i].kB : bt[i].kA, *sk, *sv;
-            rc = sort_task_device<NW>(c, cur, other, nullptr, nullptr, bt[i].n, K, sc1, &sk, &sv, false);
-            free_sort_scratch(c, sc1);
-            if (rc == HSK_OK) rc = count_task_device<NW>(c, sk, nullptr, bt[i].n, 0, d_histo, histo_len, outs[i]);
+            rc = long_way_task<NW>(c, bt[i], K, false, [&](u64 *sk, u64 *) { return count_task_device<NW>(c, sk, nullptr, bt[i].n, 0, d_histo, histo_len, outs[i]); });
             continue;
         }
         c->stats.fused_tasks++;
@@ -176,11 +164,6 @@ static int finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, u64 max_task, u
 }
 
 // ---- two passes + aggregation (hsk_agg.h): the batch's keys are sorted on their top 16 bits ---------------
-static bool agg_enabled()
-{
-    return !(g_plan_flags & (HSK_FLAG_NO_AGGREGATION | HSK_FLAG_FULL_SORT));
-}
-
 // The aggregating finish of a batch in two stages, so that the host never has to wait for the GPU with nothing queued
 // behind the wait:
 //   agg_stage1  launches bin bounds, the aggregation with the first-choice table and the bin-count scan, asks for the
@@ -191,15 +174,54 @@ static bool agg_enabled()
 // prefix_bits = 16: bins of the top 16 bits (two scatter passes), small tables with a retry ladder and the long way.
 struct AggHostRead { u32 flags[AG_BATCH]; u32 maxd[AG_BATCH]; u32 ovf[2][AG_BATCH]; u64 total[AG_BATCH]; };   // mirrors the device control block (+ totals)
 static_assert(sizeof(AggHostRead) <= sizeof PinnedTail().agg[0], "a slot of the pinned staging words holds one AggHostRead");
+static_assert(sizeof(AggLarge) * AG_BATCH <= sizeof PinnedTail().agg_large[0], "... and a slot of agg_large the batch's AggLarge structs");
+
+// The two overflow lists of the bin-by-bin ladder, ping-pong between the rungs: a rung appends the bins its table could not hold to one
+// list and reads the bins it works on from the other, the one the rung before it appended to (the first rung takes all bins).
+struct OvfLists {
+    u32 *list[2] = {nullptr, nullptr};              // device: [AG_BATCH][nbins] bin ids
+    u32 *len[2] = {nullptr, nullptr};               // device: [AG_BATCH] length words, inside the control block the host reads back
+    const u32 *h_len[2] = {nullptr, nullptr};       // host: where that read-back puts them
+    u32 nbins = 0; int w = 0;                       // w: the list the running rung appends to
+    u32 *appends(int i) const { return list[w] + (size_t)nbins * i; }
+    u32 *appends_n(int i = 0) const { return len[w] + i; }
+    const u32 *reads(int i) const { return list[w ^ 1] + (size_t)nbins * i; }
+    const u32 *reads_n(int i) const { return len[w ^ 1] + i; }
+    u32 appended(int i) const { return h_len[w][i]; }       // after a read-back: bins of task i the rung that just ran has listed
+    void swap() { w ^= 1; }
+};
+// The three rules of the ladder.  all_bins: bins of the batch's active tasks.
+// Next batch (and next call): one table size up when more than one bin in twenty did not fit the first table (each of them is read twice) ...
+static bool first_table_up(hsk_ctx *c, int first_cap, int top, u64 ovf_bins, u64 all_bins)
+{
+    if (ovf_bins * 20 > all_bins) { c->agg_first_cap = std::min(first_cap + 1, top); c->agg_clean_batches = 0; return true; }
+    return false;
+}
+// ... one size down again when nothing overflowed and no bin came anywhere near this size's limit (fullest: the kernel's report of its
+// fullest bin; null where there is none: after four batches without an overflow)
+static void first_table_down(hsk_ctx *c, int first_cap, u64 ovf_bins, const u32 *fullest)
+{
+    if (ovf_bins || first_cap <= AG_LOG2CAP_SMALL) return;
+    if (fullest ? *fullest < (1u << (first_cap - 1)) * 3 / 4 : ++c->agg_clean_batches >= 4) { c->agg_first_cap = first_cap - 1; c->agg_clean_batches = 0; }
+}
+// More than half of all bins did not fit 2048 slots: this input has (nearly) as many distinct k-mers as k-mers -- reads with 5 % errors
+// and more -- and the aggregation is the wrong tool.  No further rungs: the listed bins' tasks take the long way now, the batches after
+// them (and later calls on this context) go without prefix passes + tables (off: hsk_ctx::agg_off or agg_off_wide).
+static bool ladder_hopeless(int cap, u64 listed, u64 all_bins, bool &off)
+{
+    if (tune("agg_adapt", 1) == 0 || cap < AG_LOG2CAP_MEDIUM || listed * 2 <= all_bins) return false;
+    return off = true;
+}
+
 struct AggPending {
     bool active = false;
     BatchTask bt[AG_BATCH];
     AggArgs a;
-    u64 *d_bounds = nullptr, *d_cnt = nullptr, *d_off = nullptr; u32 *d_flags = nullptr;     // d_flags: {flags[8], maxd[8], overflow-list lengths [2][8]}
-    u32 *d_list[2] = {nullptr, nullptr};                                    // [AG_BATCH][nbins] overflowing bins, ping-pong between the rungs
+    u64 *d_bounds = nullptr, *d_cnt = nullptr, *d_off = nullptr; u32 *d_flags = nullptr;     // d_flags: the device's AggHostRead (without the totals)
+    OvfLists ovf;
     char *d_large = nullptr;                                                // bins of very many records (hsk_agg.h: AggLarge): the tasks' structs, tables and slice lists
     bool own_scratch[AG_BATCH] = {false};
-    bool big = false; int first_cap = AG_LOG2CAP_SMALL;
+    int first_cap = AG_LOG2CAP_SMALL;
     bool weighted = false;                              // the records are {key, count} pairs (combining extraction): counts are added, no long way
     u32 nbins = 0, slot_shift = 0; int K = 0; u64 ntot = 0;
     hipEvent_t ev = nullptr;
@@ -228,40 +250,31 @@ static int long_way_batch(hsk_ctx *c, const BatchTask *bt, const bool *redo, int
 
 constexpr int AG_LOG2CAP_HUGE = 13;                     // last rung for one-word keys: agg_big_kernel (8192 slots, 1024 threads) on the listed bins
 
+// The runtime table size as a compile-time constant: f(std::integral_constant<int, AG_LOG2CAP_*>) for the three tables of the finish kernels.
+template <typename F>
+static void with_cap(int log2cap, F &&f)
+{
+    if (log2cap == AG_LOG2CAP_SMALL) f(std::integral_constant<int, AG_LOG2CAP_SMALL>{});
+    else if (log2cap == AG_LOG2CAP_MEDIUM) f(std::integral_constant<int, AG_LOG2CAP_MEDIUM>{});
+    else f(std::integral_constant<int, AG_LOG2CAP_LARGE>{});
+}
+
 // One rung of the ladder: the aggregation kernel with a 2^log2cap table over all bins (grid_x = nbins) or over the listed
-// bins (grid_x = the longest list).
+// bins (grid_x = the longest list).  Three-word keys have no weighted kernel, only one-word keys the 8192-slot one.
 template <int NW>
 static int agg_launch_rung(hsk_ctx *c, AggPending &p, int log2cap, u32 grid_x, u64 records)
 {
-    const bool profile = (c->cfg.flags & HSK_FLAG_PROFILE) != 0;
-    const AggArgs &a = p.a;
-    EvPair ep{}; if (profile) { ep.a = ev_get(c); ep.b = ev_get(c); ep.kind = 2; ep.keys = records; ep.bytes = records * (NW * 8 + (p.weighted ? 8 : 0)); (void)hipEventRecord(ep.a, c->stream); }      // (record bytes READ: keys, and the counts of {k-mer, count} pairs)
-    if (NW == 3) {
-        if (log2cap == AG_LOG2CAP_SMALL) hipLaunchKernelGGL((agg3_finish_kernel<AG_LOG2CAP_SMALL>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-        else if (log2cap == AG_LOG2CAP_MEDIUM) hipLaunchKernelGGL((agg3_finish_kernel<AG_LOG2CAP_MEDIUM>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-        else hipLaunchKernelGGL((agg3_finish_kernel<AG_LOG2CAP_LARGE>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-    } else if (NW == 2) {
-        if (p.weighted) {
-            if (log2cap == AG_LOG2CAP_SMALL) hipLaunchKernelGGL((agg2_finish_kernel<AG_LOG2CAP_SMALL, true>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-            else if (log2cap == AG_LOG2CAP_MEDIUM) hipLaunchKernelGGL((agg2_finish_kernel<AG_LOG2CAP_MEDIUM, true>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-            else hipLaunchKernelGGL((agg2_finish_kernel<AG_LOG2CAP_LARGE, true>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-        }
-        else if (log2cap == AG_LOG2CAP_SMALL) hipLaunchKernelGGL((agg2_finish_kernel<AG_LOG2CAP_SMALL>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-        else if (log2cap == AG_LOG2CAP_MEDIUM) hipLaunchKernelGGL((agg2_finish_kernel<AG_LOG2CAP_MEDIUM>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-        else hipLaunchKernelGGL((agg2_finish_kernel<AG_LOG2CAP_LARGE>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-    } else
-    if (p.weighted) {
-        if constexpr (NW == 1) {
-            if (log2cap == AG_LOG2CAP_SMALL) hipLaunchKernelGGL((agg_finish_kernel<AG_LOG2CAP_SMALL, true>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-            else if (log2cap == AG_LOG2CAP_MEDIUM) hipLaunchKernelGGL((agg_finish_kernel<AG_LOG2CAP_MEDIUM, true>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-            else hipLaunchKernelGGL((agg_finish_kernel<AG_LOG2CAP_LARGE, true>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-        }
-    } else
-    if (p.big || log2cap == AG_LOG2CAP_HUGE) hipLaunchKernelGGL(agg_big_kernel, dim3(grid_x, AG_BATCH), dim3(AGB_THREADS), 0, c->stream, a);
-    else if (log2cap == AG_LOG2CAP_SMALL) hipLaunchKernelGGL((agg_finish_kernel<AG_LOG2CAP_SMALL>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-    else if (log2cap == AG_LOG2CAP_MEDIUM) hipLaunchKernelGGL((agg_finish_kernel<AG_LOG2CAP_MEDIUM>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-    else hipLaunchKernelGGL((agg_finish_kernel<AG_LOG2CAP_LARGE>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-    if (profile) { (void)hipEventRecord(ep.b, c->stream); c->ev_pending.push_back(ep); }
+    const AggArgs &a = p.a; const dim3 grid(grid_x, AG_BATCH), block(AG_THREADS);
+    // (record bytes READ: keys, and the counts of {k-mer, count} pairs)
+    profiled(c, 2, records, records * (NW * 8 + (p.weighted ? 8 : 0)), [&] {
+        if constexpr (NW == 1) if (log2cap == AG_LOG2CAP_HUGE && !p.weighted) { hipLaunchKernelGGL(agg_big_kernel, grid, dim3(AGB_THREADS), 0, c->stream, a); return; }
+        with_cap(log2cap, [&](auto cap) {
+            constexpr int CAP = decltype(cap)::value;
+            if constexpr (NW == 3) hipLaunchKernelGGL((agg3_finish_kernel<CAP>), grid, block, 0, c->stream, a);
+            else if constexpr (NW == 2) { if (p.weighted) hipLaunchKernelGGL((agg2_finish_kernel<CAP, true>), grid, block, 0, c->stream, a); else hipLaunchKernelGGL((agg2_finish_kernel<CAP>), grid, block, 0, c->stream, a); }
+            else { if (p.weighted) hipLaunchKernelGGL((agg_finish_kernel<CAP, true>), grid, block, 0, c->stream, a); else hipLaunchKernelGGL((agg_finish_kernel<CAP>), grid, block, 0, c->stream, a); }
+        });
+    });
     HIPCHK(c, hipGetLastError());
     return HSK_OK;
 }
@@ -286,7 +299,6 @@ static int agg_stage1(hsk_ctx *c, const BatchTask *bt, int K, int prefix_bits, i
     const u32 L = (u32)c->cfg.lower_freq;
     p.weighted = weighted;
     p.slot_shift = (L >= 2 && !weighted) ? 1 : 0;       // a bin of n records keeps at most n / L entries (pairs: every record may be an entry)
-    p.big = false;                                      // (8-bit bins: the one-pass experiment of rounds 1-2, removed)
     p.nbins = 1u << prefix_bits; p.K = K;
     p.h = (AggHostRead *)staging(c)->agg[slot];
     memset(p.h, 0, sizeof *p.h);
@@ -297,7 +309,8 @@ static int agg_stage1(hsk_ctx *c, const BatchTask *bt, int K, int prefix_bits, i
     DALLOC(c, p.d_off, u64 *, per * 8 * AG_BATCH);          // (the counts stay as they are: later rungs of the ladder fill in their bins and the scan runs again)
     DALLOC(c, p.d_flags, u32 *, 256);
     HIPCHK(c, hipMemsetAsync(p.d_flags, 0, 256, c->stream));
-    if (!p.big) for (int x = 0; x < 2; ++x) DALLOC(c, p.d_list[x], u32 *, (size_t)nbins * 4 * AG_BATCH);
+    OvfLists &ovf = p.ovf; ovf.nbins = nbins;
+    for (int x = 0; x < 2; ++x) { DALLOC(c, ovf.list[x], u32 *, (size_t)nbins * 4 * AG_BATCH); ovf.len[x] = p.d_flags + (2 + x) * AG_BATCH; ovf.h_len[x] = p.h->ovf[x]; }
     AggArgs &a = p.a; memset(&a, 0, sizeof a);
     a.lower = L; a.upper = (u32)c->cfg.upper_freq; a.nbins = nbins; a.shift = 64 - prefix_bits; a.nw = NW;
     a.top_bits = (NW >= 2 && prefix_bits == 16) ? prefix_top_bits(K, NW) : 0;
@@ -307,18 +320,17 @@ static int agg_stage1(hsk_ctx *c, const BatchTask *bt, int K, int prefix_bits, i
         AggTask &t = a.t[i];
         p.bt[i] = bt[i];
         if (bt[i].n == 0) continue;
-        u64 *other = (bt[i].out_k == bt[i].kA) ? bt[i].kB : bt[i].kA;
         t.keys = bt[i].out_k; t.vals = weighted ? bt[i].out_v : nullptr; t.n = bt[i].n; t.bounds = p.d_bounds + per * i; t.bin_cnt = p.d_cnt + per * i; t.bin_off = p.d_off + per * i; t.flags = p.d_flags + i;
         t.slot_shift = p.slot_shift; t.active = 1; p.ntot += bt[i].n; nmax = std::max(nmax, bt[i].n);
-        if (!p.big) { t.ovf_list = p.d_list[0] + (size_t)nbins * i; t.ovf_n = p.d_flags + 2 * AG_BATCH + i; }      // first rung: all bins, overflowing ones listed
-        if (p.slot_shift) t.scratch = other;             // the idle ping-pong buffer: n / 2 entries
+        t.ovf_list = ovf.appends(i); t.ovf_n = ovf.appends_n(i);     // first rung: all bins, overflowing ones listed
+        if (p.slot_shift) t.scratch = other_side(bt[i]);    // the idle ping-pong buffer: n / 2 entries
         else {
             t.scratch = (u64 *)c->pool.alloc(bt[i].n * EW * 8 + 64); p.own_scratch[i] = true;
             if (!t.scratch) return fail(c, HSK_ERR_OOM, "finish scratch of %llu bytes", (unsigned long long)(bt[i].n * EW * 8));
         }
     }
     hipLaunchKernelGGL(bin_bounds_kernel, dim3(nbins / AG_THREADS + 1, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-    if constexpr (NW <= 2) if (!weighted && !p.big && tune("agg_large", 1) != 0 && nmax >= AG_LARGE_BIN && (NW == 1 || a.top_bits == 0 || a.top_bits == 16)) {
+    if constexpr (NW <= 2) if (!weighted && tune("agg_large", 1) != 0 && nmax >= AG_LARGE_BIN && (NW == 1 || a.top_bits == 0 || a.top_bits == 16)) {
         // bins of very many records (one k-mer seen millions of times): found, cut into slices and counted by many workgroups before the ladder
         // starts (hsk_agg.h: AggLarge); without such bins the two launches end at once
         size_t off[AG_BATCH][7], total = (sizeof(AggLarge) * AG_BATCH + 255) / 256 * 256;
@@ -329,7 +341,7 @@ static int agg_stage1(hsk_ctx *c, const BatchTask *bt, int K, int prefix_bits, i
         }
         DALLOC(c, p.d_large, char *, total + 64);
         HIPCHK(c, hipMemsetAsync(p.d_large, 0, total, c->stream));
-        AggLarge *h_lg = (AggLarge *)((char *)c->pinned + (512u << 10) + (size_t)slot * 1024);
+        AggLarge *h_lg = (AggLarge *)staging(c)->agg_large[slot];
         for (int i = 0; i < AG_BATCH; ++i) {
             HIPCHK(c, hipMemsetAsync(p.d_large + off[i][1], 0xFF, (size_t)AGL_TABLES * AGL_TAB * 8, c->stream));
             if (NW == 2) HIPCHK(c, hipMemsetAsync(p.d_large + off[i][6], 0xFF, (size_t)AGL_TABLES * AGL_TAB * 8, c->stream));
@@ -347,7 +359,7 @@ static int agg_stage1(hsk_ctx *c, const BatchTask *bt, int K, int prefix_bits, i
     // First table: what the bins of the previous batches needed (hsk_ctx::agg_first_cap: error-free reads at ~30x stay on 1024
     // slots, reads with ~1 % errors move to 2048 after their first batch); bins of 6144 records and more on average (tasks far
     // above 2^28 k-mers) start on the large table.  Two-word keys: small / large only.
-    p.first_cap = p.big ? AG_LOG2CAP_SMALL : std::max(c->agg_first_cap, nmax / nbins >= 6144 ? AG_LOG2CAP_LARGE : AG_LOG2CAP_SMALL);
+    p.first_cap = std::max(c->agg_first_cap, nmax / nbins >= 6144 ? AG_LOG2CAP_LARGE : AG_LOG2CAP_SMALL);
     if (weighted) {                                      // pairs are (nearly) all distinct: the table that takes the average bin twice over
         const u64 avg = nmax / nbins + 1;
         p.first_cap = avg * 2 <= 600 ? AG_LOG2CAP_SMALL : avg * 2 <= 1200 ? AG_LOG2CAP_MEDIUM : AG_LOG2CAP_LARGE;
@@ -395,7 +407,8 @@ static int agg_stage2(hsk_ctx *c, AggPending &p, u64 *d_histo, u32 histo_len, Ta
     constexpr u32 EW = NW + 1;
     for (int i = 0; i < AG_BATCH; ++i) outs[i] = TaskOut();
     if (!p.active) return HSK_OK;
-    AggArgs &a = p.a; const BatchTask *bt = p.bt; const u32 nbins = p.nbins; const bool big = p.big;
+    AggArgs &a = p.a; const BatchTask *bt = p.bt; const u32 nbins = p.nbins; OvfLists &ovf = p.ovf;
+    bool &agg_off = NW == 1 ? c->agg_off : c->agg_off_wide;         // what a hopeless batch switches off for the batches after it
     c->stats.host_syncs++; if (covered) c->stats.host_waits_covered++;
     HIPCHK(c, hipEventSynchronize(p.ev));
     ev_put(c, p.ev); p.ev = nullptr;
@@ -403,23 +416,20 @@ static int agg_stage2(hsk_ctx *c, AggPending &p, u64 *d_histo, u32 histo_len, Ta
     bool done[AG_BATCH];
     int rc = HSK_OK, nact = 0;
     u64 ovf_bins = 0;
-    for (int i = 0; i < AG_BATCH; ++i) { done[i] = bt[i].n == 0 || !h.flags[i]; if (bt[i].n) { ++nact; ovf_bins += h.ovf[0][i]; } }
-    if (!big && !c->forbid_long_way && !p.weighted && nact) {
-        // next batch (and next call): one table size up when more than one bin in twenty did not fit this one (each of them is
-        // read twice), one size down again when nothing overflowed and no bin came anywhere near this size's limit (one-word
-        // keys: the kernel reports its fullest bin; multi-word keys: after four batches without an overflow)
+    for (int i = 0; i < AG_BATCH; ++i) { done[i] = bt[i].n == 0 || !h.flags[i]; if (bt[i].n) { ++nact; ovf_bins += ovf.appended(i); } }
+    const u64 all_bins = (u64)nact * nbins;
+    if (!c->forbid_long_way && !p.weighted && nact) {
+        // the next batch's first table (one-word keys: the kernel reports its fullest bin)
         u32 maxd = 0; for (int i = 0; i < AG_BATCH; ++i) if (bt[i].n) maxd = std::max(maxd, h.maxd[i]);
-        if (ovf_bins * 20 > (u64)nact * nbins) { c->agg_first_cap = std::min(p.first_cap + 1, (int)AG_LOG2CAP_LARGE); c->agg_clean_batches = 0; }
-        else if (ovf_bins == 0 && p.first_cap > AG_LOG2CAP_SMALL &&
-                 (NW == 1 ? maxd < (1u << (p.first_cap - 1)) * 3 / 4 : ++c->agg_clean_batches >= 4)) { c->agg_first_cap = p.first_cap - 1; c->agg_clean_batches = 0; }
+        if (!first_table_up(c, p.first_cap, AG_LOG2CAP_LARGE, ovf_bins, all_bins)) first_table_down(c, p.first_cap, ovf_bins, NW == 1 ? &maxd : nullptr);
     }
-    { const bool force_off = tune("agg_adapt", 1) == 2;     // (tests: as if this batch had been found hopeless, but finished normally)
-      if (force_off && !c->forbid_long_way && !p.weighted) { if (NW == 1) c->agg_off = true; else c->agg_off_wide = true; } }
+    // (tests: as if this batch had been found hopeless, but finished normally)
+    if (tune("agg_adapt", 1) == 2 && !c->forbid_long_way && !p.weighted) agg_off = true;
     // ---- the ladder, bin by bin: the listed bins again one table size up, until no bin is left or the rungs are ----------------
-    if (!big && ovf_bins) {
+    if (ovf_bins) {
         AggArgs keep = a;
-        int cap = p.first_cap, cur = 0;
-        u32 n_cur[AG_BATCH]; for (int i = 0; i < AG_BATCH; ++i) n_cur[i] = bt[i].n ? h.ovf[0][i] : 0;
+        int cap = p.first_cap;
+        u32 n_cur[AG_BATCH]; for (int i = 0; i < AG_BATCH; ++i) n_cur[i] = bt[i].n ? ovf.appended(i) : 0;
         for (;;) {
             u32 longest = 0; u64 nb = 0; for (int i = 0; i < AG_BATCH; ++i) { longest = std::max(longest, n_cur[i]); nb += n_cur[i]; }
             if (!longest) break;
@@ -427,32 +437,27 @@ static int agg_stage2(hsk_ctx *c, AggPending &p, u64 *d_histo, u32 histo_len, Ta
             int next = (NW >= 2 || p.weighted) ? (cap < AG_LOG2CAP_LARGE ? cap + 1 : 0) : (cap < AG_LOG2CAP_HUGE ? cap + 1 : 0);
             if (next > max_rung) next = 0;
             if (!next) { for (int i = 0; i < AG_BATCH; ++i) if (n_cur[i]) done[i] = false; break; }   // a bin beyond the last rung: the task takes the long way
-            // More than half of all bins did not fit 2048 slots: this input has (nearly) as many distinct k-mers as k-mers -- reads with
-            // 5 % errors and more -- and the aggregation is the wrong tool.  No further rungs: the tasks of this batch take the long way
-            // now, the batches after it (and later calls on this context) four prefix passes + the tile finish instead of two + tables.
-            const bool adapt = tune("agg_adapt", 1) != 0;
-            // (multi-word keys have no tile finish to change to: their tasks just stop climbing a ladder that ends in the long way anyway)
-            if (adapt && !c->forbid_long_way && !p.weighted && cap >= AG_LOG2CAP_MEDIUM && nb * 2 > (u64)nact * nbins) {
-                if (NW == 1) c->agg_off = true; else c->agg_off_wide = true;
+            // hopeless (one-word keys: four prefix passes + the tile finish from here on; multi-word keys have no tile finish to change
+            // to: their tasks just stop climbing a ladder that ends in the long way anyway)
+            if (!c->forbid_long_way && !p.weighted && ladder_hopeless(cap, nb, all_bins, agg_off)) {
                 for (int i = 0; i < AG_BATCH; ++i) if (n_cur[i]) done[i] = false;
                 break;
             }
-            cap = next;
+            cap = next; ovf.swap();                             // this rung reads what the one before it has listed
             const bool last = (NW >= 2 || p.weighted) ? cap == AG_LOG2CAP_LARGE : cap == AG_LOG2CAP_HUGE;
-            HIPCHK(c, hipMemsetAsync(p.d_flags + (2 + (cur ^ 1)) * AG_BATCH, 0, sizeof(u32) * AG_BATCH, c->stream));
+            HIPCHK(c, hipMemsetAsync(ovf.appends_n(), 0, sizeof(u32) * AG_BATCH, c->stream));
             for (int i = 0; i < AG_BATCH; ++i) {
                 AggTask &t = a.t[i];
                 t.active = (keep.t[i].active && n_cur[i]) ? 1 : 0;
                 if (t.active) c->stats.agg_retried_tasks++;
-                t.bin_list = p.d_list[cur] + (size_t)nbins * i; t.bin_list_n = p.d_flags + (2 + cur) * AG_BATCH + i;
-                t.ovf_list = last ? nullptr : p.d_list[cur ^ 1] + (size_t)nbins * i; t.ovf_n = p.d_flags + (2 + (cur ^ 1)) * AG_BATCH + i;
+                t.bin_list = ovf.reads(i); t.bin_list_n = ovf.reads_n(i);
+                t.ovf_list = last ? nullptr : ovf.appends(i); t.ovf_n = ovf.appends_n(i);
             }
-            rc = agg_launch_rung<NW>(c, p, cap, longest, nb * (p.ntot / ((u64)nact * nbins) + 1)); if (rc) return rc;
+            rc = agg_launch_rung<NW>(c, p, cap, longest, nb * (p.ntot / all_bins + 1)); if (rc) return rc;
             HIPCHK(c, hipMemcpyAsync(p.h->flags, p.d_flags, 4 * sizeof(u32) * AG_BATCH, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hsk_sync(c, c->stream));
             if (last) { for (int i = 0; i < AG_BATCH; ++i) if (a.t[i].active && h.flags[i]) done[i] = false; break; }
-            cur ^= 1;
-            for (int i = 0; i < AG_BATCH; ++i) n_cur[i] = a.t[i].active ? h.ovf[cur][i] : 0;
+            for (int i = 0; i < AG_BATCH; ++i) n_cur[i] = a.t[i].active ? ovf.appended(i) : 0;
         }
         a = keep;
         for (int i = 0; i < AG_BATCH; ++i) { a.t[i].bin_list = nullptr; a.t[i].bin_list_n = nullptr; }
@@ -475,8 +480,8 @@ static int agg_stage2(hsk_ctx *c, AggPending &p, u64 *d_histo, u32 histo_len, Ta
             any = true;
         }
     }
-    if (any && rc == HSK_OK) hipLaunchKernelGGL(agg_compact_kernel, dim3(big ? 64 : 256, AG_BATCH), dim3(AG_THREADS), 0, c->stream, ca);
-    if (!big && !c->forbid_long_way && !p.weighted && rc == HSK_OK) {
+    if (any && rc == HSK_OK) hipLaunchKernelGGL(agg_compact_kernel, dim3(256, AG_BATCH), dim3(AG_THREADS), 0, c->stream, ca);
+    if (!c->forbid_long_way && !p.weighted && rc == HSK_OK) {
         bool redo[AG_BATCH]; int nredo = 0;
         for (int i = 0; i < AG_BATCH; ++i) { redo[i] = bt[i].n != 0 && !done[i]; nredo += redo[i]; }
         if (nredo >= 3) {
@@ -487,34 +492,20 @@ static int agg_stage2(hsk_ctx *c, AggPending &p, u64 *d_histo, u32 histo_len, Ta
     }
     for (int i = 0; i < AG_BATCH && rc == HSK_OK; ++i) {
         if (bt[i].n == 0 || done[i]) continue;
-        if (big || c->forbid_long_way) { outs[i].failed = true; continue; }
-        if (p.weighted) {
-            // {k-mer, count} pairs with a bin beyond the last table (a skewed key prefix: poly-A, satellites): the long way for this task --
-            // full-width passes over the pairs with the counts as payload, then equal keys summed (round 4; rounds 2-3 ran the whole CALL
-            // again on the instance path, which several ranks cannot do: their peers would wait in the exchange)
-            c->stats.redone_tasks++;
-            if (p.own_scratch[i]) { c->pool.release(a.t[i].scratch); a.t[i].scratch = nullptr; p.own_scratch[i] = false; }
-            SortScratch scw; rc = alloc_sort_scratch(c, scw); if (rc) break;
-            u64 *ck = bt[i].out_k, *ok_ = (ck == bt[i].kA) ? bt[i].kB : bt[i].kA, *cv = bt[i].out_v, *ov = (cv == bt[i].vA) ? bt[i].vB : bt[i].vA, *sk, *sv;
-            rc = sort_task_device<NW>(c, ck, ok_, cv, ov, bt[i].n, p.K, scw, &sk, &sv, false);
-            free_sort_scratch(c, scw);
-            if (rc == HSK_OK) rc = merge_sorted_pairs<NW>(c, sk, sv, bt[i].n, d_histo, histo_len, outs[i]);
-            continue;
-        }
-        // the long way for this task: full-width passes from the current order, then the two-pass counter
-        c->stats.redone_tasks++;
+        if (c->forbid_long_way) { outs[i].failed = true; continue; }
+        // The long way for this task: full-width passes from the current order, then the two-pass counter.  {k-mer, count} pairs with a bin
+        // beyond the last table (a skewed key prefix: poly-A, satellites): the passes carry the counts as payload, then equal keys are summed
+        // (round 4; rounds 2-3 ran the whole CALL again on the instance path, which several ranks cannot do: their peers would wait in the exchange)
         if (p.own_scratch[i]) { c->pool.release(a.t[i].scratch); a.t[i].scratch = nullptr; p.own_scratch[i] = false; }   // (stream-ordered reuse)
-        SortScratch sc1; rc = alloc_sort_scratch(c, sc1); if (rc) break;
-        u64 *cur = bt[i].out_k, *other = (cur == bt[i].kA) ? bt[i].kB : bt[i].kA, *sk, *sv;
-        rc = sort_task_device<NW>(c, cur, other, nullptr, nullptr, bt[i].n, p.K, sc1, &sk, &sv, false);
-        free_sort_scratch(c, sc1);
-        if (rc == HSK_OK) rc = count_task_device<NW>(c, sk, nullptr, bt[i].n, 0, d_histo, histo_len, outs[i]);
+        rc = long_way_task<NW>(c, bt[i], p.K, p.weighted, [&](u64 *sk, u64 *sv) {
+            return p.weighted ? merge_sorted_pairs<NW>(c, sk, sv, bt[i].n, d_histo, histo_len, outs[i])
+                              : count_task_device<NW>(c, sk, nullptr, bt[i].n, 0, d_histo, histo_len, outs[i]); });
     }
     HIPCHK(c, hipGetLastError());
     // no wait here: the scratch (the batch's idle ping-pong buffers, or pool blocks) is next touched by work that is
     // enqueued on this stream after the compaction
     for (int i = 0; i < AG_BATCH; ++i) if (p.own_scratch[i]) c->pool.release(a.t[i].scratch);
-    c->pool.release(p.d_bounds); c->pool.release(p.d_cnt); c->pool.release(p.d_off); c->pool.release(p.d_flags); c->pool.release(p.d_list[0]); c->pool.release(p.d_list[1]); c->pool.release(p.d_large);
+    c->pool.release(p.d_bounds); c->pool.release(p.d_cnt); c->pool.release(p.d_off); c->pool.release(p.d_flags); c->pool.release(ovf.list[0]); c->pool.release(ovf.list[1]); c->pool.release(p.d_large);
     p.active = false;
     return rc;
 }
@@ -527,7 +518,6 @@ static int agg_ext_finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, const u
 {
     static_assert(NW <= 3, "keys of one to three words");
     constexpr u32 EW = NW + 1;                          // words per entry
-    const bool profile = (c->cfg.flags & HSK_FLAG_PROFILE) != 0;
     const u32 L = (u32)c->cfg.lower_freq;
     const u32 slot_shift = L >= 2 ? 1 : 0;
     const u32 nbins = AG_BINS;
@@ -547,11 +537,9 @@ static int agg_ext_finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, const u
         AggExtTask &t = a.t[i];
         outs[i] = TaskOut();
         if (bt[i].n == 0) continue;
-        u64 *other_k = (bt[i].out_k == bt[i].kA) ? bt[i].kB : bt[i].kA;
-        u64 *other_v = (bt[i].out_v == bt[i].vA) ? bt[i].vB : bt[i].vA;
         t.keys = bt[i].out_k; t.vals = bt[i].out_v; t.n = bt[i].n; t.bounds = d_bounds + per * i; t.bin_cnt = d_cnt + per * i; t.flags = d_flags + i;
         t.slot_shift = slot_shift; t.active = 1; t.payoff_add = pay_before[i]; ntot += bt[i].n;
-        if (slot_shift) { t.scratch_e = other_k; t.scratch_p = other_v; }       // n / 2 entries of 8 (NW + 1) + 8 bytes: the idle ping-pong buffers (8 NW + 8 bytes per record)
+        if (slot_shift) { t.scratch_e = other_side(bt[i]); t.scratch_p = other_vals(bt[i]); }       // n / 2 entries of 8 (NW + 1) + 8 bytes: the idle ping-pong buffers (8 NW + 8 bytes per record)
         else {
             t.scratch_e = (u64 *)c->pool.alloc(bt[i].n * EW * 8 + 64); t.scratch_p = (u64 *)c->pool.alloc(bt[i].n * 8 + 64); own_scratch[i] = true;
             if (!t.scratch_e || !t.scratch_p) return fail(c, HSK_ERR_OOM, "finish scratch");
@@ -568,65 +556,61 @@ static int agg_ext_finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, const u
     // CU), 1024 / 2048 for two and three words.  The first table follows the previous batches like agg_stage2's (reads with
     // ~1 % errors: ~900 distinct keys per bin, every bin overflows 1024 slots).
     constexpr int TOP = NW == 1 ? AG_LOG2CAP_LARGE : AG_LOG2CAP_MEDIUM;
-    u32 *d_list; DALLOC(c, d_list, u32 *, (size_t)nbins * 4 * AG_BATCH * 2);
-    struct { u32 flags[3 * AG_BATCH]; u64 total[AG_BATCH]; } h;
+    struct H { u32 flags[AG_BATCH], ovf[2][AG_BATCH]; u64 total[AG_BATCH]; } h;      // mirrors the device control block (+ totals)
+    OvfLists ovf; ovf.nbins = nbins;
+    DALLOC(c, ovf.list[0], u32 *, (size_t)nbins * 4 * AG_BATCH * 2); ovf.list[1] = ovf.list[0] + (size_t)nbins * AG_BATCH;
+    for (int x = 0; x < 2; ++x) { ovf.len[x] = d_flags + (1 + x) * AG_BATCH; ovf.h_len[x] = h.ovf[x]; }
+    // (NW > 1: no table beyond MEDIUM)
     auto launch = [&](int log2cap, u32 grid_x) {
-        EvPair ep{}; if (profile) { ep.a = ev_get(c); ep.b = ev_get(c); ep.kind = 2; ep.keys = ntot; ep.bytes = ntot * 16; (void)hipEventRecord(ep.a, c->stream); }
-        if (log2cap == AG_LOG2CAP_SMALL) hipLaunchKernelGGL((agg_ext_kernel<AG_LOG2CAP_SMALL, NW>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-        else if (log2cap == AG_LOG2CAP_MEDIUM || NW > 1) hipLaunchKernelGGL((agg_ext_kernel<AG_LOG2CAP_MEDIUM, NW>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-        else hipLaunchKernelGGL((agg_ext_kernel<(NW == 1 ? AG_LOG2CAP_LARGE : AG_LOG2CAP_MEDIUM), NW>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-        if (profile) { (void)hipEventRecord(ep.b, c->stream); c->ev_pending.push_back(ep); }
+        profiled(c, 2, ntot, ntot * 16, [&] { with_cap(log2cap, [&](auto cap) {
+            constexpr int CAP = (NW > 1 && decltype(cap)::value > AG_LOG2CAP_MEDIUM) ? AG_LOG2CAP_MEDIUM : decltype(cap)::value;
+            hipLaunchKernelGGL((agg_ext_kernel<CAP, NW>), dim3(grid_x, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
+        }); });
     };
     memset(&h, 0, sizeof h);
     hipLaunchKernelGGL(bin_bounds_ext_kernel, dim3(nbins / AG_THREADS + 1, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
     int nact = 0; for (int i = 0; i < AG_BATCH; ++i) nact += a.t[i].active ? 1 : 0;
+    const u64 all_bins = (u64)nact * nbins;
     bool hopeless[AG_BATCH] = {false};
     int cap = std::min(std::max(c->agg_first_cap, (int)AG_LOG2CAP_SMALL), TOP - 1);     // (never the last table first: its overflows are not counted)
     const int first_cap = cap;
     {
         const AggExtArgs keep = a;
-        int cur = 0;                                        // list the running rung appends to
         u32 grid_x = nbins;
         for (bool first = true;; first = false) {
             const bool last = cap == TOP;
             for (int i = 0; i < AG_BATCH; ++i) {
                 AggExtTask &t = a.t[i];
-                if (!first) { t.bin_list = d_list + ((size_t)(cur ^ 1) * AG_BATCH + i) * nbins; t.bin_list_n = d_flags + (1 + (cur ^ 1)) * AG_BATCH + i; }
-                t.ovf_list = last ? nullptr : d_list + ((size_t)cur * AG_BATCH + i) * nbins;
-                t.ovf_n = last ? nullptr : d_flags + (1 + cur) * AG_BATCH + i;
+                if (!first) { t.bin_list = ovf.reads(i); t.bin_list_n = ovf.reads_n(i); }
+                t.ovf_list = last ? nullptr : ovf.appends(i);
+                t.ovf_n = last ? nullptr : ovf.appends_n(i);
             }
-            if (!last) HIPCHK(c, hipMemsetAsync(d_flags + (1 + cur) * AG_BATCH, 0, sizeof(u32) * AG_BATCH, c->stream));
+            if (!last) HIPCHK(c, hipMemsetAsync(ovf.appends_n(), 0, sizeof(u32) * AG_BATCH, c->stream));
             launch(cap, grid_x);
             HIPCHK(c, hipGetLastError());
             if (last) break;
-            HIPCHK(c, hipMemcpyAsync(h.flags, d_flags, sizeof h.flags, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&h, d_flags, offsetof(H, total), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hsk_sync(c, c->stream));
             u32 longest = 0; u64 listed = 0;
-            for (int i = 0; i < AG_BATCH; ++i) if (keep.t[i].active) { const u32 n = std::min(h.flags[(1 + cur) * AG_BATCH + i], nbins); longest = std::max(longest, n); listed += n; }
-            if (first && nact) {                            // the next batch's first table
-                if (listed * 20 > (u64)nact * nbins) { c->agg_first_cap = std::min(first_cap + 1, TOP - 1); c->agg_clean_batches = 0; }
-                else if (listed == 0 && first_cap > AG_LOG2CAP_SMALL && ++c->agg_clean_batches >= 4) { c->agg_first_cap = first_cap - 1; c->agg_clean_batches = 0; }
-            }
+            for (int i = 0; i < AG_BATCH; ++i) if (keep.t[i].active) { const u32 n = std::min(ovf.appended(i), nbins); longest = std::max(longest, n); listed += n; }
+            // the next batch's first table
+            if (first && nact && !first_table_up(c, first_cap, TOP - 1, listed, all_bins)) first_table_down(c, first_cap, listed, nullptr);
             if (!longest) break;
-            // more than half of all bins beyond 2048 slots: (nearly) as many distinct k-mers as k-mers; the listed bins' tasks take the
-            // long way now instead of after the last table
-            const bool adapt = tune("agg_adapt", 1) != 0;
-            if (adapt && cap >= AG_LOG2CAP_MEDIUM && listed * 2 > (u64)nact * nbins) {
-                for (int i = 0; i < AG_BATCH; ++i) if (keep.t[i].active && h.flags[(1 + cur) * AG_BATCH + i]) hopeless[i] = true;
-                c->agg_off_wide = true;                      // the batches after this one: no prefix passes and tables at all
+            // hopeless: the listed bins' tasks take the long way now instead of after the last table
+            if (ladder_hopeless(cap, listed, all_bins, c->agg_off_wide)) {
+                for (int i = 0; i < AG_BATCH; ++i) if (keep.t[i].active && ovf.appended(i)) hopeless[i] = true;
                 break;
             }
-            for (int i = 0; i < AG_BATCH; ++i) { a.t[i].active = (keep.t[i].active && h.flags[(1 + cur) * AG_BATCH + i]) ? 1 : 0; c->stats.agg_retried_tasks += a.t[i].active; }
-            ++cap; cur ^= 1; grid_x = longest;
+            for (int i = 0; i < AG_BATCH; ++i) { a.t[i].active = (keep.t[i].active && ovf.appended(i)) ? 1 : 0; c->stats.agg_retried_tasks += a.t[i].active; }
+            ++cap; ovf.swap(); grid_x = longest;
         }
         a = keep;
     }
-    { const bool force_off = tune("agg_adapt", 1) == 2;     // (tests: as in agg_stage2)
-      if (force_off) c->agg_off_wide = true; }
+    if (tune("agg_adapt", 1) == 2) c->agg_off_wide = true;      // (tests: as in agg_stage2)
     for (int i = 0; i < AG_BATCH; ++i) sa.t[i].active = a.t[i].active;
     hipLaunchKernelGGL(agg_scan_kernel, dim3(AG_BATCH), dim3(AG_THREADS), 0, c->stream, sa);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h.flags, d_flags, sizeof h.flags, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&h, d_flags, offsetof(H, total), hipMemcpyDeviceToHost, c->stream));
     for (int i = 0; i < AG_BATCH; ++i) if (a.t[i].active) HIPCHK(c, hipMemcpyAsync(&h.total[i], a.t[i].bin_cnt + nbins, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hsk_sync(c, c->stream));
     int rc = HSK_OK;
@@ -665,21 +649,14 @@ static int agg_ext_finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, const u
     for (int i = 0; i < AG_BATCH && rc == HSK_OK; ++i) {
         if (bt[i].n == 0 || done[i]) continue;
         // the long way for this task: full-width passes (payload carried) from the current order, then the two-pass counter
-        c->stats.redone_tasks++;
         HIPCHK(c, hsk_sync(c, c->stream));
         if (own_scratch[i]) { c->pool.release(a.t[i].scratch_e); c->pool.release(a.t[i].scratch_p); own_scratch[i] = false; }
-        const u64 payadd = pay_before[i];
         free_task_out(c, outs[i]);
-        SortScratch sc1; rc = alloc_sort_scratch(c, sc1); if (rc) break;
-        u64 *cur = bt[i].out_k, *other = (cur == bt[i].kA) ? bt[i].kB : bt[i].kA, *sk, *sv;
-        u64 *vcur = bt[i].out_v, *vother = (vcur == bt[i].vA) ? bt[i].vB : bt[i].vA;
-        rc = sort_task_device<NW>(c, cur, other, vcur, vother, bt[i].n, K, sc1, &sk, &sv, false);
-        free_sort_scratch(c, sc1);
-        if (rc == HSK_OK) rc = count_task_device<NW>(c, sk, sv, bt[i].n, payadd, d_histo, histo_len, outs[i]);
+        rc = long_way_task<NW>(c, bt[i], K, true, [&](u64 *sk, u64 *sv) { return count_task_device<NW>(c, sk, sv, bt[i].n, pay_before[i], d_histo, histo_len, outs[i]); });
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hsk_sync(c, c->stream));
     for (int i = 0; i < AG_BATCH; ++i) if (own_scratch[i]) { c->pool.release(a.t[i].scratch_e); c->pool.release(a.t[i].scratch_p); }
-    c->pool.release(d_bounds); c->pool.release(d_cnt); c->pool.release(d_flags); c->pool.release(d_list);
+    c->pool.release(d_bounds); c->pool.release(d_cnt); c->pool.release(d_flags); c->pool.release(ovf.list[0]);
     return rc;
 }

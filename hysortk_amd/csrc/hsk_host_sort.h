@@ -67,6 +67,19 @@ static bool unstable_first_pass()
     return tune("unstable_first", 1) != 0;
 }
 
+// The profile bracket (HSK_FLAG_PROFILE): an event on the context's stream before and behind what `launch` enqueues, kept with the
+// kind of work and what it moved until the call's last wait (hsk_api.hip reads ev_pending).  Without the flag: just the launch.
+template <typename F>
+static void profiled(hsk_ctx *c, int kind, u64 keys, u64 bytes, F &&launch)
+{
+    if (!(c->cfg.flags & HSK_FLAG_PROFILE)) { launch(); return; }
+    EvPair ep{ev_get(c), ev_get(c), kind, keys, bytes};
+    (void)hipEventRecord(ep.a, c->stream);
+    launch();
+    (void)hipEventRecord(ep.b, c->stream);
+    c->ev_pending.push_back(ep);
+}
+
 struct SortScratch {
     u64 *ghist = nullptr;      // [MAX_PASSES][256]
     u64 *gbase = nullptr;      // [MAX_PASSES][256]
@@ -89,15 +102,12 @@ static int sort_task_device(hsk_ctx *c, u64 *keysA, u64 *keysB, u64 *valsA, u64 
     *out_keys = keysA; *out_vals = valsA;
     if (n < 2) return HSK_OK;
     const bool has_val = valsA != nullptr;
-    const bool profile = (c->cfg.flags & HSK_FLAG_PROFILE) != 0;
     const bool hybrid = allow_hybrid && NW == 1 && hybrid_enabled();
     HistArgs h; memset(&h, 0, sizeof h);
     h.keys = keysA; h.n = n; h.npass = hybrid ? make_hybrid_plan(h.pass) : make_pass_plan(K, NW, c->cfg.radix_bits, h.pass); h.ghist = sc.ghist;
     HIPCHK(c, hipMemsetAsync(sc.ghist, 0, (size_t)MAX_PASSES * 256 * 8, c->stream));
     const u32 hblocks = (u32)std::min<u64>((n + SORT_THREADS * 16 - 1) / (SORT_THREADS * 16), 2048);
-    EvPair hp{}; if (profile) { hp.a = ev_get(c); hp.b = ev_get(c); hp.kind = 1; hp.bytes = n * NW * 8; (void)hipEventRecord(hp.a, c->stream); }
-    hipLaunchKernelGGL((hist_kernel<NW>), dim3(hblocks), dim3(SORT_THREADS), (size_t)h.npass * 256 * 4, c->stream, h);
-    if (profile) { (void)hipEventRecord(hp.b, c->stream); c->ev_pending.push_back(hp); }
+    profiled(c, 1, 0, n * NW * 8, [&] { hipLaunchKernelGGL((hist_kernel<NW>), dim3(hblocks), dim3(SORT_THREADS), (size_t)h.npass * 256 * 4, c->stream, h); });
     u64 *hh = (u64 *)c->pinned;                          // [npass][256] histogram, then [npass][256] bases
     HIPCHK(c, hipMemcpyAsync(hh, sc.ghist, (size_t)h.npass * 256 * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hsk_sync(c, c->stream));
@@ -133,10 +143,10 @@ static int sort_task_device(hsk_ctx *c, u64 *keysA, u64 *keysB, u64 *valsA, u64 
         a.gbase = sc.gbase + (size_t)p * 256;
         a.lookback = (char *)sc.lookback + i * (size_t)ntiles * 256 * lbw;
         a.ticket = sc.tickets + i; a.err = c->d_err;
-        EvPair ep{}; if (profile) { ep.a = ev_get(c); ep.b = ev_get(c); ep.kind = 0; ep.keys = n; ep.bytes = 2 * n * (NW * 8 + (has_val ? 8 : 0)); (void)hipEventRecord(ep.a, c->stream); }
-        if (has_val) { if (wide) launch_onesweep<NW, true, u64>(c, a, ntiles); else launch_onesweep<NW, true, u32>(c, a, ntiles); }
-        else { if (wide) launch_onesweep<NW, false, u64>(c, a, ntiles); else launch_onesweep<NW, false, u32>(c, a, ntiles); }
-        if (profile) { (void)hipEventRecord(ep.b, c->stream); c->ev_pending.push_back(ep); }
+        profiled(c, 0, n, 2 * n * (NW * 8 + (has_val ? 8 : 0)), [&] {
+            if (has_val) { if (wide) launch_onesweep<NW, true, u64>(c, a, ntiles); else launch_onesweep<NW, true, u32>(c, a, ntiles); }
+            else { if (wide) launch_onesweep<NW, false, u64>(c, a, ntiles); else launch_onesweep<NW, false, u32>(c, a, ntiles); }
+        });
         std::swap(kin, kout); std::swap(vin, vout);
     }
     HIPCHK(c, hipGetLastError());
@@ -169,6 +179,23 @@ static void free_sort_scratch(hsk_ctx *c, SortScratch &sc);
 // ---- eight tasks at a time, one per XCD (onesweep_multi_kernel) -----------------------------------------
 struct BatchTask { u64 n = 0; u64 *kA = nullptr, *kB = nullptr, *vA = nullptr, *vB = nullptr; u64 *out_k = nullptr, *out_v = nullptr; };
 constexpr int XCD_BATCH = 8;
+// the idle ping-pong buffers of a task: the side that does not hold its current order
+static u64 *other_side(const BatchTask &bt) { return bt.out_k == bt.kA ? bt.kB : bt.kA; }
+static u64 *other_vals(const BatchTask &bt) { return bt.out_v == bt.vA ? bt.vB : bt.vA; }
+
+// The long way for ONE task: the full-width passes from its current order (the payload carried or left behind), then after(keys, vals)
+// on the sorted arrays -- the two-pass counter, the pair merge, or just taking note of where they are.  The caller has given back what
+// the task held before (stream-ordered reuse: the passes' scratch may take those blocks).
+template <int NW, typename After>
+static int long_way_task(hsk_ctx *c, const BatchTask &bt, int K, bool payload, After &&after)
+{
+    c->stats.redone_tasks++;
+    SortScratch sc; int rc = alloc_sort_scratch(c, sc); if (rc) return rc;
+    u64 *sk, *sv;
+    rc = sort_task_device<NW>(c, bt.out_k, other_side(bt), payload ? bt.out_v : nullptr, payload ? other_vals(bt) : nullptr, bt.n, K, sc, &sk, &sv, false);
+    free_sort_scratch(c, sc);
+    return rc ? rc : after(sk, sv);
+}
 
 template <int NW, bool HAS_VAL, typename LB>
 static void launch_onesweep_multi(hsk_ctx *c, const MultiSortArgs &m, u32 grid)
@@ -189,7 +216,6 @@ static int batch_pass_plan(hsk_ctx *c, int K, bool finish_follows, int prefix_bi
 template <int NW>
 static int sort_batch_device(hsk_ctx *c, BatchTask *bt, int K, bool finish_follows, int prefix_bits = 64 - HYBRID_SHIFT, u64 *d_ghist_pre = nullptr)
 {
-    const bool profile = (c->cfg.flags & HSK_FLAG_PROFILE) != 0;
     const bool has_val = bt[0].vA != nullptr;
     constexpr int TILE = SortTile<NW>::TILE;
     u64 *d_ghist, *d_gbase; u32 *d_tickets;
@@ -213,9 +239,7 @@ static int sort_batch_device(hsk_ctx *c, BatchTask *bt, int K, bool finish_follo
         h.keys = bt[i].kA; h.n = bt[i].n; h.npass = npass; memcpy(h.pass, plan, sizeof(PassDesc) * npass);
         h.ghist = d_ghist + (size_t)i * MAX_PASSES * 256;
         const u32 hblocks = (u32)std::min<u64>((bt[i].n + SORT_THREADS * 16 - 1) / (SORT_THREADS * 16), 2048);
-        EvPair hp{}; if (profile) { hp.a = ev_get(c); hp.b = ev_get(c); hp.kind = 1; hp.bytes = bt[i].n * NW * 8; (void)hipEventRecord(hp.a, c->stream); }
-        hipLaunchKernelGGL((hist_kernel<NW>), dim3(hblocks), dim3(SORT_THREADS), (size_t)npass * 256 * 4, c->stream, h);
-        if (profile) { (void)hipEventRecord(hp.b, c->stream); c->ev_pending.push_back(hp); }
+        profiled(c, 1, 0, bt[i].n * NW * 8, [&] { hipLaunchKernelGGL((hist_kernel<NW>), dim3(hblocks), dim3(SORT_THREADS), (size_t)npass * 256 * 4, c->stream, h); });
     }
     std::vector<u64> hh((size_t)XCD_BATCH * MAX_PASSES * 256), hb((size_t)XCD_BATCH * MAX_PASSES * 256, 0);
     HIPCHK(c, hipMemcpyAsync(hh.data(), d_ghist, hh.size() * 8, hipMemcpyDeviceToHost, c->stream));
@@ -262,10 +286,10 @@ static int sort_batch_device(hsk_ctx *c, BatchTask *bt, int K, bool finish_follo
                 a.lookback = (char *)d_lookback + j * per_pass + lb_off[i];
                 a.ticket = d_tickets + (size_t)i * MAX_PASSES + j; a.err = c->d_err;
             }
-            EvPair ep{}; if (profile) { ep.a = ev_get(c); ep.b = ev_get(c); ep.kind = 0; ep.keys = ntot; ep.bytes = 2 * ntot * (NW * 8 + (has_val ? 8 : 0)); (void)hipEventRecord(ep.a, c->stream); }
-            if (has_val) { if (wide) launch_onesweep_multi<NW, true, u64>(c, m, grid); else launch_onesweep_multi<NW, true, u32>(c, m, grid); }
-            else { if (wide) launch_onesweep_multi<NW, false, u64>(c, m, grid); else launch_onesweep_multi<NW, false, u32>(c, m, grid); }
-            if (profile) { (void)hipEventRecord(ep.b, c->stream); c->ev_pending.push_back(ep); }
+            profiled(c, 0, ntot, 2 * ntot * (NW * 8 + (has_val ? 8 : 0)), [&] {
+                if (has_val) { if (wide) launch_onesweep_multi<NW, true, u64>(c, m, grid); else launch_onesweep_multi<NW, true, u32>(c, m, grid); }
+                else { if (wide) launch_onesweep_multi<NW, false, u64>(c, m, grid); else launch_onesweep_multi<NW, false, u32>(c, m, grid); }
+            });
             for (int i = 0; i < XCD_BATCH; ++i) { if (ntiles[i]) { std::swap(kin[i], kout[i]); std::swap(vin[i], vout[i]); } }
         }
         HIPCHK(c, hipGetLastError());
@@ -275,8 +299,7 @@ static int sort_batch_device(hsk_ctx *c, BatchTask *bt, int K, bool finish_follo
     if (hybrid && !finish_follows) {
         for (int i = 0; i < XCD_BATCH; ++i) {
             if (bt[i].n < 2) continue;
-            u64 *other = (bt[i].out_k == bt[i].kA) ? bt[i].kB : bt[i].kA;
-            u64 *vother = has_val ? ((bt[i].out_v == bt[i].vA) ? bt[i].vB : bt[i].vA) : nullptr;
+            u64 *other = other_side(bt[i]), *vother = has_val ? other_vals(bt[i]) : nullptr;
             BinSortArgs b; b.in = bt[i].out_k; b.out = other; b.vin = bt[i].out_v; b.vout = vother; b.n = bt[i].n; b.hi_shift = HYBRID_SHIFT; b.mixed_giant = d_flags + i;
             hipLaunchKernelGGL(binsort_kernel, dim3((u32)((bt[i].n + BS_TILE - 1) / BS_TILE)), dim3(BS_THREADS), 0, c->stream, b);
             bt[i].out_k = other; bt[i].out_v = vother;
@@ -293,13 +316,7 @@ static int sort_batch_device(hsk_ctx *c, BatchTask *bt, int K, bool finish_follo
         if (hybrid && !finish_follows && rc == HSK_OK) {
             for (int i = 0; i < XCD_BATCH && rc == HSK_OK; ++i) {
                 if (!tk[(size_t)XCD_BATCH * MAX_PASSES + i]) continue;
-                c->stats.redone_tasks++;
-                SortScratch sc1; rc = alloc_sort_scratch(c, sc1); if (rc) break;
-                u64 *cur = bt[i].out_k, *other = (cur == bt[i].kA) ? bt[i].kB : bt[i].kA, *sk, *sv;
-                u64 *vcur = bt[i].out_v, *vother = has_val ? ((vcur == bt[i].vA) ? bt[i].vB : bt[i].vA) : nullptr;
-                rc = sort_task_device<NW>(c, cur, other, vcur, vother, bt[i].n, K, sc1, &sk, &sv, false);
-                bt[i].out_k = sk; bt[i].out_v = sv;
-                free_sort_scratch(c, sc1);
+                rc = long_way_task<NW>(c, bt[i], K, has_val, [&](u64 *sk, u64 *sv) { bt[i].out_k = sk; bt[i].out_v = sv; return (int)HSK_OK; });
             }
         }
     }
