@@ -102,7 +102,7 @@ static int validate_cfg(const hsk_config *cfg)
     if (!(0 < cfg->lower_freq && cfg->lower_freq <= cfg->upper_freq && cfg->upper_freq <= 65535)) return 0;  // compiletime.h:21
     if (cfg->extension != 0 && cfg->extension != 1) return 0;
     if (cfg->ntasks < 0 || cfg->ntasks > HSK_MAX_TASKS) return 0;
-    if (cfg->radix_bits != 0 && (cfg->radix_bits < 4 || cfg->radix_bits > 8)) return 0;
+    if (cfg->radix_bits != 0 && (cfg->radix_bits < MIN_RADIX_BITS || cfg->radix_bits > MAX_RADIX_BITS)) return 0;   // every (K, radix_bits) plan fits MAX_PASSES (hsk_passplan.h)
     return 1;
 }
 

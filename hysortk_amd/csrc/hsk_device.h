@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "hsk_passplan.h"
 
 namespace hsk {
 
@@ -243,9 +244,8 @@ __device__ __forceinline__ T block_excl_scan_256_lds(T v, T *scratch, T *total) 
     return base + inc - v;
 }
 
-// ---- radix digit plan (hsk_sort.h; hsk_expand.h builds the digit histograms while it writes the keys) ----
-constexpr int MAX_PASSES = 24;
-struct PassDesc { int word; int shift; int bits; };
+// ---- radix digit plan: MAX_PASSES, PassDesc and the plan builders are in hsk_passplan.h (hsk_sort.h; hsk_expand.h builds the
+// digit histograms while it writes the keys) ----
 
 // k[word] without dynamic register indexing (which would spill the key array to scratch)
 template <int NW> __device__ __forceinline__ u64 pick_word(const u64 *k, int word)

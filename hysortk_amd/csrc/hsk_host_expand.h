@@ -91,6 +91,13 @@ static int expand_batch(hsk_ctx *c, const ExpandJob *jobs, int njobs, int npass 
     a.ntask = nt; a.k = c->cfg.kmer_size; a.npass = npass;
     if (npass) memcpy(a.pass, plan, sizeof(PassDesc) * npass);
     const size_t dyn = (size_t)std::max(npass, 1) * 256 * 4;
+    // a full-width plan of narrow digits (radix_bits 4: up to MAX_PASSES KB of histograms) takes the workgroup past 64 KB of LDS in all
+    static bool announced[2];
+    if (dyn > 32 * 1024 && !announced[ext ? 1 : 0]) {
+        (void)hipFuncSetAttribute(ext ? reinterpret_cast<const void *>(expand_kernel<NW, true>) : reinterpret_cast<const void *>(expand_kernel<NW, false>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, MAX_PASSES * 256 * 4);
+        announced[ext ? 1 : 0] = true;
+    }
     // persistent workgroups: exactly what is resident at once (a second wave would start when the first is done)
     static std::map<size_t, int> occ_c[2];               // per dynamic-LDS size (the histogram area grows with the pass count)
     int &occ = occ_c[ext ? 1 : 0][dyn];

@@ -376,6 +376,7 @@ static int expand_slot(hsk_ctx *c, const RankPlan<NW> &P, BatchSlot &s, const u3
     s.prefix = prefix_bits;
     PassDesc plan[MAX_PASSES];
     int npass = batch_pass_plan<NW>(c, P.K, s.follow, will_combine ? AG_PREFIX_BITS : prefix_bits, plan);
+    if (npass < 0) return plan_too_long(c, P.K, NW);
     // the pairs' two digits (most significant word): the low prefix bits, then the top 8
     if (will_combine) { npass = 2; plan[0] = PassDesc{NW - 1, 64 - prefix_bits, prefix_bits - 8}; plan[1] = PassDesc{NW - 1, 56, 8}; }
     pt.begin(PH_EXTRACT);

@@ -5,30 +5,11 @@
 // ------------------------------------------------------------------------------------------------
 // stage: sort one task (a12)
 // ------------------------------------------------------------------------------------------------
-// Digit plan: the key is the little-endian integer formed by words 0..NW-1; word w carries
-// min(32, K-32w) bases in its top bits.  Digits are taken from the least significant used bit up.
-static int make_pass_plan(int K, int nw, int rb, PassDesc *out)
+// The digit plans (make_pass_plan, make_hybrid_plan, make_split_prefix_plan) are in hsk_passplan.h; every array they fill here has
+// MAX_PASSES entries, and a plan that would not fit is an error before anything is written or launched.
+static int plan_too_long(hsk_ctx *c, int K, int nw)
 {
-    int np = 0;
-    for (int w = 0; w < nw; ++w) {
-        const int nbases = std::min(32, K - 32 * w);
-        int lo = 64 - 2 * nbases;
-        while (lo < 64) { int bits = std::min(rb, 64 - lo); out[np++] = PassDesc{w, lo, bits}; lo += bits; }
-    }
-    return np;
-}
-
-// Hybrid plan (one-word keys without payload): only the top 32 bits (16 bases) are ordered by global passes
-// (digits at bit 32, 40, 48, 56, least significant first); binsort_kernel finishes the low bits inside each
-// bin.  With 32 prefix bits two different k-mers of one task rarely share a bin, so nearly every bin is the
-// copies of ONE k-mer and passes through untouched; 24 bits left 40 % of the records in multi-key bins whose
-// in-LDS ordering (serial, LDS-latency bound) cost more than the fourth pass.
-constexpr int HYBRID_SHIFT = 32;
-static int make_hybrid_plan(PassDesc *out, int prefix_bits = 64 - HYBRID_SHIFT, int word = 0)
-{
-    const int np = prefix_bits / 8;                     // LSD passes over the top prefix_bits bits (of the most significant word)
-    for (int i = 0; i < np; ++i) out[i] = PassDesc{word, 64 - prefix_bits + 8 * i, 8};
-    return np;
+    return fail(c, HSK_ERR_INTERNAL, "no digit plan of at most %d passes for K = %d, %d words, radix_bits = %d", MAX_PASSES, K, nw, c->cfg.radix_bits);
 }
 static bool hybrid_enabled()
 {
@@ -41,19 +22,6 @@ template <int NW> static bool prefix_plan_ok(int K, bool finish_follows)
 {
     return hybrid_enabled() && (NW == 1 || (NW <= 3 && finish_follows));
 }
-// bits of the 16-bit prefix that the most significant word holds (16: all of them)
-static int prefix_top_bits(int K, int nw) { return std::min(16, 2 * (K - 32 * (nw - 1))); }
-// The 16-bit prefix of a key whose most significant word has only `top` < 16 significant bits: those, then the top 16 - top
-// bits of the word below.  LSD passes, least significant digit first, no digit across a word boundary or wider than 8 bits.
-static int make_split_prefix_plan(PassDesc *out, int top, int nw)
-{
-    int np = 0;
-    const int low = 16 - top;                            // bits taken from word nw - 2
-    for (int lo = 64 - low; lo < 64; ) { const int bits = std::min(8, 64 - lo); out[np++] = PassDesc{nw - 2, lo, bits}; lo += bits; }
-    for (int lo = 64 - top; lo < 64; ) { const int bits = std::min(8, 64 - lo); out[np++] = PassDesc{nw - 1, lo, bits}; lo += bits; }
-    return np;
-}
-
 // tasks of 2^30 keys and more use 64-bit look-back words; HSK_WIDE_LOOKBACK=1 forces them (tests: such tasks do not fit a test)
 static bool force_wide_lookback()
 {
@@ -84,8 +52,10 @@ struct SortScratch {
     u64 *ghist = nullptr;      // [MAX_PASSES][256]
     u64 *gbase = nullptr;      // [MAX_PASSES][256]
     void *lookback = nullptr; size_t lookback_bytes = 0;
-    u32 *tickets = nullptr;    // [MAX_PASSES]
+    u32 *tickets = nullptr;    // [SORT_TICKET_WORDS]: a ticket per pass, and binsort_kernel's flag in word SORT_FLAG_WORD
 };
+constexpr int SORT_TICKET_WORDS = 64, SORT_FLAG_WORD = 60;
+static_assert(MAX_PASSES <= SORT_FLAG_WORD && SORT_FLAG_WORD < SORT_TICKET_WORDS, "the flag word lies behind the tickets of the longest plan, inside the block");
 
 template <int NW, bool HAS_VAL, typename LB>
 static void launch_onesweep(hsk_ctx *c, const SortArgs &a, u32 ntiles)
@@ -104,11 +74,12 @@ static int sort_task_device(hsk_ctx *c, u64 *keysA, u64 *keysB, u64 *valsA, u64 
     const bool has_val = valsA != nullptr;
     const bool hybrid = allow_hybrid && NW == 1 && hybrid_enabled();
     HistArgs h; memset(&h, 0, sizeof h);
-    h.keys = keysA; h.n = n; h.npass = hybrid ? make_hybrid_plan(h.pass) : make_pass_plan(K, NW, c->cfg.radix_bits, h.pass); h.ghist = sc.ghist;
+    h.keys = keysA; h.n = n; h.npass = hybrid ? make_hybrid_plan(h.pass, MAX_PASSES) : make_pass_plan(K, NW, c->cfg.radix_bits, h.pass, MAX_PASSES); h.ghist = sc.ghist;
+    if (h.npass < 0) return plan_too_long(c, K, NW);
     HIPCHK(c, hipMemsetAsync(sc.ghist, 0, (size_t)MAX_PASSES * 256 * 8, c->stream));
     const u32 hblocks = (u32)std::min<u64>((n + SORT_THREADS * 16 - 1) / (SORT_THREADS * 16), 2048);
     profiled(c, 1, 0, n * NW * 8, [&] { hipLaunchKernelGGL((hist_kernel<NW>), dim3(hblocks), dim3(SORT_THREADS), (size_t)h.npass * 256 * 4, c->stream, h); });
-    u64 *hh = (u64 *)c->pinned;                          // [npass][256] histogram, then [npass][256] bases
+    u64 *hh = (u64 *)c->pinned;                          // [MAX_PASSES][256] histogram, then [MAX_PASSES][256] bases (192 KB of the staging area's 1 MB)
     HIPCHK(c, hipMemcpyAsync(hh, sc.ghist, (size_t)h.npass * 256 * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hsk_sync(c, c->stream));
     u64 *hb = hh + (size_t)MAX_PASSES * 256;
@@ -153,7 +124,7 @@ static int sort_task_device(hsk_ctx *c, u64 *keysA, u64 *keysB, u64 *valsA, u64 
     }
     if (hybrid) {
         // order the low bits inside every prefix bin (one more streaming pass instead of five scatter passes)
-        u32 *d_flag = sc.tickets + 60;                         // spare word of the ticket block
+        u32 *d_flag = sc.tickets + SORT_FLAG_WORD;             // spare word of the ticket block
         HIPCHK(c, hipMemsetAsync(d_flag, 0, 4, c->stream));
         BinSortArgs b; b.in = kin; b.out = kout; b.vin = vin; b.vout = vout; b.n = n; b.hi_shift = HYBRID_SHIFT; b.mixed_giant = d_flag;
         hipLaunchKernelGGL(binsort_kernel, dim3((u32)((n + BS_TILE - 1) / BS_TILE)), dim3(BS_THREADS), 0, c->stream, b);
@@ -203,13 +174,14 @@ static void launch_onesweep_multi(hsk_ctx *c, const MultiSortArgs &m, u32 grid)
     hipLaunchKernelGGL((onesweep_multi_kernel<NW, HAS_VAL, LB>), dim3(grid), dim3(SORT_THREADS), 0, c->stream, m);
 }
 
-// the digit plan of a batch sort (shared with expand_batch, which counts the digits while it writes the keys)
+// the digit plan of a batch sort (shared with expand_batch, which counts the digits while it writes the keys); plan: [MAX_PASSES];
+// -1: it does not fit
 template <int NW>
 static int batch_pass_plan(hsk_ctx *c, int K, bool finish_follows, int prefix_bits, PassDesc *plan)
 {
     const bool hybrid = prefix_plan_ok<NW>(K, finish_follows);
-    if (hybrid && finish_follows && NW >= 2 && prefix_top_bits(K, NW) < 16 && prefix_bits == 16) return make_split_prefix_plan(plan, prefix_top_bits(K, NW), NW);
-    return hybrid ? make_hybrid_plan(plan, finish_follows ? prefix_bits : 64 - HYBRID_SHIFT, NW - 1) : make_pass_plan(K, NW, c->cfg.radix_bits, plan);
+    if (hybrid && finish_follows && NW >= 2 && prefix_top_bits(K, NW) < 16 && prefix_bits == 16) return make_split_prefix_plan(plan, MAX_PASSES, prefix_top_bits(K, NW), NW);
+    return hybrid ? make_hybrid_plan(plan, MAX_PASSES, finish_follows ? prefix_bits : 64 - HYBRID_SHIFT, NW - 1) : make_pass_plan(K, NW, c->cfg.radix_bits, plan, MAX_PASSES);
 }
 
 // d_ghist_pre: [XCD_BATCH][MAX_PASSES][256] digit histograms already counted by expand_batch (null: hist_kernel runs here)
@@ -218,6 +190,10 @@ static int sort_batch_device(hsk_ctx *c, BatchTask *bt, int K, bool finish_follo
 {
     const bool has_val = bt[0].vA != nullptr;
     constexpr int TILE = SortTile<NW>::TILE;
+    PassDesc plan[MAX_PASSES];
+    const bool hybrid = prefix_plan_ok<NW>(K, finish_follows);
+    const int npass = batch_pass_plan<NW>(c, K, finish_follows, prefix_bits, plan);
+    if (npass < 0) return plan_too_long(c, K, NW);
     u64 *d_ghist, *d_gbase; u32 *d_tickets;
     if (d_ghist_pre) d_ghist = d_ghist_pre;
     else {
@@ -227,9 +203,6 @@ static int sort_batch_device(hsk_ctx *c, BatchTask *bt, int K, bool finish_follo
     DALLOC(c, d_gbase, u64 *, (size_t)XCD_BATCH * MAX_PASSES * 256 * 8);
     DALLOC(c, d_tickets, u32 *, (size_t)XCD_BATCH * MAX_PASSES * 4 + 256);       // + 8 flag words behind the tickets
     HIPCHK(c, hipMemsetAsync(d_tickets, 0, (size_t)XCD_BATCH * MAX_PASSES * 4 + 64, c->stream));
-    PassDesc plan[MAX_PASSES];
-    const bool hybrid = prefix_plan_ok<NW>(K, finish_follows);
-    const int npass = batch_pass_plan<NW>(c, K, finish_follows, prefix_bits, plan);
     u64 ntot = 0; bool wide = force_wide_lookback();
     for (int i = 0; i < XCD_BATCH; ++i) {
         bt[i].out_k = bt[i].kA; bt[i].out_v = bt[i].vA;
@@ -328,7 +301,7 @@ static int alloc_sort_scratch(hsk_ctx *c, SortScratch &sc)
 {
     DALLOC(c, sc.ghist, u64 *, (size_t)MAX_PASSES * 256 * 8);
     DALLOC(c, sc.gbase, u64 *, (size_t)MAX_PASSES * 256 * 8);
-    DALLOC(c, sc.tickets, u32 *, 256);
+    DALLOC(c, sc.tickets, u32 *, SORT_TICKET_WORDS * 4);
     return HSK_OK;
 }
 static void free_sort_scratch(hsk_ctx *c, SortScratch &sc)

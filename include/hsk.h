@@ -51,7 +51,7 @@ typedef struct {
     int32_t plain_dispatcher; /* PLAIN_DISPATCHER: 1 = round robin, 0 = balanced (kmerops.cpp:115-119) */
     double  dispatch_upper_coe; /* DISPATCH_UPPER_COE (1.5) */
     double  dispatch_step;      /* DISPATCH_STEP      (0.05) */
-    int32_t radix_bits;       /* digit width of the LSD radix sort: 8 (default) */
+    int32_t radix_bits;       /* digit width of the full-width LSD radix plan: 4 .. 8, 0 = 8 (default 8; narrower = more passes) */
     int32_t flags;            /* HSK_FLAG_* */
     double  unbalanced_ratio; /* UNBALANCED_RATIO (2.3): a task is a heavy hitter above ratio x the mean task (kmerops.cpp:1190); ABI 3 */
     const char *tuning;       /* ABI 4 (was reserved[0]): NULL, or "name=value,name=value": forced paths for tests and a few measured thresholds, read per

@@ -126,6 +126,70 @@ def test_stage_sort_all_equal_and_sorted_inputs(H):
         assert np.array_equal(c.stage_sort(k[::-1].copy()).reshape(-1), k)
 
 
+_SORT_TILE = {1: 4096, 2: 2048, 3: 1280}                        # SortTile<NW>::TILE (hsk_sort.h)
+_SORT_CASES = {}
+
+
+def _stage_sort_cases(nw):
+    """[(name, keys, order)] for the sizes at which a tile-based pass can go wrong -- 1, 2, 63, one below / at / one above a tile, three
+    tiles plus one, ~10^5 (tiles that chain through the look-back) -- and the key shapes that narrow digits expose.  Built once per key
+    width (numpy's stable lexsort is the reference) and shared, read-only, by every digit width and look-back width."""
+    if nw in _SORT_CASES:
+        return _SORT_CASES[nw]
+    tile = _SORT_TILE[nw]
+    cases = []
+    for n in (1, 2, 63, tile - 1, tile, tile + 1, 3 * tile + 1, 100003):
+        rng = np.random.default_rng(n * 7 + nw)
+        rnd = lambda shape: rng.integers(0, 1 << 63, size=shape, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, size=shape, dtype=np.uint64)
+        shapes = []
+        keys = rnd((n, nw))
+        if n > 100:
+            keys[: n // 3] = keys[n // 3: 2 * (n // 3)]          # plenty of duplicates
+            keys[::7, nw - 1] &= np.uint64(0xFF)                  # skewed high digits
+        shapes.append(("random", keys))
+        base = rnd((1, nw))
+        # keys that differ only inside ONE digit: the lowest of word 0 (its low 4 bits are inside the first digit of every width) ...
+        keys = np.repeat(base, n, axis=0)
+        keys[:, 0] = (keys[:, 0] & ~np.uint64(15)) | (rnd(n) & np.uint64(15))
+        shapes.append(("low digit of word 0", keys))
+        # ... and the last digit of the top word: bit 63 is all of it at 7 bits, bits 60..63 at 4, 5 (the narrow one) and 8 bits' top half
+        for bits in (1, 4):
+            keys = np.repeat(base, n, axis=0)
+            keys[:, nw - 1] = (keys[:, nw - 1] & np.uint64((1 << (64 - bits)) - 1)) | (rnd(n) << np.uint64(64 - bits))
+            shapes.append(("top %d bits of word %d" % (bits, nw - 1), keys))
+        if nw >= 2:                                               # equal in all words but word nw - 2
+            keys = np.repeat(base, n, axis=0)
+            keys[:, nw - 2] = rnd(n)
+            if n > 100:
+                keys[: n // 3, nw - 2] = keys[n // 3: 2 * (n // 3), nw - 2]
+            shapes.append(("only word %d differs" % (nw - 2), keys))
+        for name, keys in shapes:
+            order = np.lexsort([keys[:, w] for w in range(nw)])   # little-endian multiword order: word nw-1 most significant
+            keys.setflags(write=False); order.setflags(write=False)
+            cases.append(("n=%d, %s" % (n, name), keys, order))
+    _SORT_CASES[nw] = cases
+    return cases
+
+
+@pytest.mark.parametrize("tuning", [None, "wide_lookback=1"])
+@pytest.mark.parametrize("radix_bits", [4, 5, 7, 8])
+@pytest.mark.parametrize("nw,plan", [(1, None), (1, "full_sort"), (2, None), (3, None)])
+def test_stage_sort_digit_widths_and_wide_lookback(H, nw, plan, radix_bits, tuning):
+    """hsk_stage_sort against numpy's stable lexsort over the full-width digit plan of every accepted digit width class -- 4 (sixteen
+    digits per word: three words are the longest plan there is, MAX_PASSES), 5 and 7 (a last digit of 4 bits / 1 bit in every word), 8 --
+    with 32-bit and with 64-bit look-back granules (wide_lookback=1: what tasks of 2^30 keys and more take), keys alone and with a payload
+    (whose order a stable sort pins too).  One-word keys take the 32-bit prefix plan + in-bin finish, which never reads radix_bits: they
+    also run with HSK_FLAG_FULL_SORT, where make_pass_plan is the plan."""
+    with H.Context(K={1: 31, 2: 51, 3: 80}[nw], radix_bits=radix_bits, plan=plan, tuning=tuning) as c:
+        for name, keys, order in _stage_sort_cases(nw):
+            vals = np.arange(len(keys), dtype=np.uint64)
+            out = c.stage_sort(keys)
+            out2, v2 = c.stage_sort(keys, vals)
+            assert np.array_equal(out, keys[order]), name
+            assert np.array_equal(out2, keys[order]), name
+            assert np.array_equal(v2, vals[order]), name          # LSD radix is stable, lexsort too
+
+
 # ---------------------------------------------------------------------------------------------------
 # a13: count_sorted_kmers
 # ---------------------------------------------------------------------------------------------------
@@ -709,6 +773,92 @@ def test_leaving_the_aggregation_in_the_middle_of_a_call(K, EXT):
         outs += [l.split() for l in subprocess.check_output([sys.executable, "-c", code], env=dict(os.environ, **util.tune_env(env))).decode().strip().splitlines()]
     assert len(outs) == 6 and len({o[0] for o in outs}) == 1, outs
     assert int(outs[0][1]) > 100000
+
+
+_BATCH_INPUT = {}
+
+
+def _batch_input(H, O, kind, K, EXT):
+    """(dna, oracle list) of the batch-path input, 24 tasks = three batches of eight, built once per shape.
+    "bins": 20 000 reads of 150 bases from a 300 kbp genome and 16 000 + 16 000 reads that share their first / last 100 bases and differ
+    in the other 40 -- prefix bins of 4 500 (K = 31) to 13 000 (K = 51, 77) distinct k-mers, beyond the first table of every ladder, beyond
+    the last one of the payload ladder (4096 slots for one-word keys, 2048 for wider ones) and beyond the last table of wide keys.
+    "deep": 60 000 reads from the same genome (30 copies of every k-mer: the combining extraction stays on)."""
+    from hysortk_amd import synth
+    if kind not in _BATCH_INPUT:
+        if kind == "bins":
+            rng = np.random.default_rng(19)
+            seqs = list(synth.reads(300000, 150, 20000, 11)) + ["AC" * 75] * 20
+            pre, suf = ("".join(rng.choice(list("ACGT"), 100)) for _ in range(2))
+            var = np.array(list("ACGT"))[rng.integers(0, 4, size=(32000, 40))]
+            seqs += ["".join(v) + suf for v in var[:16000]] + [pre + "".join(v) for v in var[16000:]]
+        else:
+            seqs = list(synth.reads(300000, 150, 60000, 11))
+        _BATCH_INPUT[kind] = H.DnaBuffer.from_sequences(seqs)
+    dna = _BATCH_INPUT[kind]
+    if (kind, K, EXT) not in _BATCH_INPUT:
+        packed, off, lens = dna.arrays()
+        _BATCH_INPUT[(kind, K, EXT)] = O.count(packed, off, lens, k=K, m=17, L=1, U=65535, ext=EXT, ntasks=24, rid_base=5, fast=True)
+    return dna, _BATCH_INPUT[(kind, K, EXT)]
+
+
+def _payload_triples(cnt, payoff, rid, pos):
+    """every (k-mer index, read, position) of a list, ordered: the payload SETS (the order inside one k-mer is free)"""
+    cnt = cnt.astype(np.int64)
+    first = np.repeat(payoff[:len(cnt)].astype(np.int64) - (np.cumsum(cnt) - cnt), cnt)
+    sel = first + np.arange(int(cnt.sum()))
+    t = np.stack([np.repeat(np.arange(len(cnt)), cnt), rid[sel].astype(np.int64), pos[sel].astype(np.int64)], 1)
+    return t[np.lexsort((t[:, 2], t[:, 1], t[:, 0]))]
+
+
+# what the case must have run, from stats(): "agg" every task finished by the batch path's aggregation or its long way, "long" some took
+# the long way (full-width passes), "combine" the combining extraction, ("passes", n) at most n eight-task scatter launches per batch
+@pytest.mark.parametrize("K,EXT,kind,kw,must", [
+    # 64-bit look-back granules in the eight-task kernel: two and three words, payload, and the weighted pass of {k-mer, count} pairs
+    (51, 0, "bins", dict(tuning="wide_lookback=1"), ("agg", "long")),
+    (77, 0, "bins", dict(tuning="wide_lookback=1"), ("agg", "long")),
+    (31, 1, "bins", dict(tuning="wide_lookback=1"), ("agg", "long")),
+    (51, 1, "bins", dict(tuning="wide_lookback=1"), ("agg", "long")),
+    (31, 0, "deep", dict(tuning="wide_lookback=1,combine_min_bytes=0"), ("agg", "combine")),
+    # narrow digits, the full-width plan on partial words: HSK_FLAG_FULL_SORT (62 bits: 16 digits of 4 / 10 of 6 and one of 2) ...
+    (31, 0, "bins", dict(radix_bits=4, plan="full_sort"), (("passes", 16),)),
+    (31, 0, "bins", dict(radix_bits=6, plan="full_sort"), (("passes", 11),)),
+    (31, 1, "bins", dict(radix_bits=4, plan="full_sort"), (("passes", 16),)),
+    # (... three words: 16 + 16 + 7 digits, whose 39 KB of histograms take expand_kernel past 64 KB of LDS)
+    (77, 0, "bins", dict(radix_bits=4, plan="full_sort"), (("passes", 39),)),
+    # ... and the long way out of the aggregation: no rung behind the first table (agg_maxrung=0), the listed bins' tasks take the
+    # full-width passes -- 64 + 38 bits (K = 51), 64 + 64 + 26 (K = 77); payload: the ladder ends by itself below the fullest bin
+    (51, 0, "bins", dict(radix_bits=4, tuning="agg_maxrung=0"), ("agg", "long")),
+    (51, 0, "bins", dict(radix_bits=6, tuning="agg_maxrung=0"), ("agg", "long")),
+    (77, 0, "bins", dict(radix_bits=4, tuning="agg_maxrung=0"), ("agg", "long")),
+    (77, 0, "bins", dict(radix_bits=6, tuning="agg_maxrung=0"), ("agg", "long")),
+    (31, 1, "bins", dict(radix_bits=4), ("agg", "long")),
+    (31, 1, "bins", dict(radix_bits=6), ("agg", "long")),
+], ids=["wide-k51", "wide-k77", "wide-k31ext", "wide-k51ext", "wide-k31combine", "rb4-k31full", "rb6-k31full", "rb4-k31extfull", "rb4-k77full",
+        "rb4-k51long", "rb6-k51long", "rb4-k77long", "rb6-k77long", "rb4-k31extlong", "rb6-k31extlong"])
+def test_batch_sort_wide_lookback_and_narrow_digits_vs_oracle(H, O, K, EXT, kind, kw, must):
+    """The eight-task kernels (onesweep_multi_kernel) with 64-bit look-back granules for every key width, with and without payload, and
+    the full-width digit plan at radix_bits 4 and 6 where it runs on partial words (K = 31, 51, 77), against the oracle's list: task
+    offsets, k-mers, counts, histogram, and for EXTENSION every k-mer's payload set."""
+    dna, ores = _batch_input(H, O, kind, K, EXT)
+    with H.Context(K=K, M=17, L=1, U=65535, EXT=EXT, ntasks=24, profile=True, **kw) as c:
+        res = c.count(dna, rid_base=5)
+        st = c.stats()
+    for m in must:
+        if m == "agg":
+            assert st["fused_tasks"] + st["redone_tasks"] == 24, st
+        elif m == "long":
+            assert st["redone_tasks"] > 0, st
+        elif m == "combine":
+            assert st["combine_launches"] > 0, st
+        else:
+            assert 0 < st["scatter_launches"] <= 3 * m[1], st
+    assert np.array_equal(res.task_off, ores.task_off)
+    assert np.array_equal(res.kmers, ores.keys)
+    assert np.array_equal(res.cnt, ores.cnt)
+    assert H.histogram_text(res.histo) == O.histogram_text(ores.cnt)
+    if EXT:
+        assert np.array_equal(_payload_triples(res.cnt, res.payload_off, res.rid, res.pos), _payload_triples(ores.cnt, ores.payoff, ores.rid, ores.pos))
 
 
 @pytest.mark.parametrize("K,L,U", [(51, 1, 65535), (51, 2, 50), (41, 2, 50), (63, 1, 65535), (35, 2, 50), (33, 1, 65535), (36, 2, 50), (39, 2, 50)])
