@@ -1,0 +1,161 @@
+"""Inputs of uneven shape for the combining extraction (tests/test_gpu_combine_ragged.py; validated on the CPU by
+tests/test_ragged_inputs.py): reads of every length class around K and around the item cut, with N, lower case and empty
+reads; records of many tiles with their edges on tile edges; tandem repeats; k-mers with more than 2^16 copies.  Plain
+functions, seeded and deterministic; every builder returns a list of strings (DnaBuffer.from_sequences / oracle.pack_reads
+take it; pack() below gives the same arrays in one numpy pass)."""
+import numpy as np
+
+_ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+_COMP = str.maketrans("ACGTacgt", "TGCAtgca")
+_CODE = np.zeros(256, dtype=np.uint8)
+for _ch, _c in (("C", 1), ("c", 1), ("G", 2), ("g", 2), ("T", 3), ("t", 3)):      # A, a, N, n -> 0 (DnaSeq::compress)
+    _CODE[ord(_ch)] = _c
+
+
+def item_cut(K):
+    """k-mers per item of the combining extraction at most (ParseArgs::item_maxk): 16, or 61 - K for two-word keys (keys the plan does not take: 1)"""
+    return max(1, min(16, 61 - K))
+
+
+def revcomp(s):
+    return s.translate(_COMP)[::-1]
+
+
+def random_seq(rng, n):
+    return _ACGT[rng.integers(0, 4, size=n, dtype=np.uint8)].tobytes().decode()
+
+
+def pack(seqs):
+    """(packed, read_off, read_len) of the reads, every read on a byte boundary: what oracle.pack_reads gives, in one pass"""
+    lens = np.array([len(s) for s in seqs], dtype=np.int64)
+    nb = (lens + 3) // 4
+    off = np.zeros(len(seqs), dtype=np.int64)
+    if len(seqs):
+        off[1:] = np.cumsum(nb)[:-1]
+    raw = np.frombuffer("".join(seqs).encode(), dtype=np.uint8)
+    first = np.zeros(len(seqs), dtype=np.int64)
+    if len(seqs):
+        first[1:] = np.cumsum(lens)[:-1]
+    at = np.arange(raw.size, dtype=np.int64) + np.repeat(off * 4 - first, lens)      # base i of read r -> position 4 off[r] + i
+    codes = np.zeros(int(nb.sum()) * 4, dtype=np.uint8)
+    codes[at] = _CODE[raw]
+    c = codes.reshape(-1, 4)
+    packed = (c[:, 0] << 6) | (c[:, 1] << 4) | (c[:, 2] << 2) | c[:, 3]
+    return np.ascontiguousarray(packed, dtype=np.uint8), off.astype(np.uint64), lens.astype(np.uint32)
+
+
+def ragged_lengths(K):
+    """the length classes of ragged(): none, one base, around K (all four len % 4 packing phases), supermers of one k-mer under the item cut,
+    exactly the cut and one over it, the usual 150 and reads of four tiles' length"""
+    kc = item_cut(K)
+    return [0, 1, K - 1, K, K + 1, K + 2, K + 3, kc - 1 + K - 1, kc + K - 1, kc + K, 150, 2047, 2048, 2049]
+
+
+def ragged(K, seed, nreads=6000, genome=60000):
+    """`nreads` reads cut from a random genome on both strands, their lengths taken in turn from ragged_lengths(K); one read in twenty carries an N,
+    one in twenty is lower case; the first and the last read are empty, and so is every fourteenth between them"""
+    rng = np.random.default_rng([seed, K, 1])
+    g = random_seq(rng, genome)
+    classes = ragged_lengths(K)
+    out = []
+    for i in range(nreads):
+        n = classes[i % len(classes)]
+        at = int(rng.integers(0, genome - n + 1))
+        s = g[at:at + n]
+        if rng.integers(0, 2):
+            s = revcomp(s)
+        what = int(rng.integers(0, 20))
+        if what == 0 and n:
+            j = int(rng.integers(0, n))
+            s = s[:j] + "N" + s[j + 1:]
+        elif what == 1:
+            s = s.lower()
+        out.append(s)
+    out.append("")
+    return out
+
+
+def long_records(K, seed, variant=0):
+    """test_long_records_and_tile_edges at a fifth of its size: a record of 2048 x 150 bases that ends on a parse tile edge (the next one starts on
+    it), a 200 kbp record, a record shorter than K, a slice of the first record (counts of 2) and a last record after which the packed buffer ends
+    exactly on a tile edge (variant 0) or two bytes behind a whole word (variant 1: the tail branch of the placement's word staging)"""
+    rng = np.random.default_rng([seed, K, 2])
+    a = random_seq(rng, 2048 * 150)
+    reads = [a, random_seq(rng, 200000), random_seq(rng, K - 1), a[1000:60000]]
+    pre = sum((len(r) + 3) // 4 for r in reads)
+    reads.append(random_seq(rng, 4 * ((-pre) % 512 + 1024) + (5 if variant else 0)))
+    return reads
+
+
+def tandem_periods(K):
+    return [1, 2, 3, 5, K - 1, K, K + 1]
+
+
+def low_complexity_reads(K, seed):
+    """the tandem repeats of low_complexity() alone: ~40 reads of 150-400 bases per period; period 1: 25 poly-A and 25 poly-T reads of 150 bases
+    (one canonical k-mer across strands, 50 x (151 - K) copies) besides poly-C and poly-G; even K: reads whose unit is its own reverse complement"""
+    rng = np.random.default_rng([seed, K, 3])
+    out = []
+    for p in tandem_periods(K):
+        if p == 1:
+            out += ["A" * 150] * 25 + ["T" * 150] * 25
+            out += [b * int(rng.integers(150, 401)) for b in "CG" for _ in range(8)]
+            continue
+        for _ in range(40):
+            unit = random_seq(rng, p)
+            n = int(rng.integers(150, 401))
+            out.append((unit * (n // p + 1))[:n])
+    if K % 2 == 0:
+        for _ in range(10):
+            half = random_seq(rng, K // 2)
+            unit = half + revcomp(half)                        # a k-mer that is its own reverse complement, once per period
+            n = int(rng.integers(150, 401))
+            out.append((unit * (n // K + 1))[:n])
+            out.append(random_seq(rng, 7) + unit + random_seq(rng, 9))
+    return out
+
+
+def low_complexity(K, seed):
+    """low_complexity_reads() shuffled into 2000 ragged reads"""
+    rng = np.random.default_rng([seed, K, 4])
+    reads = low_complexity_reads(K, seed) + ragged(K, seed, nreads=2000)
+    return [reads[i] for i in rng.permutation(len(reads))]
+
+
+PAST_16_COPIES = (65535, 65536, 65536 + 20, 2 * 65536 + 17)
+
+
+def past_16_bits_kmers(K, seed):
+    """the four k-mers of past_16_bits(), distinct as canonical k-mers"""
+    rng = np.random.default_rng([seed, K, 5])
+    while True:
+        ks = [random_seq(rng, K) for _ in range(4)]
+        if len({min(s, revcomp(s)) for s in ks}) == 4:
+            return ks
+
+
+def past_16_bits(K, seed):
+    """four k-mers as reads of exactly K bases (either strand), 65535, 65536, 65536 + 20 and 2 x 65536 + 17 copies, shuffled into 3000 ragged reads:
+    the copies spread over many tiles and workgroups.  No background read holds one of the four (asserted)."""
+    rng = np.random.default_rng([seed, K, 6])
+    ks = past_16_bits_kmers(K, seed)
+    back = ragged(K, seed, nreads=3000)
+    for s in back:
+        u = s.upper().replace("N", "A")                      # (as the reads are packed)
+        assert not any(x in u or revcomp(x) in u for x in ks), "the background holds one of the four k-mers"
+    pool = back + [x for x in ks for _ in (0, 1)]
+    for j in range(4):
+        pool[len(back) + 2 * j + 1] = revcomp(ks[j])
+    idx = [np.arange(len(back), dtype=np.int64)]
+    for j, n in enumerate(PAST_16_COPIES):
+        idx.append(len(back) + 2 * j + (rng.integers(0, 2, size=n, dtype=np.int64)))
+    idx = np.concatenate(idx)
+    return [pool[i] for i in rng.permutation(idx)]
+
+
+# the (K, M) grid of the tests: one-word keys -- (30, 15): even K, palindromes; (31, 25): the scan's largest M, a window of 7; (27, 5): a wide window,
+# the 16-k-mer cut all the time -- and two-word keys -- (40, 17): the smallest K the plan takes; (45, 17): items of exactly 16 k-mers; (55, 23): of 6
+GRID_ONE_WORD = [(31, 17), (21, 11), (30, 15), (16, 9), (13, 7), (31, 25), (27, 5)]
+GRID_TWO_WORDS = [(40, 17), (42, 21), (45, 17), (51, 17), (55, 23)]
+GRID = GRID_ONE_WORD + GRID_TWO_WORDS
+SEED = 2024

@@ -214,6 +214,108 @@ def test_stage_count_sorted(H, L, U, nw):
     assert np.array_equal(cnt, ucnt[keep].astype(np.uint64))
 
 
+def _count_reference(keys, L, U):
+    """np.unique + the filter, in the stage's order (word nw - 1 most significant)"""
+    nw = keys.shape[1]
+    if nw == 1:
+        u, ucnt = np.unique(keys[:, 0], return_counts=True)
+        u = u.reshape(-1, 1)
+    else:
+        u, ucnt = np.unique(keys, axis=0, return_counts=True)
+        uo = np.lexsort([u[:, w] for w in range(nw)])
+        u, ucnt = u[uo], ucnt[uo]
+    keep = (ucnt >= L) & (ucnt <= U)
+    return u[keep], ucnt[keep].astype(np.uint64)
+
+
+def _distinct_sorted_keys(rng, n, nw):
+    """n distinct keys in the stage's order; with several words most neighbours share the leading words (a comparison of one word would merge them)"""
+    span = {1: 1 << 62, 2: 256, 3: 48}[nw]
+    d = np.unique(rng.integers(0, span, size=(3 * n, nw), dtype=np.uint64), axis=0)
+    d = d[rng.permutation(d.shape[0])[:n]]
+    assert d.shape[0] == n
+    return d[np.lexsort([d[:, w] for w in range(nw)])]
+
+
+@pytest.mark.parametrize("L,U", [(1, 65535), (2, 5), (15, 40)])
+@pytest.mark.parametrize("nw", [1, 2, 3])
+def test_stage_count_sorted_runs_on_tile_and_halo_edges(H, L, U, nw):
+    """Runs laid out against the count kernel's tile (2048 records) and halo (256 records of the next tile staged with it): a run that ends on a
+    tile's last record, one that starts on it, one that ends with the halo's last record and one a record later, runs of exactly U and U + 1
+    across a tile edge, and runs beyond 2^16 whose length mod 2^16 lies inside [L, U] (a 16-bit count would keep them)."""
+    T, HALO = 2048, 256
+    rng = np.random.default_rng(1000 * nw + U)
+    reps = []
+
+    def pad_to(pos):                                             # single records up to position `pos`
+        at = sum(reps)
+        assert at <= pos
+        reps.extend([1] * (pos - at))
+
+    pad_to(T - 3); reps.append(3)                                # ends on the tile's last record
+    pad_to(2 * T - 1); reps.append(4)                            # starts on the tile's last record
+    pad_to(3 * T - 2); reps.append(2 + HALO)                     # ends with the halo's last record
+    pad_to(4 * T - 2); reps.append(2 + HALO + 1)                 # ... and one record behind it
+    pad_to(5 * T - 2); at_u = (len(reps), sum(reps)); reps.append(U)                 # exactly U, from the last but one record of a tile: across its edge
+    pad_to((sum(reps) // T + 1) * T - 2); at_u1 = (len(reps), sum(reps)); reps.append(U + 1)     # exactly U + 1, likewise
+    pad_to((sum(reps) // T + 1) * T - 1); wrap = [len(reps)]; reps.append(65536 + 3)
+    reps.append(1); wrap.append(len(reps)); reps.append(2 * 65536 + 3)
+    reps.append(2); reps.append(65535)
+    reps += rng.integers(1, 60, size=700).tolist()
+    reps = np.array(reps, dtype=np.int64)
+    for (i, first), n in ((at_u, U), (at_u1, U + 1)):            # the layout itself: each of the two is one run that starts in one tile and ends in a later one
+        assert reps[i] == n and first == reps[:i].sum() and first % T == T - 2 and (first + n - 1) // T > first // T, (i, first, n)
+    d = _distinct_sorted_keys(rng, reps.size, nw)
+    keys = np.repeat(d, reps, axis=0)
+    with H.Context(K={1: 31, 2: 51, 3: 80}[nw], L=L, U=U) as c:
+        k, cnt = c.stage_count_sorted(keys)
+    wk, wc = _count_reference(keys, L, U)
+    assert np.array_equal(k, wk) and np.array_equal(cnt, wc)
+    k = np.asarray(k).reshape(-1, nw)
+
+    def kept(i):                                                 # the count the stage gave run i, None where it dropped the run
+        at = np.flatnonzero((k == d[i]).all(axis=1))
+        assert at.size <= 1
+        return int(cnt[at[0]]) if at.size else None
+
+    assert kept(at_u[0]) == U and kept(at_u1[0]) is None         # U is kept through the last-run path of its tile, one more is not
+    assert [kept(i) for i in wrap] == [None, None]               # 65536 + 3 and 2 x 65536 + 3 do not come back as runs of 3
+    if (L, U) == (2, 5):
+        assert 3 in wc.tolist() and 4 in wc.tolist() and 5 in wc.tolist()      # (the runs of 3, 4 and U are kept: the filter is not simply empty)
+
+
+@pytest.mark.parametrize("n", [1, 2048, 2049])
+@pytest.mark.parametrize("nw", [1, 2, 3])
+def test_stage_count_sorted_one_tile_exactly(H, nw, n):
+    """one record, one full tile, one tile and a record (the last run crosses into a tile of one record)"""
+    rng = np.random.default_rng(n + nw)
+    reps = np.array([2, 1, 3] * (n // 6) + ([n - 6 * (n // 6)] if n % 6 else []), dtype=np.int64)      # 2048: the last run ends the tile; 2049: it is a run of three across the edge
+    assert reps.sum() == n and reps.min() >= 1
+    keys = np.repeat(_distinct_sorted_keys(rng, reps.size, nw), reps, axis=0)
+    for L, U in ((1, 65535), (2, 5)):
+        with H.Context(K={1: 31, 2: 51, 3: 80}[nw], L=L, U=U) as c:
+            k, cnt = c.stage_count_sorted(keys)
+        wk, wc = _count_reference(keys, L, U)
+        assert np.array_equal(k, wk) and np.array_equal(cnt, wc), (L, U)
+
+
+def test_stage_count_sorted_more_tiles_than_one_scan_round(H):
+    """2048 x 2048 + 5 one-word keys: 2049 tiles, count_scan_kernel goes round its carry loop (2048 tiles per round)"""
+    rng = np.random.default_rng(99)
+    n = 2048 * 2048 + 5
+    reps = rng.integers(1, 9, size=n // 4)
+    reps = reps[:np.searchsorted(np.cumsum(reps), n) + 1]
+    reps[-1] -= int(reps.sum()) - n
+    assert reps.sum() == n and reps.min() >= 1
+    d = np.sort(rng.integers(0, 1 << 62, size=reps.size, dtype=np.uint64))
+    assert np.all(d[1:] > d[:-1])
+    keys = np.repeat(d, reps).reshape(-1, 1)
+    with H.Context(K=31, L=2, U=5) as c:
+        k, cnt = c.stage_count_sorted(keys)
+    wk, wc = _count_reference(keys, 2, 5)
+    assert np.array_equal(k, wk) and np.array_equal(cnt, wc) and len(wc) > 100000
+
+
 # ---------------------------------------------------------------------------------------------------
 # the whole path against the reference's own output
 # ---------------------------------------------------------------------------------------------------
