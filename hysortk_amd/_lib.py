@@ -44,6 +44,7 @@ class Stats(C.Structure):
         ("host_syncs", C.c_uint64), ("host_waits_covered", C.c_uint64), ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64), ("h2d_ms", C.c_double), ("d2h_ms", C.c_double),
         ("bucket_launches", C.c_uint64), ("bucket_items", C.c_uint64), ("bucket_ms", C.c_double),
         ("combine_launches", C.c_uint64), ("combine_kmers", C.c_uint64), ("combine_pairs", C.c_uint64), ("combine_ms", C.c_double),
+        ("agg_large_bins", C.c_uint64), ("agg_large_slices", C.c_uint64),
     ]
 
 

@@ -66,25 +66,38 @@ struct AggTask {
 // A bin far beyond the usual few thousand records is nearly always ONE k-mer seen millions of times (poly-A, the poly-G reads of two-colour
 // sequencers, satellites).  Its records all hit one counter of one workgroup's table, and that workgroup reads them alone: 40 M copies of the
 // all-A 31-mer (5 Gbp with 2 % all-A reads) kept it busy for 108 ms while the rest of the GPU had finished the batch in 10.  Such bins are cut
-// into slices of AGL_SLICE records: agg_large_list_kernel finds them (up to AGL_TABLES per task) and lists their slices, agg_large_slice_kernel
-// counts every slice in an LDS table (a wave whose lanes all hold the same key sends one lane with the sum) and adds the table's few pairs to
-// the bin's table in GLOBAL memory (AGL_TAB slots, atomics); the bin's own workgroup then counts that table's slots instead of the records.
+// into slices of AGL_SLICE records: agg_large_list_kernel finds them (up to AGL_TABLES per task) and lists their slices, a slice kernel
+// (agg_large_slice_kernel, agg2_large_slice_kernel, agg3_large_slice_kernel: keys of one, two, three words) counts every slice in an LDS table
+// (a wave whose lanes all hold the same key sends one lane with the sum) and adds the table's few pairs to the bin's table in GLOBAL memory
+// (AGL_TAB slots, atomics); the bin's own workgroup then counts that table's slots instead of the records.  The kernels find a bin's records
+// through bounds[], so the 16 prefix bits may sit anywhere (one word, or split between the two top words: AggArgs::top_bits).
 // More distinct keys than a slice's or the bin's table holds (a large bin of another kind): the bin is marked and counted the old way.
+// EXTENSION (agg_ext_kernel) owes the payloads grouped by key as well: the bin's workgroup takes the distinct keys and their counts from the
+// table, orders them, writes entries and payload offsets as always and leaves every table slot's group offset in tgoff; then the slices run
+// a second time (agg_ext_large_place_kernel): a record finds its group through the table, takes the group's next free place with an atomic
+// on tcur and stores its payload there.  A bin qualifies from AG_LARGE_BIN = 65536 records on and U <= 65535, so the k-mer that made the
+// bin large is never kept: groups of more than U records keep their range (the neighbours' payload offsets stay right) but are not written.
 constexpr u64 AG_LARGE_BIN = 1u << 16;
 constexpr u32 AGL_SLICE = 1u << 15;
 constexpr int AGL_LOG2TAB = 11;
 constexpr u32 AGL_TAB = 1u << AGL_LOG2TAB;
 constexpr u32 AGL_TABLES = 16;
 constexpr int AGL_MAX_PROBE = 64;
+constexpr u32 AGL_WAIT = 1u << 16;                // steps a workgroup waits for the lower words of a slot another one has claimed before the bin is marked
 struct AggLarge {
     u32 *bin_tab;                  // [nbins] 0, or 1 + the bin's table
-    unsigned long long *tkeys;     // [AGL_TABLES][AGL_TAB], AG_EMPTY (two-word keys: word 1)
-    unsigned long long *tkeys0;    // two-word keys: word 0 (AG_EMPTY until the slot's claimer has stored it)
-    u32 *tcnt;                     // [AGL_TABLES][AGL_TAB], 0
-    u32 *tbad;                     // [AGL_TABLES] 1: the bin is counted the old way after all
+    unsigned long long *tkeys;     // [AGL_TABLES][AGL_TAB], AG_EMPTY (multi-word keys: the most significant word)
+    unsigned long long *tkeys0;    // multi-word keys: word 0 (two words: AG_EMPTY until the slot's claimer has stored it)
+    unsigned long long *tkeys1;    // three-word keys: word 1 (words 1 and 0 are published by the slot's first count)
+    u32 *tcnt;                     // [AGL_TABLES][AGL_TAB], 0.  EXTENSION: two more arrays of that size behind it, tcur (places taken in the group) and tgoff (agl_tcur / agl_tgoff)
+    u32 *tbad;                     // [AGL_TABLES] 1: the bin is counted the old way after all; [AGL_TABLES + table] (EXTENSION) 1: tgoff is written, the payloads can be placed
     unsigned long long *units;     // {bin << 32 | slice}; room for n / AGL_SLICE + AGL_TABLES + 1
-    u32 *ctl;                      // [0] tables handed out, [1] units listed, [2] ticket of the slice kernel
+    u32 *ctl;                      // [0] tables handed out, [1] units listed, [2] ticket of the slice kernel, [3] ticket of agg_ext_large_place_kernel
 };
+__device__ __forceinline__ u32 *agl_tcur(const AggLarge &lg) { return lg.tcnt + (size_t)AGL_TABLES * AGL_TAB; }
+__device__ __forceinline__ u32 *agl_tgoff(const AggLarge &lg) { return lg.tcnt + (size_t)2 * AGL_TABLES * AGL_TAB; }
+// a bin of n records has been counted through its table (one thread of the bin's workgroup, once the bin is known to fit this rung's table)
+__device__ __forceinline__ void agl_note(u32 *lstat, u64 n) { if (lstat) { atomicAdd(lstat, 1u); atomicAdd(lstat + 1, (u32)((n + AGL_SLICE - 1) / AGL_SLICE)); } }
 // the bin this workgroup works on (false: none) and what to do when it overflows
 __device__ __forceinline__ bool agg_pick_bin(const AggTask &t, u32 nbins, u32 &b)
 {
@@ -99,7 +112,8 @@ __device__ __forceinline__ void agg_bin_overflow(const AggTask &t, u32 nbins, u3
     atomicMax(t.flags + AG_BATCH, cap);
     t.bin_cnt[b] = 0;
 }
-struct AggArgs { AggTask t[AG_BATCH]; u32 lower, upper; u32 nbins; int shift; int nw; int top_bits; int top_sig; };   // top_sig: significant bits of the most significant word (multi-word keys)
+struct AggArgs { AggTask t[AG_BATCH]; u32 lower, upper; u32 nbins; int shift; int nw; int top_bits; int top_sig; u32 *lstat; };   // top_sig: significant bits of the most significant word (multi-word keys)
+//   // lstat (null: not counted): [0] bins that were counted through their slices' table, [1] slices of those bins (hsk_stats::agg_large_bins / agg_large_slices)
 //   // bins = key >> shift, nbins of them (65536 / 48, or 256 / 56)
 // top_bits (multi-word keys): how many of the 16 prefix bits the most significant word holds (0 or 16: all); the rest are the top
 // bits of the word below
@@ -457,6 +471,7 @@ __global__ __launch_bounds__(AG_THREADS) void agg_finish_kernel(AggArgs a)
         if (tid == 0) agg_bin_overflow(t, a.nbins, b, (u32)CAP);
         return;
     }
+    if (ltab && tid == 0) agl_note(a.lstat, e - s);
 
     // ---- 2, 3. distinct keys compacted, ordered, filtered, written -------------------------------------------
     agg_emit_bin<LOG2CAP>(a, t, b, s, s_key, s_cnt, s_bkt, s_scr);
@@ -769,6 +784,7 @@ __global__ __launch_bounds__(AG_THREADS) void agg2_finish_kernel(AggArgs a)
         if (tid == 0) agg_bin_overflow(t, a.nbins, b, (u32)CAP);
         return;
     }
+    if (ltab && tid == 0) agl_note(a.lstat, e - s);
 
     // ---- compact, order by (word 1, word 0) ----------------------------------------------------------------------
     u32 D;
@@ -832,12 +848,12 @@ __global__ __launch_bounds__(AG_THREADS) void agg2_finish_kernel(AggArgs a)
 // the lanes that found their word 2 start to wait -- written as two `if` blocks the compiler is free to run the waiting lanes
 // first (it did: every waiter timed out).  Returns the lanes that ran out of probes; timed_out: a count never appeared.
 template <u32 MASK>
-__device__ __forceinline__ u64 agg3_count_keys(u64 act, u32 k2_base, u32 k1_base, u32 k0_base, u32 cnt_base, u32 &h, u64 w2, u64 w1, u64 w0, u32 &timed_out)
+__device__ __forceinline__ u64 agg3_count_keys(u64 act, u32 k2_base, u32 k1_base, u32 k0_base, u32 cnt_base, u32 &h, u64 w2, u64 w1, u64 w0, u32 &timed_out, u32 inc = 1u)      // inc: as in agg_count_keys (never 0: the count publishes the slot)
 {
     u64 save, t, cur, v1, v0;
     u32 ka2, ka1, ka0, ca, cv, p, spin, tmo = 0;
     const u64 empty = AG_EMPTY;
-    const u32 one = 1u;
+    const u32 one = inc;
     asm volatile(
         "s_mov_b64 %[save], exec\n\t"
         "s_movk_i32 %[p], 1\n\t"
@@ -910,6 +926,98 @@ __device__ __forceinline__ bool key3_less(u64 a2, u64 a1, u64 a0, u64 b2, u64 b1
     return a2 < b2 || (a2 == b2 && (a1 < b1 || (a1 == b1 && a0 < b0)));
 }
 
+// the slice kernel for three-word keys (AggLarge): the slice's table is filled by agg3_count_keys.  In the bin's global table a slot is claimed on
+// word 2; the claimer stores words 1 and 0 and then adds its count, which publishes them (release; the count is the flag as in the LDS table: every
+// value of word 0 and word 1 occurs).  A workgroup that finds its word 2 in a slot whose count is still 0 comes back to the slot on its next step --
+// no lane ever spins while the claimer, perhaps a lane of its own wave, has its stores still ahead of it --, AGL_WAIT steps at the most: then the
+// bin is marked (tbad) and counted the old way.
+__global__ __launch_bounds__(AG_THREADS) void agg3_large_slice_kernel(AggArgs a)
+{
+    constexpr int LOG2CAP = AG_LOG2CAP_SMALL, CAP = 1 << LOG2CAP, PER = CAP / AG_THREADS, UNR = 4;
+    __shared__ u64 s_k2[CAP];
+    __shared__ u64 s_k1[CAP];
+    __shared__ u64 s_k0[CAP];
+    __shared__ u32 s_cnt[CAP];
+    __shared__ u32 s_ctl[2];
+    const AggTask &t = a.t[blockIdx.y];
+    if (!t.active || !t.lg) return;
+    const AggLarge &lg = *t.lg;
+    const u32 nunits = lg.ctl[1];
+    if (nunits == 0) return;
+    const int tid = threadIdx.x;
+    typedef __attribute__((address_space(3))) void *LdsPtr;
+    const u32 k2_lds = (u32)(uintptr_t)(LdsPtr)s_k2, k1_lds = (u32)(uintptr_t)(LdsPtr)s_k1, k0_lds = (u32)(uintptr_t)(LdsPtr)s_k0, cnt_lds = (u32)(uintptr_t)(LdsPtr)s_cnt;
+    for (;;) {
+        __syncthreads();
+        if (tid == 0) { s_ctl[0] = atomicAdd(&lg.ctl[2], 1u); s_ctl[1] = 0; }
+#pragma unroll
+        for (int j = 0; j < PER; ++j) { s_k2[j * AG_THREADS + tid] = AG_EMPTY; s_cnt[j * AG_THREADS + tid] = 0; }
+        __syncthreads();
+        const u32 u = s_ctl[0];
+        if (u >= nunits) break;
+        const unsigned long long un = lg.units[u];
+        const u32 b = (u32)(un >> 32), ti = lg.bin_tab[b] - 1u;
+        const u64 s = t.bounds[b] + (u64)(u32)un * AGL_SLICE, be = t.bounds[b + 1], e = s + AGL_SLICE < be ? s + AGL_SLICE : be;
+        for (u64 i = s + tid; i < e; i += (u64)AG_THREADS * UNR) {
+            u64 k0[UNR], k1[UNR], k2[UNR];
+#pragma unroll
+            for (int x = 0; x < UNR; ++x) {
+                const u64 idx = i + (u64)x * AG_THREADS;
+                const bool ok = idx < e;
+                k0[x] = ok ? t.keys[idx * 3] : 0; k1[x] = ok ? t.keys[idx * 3 + 1] : 0; k2[x] = ok ? t.keys[idx * 3 + 2] : AG_EMPTY;
+            }
+#pragma unroll
+            for (int x = 0; x < UNR; ++x) {
+                const u64 w0 = k0[x], w1 = k1[x], w2 = k2[x];
+                u64 act = __ballot(w2 != AG_EMPTY);
+                if (act == 0) continue;                   // (uniform; the active lanes are a prefix of the wave: lane 0 is one of them)
+                const u64 m = w0 ^ (w1 >> 7) ^ (w1 << 23) ^ (w2 >> 9) ^ (w2 << 21);
+                u32 tmo = 0, h = (((u32)(m >> 32) ^ (u32)m) * 0x9E3779B1u) >> (32 - LOG2CAP), inc = 1u;
+                const u64 f2 = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(w2 >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)w2);
+                const u64 f1 = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(w1 >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)w1);
+                const u64 f0 = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(w0 >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)w0);
+                if (__ballot(w2 == f2 && w1 == f1 && w0 == f0) == act) { inc = (u32)__popcll(act); act = 1ULL; }
+                if (agg3_count_keys<(u32)CAP - 1u>(act, k2_lds, k1_lds, k0_lds, cnt_lds, h, w2, w1, w0, tmo, inc) != 0 || tmo) s_ctl[1] = 1;      // (uniform)
+            }
+            if (__hip_atomic_load(&s_ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
+        }
+        __syncthreads();
+        if (s_ctl[1]) { if (tid == 0) lg.tbad[ti] = 1u; continue; }      // (more distinct keys than a slice's table takes: not this kind of bin)
+        const size_t tb = (size_t)ti * AGL_TAB;
+        unsigned long long *g2 = lg.tkeys + tb, *g1 = lg.tkeys1 + tb, *g0 = lg.tkeys0 + tb; u32 *gc = lg.tcnt + tb;
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            const u64 q2 = s_k2[j * AG_THREADS + tid];
+            if (q2 == AG_EMPTY) continue;
+            const u64 q1 = s_k1[j * AG_THREADS + tid], q0 = s_k0[j * AG_THREADS + tid];
+            const u32 cq = s_cnt[j * AG_THREADS + tid];
+            const u64 m = q0 ^ (q1 >> 7) ^ (q1 << 23) ^ (q2 >> 9) ^ (q2 << 21);
+            u32 h = (((u32)(m >> 32) ^ (u32)m) * 0x9E3779B1u) >> (32 - AGL_LOG2TAB);
+            bool placed = false;
+            u32 pr = 1, waited = 0;
+            while (pr <= (u32)AGL_MAX_PROBE && waited < AGL_WAIT) {      // one step per turn: claim, or look at a claimed slot, or move on
+                unsigned long long prev = __hip_atomic_load(&g2[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (prev == AG_EMPTY) {
+                    prev = atomicCAS(&g2[h], (unsigned long long)AG_EMPTY, (unsigned long long)q2);
+                    if (prev == AG_EMPTY) {
+                        __hip_atomic_store(&g1[h], (unsigned long long)q1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_store(&g0[h], (unsigned long long)q0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        __hip_atomic_fetch_add(&gc[h], cq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                        placed = true; break;
+                    }
+                }
+                if (prev == q2) {
+                    if (__hip_atomic_load(&gc[h], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0) { ++waited; __builtin_amdgcn_s_sleep(1); continue; }     // not published yet: this slot again
+                    const unsigned long long v1 = __hip_atomic_load(&g1[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), v0 = __hip_atomic_load(&g0[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (v1 == q1 && v0 == q0) { atomicAdd(&gc[h], cq); placed = true; break; }
+                }
+                h = (h + pr) & (AGL_TAB - 1u); ++pr;
+            }
+            if (!placed) lg.tbad[ti] = 1u;                // (the table is full of other keys, or words that never came -- cannot happen --: the bin is counted the old way)
+        }
+    }
+}
+
 template <int LOG2CAP>
 __global__ __launch_bounds__(AG_THREADS) void agg3_finish_kernel(AggArgs a)
 {
@@ -937,6 +1045,20 @@ __global__ __launch_bounds__(AG_THREADS) void agg3_finish_kernel(AggArgs a)
     constexpr int UNR = 4;
     typedef __attribute__((address_space(3))) void *LdsPtr;
     const u32 k2_lds = (u32)(uintptr_t)(LdsPtr)s_k2, k1_lds = (u32)(uintptr_t)(LdsPtr)s_k1, k0_lds = (u32)(uintptr_t)(LdsPtr)s_k0, cnt_lds = (u32)(uintptr_t)(LdsPtr)s_cnt;
+    u32 ltab = 0;                                       // 1 + the global table the bin's slices were counted into (agg3_large_slice_kernel)
+    if (e - s >= AG_LARGE_BIN && t.lg) { ltab = t.lg->bin_tab[b]; if (ltab && t.lg->tbad[ltab - 1]) ltab = 0; }
+    if (ltab) {
+        const size_t tb = (size_t)(ltab - 1) * AGL_TAB;
+        const unsigned long long *g2 = t.lg->tkeys + tb, *g1 = t.lg->tkeys1 + tb, *g0 = t.lg->tkeys0 + tb; const u32 *gc = t.lg->tcnt + tb;
+        for (u32 q = tid; q < AGL_TAB; q += AG_THREADS) {
+            const u64 w2 = g2[q], w1 = g1[q], w0 = g0[q];
+            const u64 act = __ballot(w2 != AG_EMPTY);
+            if (act == 0) continue;                       // (uniform)
+            const u64 m = w0 ^ (w1 >> 7) ^ (w1 << 23) ^ (w2 >> 9) ^ (w2 << 21);
+            u32 tmo = 0, h = (((u32)(m >> 32) ^ (u32)m) * 0x9E3779B1u) >> (32 - LOG2CAP);
+            if (agg3_count_keys<(u32)CAP - 1u>(act, k2_lds, k1_lds, k0_lds, cnt_lds, h, w2, w1, w0, tmo, gc[q]) != 0 || tmo) s_ovf = 1;      // (uniform)
+        }
+    } else
     for (u64 i = s + tid; i < e; i += (u64)AG_THREADS * UNR) {
         u64 k0[UNR], k1[UNR], k2[UNR];
 #pragma unroll
@@ -962,6 +1084,7 @@ __global__ __launch_bounds__(AG_THREADS) void agg3_finish_kernel(AggArgs a)
         if (tid == 0) agg_bin_overflow(t, a.nbins, b, (u32)CAP);
         return;
     }
+    if (ltab && tid == 0) agl_note(a.lstat, e - s);
 
     // ---- compact, order by (word 2, word 1, word 0) ------------------------------------------------------------------
     u32 D;
@@ -1041,8 +1164,9 @@ struct AggExtTask {
     // the table ladder bin by bin, as in AggTask: bins that overflow this launch's table are listed for the next one
     const u32 *bin_list; const u32 *bin_list_n;
     u32 *ovf_list; u32 *ovf_n;
+    const struct AggLarge *lg;     // bins of very many records: keys counted slice by slice beforehand, payloads placed slice by slice afterwards (AggLarge); null: none
 };
-struct AggExtArgs { AggExtTask t[AG_BATCH]; u32 lower, upper; u32 nbins; int shift; int nw; int top_bits; int top_sig; };     // nw, top_bits: as in AggArgs (nw = 0 reads as 1)
+struct AggExtArgs { AggExtTask t[AG_BATCH]; u32 lower, upper; u32 nbins; int shift; int nw; int top_bits; int top_sig; u32 *lstat; };     // nw, top_bits, lstat: as in AggArgs (nw = 0 reads as 1)
 
 __global__ __launch_bounds__(AG_THREADS) void bin_bounds_ext_kernel(AggExtArgs a)
 {
@@ -1146,7 +1270,33 @@ __global__ __launch_bounds__(AG_THREADS) void agg_ext_kernel(AggExtArgs a)
             if (wh) wh[u] = h;
         }
     };
-    if (in_regs) {
+    // a bin whose slices were counted into a global table beforehand (AggLarge): the table's slots instead of the records; where[j]: the LDS slot of
+    // the key in table slot tid + j * AG_THREADS (have: bit j set where there is one)
+    u32 ltab = 0, have = 0;
+    if (!in_regs && e - s >= AG_LARGE_BIN && t.lg) { ltab = t.lg->bin_tab[b]; if (ltab && t.lg->tbad[ltab - 1]) ltab = 0; }
+    if (ltab) {
+        static_assert(AGL_TAB / AG_THREADS <= REGS, "a lane remembers the LDS slot of each of its table slots");
+        const size_t tb = (size_t)(ltab - 1) * AGL_TAB;
+        const u32 *gc = t.lg->tcnt + tb;
+#pragma unroll
+        for (int j = 0; j < (int)(AGL_TAB / AG_THREADS); ++j) {
+            const u32 q = (u32)tid + (u32)j * AG_THREADS;
+            u64 k[NW];
+            k[NW - 1] = t.lg->tkeys[tb + q];
+            if (NW >= 2) k[0] = t.lg->tkeys0[tb + q];
+            if (NW == 3) k[NW > 1 ? 1 : 0] = t.lg->tkeys1[tb + q];
+            const u64 act = __ballot(k[NW - 1] != AG_EMPTY);
+            if (act == 0) continue;                       // (uniform)
+            u32 h = slot_of(k), tmo = 0;
+            const u32 inc = gc[q];
+            u64 left;
+            if (NW == 1) left = agg_count_keys<(u32)CAP - 1u>(act, tk_lds, cnt_lds, h, k[0], inc);
+            else if (NW == 2) left = agg2_count_keys<(u32)CAP - 1u>(act, tk_lds + (u32)CAP * 8u, tk_lds, cnt_lds, h, k[NW - 1], k[0], tmo, inc);
+            else left = agg3_count_keys<(u32)CAP - 1u>(act, tk_lds + 2u * (u32)CAP * 8u, tk_lds + (u32)CAP * 8u, tk_lds, cnt_lds, h, k[NW - 1], k[NW > 1 ? 1 : 0], k[0], tmo, inc);
+            if (left != 0 || tmo) s_ovf = 1;
+            if (k[NW - 1] != AG_EMPTY) { where[j] = h; have |= 1u << j; }
+        }
+    } else if (in_regs) {
 #pragma unroll
         for (int bt_ = 0; bt_ < NBAT; ++bt_)
             if (s + (u64)bt_ * AG_THREADS * UNR < e) count_batch(s + tid + (u64)bt_ * AG_THREADS * UNR, where + bt_ * UNR);      // (uniform)
@@ -1259,7 +1409,13 @@ __global__ __launch_bounds__(AG_THREADS) void agg_ext_kernel(AggExtArgs a)
     __syncthreads();
 
     // ---- 3. second sweep: every payload to its place ---------------------------------------------------------------
-    if (in_regs) {
+    if (ltab) {
+        // the slices place the payloads (agg_ext_large_place_kernel): every table slot's group offset for them, then the word that says so
+        u32 *goff = agl_tgoff(*t.lg) + (size_t)(ltab - 1) * AGL_TAB;
+#pragma unroll
+        for (int j = 0; j < (int)(AGL_TAB / AG_THREADS); ++j) if (have & (1u << j)) goff[(u32)tid + (u32)j * AG_THREADS] = s_soff[where[j]];
+        if (tid == 0) { t.lg->tbad[AGL_TABLES + ltab - 1] = 1u; agl_note(a.lstat, e - s); }
+    } else if (in_regs) {
 #pragma unroll
         for (int u = 0; u < REGS; ++u) {
             const u32 r = (u32)tid + (u32)u * AG_THREADS;
@@ -1300,6 +1456,70 @@ __global__ __launch_bounds__(AG_THREADS) void agg_ext_kernel(AggExtArgs a)
             }
             const u64 o = s + s_soff[h] + atomicSub(&s_tcnt[h], 1u) - 1u;
             t.pos[o] = (u32)v; t.rid[o] = (int32_t)(v >> 32);
+        }
+    }
+}
+
+// The slices of the bins that agg_ext_kernel has taken from their tables, a second time: every record finds its group in the bin's table (the
+// probe sequence of the slice kernels), takes the group's next free place (tcur, an atomic; a wave whose lanes all hold the same key takes its
+// places with one) and stores its payload at bin start + group offset + place.  Groups of more than U records are never kept: their range stays
+// a gap.  Persistent workgroups, one slice per ticket; launched after the table ladder, ends at once without such bins.  A record whose key is
+// not in the table (cannot happen) raises its task's AG_FLAG_OVERFLOW: the task takes the long way.
+template <int NW>
+__global__ __launch_bounds__(AG_THREADS) void agg_ext_large_place_kernel(AggExtArgs a)
+{
+    __shared__ u32 s_u;
+    const AggExtTask &t = a.t[blockIdx.y];
+    if (!t.active || !t.lg) return;
+    const AggLarge &lg = *t.lg;
+    const u32 nunits = lg.ctl[1];
+    if (nunits == 0) return;
+    const int tid = threadIdx.x, lane = tid & (WAVE - 1);
+    for (;;) {
+        __syncthreads();
+        if (tid == 0) s_u = atomicAdd(&lg.ctl[3], 1u);
+        __syncthreads();
+        const u32 u = s_u;
+        if (u >= nunits) break;
+        const unsigned long long un = lg.units[u];
+        const u32 b = (u32)(un >> 32), ti = lg.bin_tab[b] - 1u;
+        if (ti >= AGL_TABLES || lg.tbad[ti] || !lg.tbad[AGL_TABLES + ti]) continue;      // (uniform) counted the old way, payloads included, or beyond the last table
+        const size_t tb = (size_t)ti * AGL_TAB;
+        const unsigned long long *g2 = lg.tkeys + tb, *g1 = NW == 3 ? lg.tkeys1 + tb : nullptr, *g0 = NW >= 2 ? lg.tkeys0 + tb : nullptr;
+        const u32 *gc = lg.tcnt + tb, *goff = agl_tgoff(lg) + tb; u32 *cur = agl_tcur(lg) + tb;
+        const u64 s0 = t.bounds[b], s = s0 + (u64)(u32)un * AGL_SLICE, be = t.bounds[b + 1], e = s + AGL_SLICE < be ? s + AGL_SLICE : be;
+        for (u64 i0 = s; i0 < e; i0 += AG_THREADS) {
+            const u64 i = i0 + tid;
+            const bool valid = i < e;
+            u64 k[NW], v = 0;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) k[w] = valid ? t.keys[i * NW + w] : 0;
+            if (valid) v = t.vals[i];
+            u64 m = k[0];
+            if (NW == 2) m ^= (k[NW - 1] >> 9) ^ (k[NW - 1] << 21);
+            if (NW == 3) m ^= (k[NW > 1 ? 1 : 0] >> 7) ^ (k[NW > 1 ? 1 : 0] << 23) ^ (k[NW - 1] >> 9) ^ (k[NW - 1] << 21);
+            u32 h = (((u32)(m >> 32) ^ (u32)m) * 0x9E3779B1u) >> (32 - AGL_LOG2TAB);
+            bool found = false;
+            if (valid) {
+                for (u32 pr = 1; pr <= (u32)AGL_MAX_PROBE; ++pr) {
+                    bool same = g2[h] == k[NW - 1];
+                    if (NW >= 2) same = same && g0[h] == k[0];
+                    if (NW == 3) same = same && g1[h] == k[NW > 1 ? 1 : 0];
+                    if (same) { found = true; break; }
+                    h = (h + pr) & (AGL_TAB - 1u);
+                }
+                if (!found) atomicOr(t.flags, (u32)AG_FLAG_OVERFLOW);
+            }
+            const bool st = found && gc[h] <= a.upper;
+            const u64 mask = __ballot(st);
+            if (mask == 0) continue;                      // (uniform)
+            const u32 hf = (u32)__shfl((int)h, __ffsll((unsigned long long)mask) - 1, WAVE);
+            u32 at = 0;
+            if (__ballot(st && h == hf) == mask) {        // (uniform) one key in the wave: one lane takes the places of all
+                if (lane == __ffsll((unsigned long long)mask) - 1) at = atomicAdd(&cur[h], (u32)__popcll(mask));
+                at = (u32)__shfl((int)at, __ffsll((unsigned long long)mask) - 1, WAVE) + (u32)__popcll(mask & ((1ULL << lane) - 1ULL));
+            } else if (st) at = atomicAdd(&cur[h], 1u);
+            if (st && at < gc[h]) { const u64 o = s0 + goff[h] + at; t.pos[o] = (u32)v; t.rid[o] = (int32_t)(v >> 32); }      // (at < gc[h] always: the group has as many places as the table counted records)
         }
     }
 }

@@ -172,7 +172,7 @@ static int finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, u64 max_task, u
 //               retries the tasks whose bins overflowed with the large table, sizes the outputs exactly, launches the
 //               compaction and sends tasks the tables cannot take the long way.
 // prefix_bits = 16: bins of the top 16 bits (two scatter passes), small tables with a retry ladder and the long way.
-struct AggHostRead { u32 flags[AG_BATCH]; u32 maxd[AG_BATCH]; u32 ovf[2][AG_BATCH]; u64 total[AG_BATCH]; };   // mirrors the device control block (+ totals)
+struct AggHostRead { u32 flags[AG_BATCH]; u32 maxd[AG_BATCH]; u32 ovf[2][AG_BATCH]; u32 large[2]; u64 total[AG_BATCH]; };   // mirrors the device control block (+ totals); large: AggArgs::lstat
 static_assert(sizeof(AggHostRead) <= sizeof PinnedTail().agg[0], "a slot of the pinned staging words holds one AggHostRead");
 static_assert(sizeof(AggLarge) * AG_BATCH <= sizeof PinnedTail().agg_large[0], "... and a slot of agg_large the batch's AggLarge structs");
 
@@ -283,9 +283,48 @@ static int agg_launch_scan(hsk_ctx *c, AggPending &p)
 {
     hipLaunchKernelGGL(agg_scan_kernel, dim3(AG_BATCH), dim3(AG_THREADS), 0, c->stream, p.a);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(p.h->flags, p.d_flags, 4 * sizeof(u32) * AG_BATCH, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(p.h->flags, p.d_flags, offsetof(AggHostRead, total), hipMemcpyDeviceToHost, c->stream));
     // the eight totals sit behind the last bin of every task's count row: one strided copy
     HIPCHK(c, hipMemcpy2DAsync(p.h->total, 8, p.d_off + p.nbins, ((size_t)p.nbins + 8) * 8, 8, AG_BATCH, hipMemcpyDeviceToHost, c->stream));
+    return HSK_OK;
+}
+
+// Bins of very many records (hsk_agg.h: AggLarge), for the plain and the EXTENSION finish: the batch's AggLarge structs, tables and slice lists in
+// one block (d_large; the caller releases it), then the bins are found, cut into slices and counted by many workgroups before the table ladder
+// starts; without such bins the two launches end at once.  a: bounds, keys and record counts of the batch's tasks, bounds already enqueued;
+// a.t[i].lg leaves set.  ext: room for the group offsets and cursors of agg_ext_large_place_kernel.  d_large stays null when there is nothing to
+// do: switched off (agg_large=0) or no task of AG_LARGE_BIN records.
+template <int NW>
+static int agg_large_setup(hsk_ctx *c, AggArgs &a, int slot, bool ext, char *&d_large)
+{
+    d_large = nullptr;
+    u64 nmax = 0; for (int i = 0; i < AG_BATCH; ++i) if (a.t[i].active) nmax = std::max(nmax, a.t[i].n);
+    if (tune("agg_large", 1) == 0 || nmax < AG_LARGE_BIN) return HSK_OK;
+    const u32 nbins = a.nbins;
+    const size_t tab8 = (size_t)AGL_TABLES * AGL_TAB * 8, tab4 = (size_t)AGL_TABLES * AGL_TAB * 4;
+    size_t off[AG_BATCH][8], total = (sizeof(AggLarge) * AG_BATCH + 255) / 256 * 256;
+    for (int i = 0; i < AG_BATCH; ++i) {
+        const size_t sz[8] = {(size_t)nbins * 4, tab8, tab4 * (ext ? 3 : 1), 256, (size_t)(a.t[i].n / AGL_SLICE + AGL_TABLES + 1) * 8, 256, NW >= 2 ? tab8 : 0, NW == 3 ? tab8 : 0};
+        for (int q = 0; q < 8; ++q) { off[i][q] = total; total += (sz[q] + 255) / 256 * 256; }
+    }
+    DALLOC(c, d_large, char *, total + 64);
+    HIPCHK(c, hipMemsetAsync(d_large, 0, total, c->stream));
+    AggLarge *h_lg = (AggLarge *)staging(c)->agg_large[slot];
+    for (int i = 0; i < AG_BATCH; ++i) {
+        HIPCHK(c, hipMemsetAsync(d_large + off[i][1], 0xFF, tab8, c->stream));
+        if (NW == 2) HIPCHK(c, hipMemsetAsync(d_large + off[i][6], 0xFF, tab8, c->stream));     // (two words: word 0 doubles as the publication flag)
+        AggLarge &g = h_lg[i];
+        g.tkeys0 = NW >= 2 ? (unsigned long long *)(d_large + off[i][6]) : nullptr; g.tkeys1 = NW == 3 ? (unsigned long long *)(d_large + off[i][7]) : nullptr;
+        g.bin_tab = (u32 *)(d_large + off[i][0]); g.tkeys = (unsigned long long *)(d_large + off[i][1]); g.tcnt = (u32 *)(d_large + off[i][2]);
+        g.tbad = (u32 *)(d_large + off[i][3]); g.units = (unsigned long long *)(d_large + off[i][4]); g.ctl = (u32 *)(d_large + off[i][5]);
+        a.t[i].lg = (const AggLarge *)d_large + i;
+    }
+    HIPCHK(c, hipMemcpyAsync(d_large, h_lg, sizeof(AggLarge) * AG_BATCH, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(agg_large_list_kernel, dim3(nbins / AG_THREADS + 1, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
+    if (NW == 1) hipLaunchKernelGGL(agg_large_slice_kernel, dim3(160, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
+    else if (NW == 2) hipLaunchKernelGGL(agg2_large_slice_kernel, dim3(160, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
+    else hipLaunchKernelGGL(agg3_large_slice_kernel, dim3(160, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
     return HSK_OK;
 }
 
@@ -330,31 +369,9 @@ static int agg_stage1(hsk_ctx *c, const BatchTask *bt, int K, int prefix_bits, i
         }
     }
     hipLaunchKernelGGL(bin_bounds_kernel, dim3(nbins / AG_THREADS + 1, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-    if constexpr (NW <= 2) if (!weighted && tune("agg_large", 1) != 0 && nmax >= AG_LARGE_BIN && (NW == 1 || a.top_bits == 0 || a.top_bits == 16)) {
-        // bins of very many records (one k-mer seen millions of times): found, cut into slices and counted by many workgroups before the ladder
-        // starts (hsk_agg.h: AggLarge); without such bins the two launches end at once
-        size_t off[AG_BATCH][7], total = (sizeof(AggLarge) * AG_BATCH + 255) / 256 * 256;
-        for (int i = 0; i < AG_BATCH; ++i) {
-            const size_t sz[7] = {(size_t)nbins * 4, (size_t)AGL_TABLES * AGL_TAB * 8, (size_t)AGL_TABLES * AGL_TAB * 4, 256, (size_t)(bt[i].n / AGL_SLICE + AGL_TABLES + 1) * 8, 256,
-                                  NW == 2 ? (size_t)AGL_TABLES * AGL_TAB * 8 : 0};
-            for (int q = 0; q < 7; ++q) { off[i][q] = total; total += (sz[q] + 255) / 256 * 256; }
-        }
-        DALLOC(c, p.d_large, char *, total + 64);
-        HIPCHK(c, hipMemsetAsync(p.d_large, 0, total, c->stream));
-        AggLarge *h_lg = (AggLarge *)staging(c)->agg_large[slot];
-        for (int i = 0; i < AG_BATCH; ++i) {
-            HIPCHK(c, hipMemsetAsync(p.d_large + off[i][1], 0xFF, (size_t)AGL_TABLES * AGL_TAB * 8, c->stream));
-            if (NW == 2) HIPCHK(c, hipMemsetAsync(p.d_large + off[i][6], 0xFF, (size_t)AGL_TABLES * AGL_TAB * 8, c->stream));
-            AggLarge &g = h_lg[i];
-            g.tkeys0 = NW == 2 ? (unsigned long long *)(p.d_large + off[i][6]) : nullptr;
-            g.bin_tab = (u32 *)(p.d_large + off[i][0]); g.tkeys = (unsigned long long *)(p.d_large + off[i][1]); g.tcnt = (u32 *)(p.d_large + off[i][2]);
-            g.tbad = (u32 *)(p.d_large + off[i][3]); g.units = (unsigned long long *)(p.d_large + off[i][4]); g.ctl = (u32 *)(p.d_large + off[i][5]);
-            a.t[i].lg = (const AggLarge *)p.d_large + i;
-        }
-        HIPCHK(c, hipMemcpyAsync(p.d_large, h_lg, sizeof(AggLarge) * AG_BATCH, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(agg_large_list_kernel, dim3(nbins / AG_THREADS + 1, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-        if (NW == 1) hipLaunchKernelGGL(agg_large_slice_kernel, dim3(160, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-        else hipLaunchKernelGGL(agg2_large_slice_kernel, dim3(160, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
+    if (!weighted) {                                    // (the weighted finish -- combining extraction -- counts its large bins itself)
+        a.lstat = p.d_flags + 4 * AG_BATCH;             // AggHostRead::large
+        int rc = agg_large_setup<NW>(c, a, slot, false, p.d_large); if (rc) return rc;
     }
     // First table: what the bins of the previous batches needed (hsk_ctx::agg_first_cap: error-free reads at ~30x stay on 1024
     // slots, reads with ~1 % errors move to 2048 after their first batch); bins of 6144 records and more on average (tasks far
@@ -454,7 +471,7 @@ static int agg_stage2(hsk_ctx *c, AggPending &p, u64 *d_histo, u32 histo_len, Ta
                 t.ovf_list = last ? nullptr : ovf.appends(i); t.ovf_n = ovf.appends_n(i);
             }
             rc = agg_launch_rung<NW>(c, p, cap, longest, nb * (p.ntot / all_bins + 1)); if (rc) return rc;
-            HIPCHK(c, hipMemcpyAsync(p.h->flags, p.d_flags, 4 * sizeof(u32) * AG_BATCH, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(p.h->flags, p.d_flags, offsetof(AggHostRead, total), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hsk_sync(c, c->stream));
             if (last) { for (int i = 0; i < AG_BATCH; ++i) if (a.t[i].active && h.flags[i]) done[i] = false; break; }
             for (int i = 0; i < AG_BATCH; ++i) n_cur[i] = a.t[i].active ? ovf.appended(i) : 0;
@@ -466,6 +483,7 @@ static int agg_stage2(hsk_ctx *c, AggPending &p, u64 *d_histo, u32 histo_len, Ta
     }
     u64 total[AG_BATCH];
     for (int i = 0; i < AG_BATCH; ++i) total[i] = h.total[i];
+    c->stats.agg_large_bins += h.large[0]; c->stats.agg_large_slices += h.large[1];     // (the counters of the whole batch, every rung of the ladder: read with the flags)
     AggCompactArgs ca; memset(&ca, 0, sizeof ca);
     ca.slot_shift = p.slot_shift; ca.histo = d_histo; ca.histo_len = histo_len; ca.nbins = nbins; ca.ew = EW;
     bool any = false;
@@ -526,7 +544,7 @@ static int agg_ext_finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, const u
     DALLOC(c, d_bounds, u64 *, per * 8 * AG_BATCH);
     DALLOC(c, d_cnt, u64 *, per * 8 * AG_BATCH);
     DALLOC(c, d_flags, u32 *, 256);
-    HIPCHK(c, hipMemsetAsync(d_flags, 0, 64, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_flags, 0, 256, c->stream));
     AggExtArgs a; memset(&a, 0, sizeof a);
     AggArgs sa; memset(&sa, 0, sizeof sa);               // the view agg_scan_kernel needs
     a.lower = L; a.upper = (u32)c->cfg.upper_freq; a.nbins = nbins; a.shift = AG_SHIFT; a.nw = NW; a.top_bits = NW >= 2 ? prefix_top_bits(K, NW) : 0; a.top_sig = NW >= 2 ? 2 * (K - 32 * (NW - 1)) : 64;
@@ -556,7 +574,7 @@ static int agg_ext_finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, const u
     // CU), 1024 / 2048 for two and three words.  The first table follows the previous batches like agg_stage2's (reads with
     // ~1 % errors: ~900 distinct keys per bin, every bin overflows 1024 slots).
     constexpr int TOP = NW == 1 ? AG_LOG2CAP_LARGE : AG_LOG2CAP_MEDIUM;
-    struct H { u32 flags[AG_BATCH], ovf[2][AG_BATCH]; u64 total[AG_BATCH]; } h;      // mirrors the device control block (+ totals)
+    struct H { u32 flags[AG_BATCH], ovf[2][AG_BATCH], large[2]; u64 total[AG_BATCH]; } h;      // mirrors the device control block (+ totals); large: AggExtArgs::lstat
     OvfLists ovf; ovf.nbins = nbins;
     DALLOC(c, ovf.list[0], u32 *, (size_t)nbins * 4 * AG_BATCH * 2); ovf.list[1] = ovf.list[0] + (size_t)nbins * AG_BATCH;
     for (int x = 0; x < 2; ++x) { ovf.len[x] = d_flags + (1 + x) * AG_BATCH; ovf.h_len[x] = h.ovf[x]; }
@@ -569,6 +587,16 @@ static int agg_ext_finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, const u
     };
     memset(&h, 0, sizeof h);
     hipLaunchKernelGGL(bin_bounds_ext_kernel, dim3(nbins / AG_THREADS + 1, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
+    // bins of very many records: their keys are counted slice by slice before the ladder, their payloads placed slice by slice after it
+    char *d_large = nullptr;
+    {
+        AggArgs la; memset(&la, 0, sizeof la);           // the view the list and slice kernels need
+        la.nbins = nbins; la.shift = AG_SHIFT; la.nw = NW; la.top_bits = a.top_bits; la.top_sig = a.top_sig;
+        for (int i = 0; i < AG_BATCH; ++i) if (a.t[i].active) { la.t[i].keys = a.t[i].keys; la.t[i].n = a.t[i].n; la.t[i].bounds = a.t[i].bounds; la.t[i].active = 1; }
+        int rc = agg_large_setup<NW>(c, la, 0, true, d_large); if (rc) return rc;
+        for (int i = 0; i < AG_BATCH; ++i) a.t[i].lg = la.t[i].lg;
+        a.lstat = d_flags + 3 * AG_BATCH;                // H::large
+    }
     int nact = 0; for (int i = 0; i < AG_BATCH; ++i) nact += a.t[i].active ? 1 : 0;
     const u64 all_bins = (u64)nact * nbins;
     bool hopeless[AG_BATCH] = {false};
@@ -606,6 +634,7 @@ static int agg_ext_finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, const u
         }
         a = keep;
     }
+    if (d_large) hipLaunchKernelGGL((agg_ext_large_place_kernel<NW>), dim3(160, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
     if (tune("agg_adapt", 1) == 2) c->agg_off_wide = true;      // (tests: as in agg_stage2)
     for (int i = 0; i < AG_BATCH; ++i) sa.t[i].active = a.t[i].active;
     hipLaunchKernelGGL(agg_scan_kernel, dim3(AG_BATCH), dim3(AG_THREADS), 0, c->stream, sa);
@@ -617,6 +646,7 @@ static int agg_ext_finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, const u
     bool done[AG_BATCH];
     u64 total[AG_BATCH];
     for (int i = 0; i < AG_BATCH; ++i) { done[i] = bt[i].n == 0 || (!h.flags[i] && !hopeless[i]); total[i] = h.total[i]; }
+    c->stats.agg_large_bins += h.large[0]; c->stats.agg_large_slices += h.large[1];
     AggExtCompactArgs ca; memset(&ca, 0, sizeof ca);
     ca.slot_shift = slot_shift; ca.histo = d_histo; ca.histo_len = histo_len; ca.nbins = nbins; ca.ew = EW;
     bool any = false;
@@ -657,6 +687,6 @@ static int agg_ext_finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, const u
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hsk_sync(c, c->stream));
     for (int i = 0; i < AG_BATCH; ++i) if (own_scratch[i]) { c->pool.release(a.t[i].scratch_e); c->pool.release(a.t[i].scratch_p); }
-    c->pool.release(d_bounds); c->pool.release(d_cnt); c->pool.release(d_flags); c->pool.release(ovf.list[0]);
+    c->pool.release(d_bounds); c->pool.release(d_cnt); c->pool.release(d_flags); c->pool.release(ovf.list[0]); c->pool.release(d_large);
     return rc;
 }

@@ -159,6 +159,10 @@ typedef struct {
     uint64_t combine_kmers;
     uint64_t combine_pairs;
     double   combine_ms;
+    /* --- appended in ABI 4: prefix bins of very many records (one k-mer seen millions of times) that many workgroups counted slice by slice --- */
+    uint64_t agg_large_bins;      /* such bins counted through their slices since the last reset (a bin that turned out to hold too many distinct
+                                     k-mers for that and was counted by its own workgroup after all is not among them) */
+    uint64_t agg_large_slices;    /* slices of those bins */
 } hsk_stats;
 
 /* ---- lifecycle ------------------------------------------------------------------------- */
