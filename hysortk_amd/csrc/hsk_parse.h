@@ -1042,6 +1042,12 @@ __global__ __launch_bounds__(PARSE_THREADS) void place_kernel(ParseArgs a)
 // and in order, from the packed words of the step's tiles staged in LDS (as place_bytes_kernel does): nothing downstream gathers
 // windows from the packed reads any more.  The parse's tasks are VIRTUAL tasks here (16 per task, ParseArgs::vt_shift: 640 bins
 // instead of 40), so a step takes 16384 records (1024 threads, 32 tiles): a bin's run is ~25 items = 400 bytes, not 6.
+// One workgroup fills a CU's LDS, so nothing else hides a step's load latency: the steps are software-pipelined instead.  After the stage
+// into s_srt the record registers are dead, and the NEXT step's loads (16 records + 16 minimizer words per lane, ~4 packed words) are
+// issued into them before this step's output loop; they land while the loop stores, and the next step's head only consumes registers
+// (ranks by LDS atomics after the s_tcnt reset; the words go into s_words once the loop is done with it).  The next step's tile offsets
+// (s_go) are written by wave 0 one phase earlier; s_go is read by the prefetch alone, so one array serves.  A prefetch reads exactly the
+// addresses that step's own loads would read (same guards), and the slots are what they were: blk_base, the step order, the in-step rank.
 // dynamic LDS: u64 cur[nt], u32 tcnt[nt], u32 tpre[nt], u64 srt[PLACE_ITEM_REC], u32 words[PLACE_ITEM_WORDS]
 constexpr int PLACE_ITEM_THREADS = 1024;
 #ifndef PLACE_ITEM_RPT
@@ -1050,6 +1056,7 @@ constexpr int PLACE_ITEM_THREADS = 1024;
 constexpr u32 PLACE_ITEM_REC = PLACE_ITEM_RPT * 1024;  // records of one step (rec_cap * place_group)
 constexpr u32 PLACE_ITEM_TILES = PLACE_ITEM_REC / 512; // tiles per step at most
 constexpr u32 PLACE_ITEM_WORDS = PLACE_ITEM_TILES * (PARSE_TILE / 16) + 8;      // their packed words + the reach of the last supermer's second word
+struct PlaceItemStep { u32 sl, t0, ng; u64 tfirst; bool ok; };                  // a step of a workgroup's walk: slab, first tile (of the block, global), tiles
 __global__ __launch_bounds__(PLACE_ITEM_THREADS) void place_items_kernel(ParseArgs a)
 {
     // pipelined ingest (place_one): the placement of a slab is launched before the host has seen the scan's verdict.  A tile beyond the record
@@ -1057,6 +1064,9 @@ __global__ __launch_bounds__(PLACE_ITEM_THREADS) void place_items_kernel(ParseAr
     if (a.place_one && a.overflow && *(const volatile u32 *)a.overflow) return;
     constexpr int RPT = PLACE_ITEM_REC / PLACE_ITEM_THREADS;
     constexpr int T = PLACE_ITEM_THREADS;
+    constexpr int WPT = (PLACE_ITEM_WORDS + T - 1) / T;                 // packed words per thread and step at most
+    constexpr int LPR = (RPT + 5) / 6;                                  // a record's tile of the step: 5 bits, six to a register
+    static_assert(PLACE_ITEM_TILES <= 32, "a record's tile of the step takes 5 bits");
     __shared__ u32 s_w[16];
     __shared__ u32 s_go[PLACE_ITEM_TILES + 4];
     extern __shared__ __attribute__((aligned(16))) u64 s_cur[];
@@ -1070,50 +1080,99 @@ __global__ __launch_bounds__(PLACE_ITEM_THREADS) void place_items_kernel(ParseAr
     const u32 G = a.place_group < PLACE_ITEM_TILES ? a.place_group : PLACE_ITEM_TILES;
     const u32 *p32 = reinterpret_cast<const u32 *>(a.packed);
     const u32 nsl = a.nslabs > 1 ? a.nslabs : 1;
+    const u32 sl_end = a.place_one ? a.slab + 1 : nsl;
     const int lane = lane_id(), wv = tid >> 6;
-    for (u32 sl = a.place_one ? a.slab : 0; sl < (a.place_one ? a.slab + 1 : nsl); ++sl) {
-    const u64 tile0 = (u64)sl * a.slab_tiles + (u64)blockIdx.x * a.tiles_per_block;
-    const u64 tile_end = (nsl > 1 && ((u64)sl + 1) * a.slab_tiles < a.ntiles) ? ((u64)sl + 1) * a.slab_tiles : a.ntiles;
-    for (u32 t0 = 0; t0 < a.tiles_per_block; t0 += G) {
-        const u64 tfirst = tile0 + t0;
-        if (tfirst >= tile_end) break;
-        u32 ng = a.tiles_per_block - t0; if (ng > G) ng = G;
-        if (tfirst + ng > tile_end) ng = (u32)(tile_end - tfirst);
-        __syncthreads();                                                // previous step done with s_go / s_tcnt / s_srt / s_words
-        if (tid < WAVE) {                                               // record offsets of the step's tiles (one wave: 32 tiles)
-            u32 n = 0;
-            if ((u32)tid < ng) { n = a.tile_nrec[tfirst + tid]; n = n < a.rec_cap ? n : a.rec_cap; }
+    // the first step at or after (slab sl, tile t0 of the block), in the order of the walk: slab by slab, G tiles at a time, a slab's walk
+    // ending at the block's last tile or at the slab's (tile_end)
+    auto step_at = [&](u32 sl, u32 t0) {
+        PlaceItemStep s = {0, 0, 0, 0, false};
+        for (; sl < sl_end; ++sl, t0 = 0) {
+            if (t0 >= a.tiles_per_block) continue;
+            const u64 tile_end = (nsl > 1 && ((u64)sl + 1) * a.slab_tiles < a.ntiles) ? ((u64)sl + 1) * a.slab_tiles : a.ntiles;
+            const u64 tfirst = (u64)sl * a.slab_tiles + (u64)blockIdx.x * a.tiles_per_block + t0;
+            if (tfirst >= tile_end) continue;
+            u32 ng = a.tiles_per_block - t0; if (ng > G) ng = G;
+            if (tfirst + ng > tile_end) ng = (u32)(tile_end - tfirst);
+            s.sl = sl; s.t0 = t0; s.ng = ng; s.tfirst = tfirst; s.ok = true;
+            break;
+        }
+        return s;
+    };
+    // record offsets of a step's tiles (one wave: 32 tiles): the counts are loaded early, the offsets written a phase later
+    auto load_nrec = [&](const PlaceItemStep &s) {
+        u32 n = 0;
+        if (tid < WAVE && s.ok && (u32)tid < s.ng) { n = a.tile_nrec[s.tfirst + tid]; n = n < a.rec_cap ? n : a.rec_cap; }
+        return n;
+    };
+    auto write_go = [&](const PlaceItemStep &s, u32 n) {
+        if (tid < WAVE) {
             const u32 inc = wave_incl_scan(n);
-            if ((u32)tid < ng) s_go[tid] = inc - n;
+            if ((u32)tid < s.ng) s_go[tid] = inc - n;
             const u32 tot = __shfl(inc, WAVE - 1);
-            if ((u32)tid >= ng && (u32)tid <= PLACE_ITEM_TILES) s_go[tid] = tot;
+            if ((u32)tid >= s.ng && (u32)tid <= PLACE_ITEM_TILES) s_go[tid] = tot;
         }
-        for (u32 t = tid; t < nt; t += T) s_tcnt[t] = 0;
-        {   // the packed words of the step's tiles (+ reach) as big-endian words
-            const u64 w0 = tfirst * (PARSE_TILE / 16);
-            const u32 nw = ng * (PARSE_TILE / 16) + 8;
-            for (u32 i = tid; i < nw; i += T) {
-                const u64 b = (w0 + i) * 4;
-                u32 wv2 = 0;
-                if (b + 4 <= a.packed_bytes) wv2 = __builtin_bswap32(p32[w0 + i]);
-                else if (b < a.packed_bytes) { for (u64 q = b; q < a.packed_bytes; ++q) wv2 |= (u32)a.packed[q] << (24 - 8 * (q & 3)); }
-                s_words[i] = wv2;
-            }
-        }
-        __syncthreads();
-        const u32 total = s_go[PLACE_ITEM_TILES];
-        // a record here: position in tile (11 bits) | k-mers - 1 (4) << 11 | tile of the step (5) << 15 | task (10) << 20
-        u32 rec[RPT], rnk[RPT], sub[RPT];
+    };
+    // a record in flight: rec[] the scan's record as loaded, sub[] its minimizer bits, lop[] its tile of the step; words[] the packed words
+    // of the step's tiles (+ reach) as loaded (little-endian; a word that straddles the end of the reads: its bytes, byte-swapped back)
+    u32 rec[RPT], rnk[RPT], sub[RPT], lop[LPR], words[WPT];
+    auto fetch = [&](const PlaceItemStep &s, u32 total) {
+#pragma unroll
+        for (int q = 0; q < LPR; ++q) lop[q] = 0;
 #pragma unroll
         for (int x = 0; x < RPT; ++x) {
             const u32 i = x * T + tid;
-            rec[x] = 0xFFFFFFFFu; rnk[x] = 0; sub[x] = 0;
+            rec[x] = 0; sub[x] = 0;
             if (i < total) {
-                u32 lo = 0, hi = ng;                                    // the tile of record i: last j with s_go[j] <= i
+                u32 lo = 0, hi = s.ng;                                  // the tile of record i: last j with s_go[j] <= i
                 while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (s_go[mid] <= i) lo = mid; else hi = mid; }
-                const u64 at = (tfirst + lo) * (u64)a.rec_cap + (i - s_go[lo]);
-                const u32 r = a.tile_rec[at];
+                const u64 at = (s.tfirst + lo) * (u64)a.rec_cap + (i - s_go[lo]);
+                rec[x] = a.tile_rec[at];
                 sub[x] = a.tile_sub[at];
+                lop[x / 6] |= lo << (5 * (x % 6));
+            }
+        }
+        const u64 w0 = s.tfirst * (PARSE_TILE / 16);
+        const u32 nw = s.ng * (PARSE_TILE / 16) + 8;
+#pragma unroll
+        for (int q = 0; q < WPT; ++q) {
+            const u32 i = q * T + tid;
+            words[q] = 0;
+            if (i < nw) {
+                const u64 b = (w0 + i) * 4;
+                if (b + 4 <= a.packed_bytes) words[q] = p32[w0 + i];
+                else if (b < a.packed_bytes) {
+                    u32 wv2 = 0;
+                    for (u64 q2 = b; q2 < a.packed_bytes; ++q2) wv2 |= (u32)a.packed[q2] << (24 - 8 * (q2 & 3));
+                    words[q] = __builtin_bswap32(wv2);
+                }
+            }
+        }
+    };
+    auto put_words = [&](const PlaceItemStep &s) {                      // as big-endian words
+        const u32 nw = s.ng * (PARSE_TILE / 16) + 8;
+#pragma unroll
+        for (int q = 0; q < WPT; ++q) { const u32 i = q * T + tid; if (i < nw) s_words[i] = __builtin_bswap32(words[q]); }
+    };
+    PlaceItemStep cur = step_at(a.place_one ? a.slab : 0, 0);
+    if (!cur.ok) return;
+    write_go(cur, load_nrec(cur));
+    for (u32 t = tid; t < nt; t += T) s_tcnt[t] = 0;
+    __syncthreads();
+    u32 total = s_go[PLACE_ITEM_TILES];
+    fetch(cur, total);                                                  // the first step's loads: the only ones nothing covers
+    put_words(cur);
+    __syncthreads();
+    for (;;) {
+        const PlaceItemStep nxt = step_at(cur.sl, cur.t0 + G);
+        const u32 nrec_nxt = load_nrec(nxt);
+        // a record here: position in tile (11 bits) | k-mers - 1 (4) << 11 | tile of the step (5) << 15 | task (10) << 20
+#pragma unroll
+        for (int x = 0; x < RPT; ++x) {
+            const u32 i = x * T + tid;
+            const u32 r = rec[x];
+            rec[x] = 0xFFFFFFFFu; rnk[x] = 0;
+            if (i < total) {
+                const u32 lo = (lop[x / 6] >> (5 * (x % 6))) & 31u;
                 const u32 d = (r >> 18) & 1023u;
                 rec[x] = (r & 2047u) | (((r >> 11) & 15u) << 11) | (lo << 15) | (d << 20);
                 rnk[x] = atomicAdd(&s_tcnt[d], 1u);
@@ -1129,11 +1188,14 @@ __global__ __launch_bounds__(PLACE_ITEM_THREADS) void place_items_kernel(ParseAr
             for (int i = 0; i < 16; ++i) if (i < wv) base += s_w[i];
             if ((u32)tid < nt) s_tpre[tid] = base + inc - cnt;
         }
+        if (nxt.ok) write_go(nxt, nrec_nxt);                            // (s_go: last read by the prefetch of THIS step, a step ago)
         __syncthreads();
 #pragma unroll
         for (int x = 0; x < RPT; ++x)
             if (rec[x] != 0xFFFFFFFFu) s_srt[s_tpre[rec[x] >> 20] + rnk[x]] = (u64)rec[x] | ((u64)sub[x] << 32);
         __syncthreads();
+        u32 total_nxt = 0;
+        if (nxt.ok) { total_nxt = s_go[PLACE_ITEM_TILES]; fetch(nxt, total_nxt); }      // the next step's loads, in flight under the output loop
         for (u32 i = tid; i < total; i += T) {
             const u64 e = s_srt[i];
             const u32 r = (u32)e;
@@ -1144,10 +1206,13 @@ __global__ __launch_bounds__(PLACE_ITEM_THREADS) void place_items_kernel(ParseAr
             reinterpret_cast<ulonglong2 *>(a.sm_item)[slot] = make_ulonglong2(w0, (w1 & ~0xFFULL) | (u64)(((r >> 11) & 15u) + 1u));
             a.sm_sub[slot] = (u32)(e >> 32);
         }
+        __syncthreads();                                                // the output loop is done with s_srt / s_words / s_cur
+        for (u32 t = tid; t < nt; t += T) { s_cur[t] += s_tcnt[t]; s_tcnt[t] = 0; }
+        if (!nxt.ok) break;
+        put_words(nxt);
         __syncthreads();
-        for (u32 t = tid; t < nt; t += T) s_cur[t] += s_tcnt[t];
+        cur = nxt; total = total_nxt;
     }
-    }                                                                   // slabs
 }
 
 // Byte-store placement.  Same job as place_kernel, and in addition every supermer's bases are copied out of the packed
