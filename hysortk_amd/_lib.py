@@ -48,6 +48,16 @@ class Stats(C.Structure):
     ]
 
 
+class Pairs(C.Structure):
+    """hsk_pairs: the read pairs of a resident EXTENSION result (hsk_result_pairs)."""
+    _fields_ = [
+        ("n", C.c_uint64), ("rows", C.POINTER(C.c_uint64)), ("rows_dev", C.c_void_p),
+        ("records", C.c_uint64), ("self_records", C.c_uint64), ("keys", C.c_uint64), ("sort_passes", C.c_int32),
+        ("ms_expand", C.c_double), ("ms_sort", C.c_double), ("ms_reduce", C.c_double), ("ms_d2h", C.c_double), ("ms_total", C.c_double),
+        ("priv", C.c_void_p),
+    ]
+
+
 FLAG_PROFILE = 1
 FLAG_KEEP_DEVICE = 2
 FLAG_PLAIN_CLASSIFIER = 4
@@ -59,7 +69,7 @@ UNIQUE_ID_BYTES = 128
 # every symbol include/hsk.h declares (tests/test_abi.py checks the library exports all of them)
 SYMBOLS = [
     "hsk_abi_version", "hsk_device_count", "hsk_host_alloc", "hsk_host_free", "hsk_init", "hsk_destroy", "hsk_strerror", "hsk_last_error", "hsk_config_default",
-    "hsk_count", "hsk_count_device", "hsk_count_loopback", "hsk_count_loopback_device", "hsk_result_free", "hsk_result_device_task", "hsk_format_entries", "hsk_get_stats",
+    "hsk_count", "hsk_count_device", "hsk_count_loopback", "hsk_count_loopback_device", "hsk_result_free", "hsk_result_device_task", "hsk_result_pairs", "hsk_pairs_free", "hsk_format_entries", "hsk_get_stats",
     "hsk_stage_destinations", "hsk_stage_task_kmers", "hsk_stage_sort", "hsk_stage_count_sorted",
     "hsk_plan_tot_tasks", "hsk_plan_classify", "hsk_plan_dispatch", "hsk_plan_partition_reads", "hsk_plan_exchange",
     "hsk_comm_get_unique_id", "hsk_comm_init", "hsk_comm_destroy", "hsk_comm_selftest",
@@ -110,6 +120,9 @@ def load():
     L.hsk_result_free.argtypes = [vp, C.POINTER(Result)]
     L.hsk_result_free.restype = None
     L.hsk_result_device_task.argtypes = [C.POINTER(Result), C.c_int32] + [vp] * 7
+    L.hsk_result_pairs.argtypes = [vp, C.POINTER(Result), C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(Pairs)]
+    L.hsk_pairs_free.argtypes = [vp, C.POINTER(Pairs)]
+    L.hsk_pairs_free.restype = None
     L.hsk_get_stats.argtypes = [vp, C.POINTER(Stats), C.c_int]
     L.hsk_format_entries.argtypes = [vp, vp, C.c_uint64, C.c_int32, C.c_int32, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     L.hsk_stage_destinations.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp]

@@ -193,9 +193,75 @@ class KmerList:
         return [r.tobytes().decode() for r in arr]
 
 
+class ReadPairs:
+    """The read pairs that share k-mers (hsk_result_pairs, include/hsk.h): one row per pair of reads rid_a < rid_b (unsigned) with
+    `shared` common k-mer occurrence pairs; first_pos_* / last_pos_* are the smallest / largest (pos_a, pos_b) among them.  Rows are
+    in ascending (rid_a, rid_b).  With on_device the rows stay in HBM: rows_dev (n rows of four uint64 words { rid_a << 32 | rid_b,
+    shared, first, last }) and n; close() gives them back to the context.  There is no strand."""
+
+    def __init__(self, key, shared, first, last, info=None, rows_dev=None, n=None, owner=None):
+        self.key, self.shared, self.first, self.last = (np.ascontiguousarray(x, dtype=np.uint64) for x in (key, shared, first, last))
+        lo = np.uint64(0xFFFFFFFF)
+        self.rid_a, self.rid_b = (self.key >> np.uint64(32)).astype(np.uint32), (self.key & lo).astype(np.uint32)
+        self.first_pos_a, self.first_pos_b = (self.first >> np.uint64(32)).astype(np.uint32), (self.first & lo).astype(np.uint32)
+        self.last_pos_a, self.last_pos_b = (self.last >> np.uint64(32)).astype(np.uint32), (self.last & lo).astype(np.uint32)
+        self.info = info or {}
+        self.rows_dev = rows_dev
+        self.n = int(self.key.size) if n is None else int(n)
+        self._owner = owner                      # (ctx, hsk_pairs) of rows that live on the device
+
+    def __len__(self):
+        return self.n
+
+    def rows(self):
+        """[n, 4] uint64: { key, shared, first, last }, the C ABI's layout."""
+        return np.stack([self.key, self.shared, self.first, self.last], axis=1) if self.key.size else np.zeros((0, 4), np.uint64)
+
+    @classmethod
+    def from_rows(cls, rows, **kw):
+        rows = np.asarray(rows, dtype=np.uint64).reshape(-1, 4)
+        return cls(rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3], **kw)
+
+    @staticmethod
+    def combine(parts, min_shared=1):
+        """The list of the union of disjoint task ranges, or of the ranks of a several-GPU run, from their lists (host side, numpy): rows
+        with equal keys join -- shared adds up, first is the minimum, last the maximum -- and min_shared is applied afterwards.  The
+        parts must have been computed with min_shared=1."""
+        rows = [p.rows() for p in parts if len(p)]
+        if not rows:
+            return ReadPairs.from_rows(np.zeros((0, 4), np.uint64))
+        r = np.concatenate(rows)
+        r = r[np.argsort(r[:, 0], kind="stable")]
+        start = np.flatnonzero(np.concatenate([[True], r[1:, 0] != r[:-1, 0]]))
+        out = np.stack([r[start, 0], np.add.reduceat(r[:, 1], start), np.minimum.reduceat(r[:, 2], start), np.maximum.reduceat(r[:, 3], start)], axis=1)
+        info = {k: sum(int(p.info.get(k, 0)) for p in parts) for k in ("records", "self_records")}
+        info["keys"] = int(out.shape[0])
+        return ReadPairs.from_rows(out[out[:, 1] >= np.uint64(min_shared)], info=info)
+
+    def close(self):
+        if self._owner is not None:
+            ctx, pr = self._owner
+            if getattr(ctx, "h", None):
+                ctx.lib.hsk_pairs_free(ctx.h, C.byref(pr))
+            self._owner, self.rows_dev = None, None
+
+    def __del__(self):
+        try:
+            self.close()                 # (rows left on the device go back while the context is alive; after hsk_destroy there is nothing to free)
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 class DeviceResult:
     """A k-mer list that stays in HBM (HSK_FLAG_KEEP_DEVICE).  task(t) gives the device addresses of task t's entries and,
-    with EXTENSION, its CSR payload (payload_off / pos / rid); fetch(t) copies them to numpy arrays."""
+    with EXTENSION, its CSR payload (payload_off / pos / rid); fetch(t) copies them to numpy arrays; pairs() turns the payload
+    into the list of read pairs that share k-mers without leaving the GPU."""
 
     def __init__(self, ctx, res):
         self.ctx, self.res = ctx, res
@@ -219,6 +285,23 @@ class DeviceResult:
             out["pos"] = self.ctx.d2h(d["pos"], d["npay"] * 4).view(np.uint32)
             out["rid"] = self.ctx.d2h(d["rid"], d["npay"] * 4).view(np.int32)
         return out
+
+    def pairs(self, task_lo=0, task_hi=None, min_shared=1, on_device=False):
+        """hsk_result_pairs over tasks [task_lo, task_hi) (default: all): the read pairs that share at least min_shared k-mer
+        occurrence pairs, as a ReadPairs.  on_device=True leaves the rows in HBM (ReadPairs.rows_dev, .n; close() it before the
+        context goes)."""
+        pr = _lib.Pairs()
+        hi = self.ntasks if task_hi is None else task_hi
+        self.ctx._check(self.ctx.lib.hsk_result_pairs(self.ctx.h, C.byref(self.res), task_lo, hi, min_shared, 1 if on_device else 0, C.byref(pr)))
+        info = dict(records=int(pr.records), self_records=int(pr.self_records), keys=int(pr.keys), sort_passes=int(pr.sort_passes),
+                    ms_expand=pr.ms_expand, ms_sort=pr.ms_sort, ms_reduce=pr.ms_reduce, ms_d2h=pr.ms_d2h, ms_total=pr.ms_total)
+        n = int(pr.n)
+        if on_device:
+            z = np.zeros(0, np.uint64)
+            return ReadPairs(z, z, z, z, info=info, rows_dev=pr.rows_dev, n=n, owner=(self.ctx, pr))
+        rows = np.ctypeslib.as_array(pr.rows, shape=(n * 4,)).reshape(n, 4).copy() if n else np.zeros((0, 4), np.uint64)
+        self.ctx.lib.hsk_pairs_free(self.ctx.h, C.byref(pr))
+        return ReadPairs.from_rows(rows, info=info)
 
     def close(self):
         if self.res is not None:

@@ -37,6 +37,7 @@
 #include "hsk_agg.h"
 #include "hsk_combine.h"
 #include "hsk_heavy.h"
+#include "hsk_pairs.h"
 #include "hsk_estimate.h"
 #include "hsk_synth.h"
 #include "hsk_plan.h"
@@ -445,6 +446,9 @@ extern "C" int hsk_result_device_task(const hsk_result *r, int32_t task, const v
     if (payload_base) *payload_base = to.pay_base;
     return HSK_OK;
 }
+
+// read pairs that share k-mers, from a resident EXTENSION result: hsk_result_pairs, hsk_pairs_free
+#include "hsk_host_pairs.h"
 
 // Uploads the DnaBuffer description; returns device arrays with nreads+1 offsets.
 

@@ -162,7 +162,8 @@ struct PinnedTail {
     unsigned char agg[2][512];         // agg_stage1 / agg_stage2: the AggHostRead of the batch in slot 0 / 1
     unsigned char agg_large[2][512];   // agg_stage1: host copy of the batch's eight AggLarge structs (slot 0 / 1) until the copy to the device has run
     u64 pairs[2][16];                  // combining extraction: pairs per task + error word of the batch in slot 0 / 1 (combine_batch -> process_rank)
-    unsigned char free1[1280];
+    u64 read_pairs[8];                 // hsk_result_pairs: record count, row count, self records, keys, error word -- copied, waited for and read on the spot
+    unsigned char free1[1280 - 64];
     u64 estimate[16];                  // estimate_plan: the sample's counters
     unsigned char free2[64];
     u32 parse_flags[16];               // parse_count, parse_ingest_pipelined: overflow, error word, chunks, dropped k-mers.  One parse per attempt: the

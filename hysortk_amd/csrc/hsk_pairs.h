@@ -1,0 +1,301 @@
+// hsk_pairs.h -- read pairs that share k-mers, from the resident EXTENSION list (device).
+//
+// The first stage that reads a HSK_FLAG_KEEP_DEVICE result in place (include/hsk.h: hsk_result_pairs).  Every retained k-mer (an entry
+// of the per-task CSR: cnt occurrences (rid, pos)) stands for cnt (cnt - 1) / 2 occurrence pairs; every pair of two DIFFERENT reads is
+// one record { key = rid_a << 32 | rid_b, value = pos_a << 32 | pos_b }, rid_a < rid_b as unsigned 32-bit numbers.  The records of a
+// task range are sorted by key with the library's radix sort (hsk_sort.h, key + payload), and every run of equal keys becomes one row
+// { key, records of the run, smallest value, largest value }.
+//
+//   pair_tsum_kernel    t_e = cnt_e (cnt_e - 1) / 2 per entry, over all tasks of the range through one table of task descriptors:
+//                       per tile sums, count_scan_kernel (hsk_count.h), then the exclusive 64-bit offset of every entry and where
+//                       its payload slice lies.  Same-read pairs are NOT taken out here: the number of a record stays a closed
+//                       form of the counts.
+//   pair_expand_kernel  one record per lane slot, PX_TILE records per workgroup.  The workgroup finds the entry of its first record
+//                       by binary search in the offsets (the LAST entry whose offset is <= the index: entries with cnt == 1 have
+//                       no records and repeat their successor's offset), stages the offsets of the entries its tile touches in LDS,
+//                       PX_STAGE at a time, every lane finds its entry there, turns the local index into (i, j) (hsk_pairdecode.h)
+//                       and loads rid / pos at slice + i and slice + j: consecutive lanes walk i.  Key and value leave as full
+//                       8-byte words per lane.  A pair inside one read is written as key 0 -- no record has it (rid_b >= 1) --
+//                       so that it sorts to the front, leaves every digit as trivial as it was, and is counted by the reducer.
+//   pair_reduce_kernel  the shape of count_kernel: run heads of a tile as a bit mask, rows per tile, count_scan_kernel, write pass.
+//                       A run belongs to the tile it starts in.  The last run of a tile may go on for any number of tiles: the
+//                       whole workgroup reads ahead to its end (count, min, max reduced over the workgroup); tiles inside a run
+//                       have no head and nothing to do.  The zero-key run is self_records and no row.
+#pragma once
+#include "hsk_device.h"
+#include "hsk_count.h"
+#include "hsk_pairdecode.h"
+
+namespace hsk {
+
+// one task of the range that has entries (host: hsk_host_pairs.h)
+struct PairTask {
+    const u64 *entries;      // n records of nw + 1 words, the count last
+    const u64 *payoff;       // n: first payload of the entry in the rank's numbering
+    const u32 *pos;          // npay
+    const int32_t *rid;      // npay
+    u64 ent_base;            // entries of the range's tasks before this one
+    u64 n, npay, pay_base;   // entry i owns pos / rid[payoff[i] - pay_base ...][0 .. cnt_i)
+};
+
+constexpr int PAIR_THREADS = 256;
+constexpr int PC_EPT = 8, PC_TILE = PAIR_THREADS * PC_EPT;          // entries per thread / tile of pair_tsum_kernel
+constexpr int PAIR_LOC_SHIFT = 40;                                  // loc = task slot << 40 | first payload inside the task (npay < 2^40)
+constexpr u32 PAIR_ERR_COUNT = 1, PAIR_ERR_SLICE = 2;               // an entry's count above 65535 / its slice outside the task's payload
+
+struct PairSumArgs {
+    const PairTask *tasks; u32 ntasks; int nw;
+    u64 nent;
+    u64 *tile_sum;           // SUM out / WRITE in (after the scan: the tile's first record)
+    u64 *off;                // WRITE: nent + 1
+    u64 *loc;                // WRITE: nent
+    u32 *err;
+};
+
+template <bool WRITE>
+__global__ __launch_bounds__(PAIR_THREADS) void pair_tsum_kernel(PairSumArgs a)
+{
+    __shared__ u64 s_scr[8];
+    const int tid = threadIdx.x;
+    const u64 g0 = (u64)blockIdx.x * PC_TILE + (u64)tid * PC_EPT;
+    u32 t[PC_EPT]; u64 loc[PC_EPT]; u64 sum = 0;
+    u32 slot = 0;
+    if (g0 < a.nent) {                                   // the task of this thread's first entry: the last one whose base is <= g0
+        u32 lo = 0, hi = a.ntasks;
+        while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (a.tasks[mid].ent_base <= g0) lo = mid; else hi = mid; }
+        slot = lo;
+    }
+#pragma unroll
+    for (int k = 0; k < PC_EPT; ++k) {
+        const u64 g = g0 + k;
+        t[k] = 0; loc[k] = 0;
+        if (g >= a.nent) continue;
+        while (g >= a.tasks[slot].ent_base + a.tasks[slot].n) ++slot;      // (every listed task has entries; g < nent ends the walk)
+        const PairTask &tk = a.tasks[slot];
+        const u64 l = g - tk.ent_base;
+        const u64 cnt = tk.entries[l * (u64)(a.nw + 1) + a.nw];
+        const u64 first = tk.payoff[l];
+        if (cnt > PAIR_MAX_CNT) { if (!WRITE) atomicOr(a.err, PAIR_ERR_COUNT); continue; }
+        if (first < tk.pay_base || first - tk.pay_base + cnt > tk.npay) { if (!WRITE) atomicOr(a.err, PAIR_ERR_SLICE); continue; }
+        t[k] = pair_count((u32)cnt);
+        loc[k] = ((u64)slot << PAIR_LOC_SHIFT) | (first - tk.pay_base);
+        sum += t[k];
+    }
+    u64 total;
+    u64 e = block_excl_scan_256<u64>(sum, s_scr, &total);
+    if (!WRITE) { if (tid == 0) a.tile_sum[blockIdx.x] = total; return; }
+    e += a.tile_sum[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < PC_EPT; ++k) {
+        const u64 g = g0 + k;
+        if (g < a.nent) { a.off[g] = e; a.loc[g] = loc[k]; e += t[k]; if (g + 1 == a.nent) a.off[a.nent] = e; }
+    }
+}
+
+constexpr int PX_SLOTS = 4, PX_TILE = PAIR_THREADS * PX_SLOTS;      // records per lane / per workgroup
+constexpr int PX_STAGE = 1024;                                       // entry offsets staged in LDS at a time
+
+struct PairExpandArgs {
+    const PairTask *tasks;
+    const u64 *off, *loc;    // nent + 1, nent
+    u64 nent, records;
+    u64 *keys, *vals;        // records each
+};
+
+__global__ __launch_bounds__(PAIR_THREADS) void pair_expand_kernel(PairExpandArgs a)
+{
+    __shared__ u64 s_off[PX_STAGE + 1];
+    __shared__ u64 s_e0;
+    const int tid = threadIdx.x;
+    const u64 base = (u64)blockIdx.x * PX_TILE;
+    const u64 end = base + PX_TILE < a.records ? base + PX_TILE : a.records;
+    if (tid == 0) {                                      // the last entry whose offset is <= base (off[0] = 0 <= base < records = off[nent])
+        u64 lo = 0, hi = a.nent;
+        while (hi - lo > 1) { const u64 mid = (lo + hi) >> 1; if (a.off[mid] <= base) lo = mid; else hi = mid; }
+        s_e0 = lo;
+    }
+    __syncthreads();
+    u64 e_cur = s_e0;
+    u64 ent[PX_SLOTS]; u32 r[PX_SLOTS]; bool found[PX_SLOTS];
+#pragma unroll
+    for (int s = 0; s < PX_SLOTS; ++s) { ent[s] = 0; r[s] = 0; found[s] = false; }
+    for (;;) {
+        // entries e_cur .. e_cur + m - 1 and the offset behind them; a record not found yet lies at or behind s_off[0]
+        const u32 m = (u32)(a.nent - e_cur < (u64)PX_STAGE ? a.nent - e_cur : (u64)PX_STAGE);
+        for (u32 k = tid; k <= m; k += PAIR_THREADS) s_off[k] = a.off[e_cur + k];
+        __syncthreads();
+        const u64 hi_off = s_off[m];
+#pragma unroll
+        for (int s = 0; s < PX_SLOTS; ++s) {
+            const u64 idx = base + (u64)s * PAIR_THREADS + tid;
+            if (idx < end && !found[s] && idx < hi_off) {
+                u32 lo = 0, hi = m;                       // s_off[lo] <= idx < s_off[hi]
+                while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (s_off[mid] <= idx) lo = mid; else hi = mid; }
+                ent[s] = e_cur + lo; r[s] = (u32)(idx - s_off[lo]); found[s] = true;
+            }
+        }
+        const bool fin = hi_off >= end || e_cur + m >= a.nent;
+        __syncthreads();
+        if (fin) break;
+        // The first record not found yet is number hi_off.  Its entry may lie any number of entries without records further on (cnt == 1:
+        // equal offsets): thread 0 searches for it instead of the workgroup walking there, so that every step finds at least one record
+        // and a tile takes at most as many steps as it has records.
+        if (tid == 0) {                                  // the last entry whose offset is <= hi_off (off[e_cur + m] == hi_off)
+            u64 lo = e_cur + m, hi = a.nent;
+            while (hi - lo > 1) { const u64 mid = (lo + hi) >> 1; if (a.off[mid] <= hi_off) lo = mid; else hi = mid; }
+            s_e0 = lo;
+        }
+        __syncthreads();
+        e_cur = s_e0;
+    }
+#pragma unroll
+    for (int s = 0; s < PX_SLOTS; ++s) {
+        const u64 idx = base + (u64)s * PAIR_THREADS + tid;
+        if (!found[s]) continue;
+        const u64 L = a.loc[ent[s]];
+        const PairTask &tk = a.tasks[L >> PAIR_LOC_SHIFT];
+        const u64 first = L & ((1ULL << PAIR_LOC_SHIFT) - 1);
+        u32 i, j; pair_decode(r[s], &i, &j);
+        u32 ra = (u32)tk.rid[first + i], rb = (u32)tk.rid[first + j];
+        u32 pa = tk.pos[first + i], pb = tk.pos[first + j];
+        if (ra > rb) { const u32 x = ra; ra = rb; rb = x; const u32 y = pa; pa = pb; pb = y; }
+        const bool self = ra == rb;
+        a.keys[idx] = self ? 0ULL : ((u64)ra << 32) | rb;
+        a.vals[idx] = self ? 0ULL : ((u64)pa << 32) | pb;
+    }
+}
+
+constexpr int PR_PPT = 8, PR_TILE = PAIR_THREADS * PR_PPT, PR_WORDS = PR_TILE / 64;
+constexpr int PR_AHEAD = 4;                              // records per lane and step of the read-ahead
+enum { PAIR_STAT_RECORDS = 0, PAIR_STAT_ROWS, PAIR_STAT_SELF, PAIR_STAT_KEYS, PAIR_STAT_ERR, PAIR_STAT_WORDS = 8 };
+
+struct PairReduceArgs {
+    const u64 *keys, *vals;  // sorted by key, n each
+    u64 n;
+    u32 min_shared;
+    u64 *tile_cnt;           // COUNT out / EMIT in (after the scan: the tile's first row)
+    u64 *tile_keys;          // COUNT out: runs of the tile with a key other than 0 (summed by a scan of their own: no atomics on one word)
+    u64 *rows;               // EMIT: { key, shared, first, last }
+    u64 *stats;              // COUNT: [PAIR_STAT_SELF] records of the zero-key run
+};
+
+template <bool EMIT>
+__global__ __launch_bounds__(PAIR_THREADS) void pair_reduce_kernel(PairReduceArgs a)
+{
+    __shared__ u64 s_k[PR_TILE + 1];                     // [0] = the record before the tile
+    __shared__ u64 s_v[EMIT ? PR_TILE : 1];
+    __shared__ u64 s_head[PR_WORDS], s_keep[PR_WORDS];
+    __shared__ u32 s_pre[PR_WORDS + 1];
+    __shared__ u64 s_red[4][3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u64 base = (u64)blockIdx.x * PR_TILE;
+    const u32 tn = (u32)(a.n - base < (u64)PR_TILE ? a.n - base : (u64)PR_TILE);
+    const u64 obase = EMIT ? a.tile_cnt[blockIdx.x] : 0;
+    for (u32 i = tid; i < tn + 1; i += PAIR_THREADS) s_k[i] = (base + i) ? a.keys[base + i - 1] : 0;
+    if (EMIT) for (u32 i = tid; i < tn; i += PAIR_THREADS) s_v[i] = a.vals[base + i];
+    __syncthreads();
+    bool head[PR_PPT];
+#pragma unroll
+    for (int j = 0; j < PR_PPT; ++j) {
+        const u32 p = j * PAIR_THREADS + tid;
+        head[j] = p < tn && ((base + p == 0) || s_k[p + 1] != s_k[p]);
+        const u64 m = __ballot(head[j]);
+        if (lane == 0) s_head[j * 4 + wave] = m;
+    }
+    __syncthreads();
+    int lw = PR_WORDS - 1;
+    while (lw >= 0 && s_head[lw] == 0) --lw;
+    if (lw < 0) { if (!EMIT && tid == 0) { a.tile_cnt[blockIdx.x] = 0; a.tile_keys[blockIdx.x] = 0; } return; }      // the tile lies inside a run that started before it
+    const u32 p_last = (u32)lw * 64 + 63 - (u32)__builtin_clzll(s_head[lw]);
+
+    // ---- the tile's last run: the workgroup follows it to its end --------------------------------------------------
+    const u64 key_last = s_k[p_last + 1];
+    u64 lc = 0, lmn = ~0ULL, lmx = 0;
+    for (u32 i = p_last + tid; i < tn; i += PAIR_THREADS) {
+        ++lc;
+        if (EMIT) { const u64 v = s_v[i]; lmn = v < lmn ? v : lmn; lmx = v > lmx ? v : lmx; }
+    }
+    for (u64 g = base + tn;; g += (u64)PAIR_THREADS * PR_AHEAD) {
+        int stop = g >= a.n;
+        if (!stop) {
+#pragma unroll
+            for (int s = 0; s < PR_AHEAD; ++s) {
+                const u64 gi = g + (u64)s * PAIR_THREADS + tid;
+                if (gi >= a.n) { stop = 1; continue; }
+                const u64 k = a.keys[gi];
+                const u64 v = EMIT ? a.vals[gi] : 0;
+                if (k != key_last) { stop = 1; continue; }
+                ++lc;
+                if (EMIT) { lmn = v < lmn ? v : lmn; lmx = v > lmx ? v : lmx; }
+            }
+        }
+        if (__syncthreads_or(stop)) break;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lc += __shfl_xor(lc, o, WAVE);
+        if (EMIT) { const u64 n1 = __shfl_xor(lmn, o, WAVE), x1 = __shfl_xor(lmx, o, WAVE); lmn = n1 < lmn ? n1 : lmn; lmx = x1 > lmx ? x1 : lmx; }
+    }
+    if (lane == 0) { s_red[wave][0] = lc; s_red[wave][1] = lmn; s_red[wave][2] = lmx; }
+    __syncthreads();
+    lc = 0; lmn = ~0ULL; lmx = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { lc += s_red[w][0]; lmn = s_red[w][1] < lmn ? s_red[w][1] : lmn; lmx = s_red[w][2] > lmx ? s_red[w][2] : lmx; }
+
+    // ---- run lengths, the min_shared filter ----------------------------------------------------------------------------
+    u64 runlen[PR_PPT];
+    u32 nkeys = 0;
+#pragma unroll
+    for (int j = 0; j < PR_PPT; ++j) {
+        const u32 p = j * PAIR_THREADS + tid;
+        u64 c = 0; bool real = false;
+        if (head[j]) {
+            if (p == p_last) c = lc;
+            else {                                        // the next head is inside the tile
+                u32 w = p >> 6;
+                u64 m = s_head[w] & ((p & 63) == 63 ? 0ULL : (~0ULL << ((p & 63) + 1)));
+                while (m == 0) m = s_head[++w];
+                c = (w << 6) + (u32)__builtin_ctzll(m) - p;
+            }
+            real = s_k[p + 1] != 0;
+            if (!EMIT && !real) a.stats[PAIR_STAT_SELF] = c;
+        }
+        const bool keep = real && c >= a.min_shared;
+        runlen[j] = keep ? c : 0;
+        const u64 km = __ballot(keep);
+        if (lane == 0) s_keep[j * 4 + wave] = km;
+        if (!EMIT) nkeys += (u32)__popcll(__ballot(real));
+    }
+    __syncthreads();                                      // (s_red has been read by every wave)
+    if (!EMIT && lane == 0) s_red[wave][0] = nkeys;
+    __syncthreads();
+    if (tid < 64) {
+        const u32 v = tid < PR_WORDS ? (u32)__popcll(s_keep[tid]) : 0;
+        const u32 inc = wave_incl_scan<u32>(v);
+        if (tid < PR_WORDS) s_pre[tid] = inc - v;
+        if (tid == PR_WORDS - 1) s_pre[PR_WORDS] = inc;
+    }
+    __syncthreads();
+    if (!EMIT) { if (tid == 0) { a.tile_cnt[blockIdx.x] = s_pre[PR_WORDS]; a.tile_keys[blockIdx.x] = s_red[0][0] + s_red[1][0] + s_red[2][0] + s_red[3][0]; } return; }
+
+    // ---- rows: slot = popcount prefix of the kept heads, so the list stays in key order ----------------------------------
+#pragma unroll
+    for (int j = 0; j < PR_PPT; ++j) {
+        const u64 c = runlen[j];
+        if (!c) continue;
+        const u32 p = j * PAIR_THREADS + tid;
+        const u32 w = j * 4 + wave;
+        const u32 slot = s_pre[w] + (u32)__popcll(s_keep[w] & ((1ULL << lane) - 1));
+        u64 mn = lmn, mx = lmx;
+        if (p != p_last) {
+            mn = ~0ULL; mx = 0;
+            for (u32 q = p; q < p + (u32)c; ++q) { const u64 v = s_v[EMIT ? q : 0]; mn = v < mn ? v : mn; mx = v > mx ? v : mx; }
+        }
+        typedef unsigned long long v2u64r __attribute__((ext_vector_type(2)));
+        v2u64r *row = (v2u64r *)(a.rows + (obase + slot) * 4);
+        const v2u64r r0 = {s_k[p + 1], c}, r1 = {mn, mx};
+        row[0] = r0; row[1] = r1;
+    }
+}
+
+} // namespace hsk

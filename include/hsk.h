@@ -223,6 +223,47 @@ void hsk_result_free(hsk_ctx *ctx, hsk_result *res);
  * them in place; the memory belongs to the result. */
 int hsk_result_device_task(const hsk_result *res, int32_t task, const void **entries, uint64_t *n,
                            const void **payload_off, const void **pos, const void **rid, uint64_t *npay, uint64_t *payload_base);
+/*
+ * Read pairs that share k-mers (what a client such as ELBA builds from the (ReadId, PosInRead) lists, reference README.md:52,74),
+ * computed on the GPU from a result that was left there: HSK_FLAG_KEEP_DEVICE and EXTENSION, tasks [task_lo, task_hi).
+ *
+ * Definition.  Every entry of those tasks (a retained k-mer, L <= cnt <= U) has cnt occurrences (rid, pos), which form
+ * cnt (cnt - 1) / 2 unordered occurrence pairs.  A pair whose two occurrences lie in the same read is dropped (the k-mer occurs twice
+ * in that read); every other pair is one RECORD
+ *     key   = rid_a << 32 | rid_b      rid_a < rid_b, both read as unsigned 32-bit numbers
+ *     value = pos_a << 32 | pos_b      pos_a = the position in read rid_a.
+ * The records are grouped by key.  The list has one ROW of four uint64 words per key with at least min_shared records, in
+ * ascending key order:
+ *     { key, shared, first, last }     shared = records with that key, first / last = the smallest / largest value of the run
+ * (as 64-bit numbers: ordered by pos_a, then pos_b).  Minimum and maximum do not depend on the order of the payload inside an
+ * entry, which is unspecified.  There is NO STRAND in a row: the payload carries none, so a pair of reads that overlap on opposite
+ * strands is told from one on the same strand only by the way pos_b runs against pos_a, which first and last bracket.
+ *
+ * Several lists (the multi-rank contract).  The lists of disjoint task ranges combine to the list of their union, and so do the
+ * lists of the ranks of a several-GPU run (every k-mer belongs to one task and every task to one rank): rows with equal keys
+ * join -- shared adds up, first is the minimum, last the maximum -- and min_shared is applied AFTER that (compute the parts with
+ * min_shared = 1).  The call itself is rank-local and not collective; nothing is exchanged between the ranks here.
+ *
+ * Memory: two key and two value buffers of `records` 8-byte words plus the rows.  `records` is known after one counting pass and
+ * before any of them is allocated: HSK_ERR_OOM then says how many records and bytes, and a narrower task range is the way out.
+ * HSK_ERR_INVALID_ARG: a NULL pointer, a result that was not left on the device, a context without EXTENSION, a task range outside
+ * [0, ntasks], min_shared == 0.  An empty range is no error (n = 0).  hsk_pairs_free before hsk_destroy of the context.
+ */
+typedef struct {
+    uint64_t n;             /* rows */
+    uint64_t *rows;         /* host (pinned), n * 4 words; NULL when left on the device */
+    void     *rows_dev;     /* device copy when asked for */
+    uint64_t records;       /* occurrence pairs expanded, same-read ones included */
+    uint64_t self_records;  /* of which dropped: both occurrences in one read */
+    uint64_t keys;          /* distinct read pairs before min_shared */
+    int32_t  sort_passes;   /* scatter passes the key sort took (-1: not known) */
+    double   ms_expand, ms_sort, ms_reduce, ms_d2h, ms_total;   /* HIP events */
+    void    *priv;
+} hsk_pairs;
+
+int  hsk_result_pairs(hsk_ctx *ctx, const hsk_result *res, int32_t task_lo, int32_t task_hi,
+                      uint32_t min_shared, int32_t on_device, hsk_pairs *out);
+void hsk_pairs_free(hsk_ctx *ctx, hsk_pairs *p);
 /* Result egress (write_output_file, reference src/hysortk.cpp:138-164): the lines "KMERSTRING\tcount\n" of `n` entries
  * ((nw + 1)-word records: host memory, or device memory when `on_device`), formatted on the GPU into `text` (host, capacity
  * bytes); *nbytes = bytes needed (call with capacity 0 to size the buffer: K + 2 + up to 20 digits per entry). */
