@@ -1,6 +1,7 @@
 """Inputs of uneven shape for the combining extraction (tests/test_gpu_combine_ragged.py; validated on the CPU by
 tests/test_ragged_inputs.py): reads of every length class around K and around the item cut, with N, lower case and empty
-reads; records of many tiles with their edges on tile edges; tandem repeats; k-mers with more than 2^16 copies.  Plain
+reads; records of many tiles with their edges on tile edges; tandem repeats; k-mers with more than 2^16 copies; and, for the EXTENSION payloads
+(tests/test_gpu_ext_ragged.py), tiles crowded with read offsets around the scan's read-index window and runs of empty reads (crowded_index).  Plain
 functions, seeded and deterministic; every builder returns a list of strings (DnaBuffer.from_sequences / oracle.pack_reads
 take it; pack() below gives the same arrays in one numpy pass)."""
 import numpy as np
@@ -134,13 +135,14 @@ def past_16_bits_kmers(K, seed):
             return ks
 
 
-def past_16_bits(K, seed):
+def past_16_bits(K, seed, apart=True):
     """four k-mers as reads of exactly K bases (either strand), 65535, 65536, 65536 + 20 and 2 x 65536 + 17 copies, shuffled into 3000 ragged reads:
-    the copies spread over many tiles and workgroups.  No background read holds one of the four (asserted)."""
+    the copies spread over many tiles and workgroups.  No background read holds one of the four (asserted; apart=False leaves that open: at K = 5 the
+    background holds every k-mer there is, and the four only grow)."""
     rng = np.random.default_rng([seed, K, 6])
     ks = past_16_bits_kmers(K, seed)
     back = ragged(K, seed, nreads=3000)
-    for s in back:
+    for s in back if apart else ():
         u = s.upper().replace("N", "A")                      # (as the reads are packed)
         assert not any(x in u or revcomp(x) in u for x in ks), "the background holds one of the four k-mers"
     pool = back + [x for x in ks for _ in (0, 1)]
@@ -151,6 +153,95 @@ def past_16_bits(K, seed):
         idx.append(len(back) + 2 * j + (rng.integers(0, 2, size=n, dtype=np.int64)))
     idx = np.concatenate(idx)
     return [pool[i] for i in rng.permutation(idx)]
+
+
+INDEX_TILE = 512            # bytes of the packed buffer per parse tile (PARSE_TILE / 4)
+INDEX_WINDOW = 64           # read-index entries scan_kernel looks at per tile (PARSE_RWIN)
+CROWDED_COUNTS = (62, 63, 64, 65, 66)
+CROWDED_RUN = 100           # empty reads in a row
+
+
+def crowded_index(K, seed, genome=8000):
+    """~100 kbases for the read index of the EXTENSION payloads (the k-mers and counts of this input do not depend on it, every (pos, rid) does).
+    Every read with k-mers is cut from one genome of 8000 bases, on both strands, so most k-mers occur in several reads.  In turn:
+    100 empty reads in front of the first read with k-mers; 100 reads of 150 bases; for n = 62 ... 66 two tiles with exactly n read offsets
+    inside their 512 bytes (empty reads and reads of 1-4 bases, one of K bases; the last of them a read that runs past the tile's end) -- one
+    whose first read starts on the tile's first byte, the last read early in the tile, one whose first bytes belong to the read before, the last
+    read starting 3 bytes before the tile's end; a tile of 451 offsets (reads of 1-4 bases and empty ones); 100 empty reads in front of a read
+    of K bases; a record of three tiles and 40 bytes, behind it 70 reads of at most 4 bases and a read with k-mers in the same tile; reads of
+    K ... K+3 bases in threes with an empty and a one-base read, in every order; reads with N and lower case; 100 empty reads.
+    tests/test_ragged_inputs.py asserts all of it from pack()'s offsets."""
+    rng = np.random.default_rng([seed, K, 7])
+    g = random_seq(rng, genome)
+    out, at_byte = [], [0]
+    extra = (K + 3) // 4 + 1                                   # bytes past a tile's end that make a read of at least K bases
+
+    def add(s):
+        out.append(s)
+        at_byte[0] += (len(s) + 3) // 4
+
+    def cut(n):
+        at = int(rng.integers(0, genome - n + 1))
+        s = g[at:at + n]
+        return revcomp(s) if rng.integers(0, 2) else s
+
+    def tiny():
+        return random_seq(rng, int(rng.integers(1, 5)))
+
+    def fill_to(b):                                            # one read with k-mers that starts in one tile and ends in front of byte b of a later one
+        need = (b - at_byte[0]) % INDEX_TILE
+        if need <= b or 4 * need < K:
+            need += INDEX_TILE
+        add(cut(4 * need))
+
+    def shorts(n, with_k):                                     # n reads of one byte at most; with_k: one of them has K bases instead
+        for i in range(n):
+            if with_k and i == n // 2:
+                add(cut(K))
+            else:
+                add("" if i % 3 == 1 else tiny())
+
+    def past_the_edge():                                       # the last read that starts in this tile: it ends `extra` bytes into the next one
+        nb = INDEX_TILE - at_byte[0] % INDEX_TILE + extra
+        add(cut(4 * nb - int(rng.integers(0, 4))))
+
+    for _ in range(CROWDED_RUN):
+        add("")
+    add(cut(K + 2))
+    for _ in range(100):
+        add(cut(150))
+    for n in CROWDED_COUNTS:
+        fill_to(0)
+        shorts(n - 1, True)
+        past_the_edge()
+        fill_to(5)
+        shorts(n - 2, True)
+        add(cut(4 * (INDEX_TILE - at_byte[0] % INDEX_TILE - 3)))
+        past_the_edge()
+    fill_to(0)
+    shorts(450, False)
+    past_the_edge()
+    for _ in range(CROWDED_RUN):
+        add("")
+    add(cut(K))
+    fill_to(0)
+    add(cut(3 * 4 * INDEX_TILE + 160))
+    shorts(70, False)
+    past_the_edge()
+    for _ in range(2):
+        for p in range(4):
+            three = ["", random_seq(rng, 1), None]
+            for order in ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)):
+                for j in order:
+                    add(cut(K + p) if three[j] is None else three[j])
+    for _ in range(20):
+        s = cut(150)
+        j = int(rng.integers(0, 150))
+        add(s[:j] + "N" + s[j + 1:])
+        add(cut(150).lower())
+    for _ in range(CROWDED_RUN):
+        add("")
+    return out
 
 
 # the (K, M) grid of the tests: one-word keys -- (30, 15): even K, palindromes; (31, 25): the scan's largest M, a window of 7; (27, 5): a wide window,

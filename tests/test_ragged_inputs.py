@@ -33,6 +33,50 @@ def test_ragged_meets_the_item_cut_and_every_packing_phase(K, M):
     assert longer >= 100 and shorter >= 100 and exact >= 1, (longer, shorter, exact)
 
 
+@pytest.mark.parametrize("K", [5, 31, 51])
+def test_crowded_index_straddles_the_read_index_window(K):
+    """what tests/test_gpu_ext_ragged.py needs of crowded_index(), from pack()'s offsets alone"""
+    seqs = R.crowded_index(K, R.SEED)
+    assert seqs == R.crowded_index(K, R.SEED) and sum(len(s) for s in seqs) <= 200000
+    packed, off, lens = R.pack(seqs)
+    for a, b in zip((packed, off, lens), O.pack_reads(seqs)):
+        assert np.array_equal(a, b)
+    off, lens = off.astype(np.int64), lens.astype(np.int64)
+    nb = (lens + 3) // 4
+    n, T, run = len(seqs), R.INDEX_TILE, R.CROWDED_RUN
+    # runs of empty reads: at the start and in the middle in front of a read with k-mers (same offset as that read), and at the end of the buffer
+    empty = np.concatenate(([0], np.cumsum(lens == 0)))
+    behind_run = [r for r in range(run, n) if empty[r] - empty[r - run] == run and lens[r] >= K]
+    assert behind_run[0] == run and not lens[:run].any() and off[run] == 0
+    assert any(lens[:r - run].max() >= K and lens[r + 1:].max() >= K and off[r - run] == off[r] for r in behind_run[1:])
+    assert not lens[-run:].any() and lens[-run - 1] > 0 and (off[-run:] == packed.size).all()
+    # tiles by the number of read offsets inside their 512 bytes, empty reads included
+    tile = off // T
+    count = np.bincount(tile)
+    last = np.zeros(count.size, dtype=np.int64)
+    last[tile] = np.arange(n)                                           # the last read that starts in the tile (offsets ascend)
+    first = np.searchsorted(tile, np.arange(count.size))                # the first one
+    holder = np.searchsorted(off + nb, np.arange(count.size) * T, side="right")      # the read that holds the tile's first byte
+    for want in R.CROWDED_COUNTS:
+        tiles = np.flatnonzero(count == want)
+        assert (lens[last[tiles]] >= K).all()                           # a read with k-mers comes last, behind the window's edge or just inside it
+        assert any(off[first[t]] == t * T for t in tiles), want         # the window starts at the tile's first read ...
+        assert any(off[first[t]] > t * T and off[last[t]] + 3 == (t + 1) * T for t in tiles), want      # ... or one read earlier; the last read starts at the very end
+    assert R.INDEX_WINDOW in R.CROWDED_COUNTS and R.INDEX_WINDOW - 2 in R.CROWDED_COUNTS and R.INDEX_WINDOW + 2 in R.CROWDED_COUNTS
+    crowd = [t for t in np.flatnonzero(count >= 300) if lens[last[t]] >= K and lens[first[t]:last[t]].max() <= 4 and lens[first[t]:last[t]].min() == 0]
+    assert crowd, count.max()
+    # a record of several tiles; more than a window of reads follow it in its last tile, the last of them with k-mers
+    assert any(count[t] > R.INDEX_WINDOW and lens[last[t]] >= K and holder[t] < first[t] and tile[holder[t]] <= t - 3 for t in range(3, count.size))
+    # K ... K + 3 bases (the four packing phases) in threes with an empty and a one-base read, in every order
+    threes = {tuple(lens[i:i + 3]) for i in range(n - 2)}
+    for p in range(4):
+        for order in ((0, 1, K + p), (0, K + p, 1), (1, 0, K + p), (1, K + p, 0), (K + p, 0, 1), (K + p, 1, 0)):
+            assert order in threes, order
+    # one small genome: most k-mers occur in several reads
+    ores = O.count(packed, off.astype(np.uint64), lens.astype(np.uint32), k=K, m=min(17, K - 2), L=1, U=65535, ntasks=NTASKS, fast=True)
+    assert (ores.cnt >= 2).sum() > len(ores.cnt) // 2
+
+
 @pytest.mark.parametrize("K,M", R.GRID)
 def test_long_records_sit_on_the_tile_edges(K, M):
     for variant in (0, 1):
