@@ -15,7 +15,7 @@
 //   3. combine_kernel: a workgroup takes a bucket, reads its items back to back, rolls their k-mers straight into a 2048-slot LDS
 //      hash table (the probe loop of the finish, agg_count_keys, behind a first sweep that finds most k-mers in their home slots)
 //      and then writes the table's {key, count} pairs into the chunk store of the first radix pass exactly as expand_scatter2_kernel
-//      writes keys (cursor / map / chunk protocol of hsk_scatter.h), the counts into the payload chunks; a table that fills up in
+//      writes keys (cursor / map / chunk protocol of hsk_chunks.h), the counts into the payload chunks; a table that fills up in
 //      the middle of a bucket is written out and started again, so a key may leave a bucket in several partial pairs: nothing
 //      downstream assumes otherwise;
 //   4. the second radix pass carries the counts as the payload (onesweep_multi_kernel<1, true>), and the finish adds them up instead
@@ -399,13 +399,60 @@ struct CombineTask {
     const uint2 *units;        // work units {first item, end}: a bucket or a slice of a large one (bucket_units_kernel)
     const u32 *nunits;         // their number (device memory)
     u32 nb;                    // buckets (0: no task on this XCD)
-    u32 vmax;
-    u32 cap_chunks;            // chunks the pair stores hold; the one behind them takes what does not fit (error bit 512: the host runs the call again with stores
-                               // sized for the k-mers -- they are sized for the pairs the call's sketch of the input promises, four times over)
-    u64 *chunks, *vchunks;     // chunk stores of the keys and of the counts (same slots)
-    u64 *cursor; u32 *map; u32 *ctl; u64 *ghist;       // as ScatterTask; ctl[0]: bucket ticket
+    ChunkStore cs;             // chunk stores of the keys and of the counts (hsk_chunks.h; ctl[0]: bucket ticket)
 };
 struct CombineArgs { CombineTask t[8]; int k, shift0, bits0, shift1; u32 *err; };      // first-pass digit: bits0 (<= 8) bits at shift0, second-pass digit: 8 bits at shift1 (both >= 32)
+
+// The table's pairs leave for the chunk store of the first radix pass: digits counted, one reservation per digit (chunk_resolve,
+// hsk_chunks.h), every pair straight to its slot, the table empty again.  kw: the table's key arrays, most significant word last (as
+// agg_order_many takes them); records of two words leave as one 16-byte store.  Called by the whole workgroup behind a barrier (all
+// inserts done); s_cnt is zero on entry and on exit.
+template <int NW, int CAP>
+__device__ __forceinline__ void combine_dump(u64 *const (&kw)[NW], u32 *s_val, u32 *s_cnt, u32 *s_hist, uint4 *s_dl, u32 *s_scr, const ChunkStore &s,
+                                 u32 sh0, u32 dm0, u32 sh1, u32 *err)
+{
+    constexpr int CHUNK = XsCfg<NW>::CHUNK, PER = CAP / CB_THREADS;
+    static_assert(NW == 1 || NW == 2, "keys of one or two words");
+    const int tid = threadIdx.x;
+    u64 mk[NW][PER]; u32 mv[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+#pragma unroll
+        for (int x = NW - 1; x >= 0; --x) mk[x][j] = kw[x][j * CB_THREADS + tid];
+        mv[j] = s_val[j * CB_THREADS + tid];
+        if (mk[NW - 1][j] != AG_EMPTY) atomicAdd(&s_cnt[((u32)(mk[NW - 1][j] >> 32) >> sh0) & dm0], 1u);
+    }
+    xs_barrier();
+    const u32 c = s_cnt[tid];
+    u32 tot;
+    const u32 st = block_excl_scan_xs<CB_WAVES>(c, s_scr, &tot);
+    if (tot) {
+        s_cnt[tid] = st;                                        // from a count to the running cursor of the digit's range
+        if (c) {
+            const u64 p = __hip_atomic_fetch_add(&s.cursor[tid], (u64)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            s_dl[tid] = chunk_resolve<CHUNK, true>(s, (u32)tid, p, c, st, err);
+        }
+        xs_barrier();
+#pragma unroll
+        for (int j = 0; j < PER; ++j) {
+            if (mk[NW - 1][j] == AG_EMPTY) continue;
+            const u32 hi = (u32)(mk[NW - 1][j] >> 32);
+            const u32 d = (hi >> sh0) & dm0;
+            const u32 i = atomicAdd(&s_cnt[d], 1u);
+            const u32 o = chunk_slot<CHUNK>(s_dl[d], i);
+            if (NW == 2) reinterpret_cast<ulonglong2 *>(s.chunks)[o] = make_ulonglong2(mk[0][j], mk[NW - 1][j]);
+            else s.chunks[o] = mk[0][j];
+            s.vchunks[o] = (u64)mv[j];
+            atomicAdd(&s_hist[(hi >> sh1) & 255u], 1u);
+#pragma unroll
+            for (int x = NW - 1; x >= 0; --x) kw[x][j * CB_THREADS + tid] = AG_EMPTY;
+            s_val[j * CB_THREADS + tid] = 0;
+        }
+        xs_barrier();
+        s_cnt[tid] = 0;
+    }
+    xs_barrier();
+}
 
 template <int KT = 0>
 __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a)
@@ -417,7 +464,6 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a)
     __shared__ uint4 s_dl[256];
     __shared__ u32 s_scr[CB_WAVES];
     __shared__ u32 s_flag[4];                          // [0] bucket ticket, [1 + round % 3] a lane ran out of probes in that round
-    typedef __attribute__((address_space(1))) u32 G32;
     typedef __attribute__((address_space(3))) void *LdsPtr;
     const int tid = threadIdx.x;
     const u32 xcc = __builtin_amdgcn_s_getreg(XCC_ID_GETREG) & 7u;
@@ -436,69 +482,13 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a)
     if (tid == 0) { s_flag[1] = 0; s_flag[2] = 0; s_flag[3] = 0; }
     u32 round = 0;                                     // insert rounds of this workgroup (the same in every wave)
 
-    // The table's pairs leave for the chunk store of the first radix pass: digits counted, one reservation per digit (cursor, chunk map:
-    // the protocol of expand_scatter2_kernel), every pair straight to its slot, the table empty again.  Called by the whole workgroup
-    // behind a barrier (all inserts done); s_cnt is zero on entry and on exit.
-    auto dump = [&]() {
-        u64 mk[CB_PER]; u32 mv[CB_PER];
-#pragma unroll
-        for (int j = 0; j < CB_PER; ++j) {
-            mk[j] = s_key[j * CB_THREADS + tid]; mv[j] = s_val[j * CB_THREADS + tid];
-            if (mk[j] != AG_EMPTY) atomicAdd(&s_cnt[((u32)(mk[j] >> 32) >> sh0) & dm0], 1u);
-        }
-        xs_barrier();
-        const u32 c = s_cnt[tid];
-        u32 tot;
-        const u32 st = block_excl_scan_xs<CB_WAVES>(c, s_scr, &tot);
-        if (tot) {
-            s_cnt[tid] = st;                                        // from a count to the running cursor of the digit's range
-            if (c) {
-                const u64 p = __hip_atomic_fetch_add(&t.cursor[tid], (u64)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                const u64 v0 = p / CHUNK;
-                const u32 off0 = (u32)(p % CHUNK);
-                const u32 nv = (off0 + c - 1) / CHUNK + 1;
-                G32 *mp = (G32 *)(t.map + (u64)tid * t.vmax);
-                u32 ph[XS_SPAN] = {0, 0, 0};
-#pragma unroll
-                for (int q = 0; q < XS_SPAN; ++q) {
-                    if ((u32)q >= nv || (q == 0 && off0 != 0)) continue;
-                    ph[q] = __hip_atomic_fetch_add(&t.ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + 1;
-                    if (ph[q] > t.cap_chunks) { ph[q] = t.cap_chunks + 1u; atomicOr(a.err, 512u); }
-                    __hip_atomic_store(mp + v0 + q, ph[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-                if (off0 != 0) {
-                    u32 spins = 0;
-                    while ((ph[0] = __hip_atomic_load(mp + v0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0) {
-                        if (++spins > XS_SPIN_LIMIT) { atomicOr(a.err, 2u); ph[0] = 1; break; }
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                }
-                const u32 split = st + ((u32)CHUNK - off0);
-                s_dl[tid] = make_uint4(split, (ph[0] - 1) * (u32)CHUNK + off0 - st, ((ph[1] ? ph[1] : 1u) - 1) * (u32)CHUNK - split,
-                                       ((ph[2] ? ph[2] : 1u) - 1) * (u32)CHUNK - (split + (u32)CHUNK));
-            }
-            xs_barrier();
-#pragma unroll
-            for (int j = 0; j < CB_PER; ++j) {
-                if (mk[j] == AG_EMPTY) continue;
-                const u32 hi = (u32)(mk[j] >> 32);
-                const u32 d = (hi >> sh0) & dm0;
-                const u32 i = atomicAdd(&s_cnt[d], 1u);
-                const uint4 dl = s_dl[d];
-                const u32 o = i + (i < dl.x ? dl.y : (i < dl.x + (u32)CHUNK ? dl.z : dl.w));   // (mod 2^32)
-                t.chunks[o] = mk[j]; t.vchunks[o] = (u64)mv[j];
-                atomicAdd(&s_hist[(hi >> sh1) & 255u], 1u);
-                s_key[j * CB_THREADS + tid] = AG_EMPTY; s_val[j * CB_THREADS + tid] = 0;
-            }
-            xs_barrier();
-            s_cnt[tid] = 0;
-        }
-        xs_barrier();
-    };
+    u64 *const kw[1] = {s_key};
+    // (one call site: with combine_dump called from both places below the compiler needs 98 instead of 96 VGPRs -- four workgroups per CU instead of five)
+    auto dump = [&]() { combine_dump<1, CB_CAP>(kw, s_val, s_cnt, s_hist, s_dl, s_scr, t.cs, sh0, dm0, sh1, a.err); };
 
     for (;;) {
         xs_barrier();                                                 // (table cleared / previous bucket dumped; the ticket word is free)
-        if (tid == 0) s_flag[0] = __hip_atomic_fetch_add(&t.ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (tid == 0) s_flag[0] = __hip_atomic_fetch_add(&t.cs.ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         xs_barrier();
         const u32 b = s_flag[0];
         if (b >= nunits) break;
@@ -580,7 +570,7 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a)
     }
     {
         const u32 cv = s_hist[tid];
-        if (cv) atomicAdd((unsigned long long *)&t.ghist[tid], (unsigned long long)cv);
+        if (cv) atomicAdd((unsigned long long *)&t.cs.ghist[tid], (unsigned long long)cv);
     }
 }
 
@@ -609,7 +599,6 @@ __global__ __launch_bounds__(CB_THREADS) void combine2_kernel(CombineArgs a)
     __shared__ uint4 s_dl[256];
     __shared__ u32 s_scr[CB_WAVES];
     __shared__ u32 s_flag[4];
-    typedef __attribute__((address_space(1))) u32 G32;
     typedef __attribute__((address_space(3))) void *LdsPtr;
     const int tid = threadIdx.x;
     const u32 xcc = __builtin_amdgcn_s_getreg(XCC_ID_GETREG) & 7u;
@@ -627,66 +616,12 @@ __global__ __launch_bounds__(CB_THREADS) void combine2_kernel(CombineArgs a)
     if (tid == 0) { s_flag[1] = 0; s_flag[2] = 0; s_flag[3] = 0; }
     u32 round = 0;
 
-    auto dump = [&]() {                                 // as in combine_kernel, records of two words
-        u64 m1[CB_PER], m0[CB_PER]; u32 mv[CB_PER];
-#pragma unroll
-        for (int j = 0; j < CB_PER; ++j) {
-            m1[j] = s_k1[j * CB_THREADS + tid]; m0[j] = s_k0[j * CB_THREADS + tid]; mv[j] = s_val[j * CB_THREADS + tid];
-            if (m1[j] != AG_EMPTY) atomicAdd(&s_cnt[((u32)(m1[j] >> 32) >> sh0) & dm0], 1u);
-        }
-        xs_barrier();
-        const u32 c = s_cnt[tid];
-        u32 tot;
-        const u32 st = block_excl_scan_xs<CB_WAVES>(c, s_scr, &tot);
-        if (tot) {
-            s_cnt[tid] = st;
-            if (c) {
-                const u64 p = __hip_atomic_fetch_add(&t.cursor[tid], (u64)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                const u64 v0 = p / CHUNK;
-                const u32 off0 = (u32)(p % CHUNK);
-                const u32 nv = (off0 + c - 1) / CHUNK + 1;
-                G32 *mp = (G32 *)(t.map + (u64)tid * t.vmax);
-                u32 ph[XS_SPAN] = {0, 0, 0};
-#pragma unroll
-                for (int q = 0; q < XS_SPAN; ++q) {
-                    if ((u32)q >= nv || (q == 0 && off0 != 0)) continue;
-                    ph[q] = __hip_atomic_fetch_add(&t.ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + 1;
-                    if (ph[q] > t.cap_chunks) { ph[q] = t.cap_chunks + 1u; atomicOr(a.err, 512u); }
-                    __hip_atomic_store(mp + v0 + q, ph[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-                if (off0 != 0) {
-                    u32 spins = 0;
-                    while ((ph[0] = __hip_atomic_load(mp + v0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0) {
-                        if (++spins > XS_SPIN_LIMIT) { atomicOr(a.err, 2u); ph[0] = 1; break; }
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                }
-                const u32 split = st + ((u32)CHUNK - off0);
-                s_dl[tid] = make_uint4(split, (ph[0] - 1) * (u32)CHUNK + off0 - st, ((ph[1] ? ph[1] : 1u) - 1) * (u32)CHUNK - split,
-                                       ((ph[2] ? ph[2] : 1u) - 1) * (u32)CHUNK - (split + (u32)CHUNK));
-            }
-            xs_barrier();
-#pragma unroll
-            for (int j = 0; j < CB_PER; ++j) {
-                if (m1[j] == AG_EMPTY) continue;
-                const u32 hi = (u32)(m1[j] >> 32);
-                const u32 d = (hi >> sh0) & dm0;
-                const u32 i = atomicAdd(&s_cnt[d], 1u);
-                const uint4 dl = s_dl[d];
-                const u32 o = i + (i < dl.x ? dl.y : (i < dl.x + (u32)CHUNK ? dl.z : dl.w));   // (mod 2^32)
-                reinterpret_cast<ulonglong2 *>(t.chunks)[o] = make_ulonglong2(m0[j], m1[j]); t.vchunks[o] = (u64)mv[j];
-                atomicAdd(&s_hist[(hi >> sh1) & 255u], 1u);
-                s_k1[j * CB_THREADS + tid] = AG_EMPTY; s_k0[j * CB_THREADS + tid] = AG_EMPTY; s_val[j * CB_THREADS + tid] = 0;
-            }
-            xs_barrier();
-            s_cnt[tid] = 0;
-        }
-        xs_barrier();
-    };
+    u64 *const kw[2] = {s_k0, s_k1};
+    auto dump = [&]() { combine_dump<2, CB_CAP>(kw, s_val, s_cnt, s_hist, s_dl, s_scr, t.cs, sh0, dm0, sh1, a.err); };      // (as in combine_kernel)
 
     for (;;) {
         xs_barrier();
-        if (tid == 0) s_flag[0] = __hip_atomic_fetch_add(&t.ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (tid == 0) s_flag[0] = __hip_atomic_fetch_add(&t.cs.ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         xs_barrier();
         const u32 b = s_flag[0];
         if (b >= nunits) break;
@@ -771,7 +706,7 @@ __global__ __launch_bounds__(CB_THREADS) void combine2_kernel(CombineArgs a)
     }
     {
         const u32 cv = s_hist[tid];
-        if (cv) atomicAdd((unsigned long long *)&t.ghist[tid], (unsigned long long)cv);
+        if (cv) atomicAdd((unsigned long long *)&t.cs.ghist[tid], (unsigned long long)cv);
     }
 }
 

@@ -204,34 +204,20 @@ static int combine_batch(hsk_ctx *c, const u32 *tk, const BatchTask *bt, u64 *co
     bool any = false;
     for (int i = 0; i < XCD_BATCH; ++i) if (tk[i] != ~0u && bt[i].n) any = true;
     if (!any) return HSK_OK;
-    DALLOC(c, sb.d_cursor, u64 *, (size_t)XCD_BATCH * 256 * 8);
-    DALLOC(c, sb.d_ctl, u32 *, (size_t)XCD_BATCH * 16);
-    DALLOC(c, sb.d_gbase, u64 *, (size_t)XCD_BATCH * 256 * 8);
-    DALLOC(c, sb.d_ntiles, u32 *, 256);
-    DALLOC(c, sb.d_nout, u64 *, 256);
+    int rc = chunk_store_batch_begin(c, sb, stream, true); if (rc) return rc;
     sb.h_nout = h_nout;
-    HIPCHK(c, hipMemsetAsync(sb.d_ntiles, 0, 64, stream));
-    HIPCHK(c, hipMemsetAsync(sb.d_nout, 0, 64, stream));
-    HIPCHK(c, hipMemsetAsync(sb.d_cursor, 0, (size_t)XCD_BATCH * 256 * 8, stream));
-    HIPCHK(c, hipMemsetAsync(sb.d_ctl, 0, (size_t)XCD_BATCH * 16, stream));
     u64 ntot = 0;
     for (int i = 0; i < XCD_BATCH; ++i) {
         if (tk[i] == ~0u || !bt[i].n) continue;
         const u32 tid = tk[i];
         const u64 n = bt[i].n;                           // k-mers of the task: never fewer than its pairs
+        rc = chunk_store_task(c, sb, i, n, CH, bt[i].kB, bt[i].vB, ghist[i] + 256, stream); if (rc) return rc;
         ScatterTask &t = a.t[i];
-        t.vmax = (u32)(n / CH + 1);
-        DALLOC(c, sb.d_map[i], u32 *, (size_t)256 * t.vmax * 4);
-        DALLOC(c, sb.d_tile_src[i], u64 *, (size_t)(n / CH + 257) * 8);
-        HIPCHK(c, hipMemsetAsync(sb.d_map[i], 0, (size_t)256 * t.vmax * 4, stream));
         t.ntiles = 1;                                    // (chunk_tiles_kernel: the XCD has a task)
-        t.chunks = bt[i].kB; t.vchunks = bt[i].vB; t.cursor = sb.d_cursor + (size_t)i * 256; t.map = sb.d_map[i]; t.ctl = sb.d_ctl + (size_t)i * 4;
-        t.ghist = ghist[i] + 256; t.tile_src = sb.d_tile_src[i];
-        t.n = ~0ULL; t.n_out = sb.d_nout + i; t.gbase = sb.d_gbase + (size_t)i * 256; t.ntiles_out = sb.d_ntiles + i;
+        t.n = ~0ULL;
         CombineTask &q = ca.t[i];
-        q.recs = bo.recs + bo.out_base[tid]; q.units = bo.units + bo.unit_off[tid]; q.nunits = bo.d_nunits + tid; q.nb = 1u << bo.log2nb[tid]; q.vmax = t.vmax;
-        q.cap_chunks = (u32)(scatter_store_keys(pair_cap, CH) / CH);
-        q.chunks = t.chunks; q.vchunks = t.vchunks; q.cursor = t.cursor; q.map = t.map; q.ctl = t.ctl; q.ghist = t.ghist;
+        q.recs = bo.recs + bo.out_base[tid]; q.units = bo.units + bo.unit_off[tid]; q.nunits = bo.d_nunits + tid; q.nb = 1u << bo.log2nb[tid];
+        q.cs = t.cs; q.cs.cap_chunks = scatter_store_chunks(pair_cap, CH);
         ntot += n;
     }
     a.k = c->cfg.kmer_size; a.shift0 = plan[0].shift; a.shift1 = plan[1].shift; a.chunk = CH; a.err = c->d_err;

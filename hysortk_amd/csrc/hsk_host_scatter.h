@@ -23,12 +23,44 @@ static bool scatter_enabled()
 }
 // keys the chunk store of a task of n k-mers must hold (less than one chunk is wasted per digit)
 static size_t scatter_store_keys(u64 n, int chunk) { return (size_t)(n / chunk + 257) * chunk; }
+// chunks of a store for n records (ChunkStore::cap_chunks: the combining extraction's pair stores have one more, which takes what does not fit)
+static u32 scatter_store_chunks(u64 n, int chunk) { return (u32)(scatter_store_keys(n, chunk) / chunk); }
 
 static void scatter_release(hsk_ctx *c, ScatterBatch &sb)
 {
     c->pool.release(sb.d_cursor); c->pool.release(sb.d_ctl); c->pool.release(sb.d_gbase); c->pool.release(sb.d_ntiles); c->pool.release(sb.d_nout);
     for (int i = 0; i < XCD_BATCH; ++i) { c->pool.release(sb.d_map[i]); c->pool.release(sb.d_tile_src[i]); expand_release(c, sb.x[i]); }
     sb = ScatterBatch();
+}
+
+// The chunk stores of a batch (hsk_chunks.h): the batch-wide arrays, zeroed ...
+static int chunk_store_batch_begin(hsk_ctx *c, ScatterBatch &sb, hipStream_t stream, bool want_nout)
+{
+    DALLOC(c, sb.d_cursor, u64 *, (size_t)XCD_BATCH * 256 * 8);
+    DALLOC(c, sb.d_ctl, u32 *, (size_t)XCD_BATCH * 16);
+    DALLOC(c, sb.d_gbase, u64 *, (size_t)XCD_BATCH * 256 * 8);
+    DALLOC(c, sb.d_ntiles, u32 *, 256);
+    if (want_nout) DALLOC(c, sb.d_nout, u64 *, 256);
+    HIPCHK(c, hipMemsetAsync(sb.d_ntiles, 0, 64, stream));
+    if (want_nout) HIPCHK(c, hipMemsetAsync(sb.d_nout, 0, 64, stream));
+    HIPCHK(c, hipMemsetAsync(sb.d_cursor, 0, (size_t)XCD_BATCH * 256 * 8, stream));
+    HIPCHK(c, hipMemsetAsync(sb.d_ctl, 0, (size_t)XCD_BATCH * 16, stream));
+    return HSK_OK;
+}
+// ... and the store of XCD i's task: at most n records of CHUNK per chunk in keys (and vals), the histogram of the second pass's digit in
+// ghist; fills the ChunkStore and the outputs of chunk_tiles_kernel in sb.args.t[i]
+static int chunk_store_task(hsk_ctx *c, ScatterBatch &sb, int i, u64 n, int CHUNK, u64 *keys, u64 *vals, u64 *ghist, hipStream_t stream)
+{
+    ScatterTask &t = sb.args.t[i];
+    ChunkStore &s = t.cs;
+    s.vmax = (u32)(n / CHUNK + 1);
+    DALLOC(c, sb.d_map[i], u32 *, (size_t)256 * s.vmax * 4);
+    DALLOC(c, sb.d_tile_src[i], u64 *, (size_t)(n / CHUNK + 257) * 8);
+    HIPCHK(c, hipMemsetAsync(sb.d_map[i], 0, (size_t)256 * s.vmax * 4, stream));
+    s.chunks = keys; s.vchunks = vals; s.cursor = sb.d_cursor + (size_t)i * 256; s.map = sb.d_map[i]; s.ctl = sb.d_ctl + (size_t)i * 4; s.ghist = ghist;
+    t.tile_src = sb.d_tile_src[i]; t.gbase = sb.d_gbase + (size_t)i * 256; t.ntiles_out = sb.d_ntiles + i;
+    t.n_out = sb.d_nout ? sb.d_nout + i : nullptr;
+    return HSK_OK;
 }
 
 // jobs[i] is the task XCD i expands (ts->ntiles == 0: none); its keys go to the chunk store jobs[i].keys, the histogram
@@ -51,30 +83,18 @@ static int scatter_expand_batch(hsk_ctx *c, const ExpandJob *jobs, const BatchTa
     }
     if (m == 0) return HSK_OK;
     int rc = expand_prepare_batch(c, m, tsp, lens, x, stream, false, offsets); if (rc) return rc;
-    DALLOC(c, sb.d_cursor, u64 *, (size_t)XCD_BATCH * 256 * 8);
-    DALLOC(c, sb.d_ctl, u32 *, (size_t)XCD_BATCH * 16);
-    DALLOC(c, sb.d_gbase, u64 *, (size_t)XCD_BATCH * 256 * 8);
-    DALLOC(c, sb.d_ntiles, u32 *, 256);
-    HIPCHK(c, hipMemsetAsync(sb.d_ntiles, 0, 64, stream));
-    HIPCHK(c, hipMemsetAsync(sb.d_cursor, 0, (size_t)XCD_BATCH * 256 * 8, stream));
-    HIPCHK(c, hipMemsetAsync(sb.d_ctl, 0, (size_t)XCD_BATCH * 16, stream));
+    rc = chunk_store_batch_begin(c, sb, stream, false); if (rc) return rc;
     u64 ntot = 0;
     for (int i = 0; i < XCD_BATCH; ++i) {
         if (xi[i] < 0) continue;
         const ExpandJob &j = jobs[i];
         ScatterTask &t = a.t[i];
         const u64 n = bt[i].n;
-        t.vmax = (u32)(n / XS_CHUNK + 1);
-        DALLOC(c, sb.d_map[i], u32 *, (size_t)256 * t.vmax * 4);
-        DALLOC(c, sb.d_tile_src[i], u64 *, (size_t)(n / XS_CHUNK + 257) * 8);
-        HIPCHK(c, hipMemsetAsync(sb.d_map[i], 0, (size_t)256 * t.vmax * 4, stream));
+        rc = chunk_store_task(c, sb, i, n, XS_CHUNK, j.keys, j.vals, j.ghist + 256, stream); if (rc) return rc;
         t.segs = x[xi[i]].d_segs; t.nseg = (int)j.ts->segs.size(); t.sm_len = j.sm_len;
         t.src8 = j.src.src8; t.src_bit0 = j.src.bit0; t.src_words = j.src.nwords; t.sm_gpos = j.src.gpos; t.sm_boff = j.src.boff;
         t.tile_off = offsets ? x[xi[i]].d_tile_off : nullptr; t.ntiles = j.ts->ntiles;
-        t.chunks = j.keys; t.cursor = sb.d_cursor + (size_t)i * 256; t.map = sb.d_map[i]; t.ctl = sb.d_ctl + (size_t)i * 4;
-        t.ghist = j.ghist + 256; t.tile_src = sb.d_tile_src[i];
-        t.n = n; t.gbase = sb.d_gbase + (size_t)i * 256; t.ntiles_out = sb.d_ntiles + i;
-        t.sm_pos = j.sm_pos; t.sm_rid = j.sm_rid; t.vchunks = j.vals;
+        t.n = n; t.sm_pos = j.sm_pos; t.sm_rid = j.sm_rid;
         ntot += n;
     }
     a.k = c->cfg.kmer_size; a.shift0 = plan[0].shift; a.shift1 = plan[1].shift; a.chunk = XS_CHUNK; a.err = c->d_err;

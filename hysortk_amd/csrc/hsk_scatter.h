@@ -9,18 +9,7 @@
 // straight into the digit's bin: two record sizes of HBM traffic per k-mer less (the key array written by the expand and
 // read by the first pass is never materialised).
 //
-// The digit histogram of the keys is not known before they exist, so a bin is not a pre-sized range but a LIST OF CHUNKS
-// of CHUNK keys (= one tile of the second pass: 4096 one-word, 2048 two-word keys).  cursor[d] counts the keys reserved
-// for digit d; a flush takes its range [p, p + c) with one atomic add; virtual chunk v = p / CHUNK of digit d lives in
-// physical chunk map[d][v], allocated (bump counter) by the one reservation that contains the chunk's first slot and
-// published through the map; everybody else whose range touches the chunk polls the map entry.  The allocator publishes
-// before it waits for anything, so the wait is bounded by one L2 round trip (and by XS_SPIN_LIMIT: error word,
-// HSK_ERR_INTERNAL).  A task wastes less than one chunk per digit: the chunk store holds n / CHUNK + 257 chunks.
-//
-// One task per XCD (HW_REG_XCC_ID, like onesweep_multi_kernel): cursors, map and chunk counter of a task are only ever
-// touched from one XCD, so their atomics execute in that XCD's L2 (workgroup-scope RMW, L1-bypassing polls), and the
-// short runs that neighbouring reservations of a digit write into the same 128-byte line merge in that L2 before they
-// go to HBM.  The host checks afterwards that the cursors add up to the task's k-mer count.
+// A bin is a list of chunks of CHUNK keys, filled through per-digit cursors and a chunk map: the chunk store and its protocol, hsk_chunks.h.
 //
 // The kernel is a chain of short dependent phases per tile (prologue, roll + rank, digit scan, reservation, permute, run
 // stores) on two 512-thread workgroups per CU.  What keeps the chain short: tiles are claimed two blocks ahead, so the
@@ -34,6 +23,7 @@
 #pragma once
 #include "hsk_expand.h"
 #include "hsk_sort.h"
+#include "hsk_chunks.h"
 
 namespace hsk {
 
@@ -42,8 +32,6 @@ constexpr int XS_WAVES = XS_THREADS / WAVE;
 constexpr int XS_TILE = EXP_TILE;                     // supermers per tile: one per thread (the tile lists are shared with expand_kernel)
 constexpr int XS_MAXSEG = 64;                        // segments (source ranks) whose tiles are looked up in LDS; more: no prefetch
 constexpr int XS_CLAIM = 4;                          // tiles per claim
-constexpr int XS_SPAN = 3;                            // chunks one reservation can touch
-constexpr u32 XS_SPIN_LIMIT = 1u << 22;
 // per key width: k-mers per work item (one-word keys: 16, nearly every supermer is one item; two-word keys: 8, the keys of
 // an item stay in 32 registers either way), keys per chunk (= one tile of the second pass, 32 KB)
 template <int NW> struct XsCfg {
@@ -57,21 +45,16 @@ template <int NW> struct XsCfg {
 static_assert(XS_THREADS == XS_TILE, "one supermer per thread in the tile prologue");
 
 struct ScatterTask {
-    const ExpSeg *segs; int nseg; u32 vmax;          // vmax: map entries per digit (n / CHUNK + 1)
+    const ExpSeg *segs; int nseg;
     const u8 *sm_len; const u64 *src8; u64 src_bit0, src_words;
     const u64 *sm_gpos; const u64 *tile_off; u64 ntiles;
     const u32 *sm_boff;                              // byte-store mode: supermer s starts at byte seg.byte_off + sm_boff[s] of src8
-    u64 *chunks;                                     // chunk store (records of NW words)
-    u64 *cursor;                                     // [256] keys reserved per digit (zeroed)
-    u32 *map;                                        // [256][vmax] physical chunk + 1 (zeroed)
-    u32 *ctl;                                        // [0] tile ticket, [1] chunks handed out (zeroed)
-    u64 *ghist;                                      // [256] histogram of the second pass's digit (zeroed)
+    ChunkStore cs;                                   // the task's output (hsk_chunks.h; ctl[0]: tile ticket)
     u64 *tile_src;                                   // out (chunk_tiles_kernel): second-pass tiles
     u64 n;                                           // k-mers of the task (chunk_tiles_kernel checks the cursors and the histogram against it)
     u64 *gbase;                                      // out (chunk_tiles_kernel): [256] exclusive scan of ghist = digit bases of the second pass
     u32 *ntiles_out;                                 // out (chunk_tiles_kernel): number of second-pass tiles
     const u32 *sm_pos; const int32_t *sm_rid;        // EXTENSION: position in read and read id of every supermer
-    u64 *vchunks;                                    // EXTENSION: payload chunk store (same slots as `chunks`)
     u64 *n_out;                                      // optional out (chunk_tiles_kernel): records in the chunk store (combining extraction: n = ~0, not known before)
 };
 struct ScatterArgs { ScatterTask t[8]; int k, shift0, shift1, chunk; u32 *err; };     // shift0, shift1 >= 32 (the digits are in the top 16 bits)
@@ -143,7 +126,6 @@ __global__ __launch_bounds__(TPB, 4) void expand_scatter_kernel(ScatterArgs a)
     __shared__ u32 s_scr[XS_NWAVE];
     __shared__ u32 s_blk[2];
     __shared__ u64 s_seg[4][XS_MAXSEG];                                 // {first supermer slot, supermers, first tile, first byte} of the task's segments
-    typedef __attribute__((address_space(1))) u32 G32;
     const int tid = threadIdx.x;
     const u32 xcc = __builtin_amdgcn_s_getreg(XCC_ID_GETREG) & 7u;
     const ScatterTask &t = a.t[xcc];
@@ -166,8 +148,8 @@ __global__ __launch_bounds__(TPB, 4) void expand_scatter_kernel(ScatterArgs a)
     // Tiles are claimed in blocks of XS_CLAIM, two blocks ahead: the tile that follows the current one is always known,
     // so its supermer lengths and positions (and then its first windows) are requested while the current tile is worked on.
     if (tid == 0) {
-        s_blk[0] = __hip_atomic_fetch_add(&t.ctl[0], (u32)XS_CLAIM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        s_blk[1] = __hip_atomic_fetch_add(&t.ctl[0], (u32)XS_CLAIM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        s_blk[0] = __hip_atomic_fetch_add(&t.cs.ctl[0], (u32)XS_CLAIM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        s_blk[1] = __hip_atomic_fetch_add(&t.cs.ctl[0], (u32)XS_CLAIM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     xs_barrier();
     u64 blk = s_blk[0], nblk = s_blk[1];
@@ -215,7 +197,7 @@ __global__ __launch_bounds__(TPB, 4) void expand_scatter_kernel(ScatterArgs a)
         if (tile >= t.ntiles) break;                                  // uniform; blocks come in ascending order
         const u64 ntile = (j + 1 == (u32)XS_CLAIM) ? nblk : tile + 1;
         u32 claim = 0;
-        if (j == 0 && tid == 0) claim = __hip_atomic_fetch_add(&t.ctl[0], (u32)XS_CLAIM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (j == 0 && tid == 0) claim = __hip_atomic_fetch_add(&t.cs.ctl[0], (u32)XS_CLAIM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         u64 sg_sup = s0_sup, sg_n = s0_n, sg_t0 = 0, sg_byte = s0_byte;
         if (single) { }
         else if (segs_lds) {
@@ -341,7 +323,7 @@ __global__ __launch_bounds__(TPB, 4) void expand_scatter_kernel(ScatterArgs a)
             u64 p = 0;
             if (tid < 256) {
                 s_start[tid] = st; s_cnt[tid] = 0;
-                if (c) p = __hip_atomic_fetch_add(&t.cursor[tid], (u64)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (c) p = __hip_atomic_fetch_add(&t.cs.cursor[tid], (u64)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
             XS_STAMP(3);                                              // scan + reservation issued
             xs_barrier();
@@ -359,30 +341,7 @@ __global__ __launch_bounds__(TPB, 4) void expand_scatter_kernel(ScatterArgs a)
                 }
             }
             XS_STAMP(4);                                              // sync + permute
-            if (tid < 256 && c) {
-                const u64 v0 = p / XS_CHUNK;
-                const u32 off0 = (u32)(p % XS_CHUNK);
-                const u32 nv = (off0 + c - 1) / XS_CHUNK + 1;          // chunks touched
-                G32 *mp = (G32 *)(t.map + (u64)tid * t.vmax);
-                u32 ph[XS_SPAN] = {0, 0, 0};
-                // the chunks whose first slot is mine are allocated and published before anything is waited for
-#pragma unroll
-                for (int j = 0; j < XS_SPAN; ++j) {
-                    if ((u32)j >= nv || (j == 0 && off0 != 0)) continue;
-                    ph[j] = __hip_atomic_fetch_add(&t.ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + 1;
-                    __hip_atomic_store(mp + v0 + j, ph[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-                if (off0 != 0) {                                      // the chunk my range starts in was opened by another reservation
-                    u32 spins = 0;
-                    while ((ph[0] = __hip_atomic_load(mp + v0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0) {
-                        if (++spins > XS_SPIN_LIMIT) { atomicOr(a.err, 2u); ph[0] = 1; break; }
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                }
-                const u32 split = st + ((u32)XS_CHUNK - off0);         // first slot (in the sorted order of the flush) in the second chunk
-                s_dl[tid] = make_uint4(split, (ph[0] - 1) * (u32)XS_CHUNK + off0 - st, ((ph[1] ? ph[1] : 1u) - 1) * (u32)XS_CHUNK - split,
-                                       ((ph[2] ? ph[2] : 1u) - 1) * (u32)XS_CHUNK - (split + (u32)XS_CHUNK));
-            }
+            if (tid < 256 && c) s_dl[tid] = chunk_resolve<XS_CHUNK, false>(t.cs, (u32)tid, p, c, st, a.err);
             XS_STAMP(5);                                              // reservation returned, chunk resolved
             for (u32 w0 = 0; w0 < tot; w0 += XS_STG) {
                 if (w0) {
@@ -402,14 +361,13 @@ __global__ __launch_bounds__(TPB, 4) void expand_scatter_kernel(ScatterArgs a)
                     for (int x = 0; x < NW; ++x) kw[x] = s_stage[i * NW + x];
                     const u32 d = ((u32)(kw[NW - 1] >> 32) >> sh0) & 255u;
                     const u32 g = w0 + i;
-                    const uint4 dl = s_dl[d];
-                    const u32 o = g + (g < dl.x ? dl.y : (g < dl.x + (u32)XS_CHUNK ? dl.z : dl.w));   // (mod 2^32)
-                    if (NW == 2) *reinterpret_cast<ulonglong2 *>(t.chunks + (u64)o * 2) = make_ulonglong2(kw[0], kw[NW - 1]);
+                    const u32 o = chunk_slot<XS_CHUNK>(s_dl[d], g);
+                    if (NW == 2) *reinterpret_cast<ulonglong2 *>(t.cs.chunks + (u64)o * 2) = make_ulonglong2(kw[0], kw[NW - 1]);
                     else {
 #pragma unroll
-                        for (int x = 0; x < NW; ++x) t.chunks[(u64)o * NW + x] = kw[x];
+                        for (int x = 0; x < NW; ++x) t.cs.chunks[(u64)o * NW + x] = kw[x];
                     }
-                    if (EXT) { const u32 src = s_src[i]; t.vchunks[o] = s_vb[src >> 4] + (u64)(src & 15u); }
+                    if (EXT) { const u32 src = s_src[i]; t.cs.vchunks[o] = s_vb[src >> 4] + (u64)(src & 15u); }
                 }
                 xs_barrier();                                      // the stage is rewritten by the next window / flush
             }
@@ -424,7 +382,7 @@ __global__ __launch_bounds__(TPB, 4) void expand_scatter_kernel(ScatterArgs a)
     }
     if (tid < 256) {
         const u32 cv = s_hist[tid];
-        if (cv) atomicAdd((unsigned long long *)&t.ghist[tid], (unsigned long long)cv);
+        if (cv) atomicAdd((unsigned long long *)&t.cs.ghist[tid], (unsigned long long)cv);
     }
 #ifdef HSK_DIAG
     if (tid == 0) for (int i = 0; i < 15; ++i) atomicAdd(&g_xs_diag[i], xs_acc[i]);
@@ -481,7 +439,6 @@ __global__ __launch_bounds__(XS_THREADS, XS2_WAVES) void expand_scatter2_kernel(
     __shared__ u32 s_blk[2];
     __shared__ u32 s_multi;
     __shared__ u64 s_seg[4][XS_MAXSEG];                                 // {first supermer slot, supermers, first tile, first byte} of the task's segments
-    typedef __attribute__((address_space(1))) u32 G32;
     const int tid = threadIdx.x;
     const u32 xcc = __builtin_amdgcn_s_getreg(XCC_ID_GETREG) & 7u;
     const ScatterTask &t = a.t[xcc];
@@ -498,8 +455,8 @@ __global__ __launch_bounds__(XS_THREADS, XS2_WAVES) void expand_scatter2_kernel(
     if (tid < 256) { s_cnt[tid] = 0; s_hist[tid] = 0; }
     if (tid == 0) {
         s_multi = 0;
-        s_blk[0] = __hip_atomic_fetch_add(&t.ctl[0], (u32)XS_CLAIM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        s_blk[1] = __hip_atomic_fetch_add(&t.ctl[0], (u32)XS_CLAIM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        s_blk[0] = __hip_atomic_fetch_add(&t.cs.ctl[0], (u32)XS_CLAIM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        s_blk[1] = __hip_atomic_fetch_add(&t.cs.ctl[0], (u32)XS_CLAIM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     xs_barrier();
     u64 blk = s_blk[0], nblk = s_blk[1];
@@ -530,7 +487,7 @@ __global__ __launch_bounds__(XS_THREADS, XS2_WAVES) void expand_scatter2_kernel(
         if (tile >= t.ntiles) break;
         const u64 ntile = (j + 1 == (u32)XS_CLAIM) ? nblk : tile + 1;
         u32 claim = 0;
-        if (j == 0 && tid == 0) claim = __hip_atomic_fetch_add(&t.ctl[0], (u32)XS_CLAIM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (j == 0 && tid == 0) claim = __hip_atomic_fetch_add(&t.cs.ctl[0], (u32)XS_CLAIM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         u64 sg_n = s0_n, sg_t0 = 0;
         if (!single) { while (sg_tile + 1 < nseg && s_seg[2][sg_tile + 1] <= tile) ++sg_tile; sg_n = s_seg[1][sg_tile]; sg_t0 = s_seg[2][sg_tile]; }
         const u64 first = (tile - sg_t0) * XS_TILE;
@@ -599,7 +556,7 @@ __global__ __launch_bounds__(XS_THREADS, XS2_WAVES) void expand_scatter2_kernel(
                 u64 p = 0;
                 if (tid < 256) {
                     s_cnt[tid] = st;                                   // from a count to the running cursor of the digit's range in the stage
-                    if (c) p = __hip_atomic_fetch_add(&t.cursor[tid], (u64)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (c) p = __hip_atomic_fetch_add(&t.cs.cursor[tid], (u64)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
                 xs_barrier();
                 // ---- sweep 2: the k-mers again, each straight into its slot ----
@@ -609,36 +566,13 @@ __global__ __launch_bounds__(XS_THREADS, XS2_WAVES) void expand_scatter2_kernel(
                     s_stage[pos] = key;
                     atomicAdd(&s_hist[(hi >> sh1) & 255u], 1u);
                 });
-                if (tid < 256 && c) {
-                    const u64 v0 = p / XS_CHUNK;
-                    const u32 off0 = (u32)(p % XS_CHUNK);
-                    const u32 nv = (off0 + c - 1) / XS_CHUNK + 1;
-                    G32 *mp = (G32 *)(t.map + (u64)tid * t.vmax);
-                    u32 ph[XS_SPAN] = {0, 0, 0};
-#pragma unroll
-                    for (int q = 0; q < XS_SPAN; ++q) {
-                        if ((u32)q >= nv || (q == 0 && off0 != 0)) continue;
-                        ph[q] = __hip_atomic_fetch_add(&t.ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + 1;
-                        __hip_atomic_store(mp + v0 + q, ph[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                    if (off0 != 0) {
-                        u32 spins = 0;
-                        while ((ph[0] = __hip_atomic_load(mp + v0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0) {
-                            if (++spins > XS_SPIN_LIMIT) { atomicOr(a.err, 2u); ph[0] = 1; break; }
-                            __builtin_amdgcn_s_sleep(1);
-                        }
-                    }
-                    const u32 split = st + ((u32)XS_CHUNK - off0);
-                    s_dl[tid] = make_uint4(split, (ph[0] - 1) * (u32)XS_CHUNK + off0 - st, ((ph[1] ? ph[1] : 1u) - 1) * (u32)XS_CHUNK - split,
-                                           ((ph[2] ? ph[2] : 1u) - 1) * (u32)XS_CHUNK - (split + (u32)XS_CHUNK));
-                }
+                if (tid < 256 && c) s_dl[tid] = chunk_resolve<XS_CHUNK, false>(t.cs, (u32)tid, p, c, st, a.err);
                 xs_barrier();                                          // stage and digit table complete
                 for (u32 i = tid; i < tot; i += XS_THREADS) {
                     const u64 kw = s_stage[i];
                     const u32 d = ((u32)(kw >> 32) >> sh0) & 255u;
-                    const uint4 dl = s_dl[d];
-                    const u32 o = i + (i < dl.x ? dl.y : (i < dl.x + (u32)XS_CHUNK ? dl.z : dl.w));   // (mod 2^32)
-                    t.chunks[o] = kw;
+                    const u32 o = chunk_slot<XS_CHUNK>(s_dl[d], i);
+                    t.cs.chunks[o] = kw;
                 }
                 if (tid < 256) s_cnt[tid] = 0;
                 xs_barrier();                                          // the stage is rewritten by the next flush
@@ -650,7 +584,7 @@ __global__ __launch_bounds__(XS_THREADS, XS2_WAVES) void expand_scatter2_kernel(
     }
     if (tid < 256) {
         const u32 cv = s_hist[tid];
-        if (cv) atomicAdd((unsigned long long *)&t.ghist[tid], (unsigned long long)cv);
+        if (cv) atomicAdd((unsigned long long *)&t.cs.ghist[tid], (unsigned long long)cv);
     }
 }
 
@@ -665,20 +599,20 @@ __global__ __launch_bounds__(256) void chunk_tiles_kernel(ScatterArgs a)
     const ScatterTask &t = a.t[blockIdx.x];
     if (t.ntiles == 0) { if (threadIdx.x == 0 && t.ntiles_out) *t.ntiles_out = 0; return; }
     const int d = threadIdx.x;
-    const u64 cnt = t.cursor[d];
+    const u64 cnt = t.cs.cursor[d];
     const u64 CH = (u64)a.chunk;
     const u64 nch = (cnt + CH - 1) / CH;
     u64 tot_ch, placed, hsum;
     u64 off = block_excl_scan_256<u64>(nch, s_scr, &tot_ch);
     (void)block_excl_scan_256<u64>(cnt, s_scr, &placed);
-    const u64 gb = block_excl_scan_256<u64>(t.ghist[d], s_scr, &hsum);
+    const u64 gb = block_excl_scan_256<u64>(t.cs.ghist[d], s_scr, &hsum);
     if (t.gbase) t.gbase[d] = gb;
     if (d == 0) {
         if (t.ntiles_out) *t.ntiles_out = (u32)tot_ch;
         if (t.n_out) *t.n_out = placed;
         if (t.n == ~0ULL ? placed != hsum : (placed != t.n || hsum != t.n)) atomicOr(a.err, 8u);
     }
-    const u32 *mp = t.map + (u64)d * t.vmax;
+    const u32 *mp = t.cs.map + (u64)d * t.cs.vmax;
     constexpr int U = 8;                                          // map entries requested per step (a load per step is a latency per chunk)
     u64 v = 0;
     for (; v + U <= nch; v += U) {

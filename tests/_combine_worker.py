@@ -1,7 +1,7 @@
 """Helper of tests/test_gpu_combine.py (run_spec, called in process; `python _combine_worker.py <json>` prints the same as JSON lines): counts one
 synthetic input on a context with the tuning the test chose and returns one dict per call: digest of the list, entries, and the
 statistics that tell which plan ran.  spec: K, M, L, U, ntasks, genome, read_len, nreads, seed, error_rate, calls (list of
-"device" | "host" | "pinned"), plan."""
+"device" | "host" | "pinned"), plan, keep (the dicts also carry the KmerList as "result")."""
 import hashlib
 import json
 import os
@@ -80,6 +80,8 @@ def run_spec(spec):
                           "combine_launches": int(st["combine_launches"]), "combine_pairs": int(st["combine_pairs"]), "combine_kmers": int(st["combine_kmers"]),
                           "instance_extractions": int(st["hist_launches"]), "fused_tasks": int(st["fused_tasks"]), "redone_tasks": int(st["redone_tasks"]),
                           "dropped_kmers": int(st.get("dropped_kmers", 0)), "parse_fallbacks": int(st["parse_fallbacks"])})
+        if spec.get("keep"):                               # the list itself (host copies: they outlive the context)
+            out[-1]["result"] = r
     if spec.get("dump"):
         np.savez(spec["dump"], kmers=r.kmers, cnt=r.cnt, task_off=r.task_off, packed=packed, off=off, lens=lens)
     if pinned is not None:

@@ -273,17 +273,30 @@ def test_a_minimizer_that_very_many_supermers_share_is_cut_into_work_units(K, U)
     assert len({(x["digest"], x["entries"]) for x in a + b}) == 1 and a[0]["entries"] > 100000
 
 
-@pytest.mark.parametrize("K", [31, 51])
-def test_a_bin_of_very_many_records_is_counted_in_slices(K):
+@pytest.mark.parametrize("K,EXT,extra", [pytest.param(31, 0, "", id="31"), pytest.param(51, 0, "", id="51"),
+                                         pytest.param(31, 0, "xs2=0", id="31-one_sweep"), pytest.param(31, 1, "", id="31-ext")])
+def test_a_bin_of_very_many_records_is_counted_in_slices(K, EXT, extra):
     """The instance path on reads of which 5 % are all-A reads: the all-A 31-mer's 2.4 M records share ONE prefix bin of one task.  The bin is cut
     into slices that many workgroups count into a table in global memory (hsk_agg.h: AggLarge), its own workgroup counts that table: same list
-    as with the slices switched off (agg_large=0) and as the combining extraction."""
-    spec = dict(BASE, K=K, U=65535, L=2, poly_a_pct=5.0, calls=["pinned"], ntasks=8)
-    a = run(spec, {"HSK_COMBINE": "0"})[0]
-    b = run(dict(spec, tuning_extra="agg_large=0"), {"HSK_COMBINE": "0"})[0]
-    c_ = run(spec, {"HSK_COMBINE_MIN_BYTES": "0"})[0]
-    assert a["combine_launches"] == 0 and b["combine_launches"] == 0 and c_["combine_launches"] > 0
-    assert (a["digest"], a["entries"]) == (b["digest"], b["entries"]) == (c_["digest"], c_["entries"]) and a["entries"] > 100000
+    as with the slices switched off (agg_large=0) and as the combining extraction.  All-A reads also put whole flushes of the first scatter pass
+    into one digit -- reservations that span two and three chunks of the chunk store (hsk_chunks.h) -- in every kernel that writes it: the
+    two-sweep kernel, the one-sweep kernel with keys of two words, of one word (xs2=0) and with the EXTENSION payload (every payload compared,
+    tests/ext_compare.py; the combining extraction takes no payloads.  U = 25 there: the scatter pass and the slices see every record whatever U
+    is, and the list keeps the fifth of the k-mers that 30-fold coverage left with at most 25 copies -- 6 M payloads to compare instead of 45 M)."""
+    spec = dict(BASE, K=K, EXT=EXT, U=25 if EXT else 65535, L=2, poly_a_pct=5.0, calls=["pinned"], ntasks=8, keep=bool(EXT))
+    a = run(dict(spec, tuning_extra=extra) if extra else spec, {"HSK_COMBINE": "0"})[0]
+    b = run(dict(spec, tuning_extra=(extra + "," if extra else "") + "agg_large=0"), {"HSK_COMBINE": "0"})[0]
+    assert a["combine_launches"] == 0 and b["combine_launches"] == 0 and a["entries"] > 100000
+    if EXT:
+        import hysortk_amd as H
+        from tests import ext_compare
+        rb = b["result"]
+        want = ext_compare.Want(rb.task_off, rb.kmers, rb.cnt, H.histogram_text(rb.histo), ext_compare.entry_triples(rb.cnt, rb.payload_off, rb.rid, rb.pos), b["total_kmers"])
+        ext_compare.assert_list_equals(a["result"], want, "agg_large=0")
+        return
+    c_ = run(dict(spec, tuning_extra=extra) if extra else spec, {"HSK_COMBINE_MIN_BYTES": "0"})[0]
+    assert c_["combine_launches"] > 0
+    assert (a["digest"], a["entries"]) == (b["digest"], b["entries"]) == (c_["digest"], c_["entries"])
 
 
 @pytest.mark.parametrize("K,EXT,U", [(31, 0, 40), (51, 0, 40), (31, 1, 40), (31, 0, 65535)])
