@@ -45,6 +45,7 @@ class Stats(C.Structure):
         ("bucket_launches", C.c_uint64), ("bucket_items", C.c_uint64), ("bucket_ms", C.c_double),
         ("combine_launches", C.c_uint64), ("combine_kmers", C.c_uint64), ("combine_pairs", C.c_uint64), ("combine_ms", C.c_double),
         ("agg_large_bins", C.c_uint64), ("agg_large_slices", C.c_uint64),
+        ("combine_items", C.c_uint64), ("combine_distinct_items", C.c_uint64),
     ]
 
 

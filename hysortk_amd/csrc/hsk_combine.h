@@ -17,7 +17,8 @@
 //      and then writes the table's {key, count} pairs into the chunk store of the first radix pass exactly as expand_scatter2_kernel
 //      writes keys (cursor / map / chunk protocol of hsk_chunks.h), the counts into the payload chunks; a table that fills up in
 //      the middle of a bucket is written out and started again, so a key may leave a bucket in several partial pairs: nothing
-//      downstream assumes otherwise;
+//      downstream assumes otherwise; equal items of a bucket -- at c-fold coverage most of them -- are counted in an LDS item table first
+//      and rolled once, with their multiplicity as the weight (3a below; tuning combine_dedup);
 //   4. the second radix pass carries the counts as the payload (onesweep_multi_kernel<1, true>), and the finish adds them up instead
 //      of counting records (agg_finish_kernel<cap, true>) over bins of the top 14 key bits: same order, same filter, same list.
 // At 32 instances per k-mer the pass and the finish move 1/26 of the records (a k-mer next to a read end misses some windows); what
@@ -401,7 +402,7 @@ struct CombineTask {
     u32 nb;                    // buckets (0: no task on this XCD)
     ChunkStore cs;             // chunk stores of the keys and of the counts (hsk_chunks.h; ctl[0]: bucket ticket)
 };
-struct CombineArgs { CombineTask t[8]; int k, shift0, bits0, shift1; u32 *err; };      // first-pass digit: bits0 (<= 8) bits at shift0, second-pass digit: 8 bits at shift1 (both >= 32)
+struct CombineArgs { CombineTask t[8]; int k, shift0, bits0, shift1; u32 *err; u64 *stat; };      // first-pass digit: bits0 (<= 8) bits at shift0, second-pass digit: 8 bits at shift1 (both >= 32)
 
 // The table's pairs leave for the chunk store of the first radix pass: digits counted, one reservation per digit (chunk_resolve,
 // hsk_chunks.h), every pair straight to its slot, the table empty again.  kw: the table's key arrays, most significant word last (as
@@ -454,7 +455,68 @@ __device__ __forceinline__ void combine_dump(u64 *const (&kw)[NW], u32 *s_val, u
     xs_barrier();
 }
 
-template <int KT = 0>
+// ---- 3a. equal items are rolled once (combine_kernel<KT, true>) --------------------------------------------------------------------
+// At c-fold coverage a genomic supermer arrives ~c/3 times per strand, all copies in one bucket, and every copy rolls the same k-mers only
+// to add 1 to the same slots.  The deduplicating instance works a unit in two phases:
+//   A  the unit's items, CI_STEP per step, are cut back to their own cnt + K - 1 bases (what lies behind them in the 64-base window belongs to
+//      whatever followed in the read, or to the next read: equal supermers would differ there) and counted in an LDS table of CI_CAP 128-bit
+//      keys {word 1 = bases 32.. + count byte, word 0 = bases 0..31} by agg2_count_keys: claimed on word 1 -- its low byte is the count,
+//      at most 16, so it is never AG_EMPTY --, word 0 published behind it.  All-ones is that protocol's "not published yet": an item that
+//      starts with 32 T's never enters the table.  It, and an item whose probes ran out (a full table), stays with its lane as a DIRECT
+//      item, and the phase ends behind that step;
+//   B  the table's occupied slots are made a dense list (read to registers, block scan, written back: combine_dump's way) and handed out
+//      256 at a time to the first sweep and the probe loop, which add the item's multiplicity instead of 1; the direct items go first, with
+//      multiplicity 1.  A lane clears the entry it takes, so the table is empty again behind the last step.
+// A unit of more distinct items than the table holds takes several A/B rounds: the weights add up to the same counts.
+#ifndef CI_LOG2CAP
+#define CI_LOG2CAP 10
+#endif
+constexpr int CI_CAP = 1 << CI_LOG2CAP;
+constexpr int CI_PER = CI_CAP / CB_THREADS;
+#ifndef CI_IPT_N
+#define CI_IPT_N 4
+#endif
+constexpr int CI_IPT = CI_IPT_N;                     // items a lane takes per step of phase A
+constexpr u32 CI_STEP = CI_IPT * CB_THREADS;
+
+// an item cut back to its own bases: cnt + k - 1 of them (cnt >= 1; at most 60 in all), the count byte kept
+__device__ __forceinline__ ulonglong2 item_own_bases(ulonglong2 itm, u32 cnt, int k)
+{
+    const u32 nb = cnt + (u32)k - 1u;
+    if (nb <= 32u) { itm.x &= ~0ULL << (64u - 2u * nb); itm.y = (u64)cnt; }
+    else itm.y = (itm.y & (~0ULL << (128u - 2u * nb))) | (u64)cnt;
+    return itm;
+}
+__device__ __forceinline__ u32 item_slot(u64 w1, u64 w0)
+{
+    const u64 m = w0 ^ (w1 >> 9) ^ (w1 << 21);
+    return (((u32)(m >> 32) ^ (u32)m) * 0x9E3779B1u) >> (32 - CI_LOG2CAP);
+}
+// The item table as a dense list in its first `return value` slots, the slots behind them empty.  Called by the whole workgroup behind a
+// barrier (all inserts done); the barriers of the scan separate the reads from the writes, the caller's next barrier ends the writes.
+__device__ __forceinline__ u32 items_compact(u64 *s_i1, u64 *s_i0, u32 *s_im, u32 *s_scr)
+{
+    const int tid = threadIdx.x;
+    u64 m1[CI_PER], m0[CI_PER]; u32 mc[CI_PER], c = 0;
+#pragma unroll
+    for (int j = 0; j < CI_PER; ++j) {
+        m1[j] = s_i1[j * CB_THREADS + tid]; m0[j] = s_i0[j * CB_THREADS + tid]; mc[j] = s_im[j * CB_THREADS + tid];
+        c += m1[j] != AG_EMPTY;
+    }
+    u32 tot;
+    u32 o = block_excl_scan_xs<CB_WAVES>(c, s_scr, &tot);
+#pragma unroll
+    for (int j = 0; j < CI_PER; ++j) {
+        const u32 sl = (u32)(j * CB_THREADS + tid);
+        if (m1[j] == AG_EMPTY) continue;
+        if (sl >= tot) { s_i1[sl] = AG_EMPTY; s_i0[sl] = AG_EMPTY; s_im[sl] = 0; }      // (nobody's place in the list: the slot's owner empties it)
+        s_i1[o] = m1[j]; s_i0[o] = m0[j]; s_im[o] = mc[j]; ++o;
+    }
+    return tot;
+}
+
+// CombineArgs::stat (DEDUP only): [0] items read, [1] items rolled (table entries + direct ones) -- added once per workgroup, like ghist
+template <int KT = 0, bool DEDUP = false>
 __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a)
 {
     constexpr int CHUNK = XsCfg<1>::CHUNK;
@@ -486,91 +548,181 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a)
     // (one call site: with combine_dump called from both places below the compiler needs 98 instead of 96 VGPRs -- four workgroups per CU instead of five)
     auto dump = [&]() { combine_dump<1, CB_CAP>(kw, s_val, s_cnt, s_hist, s_dl, s_scr, t.cs, sh0, dm0, sh1, a.err); };
 
-    for (;;) {
-        xs_barrier();                                                 // (table cleared / previous bucket dumped; the ticket word is free)
-        if (tid == 0) s_flag[0] = __hip_atomic_fetch_add(&t.cs.ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        xs_barrier();
-        const u32 b = s_flag[0];
-        if (b >= nunits) break;
-        const uint2 un = t.units[b];
-        const u32 r0 = un.x, r1 = un.y;
-        ulonglong2 nxt = make_ulonglong2(0, 0);
-        if (r0 + (u32)tid < r1) nxt = t.recs[r0 + (u32)tid];
-        for (u32 base = r0; base < r1; base += CB_THREADS) {
-            // ---- this lane's item: a supermer of up to 16 k-mers (the next tile's is asked for before this one is worked on) ----
-            const ulonglong2 itm = nxt;
-            { const u32 s2 = base + CB_THREADS + (u32)tid; nxt = s2 < r1 ? t.recs[s2] : make_ulonglong2(0, 0); }
-            const u64 win0 = itm.x, win1 = itm.y & ~0xFFULL;
-            u32 cnt = (u32)(itm.y & 0xFFULL);
-            if (cnt > 16u) { atomicOr(a.err, 4u); cnt = 0; }
-            // ---- its k-mers into the table.  A key's home is an aligned PAIR of slots.  First sweep: the homes of CB_GROUP k-mers are read
-            //      together (one 16-byte LDS read each, one latency for the group); a k-mer that finds itself there -- at c-fold coverage
-            //      all but one in c, minus the few whose key was pushed past its home -- just adds one.  The others are remembered as a bit
-            //      mask and take the probe loop afterwards, every lane its next one per round: two or three rounds per tile instead of
-            //      one probe loop per k-mer.  A lane whose probes run out keeps its remaining bits, the table is written out behind the
-            //      round's barrier and the lanes go on (every such round starts on an empty table: it ends) ----
-            u32 mm = cnt ? (0xFFFFu >> (16u - cnt)) : 0u;
-            {
-                Mer<1> fw, rc;
-                fw.w[0] = win0 & lastmask;
-                rc = twin<1>(fw, k);
+    // ---- a lane's item -- a supermer of up to 16 k-mers -- into the table, every k-mer `mult` times.  A key's home is an aligned PAIR of slots.
+    //      First sweep: the homes of CB_GROUP k-mers are read
+    //      together (one 16-byte LDS read each, one latency for the group); a k-mer that finds itself there -- at c-fold coverage
+    //      all but one in c, minus the few whose key was pushed past its home -- just adds one.  The others are remembered as a bit
+    //      mask and take the probe loop afterwards, every lane its next one per round: two or three rounds per tile instead of
+    //      one probe loop per k-mer.  A lane whose probes run out keeps its remaining bits, the table is written out behind the
+    //      round's barrier and the lanes go on (every such round starts on an empty table: it ends) ----
+    auto roll = [&](const ulonglong2 itm, const u32 mult) {
+        const u64 win0 = itm.x, win1 = itm.y & ~0xFFULL;
+        u32 cnt = (u32)(itm.y & 0xFFULL);
+        if (cnt > 16u) { atomicOr(a.err, 4u); cnt = 0; }
+        u32 mm = cnt ? (0xFFFFu >> (16u - cnt)) : 0u;
+        {
+            Mer<1> fw, rc;
+            fw.w[0] = win0 & lastmask;
+            rc = twin<1>(fw, k);
 #pragma unroll 1
-                for (int q0 = 0; q0 < 16; q0 += CB_GROUP) {
-                    if (__ballot((u32)q0 < cnt) == 0) break;
-                    u64 key[CB_GROUP]; u32 h[CB_GROUP]; ulonglong2 cur[CB_GROUP];
+            for (int q0 = 0; q0 < 16; q0 += CB_GROUP) {
+                if (__ballot((u32)q0 < cnt) == 0) break;
+                u64 key[CB_GROUP]; u32 h[CB_GROUP]; ulonglong2 cur[CB_GROUP];
 #pragma unroll
-                    for (int q = 0; q < CB_GROUP; ++q) {
-                        const int r = q0 + q;
-                        if (r > 0) {
-                            fw.w[0] = funnel_left(win0, win1, 2 * r) & lastmask;
-                            const u64 nbase = (fw.w[0] >> low) & 3;
-                            rc.w[0] = ((rc.w[0] >> 2) | ((3 - nbase) << 62)) & lastmask;
-                        }
-                        key[q] = rc.w[0] < fw.w[0] ? rc.w[0] : fw.w[0];
-                        h[q] = agg_slot<CB_LOG2CAP>(key[q]) & ~1u;
-                        cur[q] = *reinterpret_cast<const ulonglong2 *>(&s_key[h[q]]);
+                for (int q = 0; q < CB_GROUP; ++q) {
+                    const int r = q0 + q;
+                    if (r > 0) {
+                        fw.w[0] = funnel_left(win0, win1, 2 * r) & lastmask;
+                        const u64 nbase = (fw.w[0] >> low) & 3;
+                        rc.w[0] = ((rc.w[0] >> 2) | ((3 - nbase) << 62)) & lastmask;
                     }
+                    key[q] = rc.w[0] < fw.w[0] ? rc.w[0] : fw.w[0];
+                    h[q] = agg_slot<CB_LOG2CAP>(key[q]) & ~1u;
+                    cur[q] = *reinterpret_cast<const ulonglong2 *>(&s_key[h[q]]);
+                }
 #pragma unroll
-                    for (int q = 0; q < CB_GROUP; ++q) {
-                        const u32 r = (u32)(q0 + q);
-                        if (r < cnt) {
-                            if (cur[q].x == key[q]) { atomicAdd(&s_val[h[q]], 1u); mm &= ~(1u << r); }
-                            else if (cur[q].y == key[q]) { atomicAdd(&s_val[h[q] + 1u], 1u); mm &= ~(1u << r); }
-                        }
+                for (int q = 0; q < CB_GROUP; ++q) {
+                    const u32 r = (u32)(q0 + q);
+                    if (r < cnt) {
+                        if (cur[q].x == key[q]) { atomicAdd(&s_val[h[q]], mult); mm &= ~(1u << r); }
+                        else if (cur[q].y == key[q]) { atomicAdd(&s_val[h[q] + 1u], mult); mm &= ~(1u << r); }
                     }
                 }
-            }
-            for (;;) {
-                bool stuck = false;
-                for (;;) {
-                    const bool mine = mm != 0 && !stuck;
-                    const u64 act = __ballot(mine);
-                    if (act == 0) break;
-                    const u32 r = mine ? (u32)__builtin_ctz(mm) : 0u;
-                    Mer<1> fw, rc;
-                    fw.w[0] = (r ? funnel_left(win0, win1, 2 * (int)r) : win0) & lastmask;
-                    rc = twin<1>(fw, k);
-                    const u64 key = rc.w[0] < fw.w[0] ? rc.w[0] : fw.w[0];
-                    u32 h = agg_slot<CB_LOG2CAP>(key) & ~1u;
-                    const u64 left = agg_count_keys<(u32)CB_CAP - 1u>(act, key_lds, val_lds, h, key, 1u);
-                    if (mine) { if ((left >> lane) & 1ULL) stuck = true; else mm &= mm - 1u; }
-                }
-                // one barrier per round: the round's flag is one of three taken in turn; the next round's is cleared before the barrier (its
-                // last readers read it two rounds ago, i.e. before they arrived at the previous round's barrier)
-                const u32 fl = 1u + round % 3u;
-                if (tid == 0) s_flag[1u + (round + 1u) % 3u] = 0;
-                if (mm) s_flag[fl] = 1;
-                ++round;
-                xs_barrier();
-                if (s_flag[fl] == 0) break;
-                dump();
             }
         }
-        dump();
+        for (;;) {
+            bool stuck = false;
+            for (;;) {
+                const bool mine = mm != 0 && !stuck;
+                const u64 act = __ballot(mine);
+                if (act == 0) break;
+                const u32 r = mine ? (u32)__builtin_ctz(mm) : 0u;
+                Mer<1> fw, rc;
+                fw.w[0] = (r ? funnel_left(win0, win1, 2 * (int)r) : win0) & lastmask;
+                rc = twin<1>(fw, k);
+                const u64 key = rc.w[0] < fw.w[0] ? rc.w[0] : fw.w[0];
+                u32 h = agg_slot<CB_LOG2CAP>(key) & ~1u;
+                const u64 left = agg_count_keys<(u32)CB_CAP - 1u>(act, key_lds, val_lds, h, key, mult);
+                if (mine) { if ((left >> lane) & 1ULL) stuck = true; else mm &= mm - 1u; }
+            }
+            // one barrier per round: the round's flag is one of three taken in turn; the next round's is cleared before the barrier (its
+            // last readers read it two rounds ago, i.e. before they arrived at the previous round's barrier)
+            const u32 fl = 1u + round % 3u;
+            if (tid == 0) s_flag[1u + (round + 1u) % 3u] = 0;
+            if (mm) s_flag[fl] = 1;
+            ++round;
+            xs_barrier();
+            if (s_flag[fl] == 0) break;
+            dump();
+        }
+    };
+
+    u32 n_read = 0, n_rolled = 0;                      // DEDUP: items this workgroup read / rolled (thread 0; direct items: lane 0 of every wave)
+    if constexpr (!DEDUP) {
+        for (;;) {
+            xs_barrier();                                                 // (table cleared / previous bucket dumped; the ticket word is free)
+            if (tid == 0) s_flag[0] = __hip_atomic_fetch_add(&t.cs.ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            xs_barrier();
+            const u32 b = s_flag[0];
+            if (b >= nunits) break;
+            const uint2 un = t.units[b];
+            const u32 r0 = un.x, r1 = un.y;
+            ulonglong2 nxt = make_ulonglong2(0, 0);
+            if (r0 + (u32)tid < r1) nxt = t.recs[r0 + (u32)tid];
+            for (u32 base = r0; base < r1; base += CB_THREADS) {
+                // ---- this lane's item (the next tile's is asked for before this one is worked on) ----
+                const ulonglong2 itm = nxt;
+                { const u32 s2 = base + CB_THREADS + (u32)tid; nxt = s2 < r1 ? t.recs[s2] : make_ulonglong2(0, 0); }
+                roll(itm, 1u);
+            }
+            dump();
+        }
+    } else {
+        __shared__ u64 s_i1[CI_CAP], s_i0[CI_CAP];
+        __shared__ u32 s_im[CI_CAP];
+        const u32 i1_lds = (u32)(uintptr_t)(LdsPtr)s_i1, i0_lds = (u32)(uintptr_t)(LdsPtr)s_i0, im_lds = (u32)(uintptr_t)(LdsPtr)s_im;
+#pragma unroll
+        for (int j = 0; j < CI_PER; ++j) { s_i1[j * CB_THREADS + tid] = AG_EMPTY; s_i0[j * CB_THREADS + tid] = AG_EMPTY; s_im[j * CB_THREADS + tid] = 0; }
+        // A step of phase A is short -- a load, a mask, a hash and one probe loop per item -- and a step of 256 items waited for its load
+        // longer than it worked: a lane takes CI_IPT items per step, their loads issued together, the next step's under this step's inserts.
+        auto load = [&](ulonglong2 (&x)[CI_IPT], u32 at, u32 end) {
+#pragma unroll
+            for (int j = 0; j < CI_IPT; ++j) { const u32 i = at + (u32)(j * CB_THREADS + tid); x[j] = i < end ? t.recs[i] : make_ulonglong2(0, 0); }
+        };
+        for (;;) {
+            xs_barrier();                                                 // (tables cleared / previous bucket dumped; the ticket word is free)
+            if (tid == 0) s_flag[0] = __hip_atomic_fetch_add(&t.cs.ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            xs_barrier();
+            const u32 b = s_flag[0];
+            if (b >= nunits) break;
+            const uint2 un = t.units[b];
+            const u32 r0 = un.x, r1 = un.y;
+            n_read += r1 - r0;
+            for (u32 base = r0; base < r1;) {
+                // ---- A: steps of CI_STEP items into the item table, until the unit ends or a lane has to keep an item ----
+                ulonglong2 cur[CI_IPT], ditm[CI_IPT];                 // ditm: this lane's direct items (count byte 0: none)
+                load(cur, base, r1);                                  // (what a round that ended early had asked for ahead is asked for again: it is the rare one)
+#pragma unroll
+                for (int j = 0; j < CI_IPT; ++j) ditm[j] = make_ulonglong2(0, 0);
+                u32 any_direct = 0;
+                do {
+                    ulonglong2 nx[CI_IPT];
+                    load(nx, base + CI_STEP, r1);
+                    base += CI_STEP;
+                    bool direct = false;
+#pragma unroll
+                    for (int j = 0; j < CI_IPT; ++j) {
+                        ulonglong2 itm = cur[j];
+                        const u32 cnt = (u32)(itm.y & 0xFFULL);
+                        const bool ok = cnt - 1u < 16u;
+                        if (cnt > 16u) atomicOr(a.err, 4u);
+                        if (ok) itm = item_own_bases(itm, cnt, k);
+                        const bool ins = ok && itm.x != AG_EMPTY;
+                        u64 left = __ballot(ins);
+                        if (left) {
+                            u32 h = item_slot(itm.y, itm.x), tmo = 0;
+                            // (a word 0 that never came -- it cannot happen -- sends the lane on to the next slot: the item is counted there or stays direct)
+                            left = agg2_count_keys<(u32)CI_CAP - 1u>(left, i1_lds, i0_lds, im_lds, h, itm.y, itm.x, tmo, 1u);
+                        }
+                        if (ok && (!ins || ((left >> lane) & 1ULL))) { ditm[j] = itm; direct = true; }
+                        cur[j] = nx[j];
+                    }
+                    const u32 fl = 1u + round % 3u;                    // (the rounds' flags, as in roll)
+                    if (tid == 0) s_flag[1u + (round + 1u) % 3u] = 0;
+                    if (direct) s_flag[fl] = 1;
+                    ++round;
+                    xs_barrier();
+                    any_direct = s_flag[fl];
+                } while (base < r1 && !any_direct);
+                // ---- B: the distinct items with their multiplicities; the direct ones first ----
+                const u32 nd = items_compact(s_i1, s_i0, s_im, s_scr);
+                xs_barrier();
+                u32 ndir = 0;
+#pragma unroll
+                for (int j = 0; j < CI_IPT; ++j) ndir += (u32)__popcll(__ballot((ditm[j].y & 0xFFULL) != 0));
+                if (lane == 0) n_rolled += (tid == 0 ? nd : 0u) + ndir;
+                for (u32 i = any_direct ? 0u : (u32)CI_IPT; i < (u32)CI_IPT + (nd + CB_THREADS - 1u) / CB_THREADS; ++i) {
+                    ulonglong2 itm = make_ulonglong2(0, 0); u32 mult = 1u;
+                    if (i < (u32)CI_IPT) {
+#pragma unroll
+                        for (int j = 0; j < CI_IPT; ++j) if (i == (u32)j) itm = ditm[j];
+                    } else {
+                        const u32 e = (i - (u32)CI_IPT) * CB_THREADS + (u32)tid;
+                        if (e < nd) { itm = make_ulonglong2(s_i0[e], s_i1[e]); mult = s_im[e]; s_i1[e] = AG_EMPTY; s_i0[e] = AG_EMPTY; s_im[e] = 0; }
+                    }
+                    roll(itm, mult);
+                }
+            }
+            dump();
+        }
     }
     {
         const u32 cv = s_hist[tid];
         if (cv) atomicAdd((unsigned long long *)&t.cs.ghist[tid], (unsigned long long)cv);
+    }
+    if constexpr (DEDUP) {
+        if (tid == 0 && n_read) atomicAdd((unsigned long long *)&a.stat[0], (unsigned long long)n_read);
+        if (n_rolled) atomicAdd((unsigned long long *)&a.stat[1], (unsigned long long)n_rolled);
     }
 }
 

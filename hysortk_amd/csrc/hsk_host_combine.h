@@ -35,6 +35,13 @@ static u64 combine_ratio()
 {
     return (u64)std::max<long long>(1, tune("combine_ratio", 16));
 }
+// combine_dedup=0: every item's k-mers are rolled (combine_kernel<K, false>); 1: equal items of a unit are rolled once
+static bool combine_dedup()
+{
+    return tune("combine_dedup", 1) != 0;
+}
+// words of ScatterBatch::d_nout / the pinned pair counts behind the tasks' pairs and the error word: items read, items rolled
+constexpr int COMBINE_STAT = XCD_BATCH + 2;
 static u64 combine_bucket_kmers()
 {
     return (u64)std::max<long long>(256, tune("combine_bucket", 12288));
@@ -59,7 +66,7 @@ struct BucketOrder {
     ulonglong2 *recs = nullptr; u32 *off = nullptr, *cur = nullptr, *d_log2nb = nullptr; u64 *d_out_base = nullptr; BucketItem *d_items = nullptr;
     uint2 *units = nullptr; u64 *d_unit_off = nullptr; u32 *d_nunits = nullptr;      // the work units of the combining extraction (bucket_units_kernel)
     u32 stride = 0;
-    std::vector<u32> log2nb; std::vector<u64> out_base, unit_off;
+    std::vector<u32> log2nb; std::vector<u64> out_base, unit_off, nitems;
     bool active = false;
 };
 static void bucket_release(hsk_ctx *c, BucketOrder &bo)
@@ -73,7 +80,7 @@ static void bucket_release(hsk_ctx *c, BucketOrder &bo)
 static int bucket_order_tasks(hsk_ctx *c, u32 ntasks, const std::vector<TaskSegs> &segs, const std::vector<u32> &tasks, const BaseSource &src, u32 vt_shift, BucketOrder &bo)
 {
     bo = BucketOrder();
-    bo.log2nb.assign(ntasks, 0); bo.out_base.assign(ntasks, 0); bo.unit_off.assign(ntasks, 0);
+    bo.log2nb.assign(ntasks, 0); bo.out_base.assign(ntasks, 0); bo.unit_off.assign(ntasks, 0); bo.nitems.assign(ntasks, 0);
     std::vector<BucketItem> items;
     u64 run = 0, urun = 0; u32 maxlg = 0;
     const u64 target = combine_bucket_kmers();
@@ -88,7 +95,7 @@ static int bucket_order_tasks(hsk_ctx *c, u32 ntasks, const std::vector<TaskSegs
         u32 lg = 0;
         while (lg < (u32)CS_MAX_LOG2NB && lg < (u32)CS_MAX_LOCAL + vt_shift && (segs[t].nkmers >> lg) > target) ++lg;
         bo.log2nb[t] = lg; maxlg = std::max(maxlg, lg);
-        bo.out_base[t] = run; run += nsup;
+        bo.out_base[t] = run; run += nsup; bo.nitems[t] = nsup;
         bo.unit_off[t] = urun; urun += (1ULL << lg) + nsup / CB_UNIT + 1;      // (a bucket makes at most one unit more than it has whole slices)
     }
     const bool dev_list = src.bitems != nullptr;             // scan-placed bins: the work list is on the device already (one item per chunk)
@@ -206,10 +213,11 @@ static int combine_batch(hsk_ctx *c, const u32 *tk, const BatchTask *bt, u64 *co
     if (!any) return HSK_OK;
     int rc = chunk_store_batch_begin(c, sb, stream, true); if (rc) return rc;
     sb.h_nout = h_nout;
-    u64 ntot = 0;
+    u64 ntot = 0, nitems = 0;
     for (int i = 0; i < XCD_BATCH; ++i) {
         if (tk[i] == ~0u || !bt[i].n) continue;
         const u32 tid = tk[i];
+        nitems += bo.nitems[tid];
         const u64 n = bt[i].n;                           // k-mers of the task: never fewer than its pairs
         rc = chunk_store_task(c, sb, i, n, CH, bt[i].kB, bt[i].vB, ghist[i] + 256, stream); if (rc) return rc;
         ScatterTask &t = a.t[i];
@@ -222,21 +230,28 @@ static int combine_batch(hsk_ctx *c, const u32 *tk, const BatchTask *bt, u64 *co
     }
     a.k = c->cfg.kmer_size; a.shift0 = plan[0].shift; a.shift1 = plan[1].shift; a.chunk = CH; a.err = c->d_err;
     ca.k = a.k; ca.shift0 = a.shift0; ca.bits0 = plan[0].bits; ca.shift1 = a.shift1; ca.err = c->d_err;
-    static int occ = 0;
+    const bool dedup = NW == 1 && combine_dedup();       // (two-word keys: combine2_kernel has no such instance)
+    ca.stat = sb.d_nout + COMBINE_STAT;
+    if (!dedup) sb.items_host = nitems;
+    static int occ_of[2] = {0, 0};                       // workgroups per CU of the instance that is launched
+    int &occ = occ_of[dedup];
     if (!occ) {
         int nb = 0;
-        const hipError_t e = NW == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, combine_kernel<31>, CB_THREADS, 0) : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, combine2_kernel<51>, CB_THREADS, 0);
+        const hipError_t e = NW == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, combine2_kernel<51>, CB_THREADS, 0)
+                           : dedup ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, combine_kernel<31, true>, CB_THREADS, 0)
+                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, combine_kernel<31, false>, CB_THREADS, 0);
         occ = (e == hipSuccess && nb > 0) ? nb : 2;
     }
     EvPair ep{}; if (profile) { ep.a = ev_get(c); ep.b = ev_get(c); ep.kind = 7; ep.keys = ntot; ep.bytes = 0; (void)hipEventRecord(ep.a, stream); }
     const u32 grid = (u32)occ * 256u;
     if (NW == 2) { if (a.k == 51) hipLaunchKernelGGL((combine2_kernel<51>), dim3(grid), dim3(CB_THREADS), 0, stream, ca); else hipLaunchKernelGGL((combine2_kernel<0>), dim3(grid), dim3(CB_THREADS), 0, stream, ca); }
-    else if (a.k == 31) hipLaunchKernelGGL((combine_kernel<31>), dim3(grid), dim3(CB_THREADS), 0, stream, ca);
-    else hipLaunchKernelGGL((combine_kernel<0>), dim3(grid), dim3(CB_THREADS), 0, stream, ca);
+    else if (dedup) { if (a.k == 31) hipLaunchKernelGGL((combine_kernel<31, true>), dim3(grid), dim3(CB_THREADS), 0, stream, ca); else hipLaunchKernelGGL((combine_kernel<0, true>), dim3(grid), dim3(CB_THREADS), 0, stream, ca); }
+    else if (a.k == 31) hipLaunchKernelGGL((combine_kernel<31, false>), dim3(grid), dim3(CB_THREADS), 0, stream, ca);
+    else hipLaunchKernelGGL((combine_kernel<0, false>), dim3(grid), dim3(CB_THREADS), 0, stream, ca);
     if (profile) { (void)hipEventRecord(ep.b, stream); c->ev_pending.push_back(ep); }
     // the tile lists of the second pass and the pairs of every task (the host sizes the second pass and the finish from them)
     hipLaunchKernelGGL(chunk_tiles_kernel, dim3(XCD_BATCH), dim3(256), 0, stream, sb.args);
-    HIPCHK(c, hipMemcpyAsync(sb.h_nout, sb.d_nout, XCD_BATCH * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(c, hipMemcpyAsync(sb.h_nout, sb.d_nout, (COMBINE_STAT + 2) * 8, hipMemcpyDeviceToHost, stream));      // (with the items read and rolled; the word of the error is zero here)
     HIPCHK(c, hipMemcpyAsync(sb.h_nout + XCD_BATCH, c->d_err, 4, hipMemcpyDeviceToHost, stream));      // (bit 512: the pair stores ran over)
     HIPCHK(c, hipGetLastError());
     sb.active = true; sb.tiles_done = true;

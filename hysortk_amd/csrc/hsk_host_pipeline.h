@@ -449,6 +449,7 @@ static int read_pair_counts(hsk_ctx *c, const RankPlan<NW> &P, BatchSlot &s)
     for (int i = 0; i < XCD_BATCH; ++i) { BatchTask &b = s.bt[i]; if (s.tk[i] == EMPTY_TASK || !b.n) continue; bk += b.n; b.n = h_nout[i]; bp += h_nout[i]; pmax = std::max<u64>(pmax, h_nout[i]); }
     c->combine_prefix = std::max(c->combine_prefix_floor, combine_prefix_for(pmax));      // (the batches and calls after this one)
     c->stats.combine_pairs += bp;
+    c->stats.combine_items += h_nout[COMBINE_STAT] + s.sbatch.items_host; c->stats.combine_distinct_items += h_nout[COMBINE_STAT + 1] + s.sbatch.items_host;
     if (timing_enabled()) fprintf(stderr, "[hsk] combining extraction: %llu pairs for %llu k-mers\n", (unsigned long long)bp, (unsigned long long)bk);
     // More than one pair per sixteen k-mers: this input has too few copies per k-mer for the detour to pay (measured on 10 Gbp, DESIGN.md 3.2d:
     // one pair per 25.6 k-mers 102 against 126 ms, one per 6.6 -- reads with 0.3 % errors -- 171 against 138: the tables overflow inside

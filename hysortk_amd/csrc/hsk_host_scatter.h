@@ -12,6 +12,7 @@ struct ScatterBatch {
     u64 *d_gbase = nullptr;                      // [XCD_BATCH][256] digit bases of the second pass (chunk_tiles_kernel)
     u32 *d_ntiles = nullptr;                     // [XCD_BATCH] tiles of the second pass (chunk_tiles_kernel)
     u64 *d_nout = nullptr; u64 *h_nout = nullptr; // combining extraction: [XCD_BATCH] pairs in every task's chunk store (device word / pinned copy asked for behind chunk_tiles_kernel)
+    u64 items_host = 0;                          // ... items of the batch when combine_kernel does not count them itself (COMBINE_STAT words of d_nout: the deduplicating instance)
     ExpandScratch x[EXP_BATCH];                  // segment lists (and tile offsets) the kernel reads
     bool active = false;
     bool tiles_done = false;                     // chunk_tiles_kernel has run already (combining extraction: the host reads the pair counts before the second pass is sized)
@@ -42,7 +43,7 @@ static int chunk_store_batch_begin(hsk_ctx *c, ScatterBatch &sb, hipStream_t str
     DALLOC(c, sb.d_ntiles, u32 *, 256);
     if (want_nout) DALLOC(c, sb.d_nout, u64 *, 256);
     HIPCHK(c, hipMemsetAsync(sb.d_ntiles, 0, 64, stream));
-    if (want_nout) HIPCHK(c, hipMemsetAsync(sb.d_nout, 0, 64, stream));
+    if (want_nout) HIPCHK(c, hipMemsetAsync(sb.d_nout, 0, 128, stream));
     HIPCHK(c, hipMemsetAsync(sb.d_cursor, 0, (size_t)XCD_BATCH * 256 * 8, stream));
     HIPCHK(c, hipMemsetAsync(sb.d_ctl, 0, (size_t)XCD_BATCH * 16, stream));
     return HSK_OK;

@@ -163,6 +163,10 @@ typedef struct {
     uint64_t agg_large_bins;      /* such bins counted through their slices since the last reset (a bin that turned out to hold too many distinct
                                      k-mers for that and was counted by its own workgroup after all is not among them) */
     uint64_t agg_large_slices;    /* slices of those bins */
+    /* --- appended in ABI 4: equal supermer items of a unit are rolled once (tuning combine_dedup, hsk_combine.h) --- */
+    uint64_t combine_items;           /* supermer items combine_kernel read */
+    uint64_t combine_distinct_items;  /* items whose k-mers it rolled: the distinct items of its item tables and the items that went past them;
+                                         equal to combine_items when combine_dedup=0 and for two-word keys */
 } hsk_stats;
 
 /* ---- lifecycle ------------------------------------------------------------------------- */

@@ -55,8 +55,9 @@ def base(op):
 def main():
     rate_file, out_file = sys.argv[1], sys.argv[2]
     # key[=pattern]: the JSON key bench.py looks up, and what the symbol must contain.  The instances that RUN are <.., BINS=false, DROP=false>: a bare
-    # "scan_kernelILi31ELi17E" finds the scan-placed-items instance first (until the end of round 4 the scan was priced with THAT mix: 3.94 instead of 3.96 cycles)
-    pats = sys.argv[3:] or ["scan_kernelILi31ELi17E=scan_kernelILi31ELi17ELb0ELb0E", "combine_kernelILi31E", "scan_kernelILi51ELi17E=scan_kernelILi51ELi17ELb0ELb0E"]
+    # "scan_kernelILi31ELi17E" finds the scan-placed-items instance first (until the end of round 4 the scan was priced with THAT mix: 3.94 instead of 3.96 cycles);
+    # combine_kernel<31, DEDUP = true> is the one the default combine_dedup=1 launches
+    pats = sys.argv[3:] or ["scan_kernelILi31ELi17E=scan_kernelILi31ELi17ELb0ELb0E", "combine_kernelILi31E=combine_kernelILi31ELb1E", "scan_kernelILi51ELi17E=scan_kernelILi51ELi17ELb0ELb0E"]
     cyc = rates(rate_file)
     asm = "/tmp/hsk_valu_floor.s"
     subprocess.check_call(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-S", "--cuda-device-only", "-o", asm, SRC], stderr=subprocess.DEVNULL)
