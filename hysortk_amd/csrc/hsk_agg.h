@@ -1,7 +1,7 @@
 // hsk_agg.h -- "two passes, then aggregate": the last stage of filter_kmer.
 //
 // Replaces the tail of sort_task + count_sorted_kmers (reference src/kmerops.cpp:1382-1445).  Kernels by key width and
-// payload: agg_finish_kernel (one word; described below), agg2_finish_kernel / agg3_finish_kernel (two / three words),
+// payload: agg_finish_kernel (one word; described below), aggw_finish_kernel<cap, NW> (two and three words),
 // agg_ext_kernel<cap, NW> (EXTENSION: the payloads grouped by key), agg_big_kernel (one word, 8192 slots: the last
 // rung of the ladder, on the listed bins).  The probe loops of the tables are hand-written assembly (agg_count_keys,
 // agg2_count_keys, agg3_count_keys): as loops of the WAVE they cost 6 scalar instructions per probe instead of the ~25 the
@@ -67,7 +67,7 @@ struct AggTask {
 // sequencers, satellites).  Its records all hit one counter of one workgroup's table, and that workgroup reads them alone: 40 M copies of the
 // all-A 31-mer (5 Gbp with 2 % all-A reads) kept it busy for 108 ms while the rest of the GPU had finished the batch in 10.  Such bins are cut
 // into slices of AGL_SLICE records: agg_large_list_kernel finds them (up to AGL_TABLES per task) and lists their slices, a slice kernel
-// (agg_large_slice_kernel, agg2_large_slice_kernel, agg3_large_slice_kernel: keys of one, two, three words) counts every slice in an LDS table
+// (agg_large_slice_kernel<NW>: keys of one, two, three words) counts every slice in an LDS table
 // (a wave whose lanes all hold the same key sends one lane with the sum) and adds the table's few pairs to the bin's table in GLOBAL memory
 // (AGL_TAB slots, atomics); the bin's own workgroup then counts that table's slots instead of the records.  The kernels find a bin's records
 // through bounds[], so the 16 prefix bits may sit anywhere (one word, or split between the two top words: AggArgs::top_bits).
@@ -98,52 +98,78 @@ __device__ __forceinline__ u32 *agl_tcur(const AggLarge &lg) { return lg.tcnt + 
 __device__ __forceinline__ u32 *agl_tgoff(const AggLarge &lg) { return lg.tcnt + (size_t)2 * AGL_TABLES * AGL_TAB; }
 // a bin of n records has been counted through its table (one thread of the bin's workgroup, once the bin is known to fit this rung's table)
 __device__ __forceinline__ void agl_note(u32 *lstat, u64 n) { if (lstat) { atomicAdd(lstat, 1u); atomicAdd(lstat + 1, (u32)((n + AGL_SLICE - 1) / AGL_SLICE)); } }
-// the bin this workgroup works on (false: none) and what to do when it overflows
-__device__ __forceinline__ bool agg_pick_bin(const AggTask &t, u32 nbins, u32 &b)
+// the bin this workgroup works on (false: none) and what to do when it overflows; Task: AggTask or AggExtTask
+template <typename Task>
+__device__ __forceinline__ bool agg_pick_bin(const Task &t, u32 nbins, u32 &b)
 {
     b = blockIdx.x;
     if (t.bin_list) { if (b >= *t.bin_list_n || b >= nbins) return false; b = t.bin_list[b]; }
     return b < nbins;                                   // (a list entry is a bin id: anything else would be a bug upstream, never an address)
 }
-__device__ __forceinline__ void agg_bin_overflow(const AggTask &t, u32 nbins, u32 b, u32 cap)
+// (the plain kernels also report the table that was too small: atomicMax(t.flags + AG_BATCH, cap), a word EXTENSION does not have)
+template <typename Task>
+__device__ __forceinline__ void agg_bin_overflow(const Task &t, u32 nbins, u32 b)
 {
     if (t.ovf_list) { const u32 at = atomicAdd(t.ovf_n, 1u); if (at < nbins) t.ovf_list[at] = b; else atomicOr(t.flags, (u32)AG_FLAG_OVERFLOW); }   // (a bin is listed once per rung: at < nbins)
     else atomicOr(t.flags, (u32)AG_FLAG_OVERFLOW);
-    atomicMax(t.flags + AG_BATCH, cap);
     t.bin_cnt[b] = 0;
 }
 struct AggArgs { AggTask t[AG_BATCH]; u32 lower, upper; u32 nbins; int shift; int nw; int top_bits; int top_sig; u32 *lstat; };   // top_sig: significant bits of the most significant word (multi-word keys)
 //   // lstat (null: not counted): [0] bins that were counted through their slices' table, [1] slices of those bins (hsk_stats::agg_large_bins / agg_large_slices)
 //   // bins = key >> shift, nbins of them (65536 / 48, or 256 / 56)
 // top_bits (multi-word keys): how many of the 16 prefix bits the most significant word holds (0 or 16: all); the rest are the top
-// bits of the word below
-__device__ __forceinline__ u32 agg_bin_of(const AggArgs &a, const u64 *rec)
+// bits of the word below.  Args: AggArgs or AggExtArgs; rec: a record of nw words
+template <typename Args>
+__device__ __forceinline__ u32 agg_bin_of(const Args &a, const u64 *rec, int nw)
 {
     if (a.top_bits > 0 && a.top_bits < 16)
-        return ((u32)(rec[a.nw - 1] >> (64 - a.top_bits)) << (16 - a.top_bits)) | (u32)(rec[a.nw - 2] >> (48 + a.top_bits));
-    return (u32)(rec[a.nw - 1] >> a.shift);
+        return ((u32)(rec[nw - 1] >> (64 - a.top_bits)) << (16 - a.top_bits)) | (u32)(rec[nw - 2] >> (48 + a.top_bits));
+    return (u32)(rec[nw - 1] >> a.shift);
 }
 
 // bounds[b] = index of the first key whose top bits are >= b (b = 0 .. AG_BINS); one thread per bound
-__global__ __launch_bounds__(AG_THREADS) void bin_bounds_kernel(AggArgs a)
+template <typename Args>
+__global__ __launch_bounds__(AG_THREADS) void bin_bounds_kernel(Args a)
 {
-    const AggTask &t = a.t[blockIdx.y];
+    const auto &t = a.t[blockIdx.y];
     const u32 b = blockIdx.x * AG_THREADS + threadIdx.x;
     if (!t.active || b > a.nbins) return;
+    const int nw = a.nw ? a.nw : 1;                     // (EXTENSION leaves 0 for one word)
     u64 lo = 0, hi = t.n;                               // first index in [0, n] with (key >> shift) >= b
     if (b == a.nbins) lo = t.n;
     else while (lo < hi) {
         const u64 mid = lo + ((hi - lo) >> 1);
-        if (agg_bin_of(a, t.keys + mid * a.nw) < b) lo = mid + 1; else hi = mid;    // (the prefix sits in the most significant word, or continues in the one below)
+        if (agg_bin_of(a, t.keys + mid * nw, nw) < b) lo = mid + 1; else hi = mid;    // (the prefix sits in the most significant word, or continues in the one below)
     }
     t.bounds[b] = lo;
 }
 
-template <int LOG2CAP>
-__device__ __forceinline__ u32 agg_slot(u64 k)
+// The hash of a key of NW words: the words folded into one (rotations keep the bits of every word apart), the halves folded, multiplied.
+// The top LOG2 bits are the slot (agg_key_slot).
+template <int NW>
+__device__ __forceinline__ u32 agg_key_hash(const u64 (&k)[NW])
 {
-    const u32 x = (u32)(k >> 32) ^ (u32)k;
-    return (x * 0x9E3779B1u) >> (32 - LOG2CAP);
+    static_assert(NW >= 1 && NW <= 3, "keys of one to three words");
+    u64 m = k[0];
+    if constexpr (NW == 2) m ^= (k[1] >> 9) ^ (k[1] << 21);
+    if constexpr (NW == 3) m ^= (k[1] >> 7) ^ (k[1] << 23) ^ (k[2] >> 9) ^ (k[2] << 21);
+    return ((u32)(m >> 32) ^ (u32)m) * 0x9E3779B1u;
+}
+template <int LOG2, int NW> __device__ __forceinline__ u32 agg_key_slot(const u64 (&k)[NW]) { return agg_key_hash<NW>(k) >> (32 - LOG2); }
+template <int LOG2CAP> __device__ __forceinline__ u32 agg_slot(u64 k) { const u64 kk[1] = {k}; return agg_key_slot<LOG2CAP, 1>(kk); }
+
+// Do all lanes of `act` hold lane 0's key?  (Lane 0 must be one of them: the active lanes of a record loop are a prefix of the wave.)
+// A wave that does sends ONE lane with the sum: same-address LDS atomics are taken one lane after the other.
+template <int NW>
+__device__ __forceinline__ bool agg_wave_one_key(const u64 (&k)[NW], u64 act)
+{
+    bool same = true;
+#pragma unroll
+    for (int w = NW - 1; w >= 0; --w) {
+        const u64 f = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(k[w] >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)k[w]);
+        same = same && k[w] == f;
+    }
+    return __ballot(same) == act;
 }
 
 // Counts one key per lane of `act` (a lane mask) in the LDS table: the probe sequence of section 1 of agg_finish_kernel as a
@@ -334,68 +360,6 @@ __global__ __launch_bounds__(AG_THREADS) void agg_large_list_kernel(AggArgs a)
     lg.bin_tab[b] = ti + 1u;
 }
 
-// persistent workgroups, one slice per ticket: the slice's records into an LDS table, the table's pairs into the bin's global table
-__global__ __launch_bounds__(AG_THREADS) void agg_large_slice_kernel(AggArgs a)
-{
-    constexpr int LOG2CAP = AG_LOG2CAP_MEDIUM, CAP = 1 << LOG2CAP, PER = CAP / AG_THREADS, UNR = 16;
-    __shared__ u64 s_key[CAP];
-    __shared__ u32 s_cnt[CAP];
-    __shared__ u32 s_ctl[2];
-    const AggTask &t = a.t[blockIdx.y];
-    if (!t.active || !t.lg) return;
-    const AggLarge &lg = *t.lg;
-    const u32 nunits = lg.ctl[1];
-    if (nunits == 0) return;
-    const int tid = threadIdx.x;
-    typedef __attribute__((address_space(3))) void *LdsPtr;
-    const u32 key_lds = (u32)(uintptr_t)(LdsPtr)s_key, cnt_lds = (u32)(uintptr_t)(LdsPtr)s_cnt;
-    for (;;) {
-        __syncthreads();
-        if (tid == 0) { s_ctl[0] = atomicAdd(&lg.ctl[2], 1u); s_ctl[1] = 0; }
-#pragma unroll
-        for (int j = 0; j < PER; ++j) { s_key[j * AG_THREADS + tid] = AG_EMPTY; s_cnt[j * AG_THREADS + tid] = 0; }
-        __syncthreads();
-        const u32 u = s_ctl[0];
-        if (u >= nunits) break;
-        const unsigned long long un = lg.units[u];
-        const u32 b = (u32)(un >> 32), ti = lg.bin_tab[b] - 1u;
-        const u64 s = t.bounds[b] + (u64)(u32)un * AGL_SLICE, be = t.bounds[b + 1], e = s + AGL_SLICE < be ? s + AGL_SLICE : be;
-        for (u64 i = s + tid; i < e; i += (u64)AG_THREADS * UNR) {
-            u64 k[UNR];
-#pragma unroll
-            for (int x = 0; x < UNR; ++x) { const u64 idx = i + (u64)x * AG_THREADS; k[x] = idx < e ? t.keys[idx] : AG_EMPTY; }
-#pragma unroll
-            for (int x = 0; x < UNR; ++x) {
-                u64 act = __ballot(k[x] != AG_EMPTY);
-                if (act == 0) continue;                   // (uniform; the active lanes are a prefix of the wave: lane 0 is one of them)
-                u32 h = agg_slot<LOG2CAP>(k[x]), inc = 1u;
-                const u64 k0 = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(k[x] >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)k[x]);
-                if (__ballot(k[x] == k0) == act) { inc = (u32)__popcll(act); act = 1ULL; }
-                if (agg_count_keys<(u32)CAP - 1u>(act, key_lds, cnt_lds, h, k[x], inc) != 0) s_ctl[1] = 1;      // (uniform)
-            }
-            if (__hip_atomic_load(&s_ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
-        }
-        __syncthreads();
-        if (s_ctl[1]) { if (tid == 0) lg.tbad[ti] = 1u; continue; }      // (more distinct keys than a slice's table takes: not this kind of bin)
-        unsigned long long *gk = lg.tkeys + (u64)ti * AGL_TAB; u32 *gc = lg.tcnt + (u64)ti * AGL_TAB;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const u64 kq = s_key[j * AG_THREADS + tid];
-            if (kq == AG_EMPTY) continue;
-            const u32 cq = s_cnt[j * AG_THREADS + tid];
-            u32 h = agg_slot<AGL_LOG2TAB>(kq);
-            bool placed = false;
-            for (int pr = 1; pr <= AGL_MAX_PROBE && !placed; ++pr) {
-                unsigned long long prev = gk[h];
-                if (prev == AG_EMPTY) prev = atomicCAS(&gk[h], (unsigned long long)AG_EMPTY, (unsigned long long)kq);
-                if (prev == AG_EMPTY || prev == kq) { atomicAdd(&gc[h], cq); placed = true; }
-                else h = (h + (u32)pr) & (AGL_TAB - 1u);
-            }
-            if (!placed) lg.tbad[ti] = 1u;
-        }
-    }
-}
-
 // W: the records are {key, count} pairs (AggTask::vals) and a key's counter grows by the pair's count
 template <int LOG2CAP, bool W = false>
 __global__ __launch_bounds__(AG_THREADS) void agg_finish_kernel(AggArgs a)
@@ -456,8 +420,8 @@ __global__ __launch_bounds__(AG_THREADS) void agg_finish_kernel(AggArgs a)
             u32 h = agg_slot<LOG2CAP>(k[u]);
             u32 inc = W ? wv[u] : 1u;
             if (large && act != 0) {                      // (uniform; the active lanes are a prefix of the wave: lane 0 is one of them)
-                const u64 k0 = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(k[u] >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)k[u]);
-                if (__ballot(k[u] == k0) == act) { inc = W ? wave_sum_u32(k[u] != AG_EMPTY ? wv[u] : 0u) : (u32)__popcll(act); act = 1ULL; }
+                const u64 kk[1] = {k[u]};
+                if (agg_wave_one_key<1>(kk, act)) { inc = W ? wave_sum_u32(k[u] != AG_EMPTY ? wv[u] : 0u) : (u32)__popcll(act); act = 1ULL; }
             }
             if (act != 0 && agg_count_keys<(u32)CAP - 1u>(act, key_lds, cnt_lds, h, k[u], inc) != 0) s_ovf = 1;      // (uniform)
         }
@@ -468,7 +432,7 @@ __global__ __launch_bounds__(AG_THREADS) void agg_finish_kernel(AggArgs a)
     __syncthreads();
     AG_STAMP(2);                                        // records loaded and counted
     if (s_ovf) {
-        if (tid == 0) agg_bin_overflow(t, a.nbins, b, (u32)CAP);
+        if (tid == 0) { agg_bin_overflow(t, a.nbins, b); atomicMax(t.flags + AG_BATCH, (u32)CAP); }
         return;
     }
     if (ltab && tid == 0) agl_note(a.lstat, e - s);
@@ -638,201 +602,6 @@ __device__ __forceinline__ u64 agg2_count_keys(u64 act, u32 k1_base, u32 k0_base
     return act;
 }
 
-__device__ __forceinline__ bool key2_less(u64 a1, u64 a0, u64 b1, u64 b0) { return a1 < b1 || (a1 == b1 && a0 < b0); }
-
-// the same for two-word keys: the slice's table is filled by agg2_count_keys; in the bin's global table a slot is claimed on word 1 and word 0
-// published behind it, a workgroup that finds its word 1 waits for the word 0 (the claimer stores it right after its claim)
-__global__ __launch_bounds__(AG_THREADS) void agg2_large_slice_kernel(AggArgs a)
-{
-    constexpr int LOG2CAP = AG_LOG2CAP_SMALL, CAP = 1 << LOG2CAP, PER = CAP / AG_THREADS, UNR = 8;
-    __shared__ u64 s_k1[CAP];
-    __shared__ u64 s_k0[CAP];
-    __shared__ u32 s_cnt[CAP];
-    __shared__ u32 s_ctl[2];
-    const AggTask &t = a.t[blockIdx.y];
-    if (!t.active || !t.lg) return;
-    const AggLarge &lg = *t.lg;
-    const u32 nunits = lg.ctl[1];
-    if (nunits == 0) return;
-    const int tid = threadIdx.x;
-    typedef __attribute__((address_space(3))) void *LdsPtr;
-    const u32 k1_lds = (u32)(uintptr_t)(LdsPtr)s_k1, k0_lds = (u32)(uintptr_t)(LdsPtr)s_k0, cnt_lds = (u32)(uintptr_t)(LdsPtr)s_cnt;
-    const ulonglong2 *recs = reinterpret_cast<const ulonglong2 *>(t.keys);       // {word 0, word 1}
-    for (;;) {
-        __syncthreads();
-        if (tid == 0) { s_ctl[0] = atomicAdd(&lg.ctl[2], 1u); s_ctl[1] = 0; }
-#pragma unroll
-        for (int j = 0; j < PER; ++j) { s_k1[j * AG_THREADS + tid] = AG_EMPTY; s_k0[j * AG_THREADS + tid] = AG_EMPTY; s_cnt[j * AG_THREADS + tid] = 0; }
-        __syncthreads();
-        const u32 u = s_ctl[0];
-        if (u >= nunits) break;
-        const unsigned long long un = lg.units[u];
-        const u32 b = (u32)(un >> 32), ti = lg.bin_tab[b] - 1u;
-        const u64 s = t.bounds[b] + (u64)(u32)un * AGL_SLICE, be = t.bounds[b + 1], e = s + AGL_SLICE < be ? s + AGL_SLICE : be;
-        for (u64 i = s + tid; i < e; i += (u64)AG_THREADS * UNR) {
-            ulonglong2 k[UNR];
-#pragma unroll
-            for (int x = 0; x < UNR; ++x) { const u64 idx = i + (u64)x * AG_THREADS; k[x] = idx < e ? recs[idx] : make_ulonglong2(AG_EMPTY, AG_EMPTY); }
-#pragma unroll
-            for (int x = 0; x < UNR; ++x) {
-                const u64 w0 = k[x].x, w1 = k[x].y;
-                u64 act = __ballot(w1 != AG_EMPTY);
-                if (act == 0) continue;                   // (uniform)
-                const u64 m = w0 ^ (w1 >> 9) ^ (w1 << 21);
-                u32 tmo = 0, h = (((u32)(m >> 32) ^ (u32)m) * 0x9E3779B1u) >> (32 - LOG2CAP), inc = 1u;
-                const u64 f1 = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(w1 >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)w1);
-                const u64 f0 = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(w0 >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)w0);
-                if (__ballot(w1 == f1 && w0 == f0) == act) { inc = (u32)__popcll(act); act = 1ULL; }
-                if (agg2_count_keys<(u32)CAP - 1u>(act, k1_lds, k0_lds, cnt_lds, h, w1, w0, tmo, inc) != 0 || tmo) s_ctl[1] = 1;      // (uniform)
-            }
-            if (__hip_atomic_load(&s_ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
-        }
-        __syncthreads();
-        if (s_ctl[1]) { if (tid == 0) lg.tbad[ti] = 1u; continue; }
-        unsigned long long *g1 = lg.tkeys + (u64)ti * AGL_TAB, *g0 = lg.tkeys0 + (u64)ti * AGL_TAB; u32 *gc = lg.tcnt + (u64)ti * AGL_TAB;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const u64 q1 = s_k1[j * AG_THREADS + tid], q0 = s_k0[j * AG_THREADS + tid];
-            if (q1 == AG_EMPTY) continue;
-            const u32 cq = s_cnt[j * AG_THREADS + tid];
-            const u64 m = q0 ^ (q1 >> 9) ^ (q1 << 21);
-            u32 h = (((u32)(m >> 32) ^ (u32)m) * 0x9E3779B1u) >> (32 - AGL_LOG2TAB);
-            bool placed = false;
-            for (int pr = 1; pr <= AGL_MAX_PROBE && !placed; ++pr) {
-                unsigned long long prev = __hip_atomic_load(&g1[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (prev == AG_EMPTY) {
-                    prev = atomicCAS(&g1[h], (unsigned long long)AG_EMPTY, (unsigned long long)q1);
-                    if (prev == AG_EMPTY) { __hip_atomic_store(&g0[h], (unsigned long long)q0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); atomicAdd(&gc[h], cq); placed = true; break; }
-                }
-                if (prev == q1) {
-                    unsigned long long v0 = AG_EMPTY; u32 spins = 0;
-                    while ((v0 = __hip_atomic_load(&g0[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == AG_EMPTY && ++spins < (1u << 20)) __builtin_amdgcn_s_sleep(1);
-                    if (v0 == q0) { atomicAdd(&gc[h], cq); placed = true; break; }
-                    if (v0 == AG_EMPTY) break;            // (a word 0 that never came: cannot happen; the bin is counted the old way)
-                }
-                h = (h + (u32)pr) & (AGL_TAB - 1u);
-            }
-            if (!placed) lg.tbad[ti] = 1u;
-        }
-    }
-}
-
-template <int LOG2CAP, bool W = false>      // W: the records are {k-mer, count} pairs (AggTask::vals), the table adds the counts up (combining extraction, two-word keys)
-__global__ __launch_bounds__(AG_THREADS) void agg2_finish_kernel(AggArgs a)
-{
-    constexpr int CAP = 1 << LOG2CAP;
-    constexpr int PER = CAP / AG_THREADS;
-    __shared__ u64 s_k1[CAP];
-    __shared__ u64 s_k0[CAP];
-    __shared__ u32 s_cnt[CAP];
-    __shared__ u32 s_bkt[CAP / 2];  // buckets of the counting sort that orders many distinct keys
-    __shared__ u32 s_scr[8];
-    __shared__ u32 s_ovf;
-    const AggTask &t = a.t[blockIdx.y];
-    if (!t.active) return;
-    u32 b;
-    if (!agg_pick_bin(t, a.nbins, b)) return;
-    const int tid = threadIdx.x;
-    const u64 s = t.bounds[b], e = t.bounds[b + 1];
-    if (e == s) { if (tid == 0) t.bin_cnt[b] = 0; return; }
-#pragma unroll
-    for (int j = 0; j < PER; ++j) { s_k1[j * AG_THREADS + tid] = AG_EMPTY; s_k0[j * AG_THREADS + tid] = AG_EMPTY; s_cnt[j * AG_THREADS + tid] = 0; }
-    if (tid == 0) s_ovf = 0;
-    __syncthreads();
-
-    constexpr int UNR = 8;
-    typedef __attribute__((address_space(3))) void *LdsPtr;
-    const u32 k1_lds = (u32)(uintptr_t)(LdsPtr)s_k1, k0_lds = (u32)(uintptr_t)(LdsPtr)s_k0, cnt_lds = (u32)(uintptr_t)(LdsPtr)s_cnt;
-    const bool large = e - s >= AG_LARGE_BIN;
-    const ulonglong2 *recs = reinterpret_cast<const ulonglong2 *>(t.keys);       // {word 0, word 1}
-    u32 ltab = 0;                                       // 1 + the global table the bin's slices were counted into (agg2_large_slice_kernel)
-    if (!W && large && t.lg) { ltab = t.lg->bin_tab[b]; if (ltab && t.lg->tbad[ltab - 1]) ltab = 0; }
-    if (ltab) {
-        const unsigned long long *g1 = t.lg->tkeys + (u64)(ltab - 1) * AGL_TAB, *g0 = t.lg->tkeys0 + (u64)(ltab - 1) * AGL_TAB; const u32 *gc = t.lg->tcnt + (u64)(ltab - 1) * AGL_TAB;
-        for (u32 q = tid; q < AGL_TAB; q += AG_THREADS) {
-            const u64 w1 = g1[q], w0 = g0[q];
-            const u64 act = __ballot(w1 != AG_EMPTY);
-            if (act == 0) continue;                       // (uniform)
-            const u64 m = w0 ^ (w1 >> 9) ^ (w1 << 21);
-            u32 tmo = 0, h = (((u32)(m >> 32) ^ (u32)m) * 0x9E3779B1u) >> (32 - LOG2CAP);
-            if (agg2_count_keys<(u32)CAP - 1u>(act, k1_lds, k0_lds, cnt_lds, h, w1, w0, tmo, gc[q]) != 0 || tmo) s_ovf = 1;      // (uniform)
-        }
-    } else
-    for (u64 i = s + tid; i < e; i += (u64)AG_THREADS * UNR) {
-        ulonglong2 k[UNR]; u32 wt[UNR];
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) { const u64 idx = i + (u64)u * AG_THREADS; k[u] = idx < e ? recs[idx] : make_ulonglong2(AG_EMPTY, AG_EMPTY); wt[u] = (W && idx < e) ? (u32)t.vals[idx] : 1u; }
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-            const u64 w0 = k[u].x, w1 = k[u].y;
-            u64 act = __ballot(w1 != AG_EMPTY);
-            if (act == 0) continue;                       // (uniform)
-            const u64 m = w0 ^ (w1 >> 9) ^ (w1 << 21);
-            const u32 x = (u32)(m >> 32) ^ (u32)m;
-            u32 tmo = 0, h = (x * 0x9E3779B1u) >> (32 - LOG2CAP), inc = wt[u];
-            if (large) {                                  // (uniform; one k-mer in all lanes of the wave: one lane with the sum, as in agg_finish_kernel)
-                const u64 f1 = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(w1 >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)w1);
-                const u64 f0 = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(w0 >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)w0);
-                if (__ballot(w1 == f1 && w0 == f0) == act) { inc = wave_sum_u32(w1 != AG_EMPTY ? wt[u] : 0u); act = 1ULL; }
-            }
-            if (agg2_count_keys<(u32)CAP - 1u>(act, k1_lds, k0_lds, cnt_lds, h, w1, w0, tmo, inc) != 0 || tmo) s_ovf = 1;      // (uniform)
-        }
-        if (__hip_atomic_load(&s_ovf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
-    }
-    __syncthreads();
-    if (s_ovf) {
-        if (tid == 0) agg_bin_overflow(t, a.nbins, b, (u32)CAP);
-        return;
-    }
-    if (ltab && tid == 0) agl_note(a.lstat, e - s);
-
-    // ---- compact, order by (word 1, word 0) ----------------------------------------------------------------------
-    u32 D;
-    {
-        u64 m1[PER], m0[PER]; u32 mc[PER];
-        u32 occ = 0;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) { m1[j] = s_k1[tid * PER + j]; m0[j] = s_k0[tid * PER + j]; mc[j] = s_cnt[tid * PER + j]; occ += m1[j] != AG_EMPTY; }
-        u32 o = block_excl_scan_256<u32>(occ, s_scr, &D);
-#pragma unroll
-        for (int j = 0; j < PER; ++j) if (m1[j] != AG_EMPTY) { s_k1[o] = m1[j]; s_k0[o] = m0[j]; s_cnt[o] = mc[j]; ++o; }
-    }
-    __syncthreads();
-    if (D <= (u32)AG_THREADS) {
-        u64 k1 = 0, k0 = 0; u32 c = 0, r = 0;
-        if ((u32)tid < D) {
-            k1 = s_k1[tid]; k0 = s_k0[tid]; c = s_cnt[tid];
-            for (u32 j = 0; j < D; ++j) r += key2_less(s_k1[j], s_k0[j], k1, k0);
-        }
-        __syncthreads();
-        if ((u32)tid < D) { s_k1[r] = k1; s_k0[r] = k0; s_cnt[r] = c; }
-        __syncthreads();
-    } else {
-        u64 *const kw[2] = {s_k0, s_k1};
-        agg_order_many<LOG2CAP, 2, false>(D, kw, s_cnt, nullptr, s_bkt, s_scr, a.top_sig);
-    }
-
-    // ---- filter, entries {word 0, word 1, count} in key order to the bin's slots -----------------------------------
-    u32 kept = 0;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const u32 i = tid * PER + j;
-        if (i < D) { const u32 c = s_cnt[i]; kept += (c >= a.lower && c <= a.upper); }
-    }
-    u32 tot;
-    const u32 w = block_excl_scan_256<u32>(kept, s_scr, &tot);
-    u64 *dst = t.scratch + ((s >> t.slot_shift) + w) * 3;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const u32 i = tid * PER + j;
-        if (i < D) {
-            const u32 c = s_cnt[i];
-            if (c >= a.lower && c <= a.upper) { dst[0] = s_k0[i]; dst[1] = s_k1[i]; dst[2] = (u64)c; dst += 3; }
-        }
-    }
-    if (tid == 0) t.bin_cnt[b] = tot;
-}
-
 // ------------------------------------------------------------------------------------------------------------
 // Three-word keys (64 < K <= 95): the same plan as for two
 // words -- a slot is claimed with a compare-and-swap on the most significant word, then words 1 and 0 are stored --, but
@@ -921,22 +690,129 @@ __device__ __forceinline__ u64 agg3_count_keys(u64 act, u32 k2_base, u32 k1_base
     return act;
 }
 
-__device__ __forceinline__ bool key3_less(u64 a2, u64 a1, u64 a0, u64 b2, u64 b1, u64 b0)
+// ------------------------------------------------------------------------------------------------------------
+// Keys of NW words: one probe-loop dispatcher, one slice kernel (NW = 1 .. 3), one finish kernel (NW = 2, 3).  Tables keep word w of
+// slot i at [w * CAP + i] (the most significant word, which claims the slot, last), as agg_ext_kernel does.
+// ------------------------------------------------------------------------------------------------------------
+// The probe loop for keys of NW words over a table whose word w sits at tk_lds + w * CAP * 8 (CAP = MASK + 1); tmo as timed_out (one word: untouched)
+template <u32 MASK, int NW>
+__device__ __forceinline__ u64 aggw_count_keys(u64 act, u32 tk_lds, u32 cnt_lds, u32 &h, const u64 (&k)[NW], u32 &tmo, u32 inc = 1u)
 {
-    return a2 < b2 || (a2 == b2 && (a1 < b1 || (a1 == b1 && a0 < b0)));
+    constexpr u32 WORD = (MASK + 1u) * 8u;
+    if constexpr (NW == 1) return agg_count_keys<MASK>(act, tk_lds, cnt_lds, h, k[0], inc);
+    else if constexpr (NW == 2) return agg2_count_keys<MASK>(act, tk_lds + WORD, tk_lds, cnt_lds, h, k[1], k[0], tmo, inc);
+    else return agg3_count_keys<MASK>(act, tk_lds + 2u * WORD, tk_lds + WORD, tk_lds, cnt_lds, h, k[2], k[1], k[0], tmo, inc);
 }
 
-// the slice kernel for three-word keys (AggLarge): the slice's table is filled by agg3_count_keys.  In the bin's global table a slot is claimed on
-// word 2; the claimer stores words 1 and 0 and then adds its count, which publishes them (release; the count is the flag as in the LDS table: every
-// value of word 0 and word 1 occurs).  A workgroup that finds its word 2 in a slot whose count is still 0 comes back to the slot on its next step --
-// no lane ever spins while the claimer, perhaps a lane of its own wave, has its stores still ahead of it --, AGL_WAIT steps at the most: then the
-// bin is marked (tbad) and counted the old way.
-__global__ __launch_bounds__(AG_THREADS) void agg3_large_slice_kernel(AggArgs a)
+// x < y as little-endian NW-word integers; the ranking loops run it once per pair of keys.  Compares joined by and / or stay on the mask
+// registers (two words: 13 instructions per pair in the loop; with "the first word that differs decides" the compiler selects, 18, and the
+// weighted finish of the K=51 benchmark shape took 16.2 ms instead of 14.1).  The loops around it are unrolled AGG_RANK_UNROLL times: eight pairs
+// at once as the compiler does by itself, but not for three words, where they need more mask registers than there are (8 - 16 SGPRs spilled;
+// two words without unrolling: 20.9 ms).
+template <int NW> constexpr int AGG_RANK_UNROLL = NW == 3 ? 1 : 8;
+template <int NW> __device__ __forceinline__ bool keyw_less(const u64 (&x)[NW], const u64 (&y)[NW])
 {
-    constexpr int LOG2CAP = AG_LOG2CAP_SMALL, CAP = 1 << LOG2CAP, PER = CAP / AG_THREADS, UNR = 4;
-    __shared__ u64 s_k2[CAP];
-    __shared__ u64 s_k1[CAP];
-    __shared__ u64 s_k0[CAP];
+    bool lt = x[0] < y[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) lt = x[w] < y[w] || (x[w] == y[w] && lt);
+    return lt;
+}
+
+// record idx of NW words (ok: it exists; otherwise the key no k-mer has: top word AG_EMPTY).  Two words: one 16-byte load
+template <int NW>
+__device__ __forceinline__ void aggw_load_rec(const u64 *keys, u64 idx, bool ok, u64 (&k)[NW])
+{
+    if constexpr (NW == 2) {
+        const ulonglong2 r = ok ? reinterpret_cast<const ulonglong2 *>(keys)[idx] : make_ulonglong2(AG_EMPTY, AG_EMPTY);     // {word 0, word 1}
+        k[0] = r.x; k[1] = r.y;
+    } else {
+#pragma unroll
+        for (int w = 0; w < NW; ++w) k[w] = ok ? keys[idx * NW + w] : (w == NW - 1 ? AG_EMPTY : 0);
+    }
+}
+// the key in slot `at` of the bins' global tables (AggLarge)
+template <int NW>
+__device__ __forceinline__ void agl_load_key(const AggLarge &lg, size_t at, u64 (&k)[NW])
+{
+    k[NW - 1] = lg.tkeys[at];
+    if constexpr (NW >= 2) k[0] = lg.tkeys0[at];
+    if constexpr (NW == 3) k[1] = lg.tkeys1[at];
+}
+
+// One {key, count} pair of a slice into table ti of the bins' global tables; false: not placed (the table is full of other keys, or words that
+// never came -- cannot happen --: the caller marks the bin and it is counted the old way).  Other workgroups merge into the same table at the same
+// time, and there is no compare-and-swap wider than 64 bits, so the publication protocol depends on the key width:
+//   one word     the slot is claimed with a CAS on the key, then the count is added.
+//   two words    the slot is claimed on word 1 and word 0 published behind it (~0 is no valid word 0, see agg2_count_keys; the host fills tkeys0
+//                with it); a workgroup that finds its word 1 waits for the word 0: the claimer stores it right after its claim.
+//   three words  the slot is claimed on word 2; the claimer stores words 1 and 0 and then adds its count, which publishes them (release; the
+//                count is the flag as in the LDS table, agg3_count_keys: every value of word 0 and word 1 occurs).  A workgroup that finds
+//                its word 2 in a slot whose count is still 0 comes back to the slot on its next step -- no lane ever spins while the claimer,
+//                perhaps a lane of its own wave, has its stores still ahead of it --, AGL_WAIT steps at the most.
+template <int NW>
+__device__ __forceinline__ bool agl_merge(const AggLarge &lg, u32 ti, const u64 (&k)[NW], u32 cq)
+{
+    const size_t tb = (size_t)ti * AGL_TAB;
+    unsigned long long *gk = lg.tkeys + tb; u32 *gc = lg.tcnt + tb;
+    const unsigned long long top = k[NW - 1];
+    u32 h = agg_key_slot<AGL_LOG2TAB, NW>(k);
+    if constexpr (NW == 1) {
+        bool placed = false;                              // (not `return true` from the loop: the compiler then unrolls it four times, half as many instructions again and 7 more VGPRs)
+        for (int pr = 1; pr <= AGL_MAX_PROBE && !placed; ++pr) {
+            unsigned long long prev = gk[h];
+            if (prev == AG_EMPTY) prev = atomicCAS(&gk[h], (unsigned long long)AG_EMPTY, top);
+            if (prev == AG_EMPTY || prev == top) { atomicAdd(&gc[h], cq); placed = true; }
+            else h = (h + (u32)pr) & (AGL_TAB - 1u);
+        }
+        return placed;
+    } else if constexpr (NW == 2) {
+        unsigned long long *g0 = lg.tkeys0 + tb;
+        for (int pr = 1; pr <= AGL_MAX_PROBE; ++pr) {
+            unsigned long long prev = __hip_atomic_load(&gk[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (prev == AG_EMPTY) {
+                prev = atomicCAS(&gk[h], (unsigned long long)AG_EMPTY, top);
+                if (prev == AG_EMPTY) { __hip_atomic_store(&g0[h], (unsigned long long)k[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); atomicAdd(&gc[h], cq); return true; }
+            }
+            if (prev == top) {
+                unsigned long long v0 = AG_EMPTY; u32 spins = 0;
+                while ((v0 = __hip_atomic_load(&g0[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == AG_EMPTY && ++spins < (1u << 20)) __builtin_amdgcn_s_sleep(1);
+                if (v0 == k[0]) { atomicAdd(&gc[h], cq); return true; }
+                if (v0 == AG_EMPTY) return false;         // (a word 0 that never came)
+            }
+            h = (h + (u32)pr) & (AGL_TAB - 1u);
+        }
+    } else {
+        unsigned long long *g1 = lg.tkeys1 + tb, *g0 = lg.tkeys0 + tb;
+        u32 pr = 1, waited = 0;
+        while (pr <= (u32)AGL_MAX_PROBE && waited < AGL_WAIT) {      // one step per turn: claim, or look at a claimed slot, or move on
+            unsigned long long prev = __hip_atomic_load(&gk[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (prev == AG_EMPTY) {
+                prev = atomicCAS(&gk[h], (unsigned long long)AG_EMPTY, top);
+                if (prev == AG_EMPTY) {
+                    __hip_atomic_store(&g1[h], (unsigned long long)k[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(&g0[h], (unsigned long long)k[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_fetch_add(&gc[h], cq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                    return true;
+                }
+            }
+            if (prev == top) {
+                if (__hip_atomic_load(&gc[h], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0) { ++waited; __builtin_amdgcn_s_sleep(1); continue; }     // not published yet: this slot again
+                const unsigned long long v1 = __hip_atomic_load(&g1[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), v0 = __hip_atomic_load(&g0[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (v1 == k[1] && v0 == k[0]) { atomicAdd(&gc[h], cq); return true; }
+            }
+            h = (h + pr) & (AGL_TAB - 1u); ++pr;
+        }
+    }
+    return false;
+}
+
+// The slice kernel (AggLarge).  Persistent workgroups, one slice per ticket: the slice's records into an LDS table (2048 slots for one-word keys,
+// 1024 beyond), the table's pairs into the bin's global table (agl_merge).
+template <int NW>
+__global__ __launch_bounds__(AG_THREADS) void agg_large_slice_kernel(AggArgs a)
+{
+    constexpr int LOG2CAP = NW == 1 ? AG_LOG2CAP_MEDIUM : AG_LOG2CAP_SMALL, CAP = 1 << LOG2CAP, PER = CAP / AG_THREADS, UNR = NW == 1 ? 16 : NW == 2 ? 8 : 4;
+    __shared__ u64 s_k[NW * CAP];
     __shared__ u32 s_cnt[CAP];
     __shared__ u32 s_ctl[2];
     const AggTask &t = a.t[blockIdx.y];
@@ -946,12 +822,16 @@ __global__ __launch_bounds__(AG_THREADS) void agg3_large_slice_kernel(AggArgs a)
     if (nunits == 0) return;
     const int tid = threadIdx.x;
     typedef __attribute__((address_space(3))) void *LdsPtr;
-    const u32 k2_lds = (u32)(uintptr_t)(LdsPtr)s_k2, k1_lds = (u32)(uintptr_t)(LdsPtr)s_k1, k0_lds = (u32)(uintptr_t)(LdsPtr)s_k0, cnt_lds = (u32)(uintptr_t)(LdsPtr)s_cnt;
+    const u32 tk_lds = (u32)(uintptr_t)(LdsPtr)s_k, cnt_lds = (u32)(uintptr_t)(LdsPtr)s_cnt;
     for (;;) {
         __syncthreads();
         if (tid == 0) { s_ctl[0] = atomicAdd(&lg.ctl[2], 1u); s_ctl[1] = 0; }
 #pragma unroll
-        for (int j = 0; j < PER; ++j) { s_k2[j * AG_THREADS + tid] = AG_EMPTY; s_cnt[j * AG_THREADS + tid] = 0; }
+        for (int j = 0; j < PER; ++j) {
+            const int sl = j * AG_THREADS + tid;
+            s_k[(NW - 1) * CAP + sl] = AG_EMPTY; s_cnt[sl] = 0;
+            if (NW == 2) s_k[sl] = AG_EMPTY;              // (two words: word 0 doubles as the publication flag, agg2_count_keys)
+        }
         __syncthreads();
         const u32 u = s_ctl[0];
         if (u >= nunits) break;
@@ -959,75 +839,47 @@ __global__ __launch_bounds__(AG_THREADS) void agg3_large_slice_kernel(AggArgs a)
         const u32 b = (u32)(un >> 32), ti = lg.bin_tab[b] - 1u;
         const u64 s = t.bounds[b] + (u64)(u32)un * AGL_SLICE, be = t.bounds[b + 1], e = s + AGL_SLICE < be ? s + AGL_SLICE : be;
         for (u64 i = s + tid; i < e; i += (u64)AG_THREADS * UNR) {
-            u64 k0[UNR], k1[UNR], k2[UNR];
+            u64 k[UNR][NW];
+#pragma unroll
+            for (int x = 0; x < UNR; ++x) { const u64 idx = i + (u64)x * AG_THREADS; aggw_load_rec<NW>(t.keys, idx, idx < e, k[x]); }
 #pragma unroll
             for (int x = 0; x < UNR; ++x) {
-                const u64 idx = i + (u64)x * AG_THREADS;
-                const bool ok = idx < e;
-                k0[x] = ok ? t.keys[idx * 3] : 0; k1[x] = ok ? t.keys[idx * 3 + 1] : 0; k2[x] = ok ? t.keys[idx * 3 + 2] : AG_EMPTY;
-            }
-#pragma unroll
-            for (int x = 0; x < UNR; ++x) {
-                const u64 w0 = k0[x], w1 = k1[x], w2 = k2[x];
-                u64 act = __ballot(w2 != AG_EMPTY);
+                u64 act = __ballot(k[x][NW - 1] != AG_EMPTY);
                 if (act == 0) continue;                   // (uniform; the active lanes are a prefix of the wave: lane 0 is one of them)
-                const u64 m = w0 ^ (w1 >> 7) ^ (w1 << 23) ^ (w2 >> 9) ^ (w2 << 21);
-                u32 tmo = 0, h = (((u32)(m >> 32) ^ (u32)m) * 0x9E3779B1u) >> (32 - LOG2CAP), inc = 1u;
-                const u64 f2 = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(w2 >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)w2);
-                const u64 f1 = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(w1 >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)w1);
-                const u64 f0 = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(w0 >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)w0);
-                if (__ballot(w2 == f2 && w1 == f1 && w0 == f0) == act) { inc = (u32)__popcll(act); act = 1ULL; }
-                if (agg3_count_keys<(u32)CAP - 1u>(act, k2_lds, k1_lds, k0_lds, cnt_lds, h, w2, w1, w0, tmo, inc) != 0 || tmo) s_ctl[1] = 1;      // (uniform)
+                u32 tmo = 0, h = agg_key_slot<LOG2CAP, NW>(k[x]), inc = 1u;
+                if (agg_wave_one_key<NW>(k[x], act)) { inc = (u32)__popcll(act); act = 1ULL; }
+                if (aggw_count_keys<(u32)CAP - 1u, NW>(act, tk_lds, cnt_lds, h, k[x], tmo, inc) != 0 || tmo) s_ctl[1] = 1;      // (uniform)
             }
             if (__hip_atomic_load(&s_ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
         }
         __syncthreads();
         if (s_ctl[1]) { if (tid == 0) lg.tbad[ti] = 1u; continue; }      // (more distinct keys than a slice's table takes: not this kind of bin)
-        const size_t tb = (size_t)ti * AGL_TAB;
-        unsigned long long *g2 = lg.tkeys + tb, *g1 = lg.tkeys1 + tb, *g0 = lg.tkeys0 + tb; u32 *gc = lg.tcnt + tb;
 #pragma unroll
         for (int j = 0; j < PER; ++j) {
-            const u64 q2 = s_k2[j * AG_THREADS + tid];
-            if (q2 == AG_EMPTY) continue;
-            const u64 q1 = s_k1[j * AG_THREADS + tid], q0 = s_k0[j * AG_THREADS + tid];
-            const u32 cq = s_cnt[j * AG_THREADS + tid];
-            const u64 m = q0 ^ (q1 >> 7) ^ (q1 << 23) ^ (q2 >> 9) ^ (q2 << 21);
-            u32 h = (((u32)(m >> 32) ^ (u32)m) * 0x9E3779B1u) >> (32 - AGL_LOG2TAB);
-            bool placed = false;
-            u32 pr = 1, waited = 0;
-            while (pr <= (u32)AGL_MAX_PROBE && waited < AGL_WAIT) {      // one step per turn: claim, or look at a claimed slot, or move on
-                unsigned long long prev = __hip_atomic_load(&g2[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (prev == AG_EMPTY) {
-                    prev = atomicCAS(&g2[h], (unsigned long long)AG_EMPTY, (unsigned long long)q2);
-                    if (prev == AG_EMPTY) {
-                        __hip_atomic_store(&g1[h], (unsigned long long)q1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_store(&g0[h], (unsigned long long)q0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        __hip_atomic_fetch_add(&gc[h], cq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                        placed = true; break;
-                    }
-                }
-                if (prev == q2) {
-                    if (__hip_atomic_load(&gc[h], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0) { ++waited; __builtin_amdgcn_s_sleep(1); continue; }     // not published yet: this slot again
-                    const unsigned long long v1 = __hip_atomic_load(&g1[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), v0 = __hip_atomic_load(&g0[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (v1 == q1 && v0 == q0) { atomicAdd(&gc[h], cq); placed = true; break; }
-                }
-                h = (h + pr) & (AGL_TAB - 1u); ++pr;
-            }
-            if (!placed) lg.tbad[ti] = 1u;                // (the table is full of other keys, or words that never came -- cannot happen --: the bin is counted the old way)
+            const int sl = j * AG_THREADS + tid;
+            if (s_k[(NW - 1) * CAP + sl] == AG_EMPTY) continue;
+            u64 kq[NW];
+#pragma unroll
+            for (int w = 0; w < NW; ++w) kq[w] = s_k[w * CAP + sl];
+            if (!agl_merge<NW>(lg, ti, kq, s_cnt[sl])) lg.tbad[ti] = 1u;
         }
     }
 }
 
-template <int LOG2CAP>
-__global__ __launch_bounds__(AG_THREADS) void agg3_finish_kernel(AggArgs a)
+// The finish for keys of two and three words: the plan of agg_finish_kernel (count the bin's records in the LDS table, compact, order, filter,
+// write), entries {word 0 .. word NW-1, count}.  W: the records are {k-mer, count} pairs (AggTask::vals), the table adds the counts up
+// (combining extraction: two-word keys only).
+template <int LOG2CAP, int NW, bool W = false>
+__global__ __launch_bounds__(AG_THREADS) void aggw_finish_kernel(AggArgs a)
 {
-    constexpr int CAP = 1 << LOG2CAP;
-    constexpr int PER = CAP / AG_THREADS;
-    __shared__ u64 s_k2[CAP];
-    __shared__ u64 s_k1[CAP];
-    __shared__ u64 s_k0[CAP];
+    static_assert(NW == 2 || NW == 3, "keys of two and three words (one word: agg_finish_kernel)");
+    static_assert(!(NW == 3 && W), "there is no weighted finish for three-word keys");
+    constexpr int CAP = 1 << LOG2CAP, PER = CAP / AG_THREADS;
+    constexpr int UNR = NW == 2 ? 8 : 4;                // record loads per lane in flight
+    constexpr bool CLEAR_WORD0 = NW == 2;               // two words: word 0 doubles as the publication flag (agg2_count_keys); three: the count does
+    __shared__ u64 s_k[NW * CAP];                       // word w of slot i: s_k[w * CAP + i]
     __shared__ u32 s_cnt[CAP];
-    __shared__ u32 s_bkt[CAP / 2];
+    __shared__ u32 s_bkt[CAP / 2];                      // buckets of the counting sort that orders many distinct keys
     __shared__ u32 s_scr[8];
     __shared__ u32 s_ovf;
     const AggTask &t = a.t[blockIdx.y];
@@ -1038,85 +890,115 @@ __global__ __launch_bounds__(AG_THREADS) void agg3_finish_kernel(AggArgs a)
     const u64 s = t.bounds[b], e = t.bounds[b + 1];
     if (e == s) { if (tid == 0) t.bin_cnt[b] = 0; return; }
 #pragma unroll
-    for (int j = 0; j < PER; ++j) { s_k2[j * AG_THREADS + tid] = AG_EMPTY; s_cnt[j * AG_THREADS + tid] = 0; }
+    for (int j = 0; j < PER; ++j) {
+        const int sl = j * AG_THREADS + tid;
+        s_k[(NW - 1) * CAP + sl] = AG_EMPTY; s_cnt[sl] = 0;
+        if (CLEAR_WORD0) s_k[sl] = AG_EMPTY;
+    }
     if (tid == 0) s_ovf = 0;
     __syncthreads();
 
-    constexpr int UNR = 4;
+    // ---- count the records of the bin in the table -------------------------------------------------------------------
     typedef __attribute__((address_space(3))) void *LdsPtr;
-    const u32 k2_lds = (u32)(uintptr_t)(LdsPtr)s_k2, k1_lds = (u32)(uintptr_t)(LdsPtr)s_k1, k0_lds = (u32)(uintptr_t)(LdsPtr)s_k0, cnt_lds = (u32)(uintptr_t)(LdsPtr)s_cnt;
-    u32 ltab = 0;                                       // 1 + the global table the bin's slices were counted into (agg3_large_slice_kernel)
-    if (e - s >= AG_LARGE_BIN && t.lg) { ltab = t.lg->bin_tab[b]; if (ltab && t.lg->tbad[ltab - 1]) ltab = 0; }
+    const u32 tk_lds = (u32)(uintptr_t)(LdsPtr)s_k, cnt_lds = (u32)(uintptr_t)(LdsPtr)s_cnt;
+    const bool large = e - s >= AG_LARGE_BIN;
+    u32 ltab = 0;                                       // 1 + the global table the bin's slices were counted into (agg_large_slice_kernel)
+    if (!W && large && t.lg) { ltab = t.lg->bin_tab[b]; if (ltab && t.lg->tbad[ltab - 1]) ltab = 0; }
     if (ltab) {
         const size_t tb = (size_t)(ltab - 1) * AGL_TAB;
-        const unsigned long long *g2 = t.lg->tkeys + tb, *g1 = t.lg->tkeys1 + tb, *g0 = t.lg->tkeys0 + tb; const u32 *gc = t.lg->tcnt + tb;
+        const u32 *gc = t.lg->tcnt + tb;
         for (u32 q = tid; q < AGL_TAB; q += AG_THREADS) {
-            const u64 w2 = g2[q], w1 = g1[q], w0 = g0[q];
-            const u64 act = __ballot(w2 != AG_EMPTY);
+            u64 k[NW];
+            agl_load_key<NW>(*t.lg, tb + q, k);
+            const u64 act = __ballot(k[NW - 1] != AG_EMPTY);
             if (act == 0) continue;                       // (uniform)
-            const u64 m = w0 ^ (w1 >> 7) ^ (w1 << 23) ^ (w2 >> 9) ^ (w2 << 21);
-            u32 tmo = 0, h = (((u32)(m >> 32) ^ (u32)m) * 0x9E3779B1u) >> (32 - LOG2CAP);
-            if (agg3_count_keys<(u32)CAP - 1u>(act, k2_lds, k1_lds, k0_lds, cnt_lds, h, w2, w1, w0, tmo, gc[q]) != 0 || tmo) s_ovf = 1;      // (uniform)
+            u32 tmo = 0, h = agg_key_slot<LOG2CAP, NW>(k);
+            if (aggw_count_keys<(u32)CAP - 1u, NW>(act, tk_lds, cnt_lds, h, k, tmo, gc[q]) != 0 || tmo) s_ovf = 1;      // (uniform)
         }
     } else
     for (u64 i = s + tid; i < e; i += (u64)AG_THREADS * UNR) {
-        u64 k0[UNR], k1[UNR], k2[UNR];
+        u64 k[UNR][NW]; u32 wt[UNR];
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
             const u64 idx = i + (u64)u * AG_THREADS;
-            const bool ok = idx < e;
-            k0[u] = ok ? t.keys[idx * 3] : 0; k1[u] = ok ? t.keys[idx * 3 + 1] : 0; k2[u] = ok ? t.keys[idx * 3 + 2] : AG_EMPTY;
+            aggw_load_rec<NW>(t.keys, idx, idx < e, k[u]);
+            wt[u] = (W && idx < e) ? (u32)t.vals[idx] : 1u;
         }
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
-            const u64 w0 = k0[u], w1 = k1[u], w2 = k2[u];
-            const u64 act = __ballot(w2 != AG_EMPTY);
-            if (act == 0) continue;                       // (uniform)
-            const u64 m = w0 ^ (w1 >> 7) ^ (w1 << 23) ^ (w2 >> 9) ^ (w2 << 21);
-            const u32 x = (u32)(m >> 32) ^ (u32)m;
-            u32 tmo = 0, h = (x * 0x9E3779B1u) >> (32 - LOG2CAP);
-            if (agg3_count_keys<(u32)CAP - 1u>(act, k2_lds, k1_lds, k0_lds, cnt_lds, h, w2, w1, w0, tmo) != 0 || tmo) s_ovf = 1;      // (uniform)
+            u64 act = __ballot(k[u][NW - 1] != AG_EMPTY);
+            if (act == 0) continue;                       // (uniform; the active lanes are a prefix of the wave: lane 0 is one of them)
+            u32 tmo = 0, h = agg_key_slot<LOG2CAP, NW>(k[u]), inc = wt[u];
+            if (large && agg_wave_one_key<NW>(k[u], act)) {   // (uniform; one k-mer in all lanes of the wave: one lane with the sum, as in agg_finish_kernel)
+                inc = W ? wave_sum_u32(k[u][NW - 1] != AG_EMPTY ? wt[u] : 0u) : (u32)__popcll(act); act = 1ULL;
+            }
+            if (aggw_count_keys<(u32)CAP - 1u, NW>(act, tk_lds, cnt_lds, h, k[u], tmo, inc) != 0 || tmo) s_ovf = 1;      // (uniform)
         }
         if (__hip_atomic_load(&s_ovf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
     }
     __syncthreads();
     if (s_ovf) {
-        if (tid == 0) agg_bin_overflow(t, a.nbins, b, (u32)CAP);
+        if (tid == 0) { agg_bin_overflow(t, a.nbins, b); atomicMax(t.flags + AG_BATCH, (u32)CAP); }
         return;
     }
     if (ltab && tid == 0) agl_note(a.lstat, e - s);
 
-    // ---- compact, order by (word 2, word 1, word 0) ------------------------------------------------------------------
+    // ---- compact, order by (word NW-1, .., word 0) -------------------------------------------------------------------
     u32 D;
     {
-        u64 m2[PER], m1[PER], m0[PER]; u32 mc[PER];
+        u64 mk[PER][NW]; u32 mc[PER];
         u32 occ = 0;
 #pragma unroll
         for (int j = 0; j < PER; ++j) {
             const int sl = tid * PER + j;
-            m2[j] = s_k2[sl]; m1[j] = s_k1[sl]; m0[j] = s_k0[sl]; mc[j] = s_cnt[sl]; occ += m2[j] != AG_EMPTY;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) mk[j][w] = s_k[w * CAP + sl];
+            mc[j] = s_cnt[sl]; occ += mk[j][NW - 1] != AG_EMPTY;
         }
         u32 o = block_excl_scan_256<u32>(occ, s_scr, &D);
 #pragma unroll
-        for (int j = 0; j < PER; ++j) if (m2[j] != AG_EMPTY) { s_k2[o] = m2[j]; s_k1[o] = m1[j]; s_k0[o] = m0[j]; s_cnt[o] = mc[j]; ++o; }
+        for (int j = 0; j < PER; ++j)
+            if (mk[j][NW - 1] != AG_EMPTY) {
+#pragma unroll
+                for (int w = 0; w < NW; ++w) s_k[w * CAP + o] = mk[j][w];
+                s_cnt[o] = mc[j]; ++o;
+            }
     }
     __syncthreads();
-    D = (u32)__builtin_amdgcn_readfirstlane((int)D);
+    D = (u32)__builtin_amdgcn_readfirstlane((int)D);        // (the same in every lane: loops and branches on it are the wave's, scalar)
     if (D <= (u32)AG_THREADS) {
-        u64 k2 = 0, k1 = 0, k0 = 0; u32 c = 0, r = 0;
+        // rank by counting: keys are distinct, so ranks are a permutation; the key of slot j is a broadcast read
+        u64 k[NW]; u32 c = 0, r = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) k[w] = 0;
         if ((u32)tid < D) {
-            k2 = s_k2[tid]; k1 = s_k1[tid]; k0 = s_k0[tid]; c = s_cnt[tid];
-            for (u32 j = 0; j < D; ++j) r += key3_less(s_k2[j], s_k1[j], s_k0[j], k2, k1, k0);
+#pragma unroll
+            for (int w = 0; w < NW; ++w) k[w] = s_k[w * CAP + tid];
+            c = s_cnt[tid];
+#pragma unroll AGG_RANK_UNROLL<NW>
+            for (u32 j = 0; j < D; ++j) {
+                u64 o[NW];
+#pragma unroll
+                for (int w = 0; w < NW; ++w) o[w] = s_k[w * CAP + j];
+                r += keyw_less<NW>(o, k);
+            }
         }
         __syncthreads();
-        if ((u32)tid < D) { s_k2[r] = k2; s_k1[r] = k1; s_k0[r] = k0; s_cnt[r] = c; }
+        if ((u32)tid < D) {
+#pragma unroll
+            for (int w = 0; w < NW; ++w) s_k[w * CAP + r] = k[w];
+            s_cnt[r] = c;
+        }
         __syncthreads();
     } else {
-        u64 *const kw[3] = {s_k0, s_k1, s_k2};
-        agg_order_many<LOG2CAP, 3, false>(D, kw, s_cnt, nullptr, s_bkt, s_scr, a.top_sig);
+        u64 *kw[NW];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) kw[w] = s_k + (size_t)w * CAP;
+        u64 *const (&kwc)[NW] = reinterpret_cast<u64 *const (&)[NW]>(kw);
+        agg_order_many<LOG2CAP, NW, false>(D, kwc, s_cnt, nullptr, s_bkt, s_scr, a.top_sig);
     }
 
-    // ---- filter, entries {word 0, word 1, word 2, count} in key order to the bin's slots -----------------------------
+    // ---- filter, entries {word 0 .. word NW-1, count} in key order to the bin's slots (the layout agg_compact_kernel reads) --------------
     u32 kept = 0;
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
@@ -1124,14 +1006,18 @@ __global__ __launch_bounds__(AG_THREADS) void agg3_finish_kernel(AggArgs a)
         if (i < D) { const u32 c = s_cnt[i]; kept += (c >= a.lower && c <= a.upper); }
     }
     u32 tot;
-    const u32 w = block_excl_scan_256<u32>(kept, s_scr, &tot);
-    u64 *dst = t.scratch + ((s >> t.slot_shift) + w) * 4;
+    const u32 at = block_excl_scan_256<u32>(kept, s_scr, &tot);
+    u64 *dst = t.scratch + ((s >> t.slot_shift) + at) * (NW + 1);
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
         const u32 i = tid * PER + j;
         if (i < D) {
             const u32 c = s_cnt[i];
-            if (c >= a.lower && c <= a.upper) { dst[0] = s_k0[i]; dst[1] = s_k1[i]; dst[2] = s_k2[i]; dst[3] = (u64)c; dst += 4; }
+            if (c >= a.lower && c <= a.upper) {
+#pragma unroll
+                for (int w = 0; w < NW; ++w) dst[w] = s_k[w * CAP + i];
+                dst[NW] = (u64)c; dst += NW + 1;
+            }
         }
     }
     if (tid == 0) t.bin_cnt[b] = tot;
@@ -1168,36 +1054,12 @@ struct AggExtTask {
 };
 struct AggExtArgs { AggExtTask t[AG_BATCH]; u32 lower, upper; u32 nbins; int shift; int nw; int top_bits; int top_sig; u32 *lstat; };     // nw, top_bits, lstat: as in AggArgs (nw = 0 reads as 1)
 
-__global__ __launch_bounds__(AG_THREADS) void bin_bounds_ext_kernel(AggExtArgs a)
-{
-    const AggExtTask &t = a.t[blockIdx.y];
-    const u32 b = blockIdx.x * AG_THREADS + threadIdx.x;
-    if (!t.active || b > a.nbins) return;
-    u64 lo = 0, hi = t.n;
-    if (b == a.nbins) lo = t.n;
-    else while (lo < hi) {
-        const u64 mid = lo + ((hi - lo) >> 1);
-        const int nw = a.nw ? a.nw : 1;
-        const u64 *rec = t.keys + mid * nw;
-        const u32 bin = (a.top_bits > 0 && a.top_bits < 16) ? (((u32)(rec[nw - 1] >> (64 - a.top_bits)) << (16 - a.top_bits)) | (u32)(rec[nw - 2] >> (48 + a.top_bits)))
-                                                             : (u32)(rec[nw - 1] >> a.shift);
-        if (bin < b) lo = mid + 1; else hi = mid;
-    }
-    t.bounds[b] = lo;
-}
-
 // The kernel, for keys of NW = 1 .. 3 words (records {word 0 .. word NW-1}, entries {words, count}).  14 + 16 NW bytes of LDS per
 // slot -- the table's keys, the distinct keys compacted / ordered with their counts and origin slots, slot -> first record of the
 // slot's group, records per slot --, all of which becomes the payload stage once every record of a bin in registers knows its
 // place.  Tables: 1024 slots first; 4096 (one word) or 2048 (two, three words) for the bins the first could not hold.  Slots are
-// claimed with agg_count_keys / agg2_count_keys / agg3_count_keys.  (Multi-word keys with EXTENSION took 13 - 20 full LSD passes over
+// claimed through aggw_count_keys.  (Multi-word keys with EXTENSION took 13 - 20 full LSD passes over
 // records of 24 - 32 bytes until round 2.)
-template <int NW> __device__ __forceinline__ bool keyw_less(const u64 (&x)[NW], const u64 (&y)[NW])
-{
-#pragma unroll
-    for (int w = NW - 1; w > 0; --w) if (x[w] != y[w]) return x[w] < y[w];
-    return x[0] < y[0];
-}
 template <int LOG2CAP, int NW>
 __global__ __launch_bounds__(AG_THREADS) void agg_ext_kernel(AggExtArgs a)
 {
@@ -1221,8 +1083,8 @@ __global__ __launch_bounds__(AG_THREADS) void agg_ext_kernel(AggExtArgs a)
     u32 *s_tcnt = s_soff + CAP;
     const AggExtTask &t = a.t[blockIdx.y];
     if (!t.active) return;
-    u32 b = blockIdx.x;
-    if (t.bin_list) { if (b >= *t.bin_list_n || b >= a.nbins) return; b = t.bin_list[b]; if (b >= a.nbins) return; }
+    u32 b;
+    if (!agg_pick_bin(t, a.nbins, b)) return;
     const int tid = threadIdx.x;
     const u64 s = t.bounds[b], e = t.bounds[b + 1];
     if (e == s) { if (tid == 0) t.bin_cnt[b] = 0; return; }
@@ -1243,12 +1105,6 @@ __global__ __launch_bounds__(AG_THREADS) void agg_ext_kernel(AggExtArgs a)
     u32 where[REGS];
 #pragma unroll
     for (int u = 0; u < REGS; ++u) where[u] = 0;
-    auto slot_of = [&](const u64 (&k)[NW]) -> u32 {
-        if (NW == 1) return agg_slot<LOG2CAP>(k[0]);
-        const u64 m = NW == 2 ? (k[0] ^ (k[NW - 1] >> 9) ^ (k[NW - 1] << 21)) : (k[0] ^ (k[NW > 1 ? 1 : 0] >> 7) ^ (k[NW > 1 ? 1 : 0] << 23) ^ (k[NW - 1] >> 9) ^ (k[NW - 1] << 21));
-        const u32 x = (u32)(m >> 32) ^ (u32)m;
-        return (x * 0x9E3779B1u) >> (32 - LOG2CAP);
-    };
     auto count_batch = [&](u64 i, u32 *wh) {
         u64 k[UNR][NW];
 #pragma unroll
@@ -1261,12 +1117,8 @@ __global__ __launch_bounds__(AG_THREADS) void agg_ext_kernel(AggExtArgs a)
         for (int u = 0; u < UNR; ++u) {
             const u64 act = __ballot(k[u][NW - 1] != AG_EMPTY);
             if (act == 0) continue;                       // (uniform)
-            u32 h = slot_of(k[u]), tmo = 0;
-            u64 left;
-            if (NW == 1) left = agg_count_keys<(u32)CAP - 1u>(act, tk_lds, cnt_lds, h, k[u][0]);
-            else if (NW == 2) left = agg2_count_keys<(u32)CAP - 1u>(act, tk_lds + (u32)CAP * 8u, tk_lds, cnt_lds, h, k[u][NW - 1], k[u][0], tmo);
-            else left = agg3_count_keys<(u32)CAP - 1u>(act, tk_lds + 2u * (u32)CAP * 8u, tk_lds + (u32)CAP * 8u, tk_lds, cnt_lds, h, k[u][NW - 1], k[u][NW > 1 ? 1 : 0], k[u][0], tmo);
-            if (left != 0 || tmo) s_ovf = 1;
+            u32 h = agg_key_slot<LOG2CAP, NW>(k[u]), tmo = 0;
+            if (aggw_count_keys<(u32)CAP - 1u, NW>(act, tk_lds, cnt_lds, h, k[u], tmo) != 0 || tmo) s_ovf = 1;
             if (wh) wh[u] = h;
         }
     };
@@ -1282,18 +1134,11 @@ __global__ __launch_bounds__(AG_THREADS) void agg_ext_kernel(AggExtArgs a)
         for (int j = 0; j < (int)(AGL_TAB / AG_THREADS); ++j) {
             const u32 q = (u32)tid + (u32)j * AG_THREADS;
             u64 k[NW];
-            k[NW - 1] = t.lg->tkeys[tb + q];
-            if (NW >= 2) k[0] = t.lg->tkeys0[tb + q];
-            if (NW == 3) k[NW > 1 ? 1 : 0] = t.lg->tkeys1[tb + q];
+            agl_load_key<NW>(*t.lg, tb + q, k);
             const u64 act = __ballot(k[NW - 1] != AG_EMPTY);
             if (act == 0) continue;                       // (uniform)
-            u32 h = slot_of(k), tmo = 0;
-            const u32 inc = gc[q];
-            u64 left;
-            if (NW == 1) left = agg_count_keys<(u32)CAP - 1u>(act, tk_lds, cnt_lds, h, k[0], inc);
-            else if (NW == 2) left = agg2_count_keys<(u32)CAP - 1u>(act, tk_lds + (u32)CAP * 8u, tk_lds, cnt_lds, h, k[NW - 1], k[0], tmo, inc);
-            else left = agg3_count_keys<(u32)CAP - 1u>(act, tk_lds + 2u * (u32)CAP * 8u, tk_lds + (u32)CAP * 8u, tk_lds, cnt_lds, h, k[NW - 1], k[NW > 1 ? 1 : 0], k[0], tmo, inc);
-            if (left != 0 || tmo) s_ovf = 1;
+            u32 h = agg_key_slot<LOG2CAP, NW>(k), tmo = 0;
+            if (aggw_count_keys<(u32)CAP - 1u, NW>(act, tk_lds, cnt_lds, h, k, tmo, gc[q]) != 0 || tmo) s_ovf = 1;
             if (k[NW - 1] != AG_EMPTY) { where[j] = h; have |= 1u << j; }
         }
     } else if (in_regs) {
@@ -1308,11 +1153,7 @@ __global__ __launch_bounds__(AG_THREADS) void agg_ext_kernel(AggExtArgs a)
     }
     __syncthreads();
     if (s_ovf) {
-        if (tid == 0) {
-            if (t.ovf_list) { const u32 at = atomicAdd(t.ovf_n, 1u); if (at < a.nbins) t.ovf_list[at] = b; else atomicOr(t.flags, (u32)AG_FLAG_OVERFLOW); }
-            else atomicOr(t.flags, (u32)AG_FLAG_OVERFLOW);
-            t.bin_cnt[b] = 0;
-        }
+        if (tid == 0) agg_bin_overflow(t, a.nbins, b);
         return;
     }
 
@@ -1347,6 +1188,7 @@ __global__ __launch_bounds__(AG_THREADS) void agg_ext_kernel(AggExtArgs a)
 #pragma unroll
             for (int w = 0; w < NW; ++w) k[w] = s_k[w * CAP + tid];
             c = s_cnt[tid]; sl = s_slot[tid];
+#pragma unroll AGG_RANK_UNROLL<NW>
             for (u32 j = 0; j < D; ++j) {
                 u64 o[NW];
 #pragma unroll
@@ -1446,7 +1288,7 @@ __global__ __launch_bounds__(AG_THREADS) void agg_ext_kernel(AggExtArgs a)
 #pragma unroll
             for (int w = 0; w < NW; ++w) k[w] = t.keys[i * NW + w];
             const u64 v = t.vals[i];
-            u32 h = slot_of(k);
+            u32 h = agg_key_slot<LOG2CAP, NW>(k);
             for (;;) {
                 bool same = true;
 #pragma unroll
@@ -1495,10 +1337,7 @@ __global__ __launch_bounds__(AG_THREADS) void agg_ext_large_place_kernel(AggExtA
 #pragma unroll
             for (int w = 0; w < NW; ++w) k[w] = valid ? t.keys[i * NW + w] : 0;
             if (valid) v = t.vals[i];
-            u64 m = k[0];
-            if (NW == 2) m ^= (k[NW - 1] >> 9) ^ (k[NW - 1] << 21);
-            if (NW == 3) m ^= (k[NW > 1 ? 1 : 0] >> 7) ^ (k[NW > 1 ? 1 : 0] << 23) ^ (k[NW - 1] >> 9) ^ (k[NW - 1] << 21);
-            u32 h = (((u32)(m >> 32) ^ (u32)m) * 0x9E3779B1u) >> (32 - AGL_LOG2TAB);
+            u32 h = agg_key_slot<AGL_LOG2TAB, NW>(k);
             bool found = false;
             if (valid) {
                 for (u32 pr = 1; pr <= (u32)AGL_MAX_PROBE; ++pr) {
@@ -1622,7 +1461,7 @@ __global__ __launch_bounds__(AGB_THREADS) void agg_big_kernel(AggArgs a)
         // already sits in its home slot -- nearly all of them after a key's first occurrence -- is one more LDS atomic
         u32 hh[UNR]; u64 cur0[UNR];
 #pragma unroll
-        for (int u = 0; u < UNR; ++u) { const u32 x = (u32)(k[u] >> 32) ^ (u32)k[u]; hh[u] = (x * 0x9E3779B1u) >> (32 - AGB_LOG2CAP); }
+        for (int u = 0; u < UNR; ++u) hh[u] = agg_slot<AGB_LOG2CAP>(k[u]);
 #pragma unroll
         for (int u = 0; u < UNR; ++u) cur0[u] = __hip_atomic_load(&s_key[hh[u]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #pragma unroll
@@ -1655,7 +1494,7 @@ __global__ __launch_bounds__(AGB_THREADS) void agg_big_kernel(AggArgs a)
     }
     __syncthreads();
     if (s_ovf || D > (u32)AGB_MAX_LOAD) {
-        if (tid == 0) agg_bin_overflow(t, a.nbins, b, (u32)AGB_CAP);
+        if (tid == 0) { agg_bin_overflow(t, a.nbins, b); atomicMax(t.flags + AG_BATCH, (u32)AGB_CAP); }
         return;
     }
 

@@ -270,9 +270,10 @@ static int agg_launch_rung(hsk_ctx *c, AggPending &p, int log2cap, u32 grid_x, u
         if constexpr (NW == 1) if (log2cap == AG_LOG2CAP_HUGE && !p.weighted) { hipLaunchKernelGGL(agg_big_kernel, grid, dim3(AGB_THREADS), 0, c->stream, a); return; }
         with_cap(log2cap, [&](auto cap) {
             constexpr int CAP = decltype(cap)::value;
-            if constexpr (NW == 3) hipLaunchKernelGGL((agg3_finish_kernel<CAP>), grid, block, 0, c->stream, a);
-            else if constexpr (NW == 2) { if (p.weighted) hipLaunchKernelGGL((agg2_finish_kernel<CAP, true>), grid, block, 0, c->stream, a); else hipLaunchKernelGGL((agg2_finish_kernel<CAP>), grid, block, 0, c->stream, a); }
-            else { if (p.weighted) hipLaunchKernelGGL((agg_finish_kernel<CAP, true>), grid, block, 0, c->stream, a); else hipLaunchKernelGGL((agg_finish_kernel<CAP>), grid, block, 0, c->stream, a); }
+            if constexpr (NW >= 2) {
+                if constexpr (NW == 2) if (p.weighted) { hipLaunchKernelGGL((aggw_finish_kernel<CAP, NW, true>), grid, block, 0, c->stream, a); return; }
+                hipLaunchKernelGGL((aggw_finish_kernel<CAP, NW>), grid, block, 0, c->stream, a);
+            } else { if (p.weighted) hipLaunchKernelGGL((agg_finish_kernel<CAP, true>), grid, block, 0, c->stream, a); else hipLaunchKernelGGL((agg_finish_kernel<CAP>), grid, block, 0, c->stream, a); }
         });
     });
     HIPCHK(c, hipGetLastError());
@@ -321,9 +322,7 @@ static int agg_large_setup(hsk_ctx *c, AggArgs &a, int slot, bool ext, char *&d_
     }
     HIPCHK(c, hipMemcpyAsync(d_large, h_lg, sizeof(AggLarge) * AG_BATCH, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(agg_large_list_kernel, dim3(nbins / AG_THREADS + 1, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-    if (NW == 1) hipLaunchKernelGGL(agg_large_slice_kernel, dim3(160, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-    else if (NW == 2) hipLaunchKernelGGL(agg2_large_slice_kernel, dim3(160, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-    else hipLaunchKernelGGL(agg3_large_slice_kernel, dim3(160, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(agg_large_slice_kernel<NW>, dim3(160, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
     return HSK_OK;
 }
@@ -368,7 +367,7 @@ static int agg_stage1(hsk_ctx *c, const BatchTask *bt, int K, int prefix_bits, i
             if (!t.scratch) return fail(c, HSK_ERR_OOM, "finish scratch of %llu bytes", (unsigned long long)(bt[i].n * EW * 8));
         }
     }
-    hipLaunchKernelGGL(bin_bounds_kernel, dim3(nbins / AG_THREADS + 1, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(bin_bounds_kernel<AggArgs>, dim3(nbins / AG_THREADS + 1, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
     if (!weighted) {                                    // (the weighted finish -- combining extraction -- counts its large bins itself)
         a.lstat = p.d_flags + 4 * AG_BATCH;             // AggHostRead::large
         int rc = agg_large_setup<NW>(c, a, slot, false, p.d_large); if (rc) return rc;
@@ -586,7 +585,7 @@ static int agg_ext_finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, const u
         }); });
     };
     memset(&h, 0, sizeof h);
-    hipLaunchKernelGGL(bin_bounds_ext_kernel, dim3(nbins / AG_THREADS + 1, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
+    hipLaunchKernelGGL(bin_bounds_kernel<AggExtArgs>, dim3(nbins / AG_THREADS + 1, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
     // bins of very many records: their keys are counted slice by slice before the ladder, their payloads placed slice by slice after it
     char *d_large = nullptr;
     {
