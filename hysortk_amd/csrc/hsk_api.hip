@@ -572,14 +572,15 @@ extern "C" int hsk_count(hsk_ctx *c, const uint8_t *packed, uint64_t packed_byte
             if (hipPointerGetAttributes(&at, packed) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) zc = (const u8 *)at.devicePointer;
             else (void)hipGetLastError();
         }
-        // pinned input of some size: slab ingest (DMA copies pipelined with the scan, parse_count) instead of reads over PCIe in place;
+        // pinned input of some size: slab ingest (DMA copies pipelined with the scan: enqueue_slab_copies, for parse_ingest_pipelined or
+        // parse_count's fast scan) instead of reads over PCIe in place;
         // HSK_H2D_SLABS=0: in place as in round 2, =n: n slabs
         const int slabs_env = (int)tune("h2d_slabs", 16);
         const bool slab_ingest = zc != nullptr && slabs_env > 1 && packed_bytes >= (32u << 20);
         const bool profile = (c->cfg.flags & HSK_FLAG_PROFILE) != 0;
         const bool derive_enabled = tune("derive_offsets", 1) != 0;
         // only the read lengths travel ahead of the scan (see roff_tilesum_kernel).  The host threads' verdict on the derived index is read by the
-        // fast parse (parse_count's scan branch, parse_ingest_pipelined): with the general parse kernels from the start (M > SCAN_MAX_M, HSK_PARSE_FAST=0)
+        // fast parse (count_verdict for parse_count, parse_ingest_pipelined): with the general parse kernels from the start (M > SCAN_MAX_M, HSK_PARSE_FAST=0)
         // the caller's index travels and is checked on the device like a pageable one
         const bool derive = zc != nullptr && device_check && derive_enabled && parse_fast_enabled() && c->cfg.minimizer_size <= SCAN_MAX_M;
         DevInput d;
@@ -695,7 +696,7 @@ extern "C" int hsk_stage_destinations(hsk_ctx *c, const uint8_t *packed, uint64_
         if (!nreads || !packed_bytes) return HSK_OK;
         DevInput d; rc = upload_input(c, packed, packed_bytes, off, len, nreads, d); if (rc) return rc;
         const u32 ntasks = c->cfg.ntasks ? (u32)c->cfg.ntasks : 1;
-        u32 nblocks; ParseArgs a = make_parse_args(c, d.packed, packed_bytes, d.roff, d.rlen, nreads, 0, ntasks, &nblocks);
+        const ParseTiling t = call_tiling(c, packed_bytes); const u32 nblocks = t.nblocks; ParseArgs a = make_parse_args(c, t, d.packed, packed_bytes, d.roff, d.rlen, nreads, 0, ntasks);
         int32_t *d_dump; DALLOC(c, d_dump, int32_t *, packed_bytes * 4 * 4);
         a.dump_dest = d_dump;
         hipLaunchKernelGGL((parse_kernel<PARSE_DUMP, false>), dim3(nblocks), dim3(PARSE_THREADS), 64, c->stream, a);
@@ -1134,7 +1135,7 @@ extern "C" int hsk_copy_peak(hsk_ctx *c, uint64_t bytes, int iters, double *gbs)
 }
 
 // Experiment (tools/parse_overlap.py; not part of include/hsk.h): can the placement of one set of reads run BESIDE the minimizer scan of
-// another?  out_ms: [0] scan with 1024 workgroups, [1] scan with `blocks` workgroups, [2] placement alone, [3] scan(`blocks`) on the
+// another?  out_ms: [0] scan with 1024 workgroups, [1] scan with `blocks` workgroups (PARSE_MAX_BLOCKS at most: the COUNT matrix has no more rows), [2] placement alone, [3] scan(`blocks`) on the
 // main stream and the placement on the second stream at the same time (start of both to end of both), [4] scan inside [3], [5] placement inside [3].
 extern "C" int hsk_debug_parse_overlap(hsk_ctx *c, const void *d_packed, uint64_t packed_bytes, const void *d_off, const void *d_len, uint64_t nreads,
                                        uint32_t blocks, double *out_ms)

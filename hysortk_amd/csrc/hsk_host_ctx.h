@@ -100,19 +100,19 @@ struct CallState {
     u64 dropped_now = 0;               // ... and how many it left out (they count as k-mers of the input: hsk_result::total_kmers)
     // the input
     const u8 *zc_src = nullptr;        // hsk_count() with pinned input: device view of the caller's packed reads (scan_kernel reads them in place)
-    const u8 *h2d_src = nullptr;       // hsk_count() with pinned input, slab ingest: the caller's packed reads (host pointer); parse_count copies them slab by
-    int h2d_slabs = 0;                 // slab (DMA, d2h_stream) and hashes slab s while slab s + 2 is on the link
+    const u8 *h2d_src = nullptr;       // hsk_count() with pinned input, slab ingest: the caller's packed reads (host pointer); enqueue_slab_copies sends them slab by
+    int h2d_slabs = 0;                 // slab (DMA, d2h_stream) and the driver (parse_ingest_pipelined, parse_count) hashes slab s while slab s + 2 is on the link
     // hsk_count() with derived read offsets: host threads compare the caller's offsets with the back-to-back layout while the GPU
     // scans (result collected with the task totals); roff_host / roff_given: the caller's array and a device buffer for it, used
     // only when the comparison fails (a buffer with gaps)
     std::future<bool> roff_check;
-    bool roff_bad = false;             // ... its verdict, when somebody other than parse_count collected it (parse_ingest_pipelined)
+    bool roff_bad = false;             // ... its verdict, when somebody other than count_verdict collected it (parse_ingest_pipelined)
     const uint32_t *rlen_host = nullptr;   // the read lengths were generated on the device from a sample (all reads equally long): the caller's array,
                                            // copied after all if the host threads find a read of another length (same fallback as a buffer with gaps)
     const uint64_t *roff_host = nullptr;
     u64 *roff_given = nullptr;
     bool index_unchecked = false;      // hsk_count(): the read index is validated on the device (index_check_kernel), the verdict is read with the task totals
-    u32 scan_blocks = 0;               // experiments (hsk_debug_parse_overlap): workgroups of the parse kernels instead of 1024
+    u32 scan_blocks = 0;               // experiments (hsk_debug_parse_overlap): workgroups of the parse kernels instead of PARSE_MAX_BLOCKS (never more: parse_tiling)
 };
 
 struct hsk_ctx {
@@ -166,8 +166,8 @@ struct PinnedTail {
     unsigned char free1[1280 - 64];
     u64 estimate[16];                  // estimate_plan: the sample's counters
     unsigned char free2[64];
-    u32 parse_flags[16];               // parse_count, parse_ingest_pipelined: overflow, error word, chunks, dropped k-mers.  One parse per attempt: the
-                                       // pipelined ingest has read its words before it falls back to parse_count
+    u32 parse_flags[16];               // the parse's verdict words (ParseFlags, hsk_host_parse.h: read_parse_flags writes, the drivers read).  One parse per attempt:
+                                       // the pipelined ingest has read its words before it falls back to parse_count
     alignas(64) u64 packed_bytes;      // the last read offset on its way to the device: one entry point per call writes it, and every call ends with a wait
     alignas(64) u32 sort_flag;         // sort_task_device: a long bin with several keys
     alignas(64) u64 total;             // count_task_device, merge_sorted_pairs, hsk_format: entries kept -- copied, waited for and read on the spot

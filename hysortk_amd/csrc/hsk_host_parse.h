@@ -1,4 +1,6 @@
-// hsk_host_parse.h -- host side of the parse stage: supermer store, parse_count / parse_place (kernels: hsk_parse.h).
+// hsk_host_parse.h -- host side of the parse stage (kernels: hsk_parse.h; tiling and capacities: hsk_parseplan.h).  The supermer store; what
+// both drivers share -- the scan's buffers (ScanBufs), the verdict words (ParseFlags), launch_scan / launch_place, the slab copies; and the
+// drivers: parse_count (fast scan, verdict, general count) + parse_place, and parse_ingest_pipelined for hsk_count() from pinned memory.
 // Part of the single translation unit hsk_api.hip (included in this order; everything here is file-local).
 #pragma once
 
@@ -72,29 +74,18 @@ static bool place_bytes_enabled(bool supermers_travel)
     return env < 0 ? supermers_travel : env != 0;
 }
 
-// nslabs > 1 (scan_kernel / place_kernel / place_bytes_kernel only): every workgroup owns one run of tiles per slab, see ParseArgs
-static ParseArgs make_parse_args(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u64 *d_roff, const u32 *d_rlen,
-                                 u64 nreads, int64_t rid_base, u32 ntasks, u32 *nblocks_out, u32 nslabs = 1)
+// this call's tiling (hsk_parseplan.h); nslabs > 1: the slab ingest wants that many slabs
+static ParseTiling call_tiling(hsk_ctx *c, u64 packed_bytes, u32 nslabs = 1) { return parse_tiling(packed_bytes, c->call.scan_blocks, nslabs); }
+// the tiling and the call's constants as the kernels take them (t.nslabs > 1: scan_kernel and the three placement kernels only, see ParseArgs)
+static ParseArgs make_parse_args(hsk_ctx *c, const ParseTiling &t, const u8 *d_packed, u64 packed_bytes, const u64 *d_roff, const u32 *d_rlen,
+                                 u64 nreads, int64_t rid_base, u32 ntasks)
 {
     ParseArgs a; memset(&a, 0, sizeof a);
     a.packed = d_packed; a.packed_bytes = packed_bytes; a.roff = d_roff; a.rlen = d_rlen; a.nreads = nreads;
     a.k = c->cfg.kmer_size; a.m = c->cfg.minimizer_size; a.ntasks = ntasks; a.fm = make_fastmod(ntasks >> c->call.vt_shift); a.vt_shift = c->call.vt_shift;      // (virtual tasks: `ntasks` counts them)
     a.item_maxk = (u32)std::max(1, std::min(16, 61 - c->cfg.kmer_size));
-    a.ntiles = (packed_bytes * 4 + PARSE_TILE - 1) / PARSE_TILE;
-    u32 nblocks = (u32)std::min<u64>(a.ntiles, c->call.scan_blocks ? c->call.scan_blocks : 1024);
     a.rid_base = rid_base;
-    if (nslabs > 1 && a.ntiles >= (u64)nblocks * nslabs) {
-        const u64 per_slab = (a.ntiles + nslabs - 1) / nslabs;
-        a.tiles_per_block = (u32)((per_slab + nblocks - 1) / nblocks);
-        a.slab_tiles = (u64)a.tiles_per_block * nblocks;
-        a.nslabs = (u32)((a.ntiles + a.slab_tiles - 1) / a.slab_tiles);
-        *nblocks_out = nblocks;
-        return a;
-    }
-    a.tiles_per_block = (u32)((a.ntiles + nblocks - 1) / nblocks);
-    nblocks = (u32)((a.ntiles + a.tiles_per_block - 1) / a.tiles_per_block);
-    a.nslabs = 1; a.slab = 0; a.slab_tiles = 0;
-    *nblocks_out = nblocks;
+    a.ntiles = t.ntiles; a.tiles_per_block = t.tiles_per_block; a.nslabs = t.nslabs; a.slab = 0; a.slab_tiles = t.slab_tiles;
     return a;
 }
 
@@ -102,19 +93,19 @@ static ParseArgs make_parse_args(hsk_ctx *c, const u8 *d_packed, u64 packed_byte
 // (multi-GPU: sizes -> all-reduce -> dispatcher -> owner-grouped order) hashes the reads only once:
 //   parse_count: minimizers + supermer boundaries of every tile; per-(workgroup, task) counts; task totals
 //   parse_place: exclusive scan of the counts in the storage order `order`, supermers to their slots
-// Fast path = scan_kernel + place_kernel (compact supermer records kept in between); the general path
+// Fast path = scan_kernel + a placement kernel (compact supermer records kept in between); the general path
 // (M > 25, or a tile with more supermers than the record capacity) = parse_kernel<COUNT> + emit_kernel.
 // scan_kernel places the items of the combining extraction itself (one GPU; ParseArgs::bin_*, hsk_parse.h: bin_place): bins = (XCD, virtual
 // task) chunk lists.  The chunk store is sized from the EXPECTED supermer count (a window of W k-mers starts a supermer every (W + 1) / 2
 // positions on random sequence, every 16 k-mers at least, once per read) with a quarter to spare; real genomes with long low-complexity
 // stretches make FEWER supermers, and an input that does overrun it (error bit 128; a bin beyond its map: 256) sends the call round again
-// without the combining extraction.  tuning "scan_place=1" selects it (default: tile records + place_items_kernel, see scan_place_enabled).
+// without the combining extraction.  tuning "scan_place=1" selects it (default: tile records + the item placement, see scan_place_enabled).
 struct ScanBins {
     u32 *cursor = nullptr, *map = nullptr, *ctl = nullptr, *chunk_bin = nullptr, *subs = nullptr; ulonglong2 *items = nullptr;
     BinTable *d_table = nullptr;                          // the table scan_kernel<.., true> reads (ParseArgs::bins)
     u32 vmax = 0, cap = 0, nchunks = 0, nbins = 0;
 };
-// Measured (10 Gbp, round 4): scan 47.6 ms with the items placed by it against 33.9 + 13.4 ms (scan + place_items_kernel): the same ~13.5 ms wherever the
+// Measured (10 Gbp, round 4): scan 47.6 ms with the items placed by it against 33.9 + 13.4 ms (scan + item placement): the same ~13.5 ms wherever the
 // placement runs, 101.7 ms per step either way -- and from host memory the separate placement hides behind the ingest's DMA while the longer scan
 // does not (140 against 123 ms).  So the default stays the placement kernel; "scan_place=1" takes the fused form (no tile records: 13 GB less device
 // memory and 20 GB less traffic per 10 Gbp).
@@ -153,38 +144,171 @@ static int bins_alloc(hsk_ctx *c, ScanBins &b, u32 nvt, u64 packed_bytes, u64 nr
     hipLaunchKernelGGL(bins_init_kernel, dim3((b.nbins + 255) / 256), dim3(256), 0, stream, *h, b.nbins);
     return HSK_OK;
 }
-static void bins_args(hsk_ctx *, ParseArgs &a, const ScanBins &b) { a.bins = b.d_table; }
 // the store takes the bins over: items and minimizer bits where they are, the bucket order's work list from the chunk lists
 static int bins_to_store(hsk_ctx *c, ScanBins &b, SupermerStore &st, u32 nvt, u32 vt_shift, hipStream_t stream);
 
-constexpr u64 SLAB_HEAD = 4096;                    // bytes at the start of an ingest slab that the scan of the slab before it reads (>= (PARSE_WORDS - 128) * 4 + the prefetch's reach)
+// What the fast scan writes besides the COUNT matrix.  Both drivers (parse_count, parse_ingest_pipelined) own one: scan_setup decides
+// what the call needs, allocates, clears and names it in the kernels' arguments; scan_release gives it back.
+struct ScanBufs {
+    u32 *d_overflow = nullptr;                            // set by a tile with more supermers than the record capacity
+    u32 *d_tile_rec = nullptr, *d_tile_nrec = nullptr;    // the tiles' supermer records, kept for the placement ...
+    ScanBins bins;                                        // ... or no records at all: scan_kernel places the items itself
+    u32 *d_tile_r0 = nullptr;                             // EXTENSION: first read of every tile (hint for the (pos, rid) lookup)
+    u32 *d_tile_sub = nullptr;                            // combining extraction: minimizer bits of every record
+    unsigned long long *d_dropped = nullptr;              // scan_kernel<.., DROP>: positions left out (CallState::drop_mask_now)
+};
+static void scan_release(hsk_ctx *c, ScanBufs &s)
+{
+    c->pool.release(s.d_overflow); c->pool.release(s.d_tile_rec); c->pool.release(s.d_tile_nrec); c->pool.release(s.d_tile_r0); c->pool.release(s.d_tile_sub); c->pool.release(s.d_dropped);
+    bins_release(c, s.bins);
+    s = ScanBufs();
+}
+static int scan_setup(hsk_ctx *c, ScanBufs &s, ParseArgs &a, hipStream_t stream)
+{
+    const int W = c->cfg.kmer_size - c->cfg.minimizer_size + 1;
+    a.rec_cap = parse_rec_cap(W, tune("parse_rec_cap", 0));
+    a.place_group = place_group(PLACE_RECORDS, a.rec_cap);               // (launch_place: each kind's own)
+    const bool items = c->call.combine_now && a.rec_cap <= PLACE_ITEM_REC;
+    const bool bins = items && c->call.item_mode_now && scan_place_enabled();
+    DALLOC(c, s.d_overflow, u32 *, 256);
+    HIPCHK(c, hipMemsetAsync(s.d_overflow, 0, 4, stream));
+    a.overflow = s.d_overflow;
+    if (bins) {
+        int brc = bins_alloc(c, s.bins, a.ntasks, a.packed_bytes, a.nreads, W, stream); if (brc) return brc;
+        a.bins = s.bins.d_table;
+    } else {
+        DALLOC(c, s.d_tile_rec, u32 *, (size_t)a.ntiles * a.rec_cap * 4 + 64);
+        DALLOC(c, s.d_tile_nrec, u32 *, (size_t)a.ntiles * 4 + 64);
+        a.tile_rec = s.d_tile_rec; a.tile_nrec = s.d_tile_nrec;
+    }
+    if (c->cfg.extension && a.nreads < (1ULL << 32)) { DALLOC(c, s.d_tile_r0, u32 *, (size_t)a.ntiles * 4 + 64); a.tile_r0 = s.d_tile_r0; }
+    if (items && !bins) { DALLOC(c, s.d_tile_sub, u32 *, (size_t)a.ntiles * a.rec_cap * 4 + 64); a.tile_sub = s.d_tile_sub; }
+    c->call.dropped_now = 0;
+    a.drop_mask = bins ? 0u : c->call.drop_mask_now;
+    if (a.drop_mask) { DALLOC(c, s.d_dropped, unsigned long long *, 256); HIPCHK(c, hipMemsetAsync(s.d_dropped, 0, 8, stream)); a.dropped = s.d_dropped; }
+    return HSK_OK;
+}
+
 struct ParseJob {
     ParseArgs a; u32 nblocks = 0, ntasks = 0; bool fast = false, empty = true;
     const u64 *d_roff = nullptr; u64 nreads = 0; int64_t rid_base = 0;
-    u64 *d_blk_cnt = nullptr; u16 *d_dest_cache = nullptr; u32 *d_tile_rec = nullptr, *d_tile_nrec = nullptr, *d_overflow = nullptr;
-    u32 *d_tile_r0 = nullptr;     // EXTENSION: first read of every tile (hint for the (pos, rid) lookup)
-    u32 *d_tile_sub = nullptr;    // combining extraction: minimizer bits of every record
-    unsigned long long *d_dropped = nullptr;      // scan_kernel<.., DROP>: positions left out (CallState::drop_mask_now)
-    ScanBins bins;                // ... or no records at all: scan_kernel places the items itself
+    u64 *d_blk_cnt = nullptr; u16 *d_dest_cache = nullptr;
+    ScanBufs scan;                // fast path
     std::vector<u64> task_tot;    // [ntasks][3] supermers, bytes, kmers of this rank
 };
 
 static void parse_release(hsk_ctx *c, ParseJob &j)
 {
-    c->pool.release(j.d_blk_cnt); c->pool.release(j.d_dest_cache); c->pool.release(j.d_tile_rec); c->pool.release(j.d_tile_nrec); c->pool.release(j.d_overflow);
-    c->pool.release(j.d_tile_r0); j.d_tile_r0 = nullptr; c->pool.release(j.d_tile_sub); j.d_tile_sub = nullptr;
-    c->pool.release(j.d_dropped); j.d_dropped = nullptr;
-    bins_release(c, j.bins);
-    j.d_blk_cnt = nullptr; j.d_dest_cache = nullptr; j.d_tile_rec = j.d_tile_nrec = j.d_overflow = nullptr;
+    c->pool.release(j.d_blk_cnt); c->pool.release(j.d_dest_cache); j.d_blk_cnt = nullptr; j.d_dest_cache = nullptr;
+    scan_release(c, j.scan);
 }
 
-// place_items_kernel stages 16384 records + 32 tiles of packed words: ~158 KB of dynamic LDS, which the runtime wants announced
-static size_t place_items_lds(u32 ntasks)
+// The verdict words of a parse as the host reads them from the staging area (PinnedTail::parse_flags): a tile held more supermers than the
+// record capacity; the device's error word; scan-placed items: chunks handed out; positions the drop mask left out
+struct ParseFlags { u32 overflow, err, chunks, unused; unsigned long long dropped; };
+static_assert(offsetof(ParseFlags, overflow) == 0 && offsetof(ParseFlags, err) == 4 && offsetof(ParseFlags, chunks) == 8 && offsetof(ParseFlags, dropped) == 16, "verdict words");
+static_assert(sizeof(ParseFlags) <= sizeof(PinnedTail::parse_flags), "the verdict words live in PinnedTail::parse_flags");
+constexpr u32 PARSE_ERR_INDEX = 32u;                      // error word: index_check_kernel refused the read index
+constexpr u32 PARSE_ERR_BINS = 2u | 128u | 256u;          // error word: the scan-placed items' chunk store or a bin's map ran out
+static ParseFlags *parse_flags(hsk_ctx *c) { return reinterpret_cast<ParseFlags *>(staging(c)->parse_flags); }
+// the words on their way to the host; scan: the fast scan's own (overflow, chunks) among them
+static int read_parse_flags(hsk_ctx *c, hipStream_t stream, const ScanBufs &s, bool scan)
 {
-    static bool announced = false;
-    if (!announced) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(place_items_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512); announced = true; }
-    return (size_t)ntasks * 16 + 8 + (size_t)PLACE_ITEM_REC * 8 + (size_t)PLACE_ITEM_WORDS * 4;
+    ParseFlags *h = parse_flags(c);
+    if (scan) HIPCHK(c, hipMemcpyAsync(&h->overflow, s.d_overflow, 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(c, hipMemcpyAsync(&h->err, c->d_err, 4, hipMemcpyDeviceToHost, stream));
+    if (scan && s.bins.items) HIPCHK(c, hipMemcpyAsync(&h->chunks, s.bins.ctl, 4, hipMemcpyDeviceToHost, stream));
+    if (s.d_dropped) HIPCHK(c, hipMemcpyAsync(&h->dropped, s.d_dropped, 8, hipMemcpyDeviceToHost, stream));
+    return HSK_OK;
 }
+
+// an event pair of the profile (HSK_FLAG_PROFILE; kind: drain_profile_events, hsk_api.hip) around what follows on `stream`
+static EvPair prof_begin(hsk_ctx *c, int kind, hipStream_t stream)
+{
+    EvPair ep{};
+    if (c->cfg.flags & HSK_FLAG_PROFILE) { ep.a = ev_get(c); ep.b = ev_get(c); ep.kind = kind; (void)hipEventRecord(ep.a, stream); }
+    return ep;
+}
+static void prof_end(hsk_ctx *c, const EvPair &ep, hipStream_t stream)
+{
+    if (c->cfg.flags & HSK_FLAG_PROFILE) { (void)hipEventRecord(ep.b, stream); c->ev_pending.push_back(ep); }
+}
+
+// The one place that names the instances of scan_kernel.  (k, m) = (31, 17) and (51, 17) have instances of their own;
+// "scan_generic=1" (tests) sends them through the generic one.
+static void launch_scan(hsk_ctx *, hipStream_t stream, u32 nblocks, u32 ntasks, const ParseArgs &a)
+{
+    const dim3 grid(nblocks), block(PARSE_THREADS);
+    const size_t lds = (size_t)ntasks * 16;
+    const bool generic = tune("scan_generic", 0) != 0;
+    const bool k31 = a.k == 31 && a.m == 17 && !generic, k51 = a.k == 51 && a.m == 17 && !generic;
+    if (a.drop_mask) hipLaunchKernelGGL((scan_kernel<0, 0, false, true>), grid, block, lds, stream, a);
+    else if (a.bins && k31) hipLaunchKernelGGL((scan_kernel<31, 17, true>), grid, block, lds, stream, a);
+    else if (a.bins) hipLaunchKernelGGL((scan_kernel<0, 0, true>), grid, block, lds, stream, a);
+    else if (k31) hipLaunchKernelGGL((scan_kernel<31, 17>), grid, block, lds, stream, a);
+    else if (k51) hipLaunchKernelGGL((scan_kernel<51, 17>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((scan_kernel<0, 0>), grid, block, lds, stream, a);
+}
+
+// The one place that names the placement kernels of the fast path.  place_items_kernel stages 16384 records + 32 tiles of packed
+// words (~158 KB of dynamic LDS) and place_bytes_kernel nearly as much, which the runtime wants announced.
+static void launch_place(hsk_ctx *, hipStream_t stream, PlaceKind kind, ParseArgs a, u32 nblocks, u32 ntasks)
+{
+    static bool announced[3] = {false, false, false};
+    a.place_group = place_group(kind, a.rec_cap);
+    if (kind == PLACE_RECORDS) {
+        hipLaunchKernelGGL(place_kernel, dim3(nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16 + PLACE_MAX_REC * 4, stream, a);
+        return;
+    }
+    const void *fn = kind == PLACE_ITEMS ? reinterpret_cast<const void *>(place_items_kernel) : reinterpret_cast<const void *>(place_bytes_kernel);
+    if (!announced[kind]) { (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512); announced[kind] = true; }
+    if (kind == PLACE_ITEMS)
+        hipLaunchKernelGGL(place_items_kernel, dim3(nblocks), dim3(PLACE_ITEM_THREADS), (size_t)ntasks * 16 + 8 + (size_t)PLACE_ITEM_REC * 8 + (size_t)PLACE_ITEM_WORDS * 4, stream, a);
+    else
+        hipLaunchKernelGGL(place_bytes_kernel, dim3(nblocks), dim3(PLACE_BYTES_THREADS),
+                           (size_t)ntasks * 40 + PLACE_BYTES_REC * 8 + PLACE_BYTES_WORDS * 4 + (a.sm_sub16 ? PLACE_BYTES_REC * 2 : 0), stream, a);
+}
+// ... and the general path's: emit_kernel reads the task ids COUNT has kept, without them the parse kernel hashes again
+static void launch_emit(hsk_ctx *, hipStream_t stream, const ParseArgs &a, u32 nblocks, u32 ntasks)
+{
+    if (a.dest_cache) hipLaunchKernelGGL(emit_kernel, dim3(nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, stream, a);
+    else if (a.drop_mask) hipLaunchKernelGGL((parse_kernel<PARSE_EMIT, false, true>), dim3(nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, stream, a);
+    else hipLaunchKernelGGL((parse_kernel<PARSE_EMIT, false>), dim3(nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, stream, a);
+}
+
+// The slab ingest.  The packed reads cross PCIe as DMA copies, slab by slab, on the copy stream -- all of them enqueued before the
+// first scan -- while the main stream hashes the slabs that have landed, so the link and the VALUs work side by side: the parse takes
+// about as long as the transfer (a kernel reading the host buffer in place gets ~40 GB/s out of the link, the DMA engine ~55).
+// A slab's scan reaches PARSE_WORDS - 128 words into the NEXT slab (the windows of its last k-mers), not further: every slab's first
+// SLAB_HEAD bytes travel as a copy of their own with an event (`head`), and the scan of slab s waits for slab s (`landed`) and for the
+// head of slab s + 1 -- not for all of slab s + 1 (the first scan started after two slabs, 5.6 ms into the call; now after one).
+struct SlabEvents { std::vector<hipEvent_t> head, landed; };
+static int enqueue_slab_copies(hsk_ctx *c, EvList &evs, const ParseTiling &t, const u8 *h2d_src, const u8 *d_packed, u64 packed_bytes, SlabEvents &ev)
+{
+    hipStream_t s = c->d2h_stream;
+    u8 *dst = const_cast<u8 *>(d_packed);
+    ev.head.resize(t.nslabs); ev.landed.resize(t.nslabs);
+    const EvPair hp = prof_begin(c, 5, s);
+    for (u32 sl = 0; sl < t.nslabs; ++sl) {
+        const SlabBytes b = slab_bytes(t, sl, packed_bytes);
+        if (b.bh > b.b0) HIPCHK(c, hipMemcpyAsync(dst + b.b0, h2d_src + b.b0, b.bh - b.b0, hipMemcpyHostToDevice, s));
+        ev.head[sl] = evs.get();
+        HIPCHK(c, hipEventRecord(ev.head[sl], s));
+        if (b.b1 > b.bh) HIPCHK(c, hipMemcpyAsync(dst + b.bh, h2d_src + b.bh, b.b1 - b.bh, hipMemcpyHostToDevice, s));
+        ev.landed[sl] = evs.get();
+        HIPCHK(c, hipEventRecord(ev.landed[sl], s));
+    }
+    prof_end(c, hp, s);
+    return HSK_OK;
+}
+// `stream` may scan slab sl after this
+static int wait_for_slab(hsk_ctx *c, hipStream_t stream, const SlabEvents &ev, u32 sl)
+{
+    HIPCHK(c, hipStreamWaitEvent(stream, ev.landed[sl], 0));
+    if (sl + 1 < ev.head.size()) HIPCHK(c, hipStreamWaitEvent(stream, ev.head[sl + 1], 0));
+    return HSK_OK;
+}
+
 // the scan of the COUNT matrix: parse_scan_kernel (one workgroup) for the usual few dozen tasks, the three-kernel form from 128 columns on
 static int launch_parse_scan(hsk_ctx *c, hipStream_t st, const u64 *blk_cnt, u32 nblocks, u32 ntasks, const u32 *d_order, const u8 *d_skip,
                              u64 *d_task_tot, u64 *d_task_base, u64 *d_blk_base, u64 *d_run = nullptr, u64 *d_scratch = nullptr)
@@ -202,21 +326,119 @@ static int launch_parse_scan(hsk_ctx *c, hipStream_t st, const u64 *blk_cnt, u32
     if (!d_scratch) c->pool.release(d_part);              // (stream-ordered reuse: the caller's later work is enqueued on the same stream)
     return HSK_OK;
 }
-static bool parse_fast_enabled()
+static bool parse_fast_enabled() { return tune("parse_fast", 1) != 0; }
+
+// parse_count, part 1 -- the fast scan: its buffers, scan_kernel over the whole input or slab by slab behind the DMA copies (h2d_src),
+// the task totals and the verdict words; returns when the host has them
+static int count_fast_scan(hsk_ctx *c, ParseJob &j, const ParseTiling &t, const u8 *h2d_src, u64 *d_task_tot)
 {
-    return tune("parse_fast", 1) != 0;
+    ParseArgs &a = j.a;
+    const u8 *d_packed = a.packed;
+    int rc = scan_setup(c, j.scan, a, c->stream); if (rc) return rc;
+    if (c->call.zc_src) { a.packed = c->call.zc_src; a.packed_copy = (u32 *)const_cast<u8 *>(d_packed); }      // ingest fused into the scan
+    EvPair ep = prof_begin(c, 3, c->stream); ep.bytes = a.packed_bytes;
+    if (h2d_src) {
+        EvList evs(c); SlabEvents ev;
+        rc = enqueue_slab_copies(c, evs, t, h2d_src, d_packed, a.packed_bytes, ev); if (rc) return rc;
+        for (u32 sl = 0; sl < a.nslabs; ++sl) {
+            rc = wait_for_slab(c, c->stream, ev, sl); if (rc) return rc;
+            a.slab = sl;
+            launch_scan(c, c->stream, j.nblocks, j.ntasks, a);
+        }
+        a.slab = 0;
+    } else launch_scan(c, c->stream, j.nblocks, j.ntasks, a);
+    prof_end(c, ep, c->stream);
+    a.packed = d_packed; a.packed_copy = nullptr; c->call.zc_src = nullptr;                                  // everything after the scan reads the copy in HBM
+    hipLaunchKernelGGL(task_totals_kernel, dim3(1), dim3(HSK_MAX_TASKS), 0, c->stream, j.d_blk_cnt, j.nblocks, j.ntasks, d_task_tot);
+    rc = read_parse_flags(c, c->stream, j.scan, true); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(j.task_tot.data(), d_task_tot, (size_t)j.ntasks * 3 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hsk_sync(c, c->stream));
+    if (j.scan.d_dropped) c->call.dropped_now = parse_flags(c)->dropped;
+    if (j.scan.bins.items) j.scan.bins.nchunks = std::min(parse_flags(c)->chunks, j.scan.bins.cap);
+    return HSK_OK;
 }
-// Record slots per 2048-position tile.  A window of W k-mers starts a supermer every (W + 1) / 2 positions on random
-// sequence (+ one per 128 positions and per read): 40 % head room, a power of two from SCAN_REC_CAP (W >= 12) to 2048
-// (tiny windows); a tile that still overflows sends the parse through the general kernels.
-static u32 parse_rec_cap(int W)
+
+// parse_count, part 2 -- the verdict on the fast scan: counted, or one of the two ways on; an error, or the call again (retry_plan)
+enum ParseVerdict { PARSE_COUNTED, PARSE_GAPS, PARSE_OVERFLOW };
+static int count_verdict(hsk_ctx *c, const ParseJob &j, ParseVerdict &v)
 {
-    const int forced = tune("parse_rec_cap", 0) ? (int)std::min<long long>(std::max<long long>(tune("parse_rec_cap", 0), 1), (long long)PLACE_MAX_REC) : 0;
-    if (forced) return (u32)forced;
-    const u32 need = (u32)(1.4 * (2.0 * PARSE_TILE / (W + 1) + 40));
-    u32 cap = SCAN_REC_CAP;
-    while (cap < need && cap < 2048) cap <<= 1;
-    return cap;
+    const ParseFlags &f = *parse_flags(c);
+    v = PARSE_COUNTED;
+    bool gaps = c->call.roff_bad; c->call.roff_bad = false;
+    if (c->call.roff_check.valid() && !c->call.roff_check.get()) gaps = true;
+    if (gaps) { v = PARSE_GAPS; return HSK_OK; }                   // the host threads found a gap while the GPU scanned
+    if (c->call.index_unchecked) {
+        c->call.index_unchecked = false;
+        if (f.err & PARSE_ERR_INDEX) { (void)hipMemsetAsync(c->d_err, 0, 4, c->stream); return fail(c, HSK_ERR_INVALID_ARG, "the read index is not ascending / overlaps / leaves the packed buffer"); }
+    }
+    if (j.scan.bins.items && (f.err & PARSE_ERR_BINS)) {           // the call again, without the combining extraction
+        (void)hipMemsetAsync(c->d_err, 0, 4, c->stream); c->call.combine_veto = true; return retry_plan("the scan-placed items' chunk store or a bin's map ran out (error word)", f.err);
+    }
+    if (f.overflow && c->call.vt_shift) { c->call.combine_veto = true; return retry_plan("a tile beyond the record capacity"); }      // (the general kernels know no virtual tasks: the call again, without them)
+    if (f.overflow) v = PARSE_OVERFLOW;                            // a tile with more supermers than the record capacity: the general kernels
+    return HSK_OK;
+}
+// PARSE_GAPS: the buffer's reads do not lie back to back.  The caller's offsets (and lengths, where those were a guess from a sample)
+// are copied now and validated on the device; the fast part then runs again with them
+static int send_given_index(hsk_ctx *c, const u64 *d_roff, const u32 *d_rlen, u64 nreads, u64 packed_bytes)
+{
+    u64 *given = c->call.roff_given;
+    if (c->call.rlen_host) {
+        HIPCHK(c, hipMemcpyAsync(const_cast<u32 *>(d_rlen), c->call.rlen_host, nreads * 4, hipMemcpyHostToDevice, c->stream));
+        c->stats.h2d_bytes += nreads * 4; c->call.rlen_host = nullptr;
+    }
+    HIPCHK(c, hipMemcpyAsync(given, c->call.roff_host, nreads * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(given + nreads, d_roff + nreads, 8, hipMemcpyDeviceToDevice, c->stream));
+    hipLaunchKernelGGL(index_check_kernel, dim3(1024), dim3(256), 0, c->stream, given, d_rlen, nreads, packed_bytes, c->d_err);
+    c->call.index_unchecked = true;
+    c->stats.h2d_bytes += nreads * 8;
+    return HSK_OK;
+}
+// PARSE_OVERFLOW: the job leaves the fast path.  The general kernels know one tile range per workgroup and no records
+static void leave_fast_path(hsk_ctx *c, ParseJob &j)
+{
+    ParseArgs &a = j.a;
+    j.fast = false; c->stats.parse_fallbacks++;
+    c->call.dropped_now = 0;                                       // (the general kernels count again; they honour the same mask: several ranks stay consistent)
+    if (a.nslabs > 1) {
+        const ParseTiling t = call_tiling(c, a.packed_bytes);
+        ParseArgs b = make_parse_args(c, t, a.packed, a.packed_bytes, a.roff, a.rlen, a.nreads, a.rid_base, a.ntasks);
+        b.blk_cnt = a.blk_cnt; b.rec_cap = a.rec_cap; b.place_group = a.place_group;
+        a = b; j.nblocks = t.nblocks;
+    }
+    ScanBufs &s = j.scan;
+    c->pool.release(s.d_tile_r0); c->pool.release(s.d_tile_rec); c->pool.release(s.d_tile_nrec); c->pool.release(s.d_tile_sub);
+    s.d_tile_r0 = s.d_tile_rec = s.d_tile_nrec = s.d_tile_sub = nullptr;
+    a.tile_r0 = a.tile_rec = a.tile_nrec = a.tile_sub = nullptr;
+}
+
+// parse_count, part 3 -- the general kernels' COUNT (M > SCAN_MAX_M, "parse_fast=0", or after PARSE_OVERFLOW)
+static int count_general(hsk_ctx *c, ParseJob &j, u64 *d_task_tot)
+{
+    ParseArgs &a = j.a;
+    // task id per base position, kept from COUNT to EMIT (2 B x 4 x packed_bytes); optional: without it EMIT re-hashes
+    j.d_dest_cache = (u16 *)c->pool.alloc((size_t)a.ntiles * PARSE_TILE * 2);
+    a.dest_cache = j.d_dest_cache;
+    a.drop_mask = c->call.drop_mask_now;                               // (a fresh ParseArgs after a slab fallback has lost it)
+    if (a.drop_mask) {
+        if (!j.scan.d_dropped) DALLOC(c, j.scan.d_dropped, unsigned long long *, 256);
+        HIPCHK(c, hipMemsetAsync(j.scan.d_dropped, 0, 8, c->stream)); a.dropped = j.scan.d_dropped;
+    }
+    if (a.drop_mask) hipLaunchKernelGGL((parse_kernel<PARSE_COUNT, false, true>), dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)j.ntasks * 16, c->stream, a);
+    else hipLaunchKernelGGL((parse_kernel<PARSE_COUNT, false>), dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)j.ntasks * 16, c->stream, a);
+    hipLaunchKernelGGL(task_totals_kernel, dim3(1), dim3(HSK_MAX_TASKS), 0, c->stream, j.d_blk_cnt, j.nblocks, j.ntasks, d_task_tot);
+    int rc = read_parse_flags(c, c->stream, j.scan, false); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(j.task_tot.data(), d_task_tot, (size_t)j.ntasks * 3 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hsk_sync(c, c->stream));
+    if (a.drop_mask) c->call.dropped_now = parse_flags(c)->dropped;
+    // (hsk_count derives the read index only for the fast parse; should a derived index ever arrive here with its verdict still open, a
+    //  wrong guess must not be counted: the call fails instead of trusting lengths and offsets nobody has confirmed)
+    if (c->call.roff_check.valid() && !c->call.roff_check.get()) return fail(c, HSK_ERR_INTERNAL, "derived read index reached the general parse unverified and does not match the caller's");
+    if (c->call.index_unchecked) {
+        c->call.index_unchecked = false;
+        if (parse_flags(c)->err & PARSE_ERR_INDEX) { (void)hipMemsetAsync(c->d_err, 0, 4, c->stream); return fail(c, HSK_ERR_INVALID_ARG, "the read index is not ascending / overlaps / leaves the packed buffer"); }
+    }
+    return HSK_OK;
 }
 
 static int parse_count(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u64 *d_roff, const u32 *d_rlen, u64 nreads,
@@ -228,162 +450,38 @@ static int parse_count(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u
     if (nreads == 0 || packed_bytes == 0) return HSK_OK;            // nothing to parse on this rank
     j.empty = false;
     j.fast = parse_fast_enabled() && c->cfg.minimizer_size <= SCAN_MAX_M;
-    // slab ingest (hsk_count() from pinned memory): only the fast path hashes slab by slab; everything else wants the reads in HBM first
+    // slab ingest (hsk_count() from pinned memory): only the fast path hashes slab by slab, and only an input large enough for slabs;
+    // everything else wants the reads in HBM first
     const u8 *h2d_src = c->call.h2d_src; c->call.h2d_src = nullptr;
-    if (h2d_src && !j.fast) { HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed), h2d_src, packed_bytes, hipMemcpyHostToDevice, c->stream)); h2d_src = nullptr; }
-    j.a = make_parse_args(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, ntasks, &j.nblocks, h2d_src ? (u32)c->call.h2d_slabs : 1);
-    ParseArgs &a = j.a;
-    if (h2d_src && a.nslabs <= 1) { HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed), h2d_src, packed_bytes, hipMemcpyHostToDevice, c->stream)); h2d_src = nullptr; }   // (too small for slabs)
-    DALLOC(c, j.d_blk_cnt, u64 *, (size_t)1024 * ntasks * 3 * 8);
-    a.blk_cnt = j.d_blk_cnt;
+    const ParseTiling t = call_tiling(c, packed_bytes, h2d_src && j.fast ? (u32)c->call.h2d_slabs : 1);
+    if (h2d_src && t.nslabs <= 1) { HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed), h2d_src, packed_bytes, hipMemcpyHostToDevice, c->stream)); h2d_src = nullptr; }
+    j.a = make_parse_args(c, t, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, ntasks);
+    j.nblocks = t.nblocks;
+    DALLOC(c, j.d_blk_cnt, u64 *, (size_t)PARSE_MAX_BLOCKS * ntasks * 3 * 8);
+    j.a.blk_cnt = j.d_blk_cnt;
     u64 *d_task_tot; DALLOC(c, d_task_tot, u64 *, (size_t)ntasks * 3 * 8 + 64);
-    u32 *h_ovf = staging(c)->parse_flags;
-    *h_ovf = 0;
+    parse_flags(c)->overflow = 0;
+    int rc = HSK_OK;
     if (j.fast) {
-        a.rec_cap = parse_rec_cap(c->cfg.kmer_size - c->cfg.minimizer_size + 1);
-        a.place_group = std::max<u32>(1, std::min<u32>(16, PLACE_MAX_REC / a.rec_cap));
-        const bool bins = c->call.item_mode_now && c->call.combine_now && scan_place_enabled() && a.rec_cap <= PLACE_ITEM_REC;
-        DALLOC(c, j.d_overflow, u32 *, 256);
-        HIPCHK(c, hipMemsetAsync(j.d_overflow, 0, 4, c->stream));
-        a.overflow = j.d_overflow;
-        if (bins) {
-            int brc = bins_alloc(c, j.bins, ntasks, packed_bytes, nreads, c->cfg.kmer_size - c->cfg.minimizer_size + 1, c->stream); if (brc) return brc;
-            bins_args(c, a, j.bins);
-        } else {
-            DALLOC(c, j.d_tile_rec, u32 *, (size_t)a.ntiles * a.rec_cap * 4 + 64);
-            DALLOC(c, j.d_tile_nrec, u32 *, (size_t)a.ntiles * 4 + 64);
-            a.tile_rec = j.d_tile_rec; a.tile_nrec = j.d_tile_nrec;
-        }
-        if (c->cfg.extension && nreads < (1ULL << 32)) { DALLOC(c, j.d_tile_r0, u32 *, (size_t)a.ntiles * 4 + 64); a.tile_r0 = j.d_tile_r0; }
-        if (!bins && c->call.combine_now && a.rec_cap <= PLACE_ITEM_REC) { DALLOC(c, j.d_tile_sub, u32 *, (size_t)a.ntiles * a.rec_cap * 4 + 64); a.tile_sub = j.d_tile_sub; }
-        const bool profile = (c->cfg.flags & HSK_FLAG_PROFILE) != 0;
-        if (c->call.zc_src) { a.packed = c->call.zc_src; a.packed_copy = (u32 *)const_cast<u8 *>(d_packed); }      // ingest fused into the scan
-        EvPair ep{}; if (profile) { ep.a = ev_get(c); ep.b = ev_get(c); ep.kind = 3; ep.bytes = packed_bytes; (void)hipEventRecord(ep.a, c->stream); }
-        const bool scan_generic = tune("scan_generic", 0) != 0;      // (tests: the default (k, m) through the generic instance)
-        c->call.dropped_now = 0;
-        a.drop_mask = bins ? 0u : c->call.drop_mask_now;
-        if (a.drop_mask) { DALLOC(c, j.d_dropped, unsigned long long *, 256); HIPCHK(c, hipMemsetAsync(j.d_dropped, 0, 8, c->stream)); a.dropped = j.d_dropped; }
-        auto launch_scan = [&]() {
-            if (a.drop_mask) hipLaunchKernelGGL((scan_kernel<0, 0, false, true>), dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, c->stream, a);
-            else if (a.bins) {
-                if (a.k == 31 && a.m == 17 && !scan_generic) hipLaunchKernelGGL((scan_kernel<31, 17, true>), dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, c->stream, a);
-                else hipLaunchKernelGGL((scan_kernel<0, 0, true>), dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, c->stream, a);
-            }
-            else if (a.k == 31 && a.m == 17 && !scan_generic) hipLaunchKernelGGL((scan_kernel<31, 17>), dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, c->stream, a);
-            else if (a.k == 51 && a.m == 17 && !scan_generic) hipLaunchKernelGGL((scan_kernel<51, 17>), dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, c->stream, a);
-            else hipLaunchKernelGGL((scan_kernel<0, 0>), dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, c->stream, a);
-        };
-        if (h2d_src) {
-            // The packed reads cross PCIe as DMA copies, slab by slab, on the copy stream; the scan of slab s is launched behind the
-            // copy of slab s + 1 (a tile's windows reach a few words into the next tile), so the link and the VALUs work side by side:
-            // the parse takes about as long as the transfer (a kernel reading the host buffer in place gets ~40 GB/s out of the link,
-            // the DMA engine ~55).
-            EvList evs(c);
-            std::vector<hipEvent_t> landed(a.nslabs), head(a.nslabs);      // (head: the first SLAB_HEAD bytes of a slab -- all the scan of the slab before it needs of it)
-            EvPair hp{}; if (profile) { hp.a = ev_get(c); hp.b = ev_get(c); hp.kind = 5; (void)hipEventRecord(hp.a, c->d2h_stream); }
-            for (u32 sl = 0; sl < a.nslabs; ++sl) {
-                const u64 b0 = std::min<u64>((u64)sl * a.slab_tiles * (PARSE_TILE / 4), packed_bytes), b1 = std::min<u64>(((u64)sl + 1) * a.slab_tiles * (PARSE_TILE / 4), packed_bytes);
-                const u64 bh = std::min<u64>(b0 + SLAB_HEAD, b1);
-                if (bh > b0) HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed) + b0, h2d_src + b0, bh - b0, hipMemcpyHostToDevice, c->d2h_stream));
-                head[sl] = evs.get();
-                HIPCHK(c, hipEventRecord(head[sl], c->d2h_stream));
-                if (b1 > bh) HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed) + bh, h2d_src + bh, b1 - bh, hipMemcpyHostToDevice, c->d2h_stream));
-                landed[sl] = evs.get();
-                HIPCHK(c, hipEventRecord(landed[sl], c->d2h_stream));
-            }
-            if (profile) { (void)hipEventRecord(hp.b, c->d2h_stream); c->ev_pending.push_back(hp); }
-            for (u32 sl = 0; sl < a.nslabs; ++sl) {
-                HIPCHK(c, hipStreamWaitEvent(c->stream, landed[sl], 0));
-                if (sl + 1 < a.nslabs) HIPCHK(c, hipStreamWaitEvent(c->stream, head[sl + 1], 0));
-                a.slab = sl;
-                launch_scan();
-            }
-            a.slab = 0;
-        } else launch_scan();
-        if (profile) { (void)hipEventRecord(ep.b, c->stream); c->ev_pending.push_back(ep); }
-        a.packed = d_packed; a.packed_copy = nullptr; c->call.zc_src = nullptr;                                  // everything after the scan reads the copy in HBM
-        hipLaunchKernelGGL(task_totals_kernel, dim3(1), dim3(HSK_MAX_TASKS), 0, c->stream, j.d_blk_cnt, j.nblocks, ntasks, d_task_tot);
-        HIPCHK(c, hipMemcpyAsync(h_ovf, j.d_overflow, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(h_ovf + 1, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
-        if (j.bins.items) HIPCHK(c, hipMemcpyAsync(h_ovf + 2, j.bins.ctl, 4, hipMemcpyDeviceToHost, c->stream));
-        if (j.d_dropped) HIPCHK(c, hipMemcpyAsync(h_ovf + 4, j.d_dropped, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(j.task_tot.data(), d_task_tot, (size_t)ntasks * 3 * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hsk_sync(c, c->stream));
-        if (j.d_dropped) c->call.dropped_now = *(const unsigned long long *)(h_ovf + 4);
-        if (j.bins.items) j.bins.nchunks = std::min(h_ovf[2], j.bins.cap);
-        bool gaps = c->call.roff_bad; c->call.roff_bad = false;
-        if (c->call.roff_check.valid() && !c->call.roff_check.get()) gaps = true;
-        if (gaps) {
-            // the buffer's reads do not lie back to back (the host threads found a gap while the GPU scanned): everything again
-            // with the caller's offsets, copied now and validated on the device
-            u64 *given = c->call.roff_given;
+        ParseVerdict v = PARSE_COUNTED;
+        rc = count_fast_scan(c, j, t, h2d_src, d_task_tot);
+        if (rc == HSK_OK) rc = count_verdict(c, j, v);
+        if (rc == HSK_OK && v == PARSE_GAPS) {                      // everything again with the caller's offsets: a second call of the fast part
             c->pool.release(d_task_tot);
             parse_release(c, j);
-            if (c->call.rlen_host) {                                    // (the lengths were a guess from a sample: the real ones now)
-                HIPCHK(c, hipMemcpyAsync(const_cast<u32 *>(d_rlen), c->call.rlen_host, nreads * 4, hipMemcpyHostToDevice, c->stream));
-                c->stats.h2d_bytes += nreads * 4; c->call.rlen_host = nullptr;
-            }
-            HIPCHK(c, hipMemcpyAsync(given, c->call.roff_host, nreads * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(given + nreads, d_roff + nreads, 8, hipMemcpyDeviceToDevice, c->stream));
-            hipLaunchKernelGGL(index_check_kernel, dim3(1024), dim3(256), 0, c->stream, given, d_rlen, nreads, packed_bytes, c->d_err);
-            c->call.index_unchecked = true;
-            c->stats.h2d_bytes += nreads * 8;
-            return parse_count(c, d_packed, packed_bytes, given, d_rlen, nreads, rid_base, ntasks, j);
+            rc = send_given_index(c, d_roff, d_rlen, nreads, packed_bytes); if (rc) return rc;
+            return parse_count(c, d_packed, packed_bytes, c->call.roff_given, d_rlen, nreads, rid_base, ntasks, j);
         }
-        if (c->call.index_unchecked) {
-            c->call.index_unchecked = false;
-            if (h_ovf[1] & 32u) { (void)hipMemsetAsync(c->d_err, 0, 4, c->stream); c->pool.release(d_task_tot); return fail(c, HSK_ERR_INVALID_ARG, "the read index is not ascending / overlaps / leaves the packed buffer"); }
-        }
-        if (j.bins.items && (h_ovf[1] & (2u | 128u | 256u))) {          // the chunk store or a bin's map ran out: the call again, without the combining extraction
-            (void)hipMemsetAsync(c->d_err, 0, 4, c->stream); c->pool.release(d_task_tot); c->call.combine_veto = true; return retry_plan("the scan-placed items' chunk store or a bin's map ran out (error word)", h_ovf[1]);
-        }
-        if (*h_ovf && c->call.vt_shift) { c->pool.release(d_task_tot); c->call.combine_veto = true; return retry_plan("a tile beyond the record capacity"); }      // (the general kernels know no virtual tasks: the call again, without them)
-        if (*h_ovf) {                                                // a tile with more supermers than the record capacity
-            j.fast = false; c->stats.parse_fallbacks++;
-            c->call.dropped_now = 0;                                       // (the general kernels count again; they honour the same mask: several ranks stay consistent)
-            if (a.nslabs > 1) {                                       // the general kernels know one tile range per workgroup
-                ParseArgs b = make_parse_args(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, ntasks, &j.nblocks);
-                b.blk_cnt = a.blk_cnt; b.rec_cap = a.rec_cap; b.place_group = a.place_group;
-                a = b;
-            }
-            c->pool.release(j.d_tile_r0); j.d_tile_r0 = nullptr; a.tile_r0 = nullptr;
-            c->pool.release(j.d_tile_rec); c->pool.release(j.d_tile_nrec); j.d_tile_rec = j.d_tile_nrec = nullptr;
-            a.tile_rec = a.tile_nrec = nullptr;
-            c->pool.release(j.d_tile_sub); j.d_tile_sub = nullptr; a.tile_sub = nullptr;
-        }
+        if (rc == HSK_OK && v == PARSE_OVERFLOW) leave_fast_path(c, j);
     }
-    if (c->call.zc_src) {                                                  // the general kernels read the reads more than once: plain copy first
+    if (rc == HSK_OK && c->call.zc_src) {                           // the general kernels read the reads more than once: plain copy first
         HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed), c->call.zc_src, packed_bytes, hipMemcpyDefault, c->stream));
         c->call.zc_src = nullptr;
     }
-    if (!j.fast) {
-        // task id per base position, kept from COUNT to EMIT (2 B x 4 x packed_bytes); optional: without it EMIT re-hashes
-        j.d_dest_cache = (u16 *)c->pool.alloc((size_t)a.ntiles * PARSE_TILE * 2);
-        a.dest_cache = j.d_dest_cache;
-        a.drop_mask = c->call.drop_mask_now;                               // (a fresh ParseArgs after a slab fallback has lost it)
-        if (a.drop_mask) {
-            if (!j.d_dropped) DALLOC(c, j.d_dropped, unsigned long long *, 256);
-            HIPCHK(c, hipMemsetAsync(j.d_dropped, 0, 8, c->stream)); a.dropped = j.d_dropped;
-        }
-        if (a.drop_mask) hipLaunchKernelGGL((parse_kernel<PARSE_COUNT, false, true>), dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, c->stream, a);
-        else hipLaunchKernelGGL((parse_kernel<PARSE_COUNT, false>), dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, c->stream, a);
-        hipLaunchKernelGGL(task_totals_kernel, dim3(1), dim3(HSK_MAX_TASKS), 0, c->stream, j.d_blk_cnt, j.nblocks, ntasks, d_task_tot);
-        HIPCHK(c, hipMemcpyAsync(h_ovf + 1, c->d_err, 4, hipMemcpyDeviceToHost, c->stream));
-        if (a.drop_mask) HIPCHK(c, hipMemcpyAsync(h_ovf + 4, j.d_dropped, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(j.task_tot.data(), d_task_tot, (size_t)ntasks * 3 * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hsk_sync(c, c->stream));
-        if (a.drop_mask) c->call.dropped_now = *(const unsigned long long *)(h_ovf + 4);
-        // (hsk_count derives the read index only for the fast parse; should a derived index ever arrive here with its verdict still open, a
-        //  wrong guess must not be counted: the call fails instead of trusting lengths and offsets nobody has confirmed)
-        if (c->call.roff_check.valid() && !c->call.roff_check.get()) { c->pool.release(d_task_tot); return fail(c, HSK_ERR_INTERNAL, "derived read index reached the general parse unverified and does not match the caller's"); }
-        if (c->call.index_unchecked) {
-            c->call.index_unchecked = false;
-            if (h_ovf[1] & 32u) { (void)hipMemsetAsync(c->d_err, 0, 4, c->stream); c->pool.release(d_task_tot); return fail(c, HSK_ERR_INVALID_ARG, "the read index is not ascending / overlaps / leaves the packed buffer"); }
-        }
-    }
-    HIPCHK(c, hipGetLastError());
+    if (rc == HSK_OK && !j.fast) rc = count_general(c, j, d_task_tot);
+    if (rc == HSK_OK) HIPCHK(c, hipGetLastError());
     c->pool.release(d_task_tot);
-    return HSK_OK;
+    return rc;
 }
 
 // `order` (storage order of tasks) must be a permutation of 0..ntasks-1.
@@ -417,11 +515,18 @@ static int parse_place(hsk_ctx *c, ParseJob &j, const std::vector<u32> &order, S
     }
     a.task_skip = d_skip;
     { int prc = launch_parse_scan(c, c->stream, j.d_blk_cnt, j.nblocks, ntasks, d_order, d_skip, d_task_tot, d_task_base, d_blk_base); if (prc) return prc; }
-    const bool from_bins = j.fast && j.bins.items != nullptr && !skip && !supermers_travel && !ext;      // scan_kernel has placed the items already
+    // the small matrices are released once their last reader is enqueued (pool reuse is stream-ordered: every later user of these
+    // blocks is enqueued on the same stream)
+    auto done = [&](int rc) {
+        c->pool.release(d_blk_base); c->pool.release(d_task_tot); c->pool.release(d_task_base); c->pool.release(d_order); c->pool.release(d_skip);
+        a.task_skip = nullptr;
+        return rc;
+    };
+    const bool from_bins = j.fast && j.scan.bins.items != nullptr && !skip && !supermers_travel && !ext;      // scan_kernel has placed the items already
     const bool item_mode = from_bins || (j.fast && a.tile_sub && !skip && !supermers_travel && !ext);      // combining extraction: the slots hold the supermers themselves
     if (!item_mode) DALLOC(c, st.sm_len, u8 *, st.tot_sup + 64);
     // byte-store mode (fast parse path): the supermers' bases are copied into per-task byte runs while the reads stream through
-    // place_bytes_kernel once; positions are kept only where something still needs them (EXTENSION: pos / rid lookup)
+    // the byte placement once; positions are kept only where something still needs them (EXTENSION: pos / rid lookup)
     bool bytes_mode = !item_mode && j.fast && place_bytes_enabled(supermers_travel) && a.rec_cap <= PLACE_BYTES_REC;
     for (u32 t = 0; t < ntasks && bytes_mode; ++t) if (st.task_tot[3 * t + 1] >= (1ULL << 32)) bytes_mode = false;     // 32-bit offsets inside a task's run
     // several ranks with the combining extraction planned (c->call.combine_now): the supermers' minimizer bits go into the store as well
@@ -437,50 +542,27 @@ static int parse_place(hsk_ctx *c, ParseJob &j, const std::vector<u32> &order, S
     if ((!bytes_mode && !item_mode) || ext) DALLOC(c, st.sm_gpos, u64 *, st.tot_sup * 8 + 64);      // position mode: bases stay in the packed reads
     if (ext) { DALLOC(c, st.sm_pos, u32 *, st.tot_sup * 4 + 64); DALLOC(c, st.sm_rid, int32_t *, st.tot_sup * 4 + 64); }
     a.sm_sub = nullptr; a.sm_item = nullptr;
-    if (from_bins) {
-        int brc = bins_to_store(c, j.bins, st, ntasks, c->call.vt_shift, c->stream);
-        c->pool.release(d_blk_base); c->pool.release(d_task_tot); c->pool.release(d_task_base); c->pool.release(d_order); c->pool.release(d_skip);
-        a.task_skip = nullptr;
-        return brc;
-    }
+    if (from_bins) return done(bins_to_store(c, j.scan.bins, st, ntasks, c->call.vt_shift, c->stream));
     if (item_mode) { DALLOC(c, st.sm_sub, u32 *, st.tot_sup * 4 + 64); DALLOC(c, st.sm_item, u64 *, st.tot_sup * 16 + 64); a.sm_sub = st.sm_sub; a.sm_item = st.sm_item; }
     a.blk_base = d_blk_base; a.sm_len = st.sm_len; a.sm_gpos = st.sm_gpos; a.sm_bytes = st.sm_bytes; a.sm_boff = st.sm_boff; a.task_base3 = d_task_base;
     if (st.tot_sup) {
         if (j.fast) {
-            const bool profile = (c->cfg.flags & HSK_FLAG_PROFILE) != 0;
-            EvPair ep{}; if (profile) { ep.a = ev_get(c); ep.b = ev_get(c); ep.kind = 4; ep.keys = st.tot_sup; (void)hipEventRecord(ep.a, c->stream); }
-            if (bytes_mode) {
-                ParseArgs ab = a;
-                ab.place_group = std::max<u32>(1, std::min<u32>(PLACE_BYTES_TILES, PLACE_BYTES_REC / a.rec_cap));
-                const size_t lds = (size_t)ntasks * 40 + PLACE_BYTES_REC * 8 + PLACE_BYTES_WORDS * 4 + (ab.sm_sub16 ? PLACE_BYTES_REC * 2 : 0);
-                static bool announced = false;
-                if (!announced) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(place_bytes_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512); announced = true; }
-                hipLaunchKernelGGL(place_bytes_kernel, dim3(j.nblocks), dim3(PLACE_BYTES_THREADS), lds, c->stream, ab);
-            } else if (item_mode) {
-                ParseArgs ai = a;
-                ai.place_group = std::max<u32>(1, std::min<u32>(PLACE_ITEM_TILES, PLACE_ITEM_REC / a.rec_cap));
-                hipLaunchKernelGGL(place_items_kernel, dim3(j.nblocks), dim3(PLACE_ITEM_THREADS), place_items_lds(ntasks), c->stream, ai);
-            } else hipLaunchKernelGGL(place_kernel, dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16 + PLACE_MAX_REC * 4, c->stream, a);
-            if (profile) { (void)hipEventRecord(ep.b, c->stream); c->ev_pending.push_back(ep); }
+            EvPair ep = prof_begin(c, 4, c->stream); ep.keys = st.tot_sup;
+            launch_place(c, c->stream, bytes_mode ? PLACE_BYTES : item_mode ? PLACE_ITEMS : PLACE_RECORDS, a, j.nblocks, ntasks);
+            prof_end(c, ep, c->stream);
         }
-        else if (a.dest_cache) hipLaunchKernelGGL(emit_kernel, dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, c->stream, a);
-        else if (a.drop_mask) hipLaunchKernelGGL((parse_kernel<PARSE_EMIT, false, true>), dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, c->stream, a);
-        else hipLaunchKernelGGL((parse_kernel<PARSE_EMIT, false>), dim3(j.nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, c->stream, a);
+        else launch_emit(c, c->stream, a, j.nblocks, ntasks);
         if (ext) hipLaunchKernelGGL(resolve_pos_rid_kernel, dim3((u32)std::min<u64>((st.tot_sup + 255) / 256, 8192)), dim3(256), 0, c->stream,
-                                    st.sm_gpos, st.tot_sup, j.d_roff, j.nreads, j.rid_base, st.sm_pos, st.sm_rid, (const u32 *)j.d_tile_r0, a.ntiles);
+                                    st.sm_gpos, st.tot_sup, j.d_roff, j.nreads, j.rid_base, st.sm_pos, st.sm_rid, (const u32 *)j.scan.d_tile_r0, a.ntiles);
     }
     HIPCHK(c, hipGetLastError());
-    // the small matrices are released after the stream has consumed them (pool reuse is stream-ordered:
-    // every later user of these blocks is enqueued on the same stream)
-    c->pool.release(d_blk_base); c->pool.release(d_task_tot); c->pool.release(d_task_base); c->pool.release(d_order); c->pool.release(d_skip);
-    a.task_skip = nullptr;
-    return HSK_OK;
+    return done(HSK_OK);
 }
 
 // hsk_count() from pinned host memory on one GPU (no payload): ingest, scan and placement as ONE pipeline over slabs.
 //   copy stream   DMA copy of slab s + 2          (the link: ~55 GB/s, the floor of the whole parse)
 //   main stream   scan_kernel of slab s            (behind the copy of slab s + 1; the VALUs have ~0.8 ms to spare per slab)
-//   second stream task totals, slot bases and place_kernel of slab s - 1   (fills those gaps: the placement, 8.6 ms when it
+//   second stream task totals, slot bases and the placement of slab s - 1   (fills those gaps: the placement, 8.6 ms when it
 //                 runs after the last scan, is off the critical path)
 // The store is laid out [slab][task] (a slab's slot bases need only the slabs before it: parse_scan_kernel carries the
 // running totals on the device), so a task's supermers are one segment per slab (`segs`), which the extraction takes like the
@@ -488,143 +570,57 @@ static int parse_place(hsk_ctx *c, ParseJob &j, const std::vector<u32> &order, S
 // are in HBM, the caller takes parse_count / parse_place (a tile beyond the record capacity, an index that needs the
 // caller's offsets, a device-side index check that failed).
 constexpr int PARSE_FALLBACK = -1000;
-static int parse_ingest_pipelined(hsk_ctx *c, const u8 *h2d_src, const u8 *d_packed, u64 packed_bytes, const u64 *d_roff, const u32 *d_rlen, u64 nreads,
-                                  int64_t rid_base, u32 ntasks, SupermerStore &st, std::vector<TaskSegs> &segs)
+// its buffers: the scan's, a COUNT matrix per slab, and what the slabs' placements share
+struct PipeBufs {
+    ScanBufs scan;
+    u64 *d_blk_cnt = nullptr, *d_blk_base = nullptr, *d_tot = nullptr, *d_task_base = nullptr, *d_run = nullptr, *d_ps = nullptr; u32 *d_order = nullptr;
+};
+static void pipe_release(hsk_ctx *c, PipeBufs &p)
 {
-    u32 nblocks = 0;
-    ParseArgs a = make_parse_args(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, ntasks, &nblocks, (u32)c->call.h2d_slabs);
-    if (a.nslabs <= 1) return PARSE_FALLBACK;
-    const u32 nsl = a.nslabs;
-    const bool profile = (c->cfg.flags & HSK_FLAG_PROFILE) != 0;
-    a.rec_cap = parse_rec_cap(c->cfg.kmer_size - c->cfg.minimizer_size + 1);
-    a.place_group = std::max<u32>(1, std::min<u32>(16, PLACE_MAX_REC / a.rec_cap));
-    a.place_one = 1;
-    const bool bins = c->call.item_mode_now && c->call.combine_now && scan_place_enabled() && a.rec_cap <= PLACE_ITEM_REC;      // scan_kernel places the items itself: no records, no placement kernel
-    ScanBins sbins;
-    u64 *d_blk_cnt, *d_blk_base, *d_tot, *d_task_base, *d_run; u32 *d_order, *d_tile_rec = nullptr, *d_tile_nrec = nullptr, *d_overflow, *d_tile_sub = nullptr;
+    scan_release(c, p.scan);
+    c->pool.release(p.d_blk_cnt); c->pool.release(p.d_blk_base); c->pool.release(p.d_tot); c->pool.release(p.d_task_base); c->pool.release(p.d_run); c->pool.release(p.d_ps); c->pool.release(p.d_order);
+    p = PipeBufs();
+}
+// buffers, store (at most rec_cap supermers per tile -- a tile beyond that falls back; its real size is known when the last slab is in)
+// and the arguments; everything it enqueues is on the main stream
+static int pipe_setup(hsk_ctx *c, PipeBufs &p, ParseArgs &a, u32 nblocks, SupermerStore &st)
+{
+    const u32 ntasks = a.ntasks, nsl = a.nslabs;
     const size_t mat = (size_t)nblocks * ntasks;
-    DALLOC(c, d_blk_cnt, u64 *, mat * 3 * 8 * nsl);
-    DALLOC(c, d_blk_base, u64 *, mat * 2 * 8);
-    DALLOC(c, d_tot, u64 *, (size_t)nsl * ntasks * 3 * 8 + 64);
-    DALLOC(c, d_task_base, u64 *, (size_t)ntasks * 3 * 8);
-    DALLOC(c, d_run, u64 *, 256);
-    DALLOC(c, d_order, u32 *, (size_t)ntasks * 4);
-    if (!bins) { DALLOC(c, d_tile_rec, u32 *, (size_t)a.ntiles * a.rec_cap * 4 + 64); DALLOC(c, d_tile_nrec, u32 *, (size_t)a.ntiles * 4 + 64); }
-    DALLOC(c, d_overflow, u32 *, 256);
-    if (!bins && c->call.combine_now && a.rec_cap <= PLACE_ITEM_REC) DALLOC(c, d_tile_sub, u32 *, (size_t)a.ntiles * a.rec_cap * 4 + 64);
-    if (bins) { int brc = bins_alloc(c, sbins, ntasks, packed_bytes, nreads, c->cfg.kmer_size - c->cfg.minimizer_size + 1, c->stream); if (brc) return brc; }
-    u64 *d_ps; DALLOC(c, d_ps, u64 *, (size_t)PS_SEGS * ntasks * 3 * 8);
-    unsigned long long *d_dropped = nullptr;                                // scan_kernel<.., DROP>: positions left out (CallState::drop_mask_now)
-    // the store holds at most rec_cap supermers per tile (a tile beyond that falls back); its real size is known when the last slab is in
+    DALLOC(c, p.d_blk_cnt, u64 *, mat * 3 * 8 * nsl);
+    DALLOC(c, p.d_blk_base, u64 *, mat * 2 * 8);
+    DALLOC(c, p.d_tot, u64 *, (size_t)nsl * ntasks * 3 * 8 + 64);
+    DALLOC(c, p.d_task_base, u64 *, (size_t)ntasks * 3 * 8);
+    DALLOC(c, p.d_run, u64 *, 256);
+    DALLOC(c, p.d_order, u32 *, (size_t)ntasks * 4);
+    DALLOC(c, p.d_ps, u64 *, (size_t)PS_SEGS * ntasks * 3 * 8);
+    int rc = scan_setup(c, p.scan, a, c->stream); if (rc) return rc;
     const u64 cap_sup = a.ntiles * (u64)a.rec_cap;
     st = SupermerStore();
     st.ntasks = ntasks; st.nblocks = nblocks;
-    if (bins) {}                                                            // (the items live in the bins' chunk store)
-    else if (d_tile_sub) { DALLOC(c, st.sm_sub, u32 *, cap_sup * 4 + 64); DALLOC(c, st.sm_item, u64 *, cap_sup * 16 + 64); }      // item mode (combining extraction)
+    if (a.bins) {}                                                          // (the items live in the bins' chunk store)
+    else if (a.tile_sub) { DALLOC(c, st.sm_sub, u32 *, cap_sup * 4 + 64); DALLOC(c, st.sm_item, u64 *, cap_sup * 16 + 64); }      // item mode (combining extraction)
     else { DALLOC(c, st.sm_len, u8 *, cap_sup + 64); DALLOC(c, st.sm_gpos, u64 *, cap_sup * 8 + 64); }
-    auto release_all = [&]() {
-        bins_release(c, sbins);
-        c->pool.release(d_tile_sub); c->pool.release(d_ps); c->pool.release(d_dropped);
-        c->pool.release(d_blk_cnt); c->pool.release(d_blk_base); c->pool.release(d_tot); c->pool.release(d_task_base); c->pool.release(d_run);
-        c->pool.release(d_order); c->pool.release(d_tile_rec); c->pool.release(d_tile_nrec); c->pool.release(d_overflow);
-    };
-    std::vector<u32> order(ntasks); for (u32 t = 0; t < ntasks; ++t) order[t] = t;
-    st.order = order;
+    st.order.resize(ntasks); for (u32 t = 0; t < ntasks; ++t) st.order[t] = t;
     u32 *h_order = (u32 *)((char *)c->pinned + (128u << 10));              // (pinned staging: the copy is asynchronous)
-    memcpy(h_order, order.data(), (size_t)ntasks * 4);
-    hipStream_t sA = c->stream, sB = c->comm_stream, sC = c->d2h_stream;
-    HIPCHK(c, hipMemsetAsync(d_overflow, 0, 4, sA));
-    HIPCHK(c, hipMemsetAsync(d_run, 0, 24, sA));
-    HIPCHK(c, hipMemcpyAsync(d_order, h_order, (size_t)ntasks * 4, hipMemcpyHostToDevice, sA));
-    a.tile_rec = d_tile_rec; a.tile_nrec = d_tile_nrec; a.overflow = d_overflow;
-    a.sm_len = st.sm_len; a.sm_gpos = st.sm_gpos; a.blk_base = d_blk_base; a.task_base3 = d_task_base;
-    a.tile_sub = d_tile_sub; a.sm_sub = st.sm_sub; a.sm_item = st.sm_item;
-    if (d_tile_sub) a.place_group = std::max<u32>(1, std::min<u32>(PLACE_ITEM_TILES, PLACE_ITEM_REC / a.rec_cap));
-    if (bins) bins_args(c, a, sbins);
-    c->call.dropped_now = 0;
-    a.drop_mask = bins ? 0u : c->call.drop_mask_now;
-    if (a.drop_mask) { DALLOC(c, d_dropped, unsigned long long *, 256); HIPCHK(c, hipMemsetAsync(d_dropped, 0, 8, sA)); a.dropped = d_dropped; }
-    EvList evs(c);
-    hipEvent_t ready = evs.get();                                          // the small buffers above are set up; the second stream may start
-    HIPCHK(c, hipEventRecord(ready, sA));
-    HIPCHK(c, hipStreamWaitEvent(sB, ready, 0));
-    // A slab's scan reaches PARSE_WORDS - 128 words into the NEXT slab (the windows of its last k-mers), not further: every slab's first
-    // SLAB_HEAD bytes travel as a copy of their own with an event (`head`), and the scan of slab s waits for slab s and for the head of slab
-    // s + 1 -- not for all of slab s + 1 (the first scan started after two slabs, 5.6 ms into the call; now after one)
-    std::vector<hipEvent_t> landed(nsl), head(nsl), scanned(nsl);
-    EvPair hp{}; if (profile) { hp.a = ev_get(c); hp.b = ev_get(c); hp.kind = 5; (void)hipEventRecord(hp.a, sC); }
-    for (u32 sl = 0; sl < nsl; ++sl) {
-        const u64 b0 = std::min<u64>((u64)sl * a.slab_tiles * (PARSE_TILE / 4), packed_bytes), b1 = std::min<u64>(((u64)sl + 1) * a.slab_tiles * (PARSE_TILE / 4), packed_bytes);
-        const u64 bh = std::min<u64>(b0 + SLAB_HEAD, b1);
-        if (bh > b0) HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed) + b0, h2d_src + b0, bh - b0, hipMemcpyHostToDevice, sC));
-        head[sl] = evs.get();
-        HIPCHK(c, hipEventRecord(head[sl], sC));
-        if (b1 > bh) HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed) + bh, h2d_src + bh, b1 - bh, hipMemcpyHostToDevice, sC));
-        landed[sl] = evs.get();
-        HIPCHK(c, hipEventRecord(landed[sl], sC));
-    }
-    if (profile) { (void)hipEventRecord(hp.b, sC); c->ev_pending.push_back(hp); }
-    EvPair sp{}, pp{};
-    if (profile) { sp.a = ev_get(c); sp.b = ev_get(c); sp.kind = 3; sp.bytes = packed_bytes; (void)hipEventRecord(sp.a, sA);
-                   pp.a = ev_get(c); pp.b = ev_get(c); pp.kind = 4; (void)hipEventRecord(pp.a, sB); }
-    const bool scan_generic = tune("scan_generic", 0) != 0;
-    for (u32 sl = 0; sl < nsl; ++sl) {
-        HIPCHK(c, hipStreamWaitEvent(sA, landed[sl], 0));
-        if (sl + 1 < nsl) HIPCHK(c, hipStreamWaitEvent(sA, head[sl + 1], 0));
-        a.slab = sl; a.blk_cnt = d_blk_cnt + (size_t)sl * mat * 3;
-        if (a.drop_mask) hipLaunchKernelGGL((scan_kernel<0, 0, false, true>), dim3(nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, sA, a);
-        else if (a.bins) {
-            if (a.k == 31 && a.m == 17 && !scan_generic) hipLaunchKernelGGL((scan_kernel<31, 17, true>), dim3(nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, sA, a);
-            else hipLaunchKernelGGL((scan_kernel<0, 0, true>), dim3(nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, sA, a);
-        }
-        else if (a.k == 31 && a.m == 17 && !scan_generic) hipLaunchKernelGGL((scan_kernel<31, 17>), dim3(nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, sA, a);
-        else if (a.k == 51 && a.m == 17 && !scan_generic) hipLaunchKernelGGL((scan_kernel<51, 17>), dim3(nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, sA, a);
-        else hipLaunchKernelGGL((scan_kernel<0, 0>), dim3(nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16, sA, a);
-        scanned[sl] = evs.get();
-        HIPCHK(c, hipEventRecord(scanned[sl], sA));
-        // the slab's placement on the second stream: totals, bases (behind everything the slabs before laid out), supermers to their slots
-        HIPCHK(c, hipStreamWaitEvent(sB, scanned[sl], 0));
-        { int prc = launch_parse_scan(c, sB, (const u64 *)a.blk_cnt, nblocks, ntasks, (const u32 *)d_order, (const u8 *)nullptr,
-                                      d_tot + (size_t)sl * ntasks * 3, d_task_base, d_blk_base, d_run, d_ps); if (prc) return prc; }
-        if (bins) {}                                                        // (placed by the scan)
-        else if (d_tile_sub) hipLaunchKernelGGL(place_items_kernel, dim3(nblocks), dim3(PLACE_ITEM_THREADS), place_items_lds(ntasks), sB, a);
-        else hipLaunchKernelGGL(place_kernel, dim3(nblocks), dim3(PARSE_THREADS), (size_t)ntasks * 16 + PLACE_MAX_REC * 4, sB, a);
-    }
-    if (profile) { (void)hipEventRecord(sp.b, sA); c->ev_pending.push_back(sp); (void)hipEventRecord(pp.b, sB); }
-    // the verdicts and the totals
-    u32 *h_flags = staging(c)->parse_flags;
-    std::vector<u64> tot((size_t)nsl * ntasks * 3);
-    u64 *h_tot = (u64 *)((char *)c->pinned + (192u << 10));
-    const bool staged = (size_t)nsl * ntasks * 24 <= (64u << 10);
-    HIPCHK(c, hipMemcpyAsync(h_flags, d_overflow, 4, hipMemcpyDeviceToHost, sB));
-    HIPCHK(c, hipMemcpyAsync(h_flags + 1, c->d_err, 4, hipMemcpyDeviceToHost, sB));
-    if (bins) HIPCHK(c, hipMemcpyAsync(h_flags + 2, sbins.ctl, 4, hipMemcpyDeviceToHost, sB));
-    if (d_dropped) HIPCHK(c, hipMemcpyAsync(h_flags + 4, d_dropped, 8, hipMemcpyDeviceToHost, sB));      // (sB is behind every scan: placed / scanned events)
-    HIPCHK(c, hipMemcpyAsync(staged ? h_tot : tot.data(), d_tot, (size_t)nsl * ntasks * 24, hipMemcpyDeviceToHost, sB));
-    hipEvent_t placed = evs.get();
-    HIPCHK(c, hipEventRecord(placed, sB));
-    HIPCHK(c, hipStreamWaitEvent(sA, placed, 0));                          // the extraction (main stream) reads the store
-    HIPCHK(c, hsk_sync(c, sB));
-    if (profile) { pp.keys = 0; c->ev_pending.push_back(pp); }
-    if (staged) memcpy(tot.data(), h_tot, (size_t)nsl * ntasks * 24);
-    bool fallback = *h_flags != 0;                                          // a tile with more supermers than the record capacity
-    if (c->call.roff_check.valid() && !c->call.roff_check.get()) { fallback = true; c->call.roff_bad = true; }     // the reads do not lie back to back: the caller's offsets are needed
-    if (c->call.index_unchecked && (h_flags[1] & 32u)) fallback = true;          // (parse_count reports it)
-    if (bins && (h_flags[1] & (2u | 128u | 256u))) { fallback = true; (void)hipMemsetAsync(c->d_err, 0, 4, sA); }      // the chunk store or a bin's map ran out (run_pipeline: the call again, without virtual tasks)
-    if (fallback) { HIPCHK(c, hsk_sync(c, sA)); release_all(); free_store(c, st); return PARSE_FALLBACK; }
-    if (d_dropped) c->call.dropped_now = *(const unsigned long long *)(h_flags + 4);
-    if (bins) {
-        sbins.nchunks = std::min(h_flags[2], sbins.cap);
-        int brc = bins_to_store(c, sbins, st, ntasks, c->call.vt_shift, sA); if (brc) { release_all(); return brc; }      // (main stream: behind the `placed` wait above)
-    }
-    c->call.index_unchecked = false;
-    // segments: slab by slab, tasks in storage order inside a slab (what parse_scan_kernel laid out on the device)
+    memcpy(h_order, st.order.data(), (size_t)ntasks * 4);
+    HIPCHK(c, hipMemsetAsync(p.d_run, 0, 24, c->stream));
+    HIPCHK(c, hipMemcpyAsync(p.d_order, h_order, (size_t)ntasks * 4, hipMemcpyHostToDevice, c->stream));
+    a.place_one = 1;
+    a.sm_len = st.sm_len; a.sm_gpos = st.sm_gpos; a.blk_base = p.d_blk_base; a.task_base3 = p.d_task_base;
+    a.sm_sub = st.sm_sub; a.sm_item = st.sm_item;
+    return HSK_OK;
+}
+// segments: slab by slab, tasks in storage order inside a slab (what parse_scan_kernel laid out on the device)
+static void pipe_segments(const std::vector<u64> &tot, u32 nsl, bool bins, SupermerStore &st, std::vector<TaskSegs> &segs)
+{
+    const u32 ntasks = st.ntasks;
     st.task_tot.assign((size_t)ntasks * 3, 0); st.task_base.assign((size_t)ntasks * 3, 0);
     segs.assign(ntasks, TaskSegs());
     u64 run_s = 0, run_b = 0;
     for (u32 sl = 0; sl < nsl; ++sl)
         for (u32 i = 0; i < ntasks; ++i) {
-            const u32 t = order[i];
+            const u32 t = st.order[i];
             const u64 *m = &tot[((size_t)sl * ntasks + t) * 3];
             if (m[0] && bins && !segs[t].segs.empty()) segs[t].segs[0].n_sup += m[0];      // (bins: one pseudo segment per task -- only its supermer total is used)
             else if (m[0]) {
@@ -637,9 +633,68 @@ static int parse_ingest_pipelined(hsk_ctx *c, const u8 *h2d_src, const u8 *d_pac
         }
     st.tot_sup = run_s; st.tot_bytes = run_b; st.tot_kmers = 0;
     for (u32 t = 0; t < ntasks; ++t) st.tot_kmers += st.task_tot[3 * t + 2];
-    if (!bins && run_s > cap_sup) { release_all(); free_store(c, st); return fail(c, HSK_ERR_INTERNAL, "supermer store overrun (%llu > %llu)", (unsigned long long)run_s, (unsigned long long)cap_sup); }
-    if (profile && !c->ev_pending.empty()) c->ev_pending.back().keys = run_s;
-    release_all();                                                          // (stream-ordered reuse: later users are enqueued behind the kernels above)
+}
+static int parse_ingest_pipelined(hsk_ctx *c, const u8 *h2d_src, const u8 *d_packed, u64 packed_bytes, const u64 *d_roff, const u32 *d_rlen, u64 nreads,
+                                  int64_t rid_base, u32 ntasks, SupermerStore &st, std::vector<TaskSegs> &segs)
+{
+    const ParseTiling t = call_tiling(c, packed_bytes, (u32)c->call.h2d_slabs);
+    if (t.nslabs <= 1) return PARSE_FALLBACK;
+    const u32 nsl = t.nslabs, nblocks = t.nblocks;
+    ParseArgs a = make_parse_args(c, t, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, ntasks);
+    hipStream_t sA = c->stream, sB = c->comm_stream;
+    PipeBufs p;
+    int rc = pipe_setup(c, p, a, nblocks, st); if (rc) return rc;
+    const bool bins = a.bins != nullptr;                                    // scan_kernel places the items itself: no records, no placement kernel
+    const PlaceKind kind = a.tile_sub ? PLACE_ITEMS : PLACE_RECORDS;
+    EvList evs(c);
+    hipEvent_t ready = evs.get();                                          // the small buffers are set up; the second stream may start
+    HIPCHK(c, hipEventRecord(ready, sA));
+    HIPCHK(c, hipStreamWaitEvent(sB, ready, 0));
+    SlabEvents ev;
+    rc = enqueue_slab_copies(c, evs, t, h2d_src, d_packed, packed_bytes, ev); if (rc) return rc;
+    EvPair sp = prof_begin(c, 3, sA), pp = prof_begin(c, 4, sB); sp.bytes = packed_bytes;
+    for (u32 sl = 0; sl < nsl; ++sl) {
+        rc = wait_for_slab(c, sA, ev, sl); if (rc) return rc;
+        a.slab = sl; a.blk_cnt = p.d_blk_cnt + (size_t)sl * nblocks * ntasks * 3;
+        launch_scan(c, sA, nblocks, ntasks, a);
+        hipEvent_t scanned = evs.get();
+        HIPCHK(c, hipEventRecord(scanned, sA));
+        // the slab's placement on the second stream: totals, bases (behind everything the slabs before laid out), supermers to their slots
+        // -- before the host has seen the overflow word: the placement kernels read it themselves (ParseArgs::place_one)
+        HIPCHK(c, hipStreamWaitEvent(sB, scanned, 0));
+        rc = launch_parse_scan(c, sB, (const u64 *)a.blk_cnt, nblocks, ntasks, (const u32 *)p.d_order, (const u8 *)nullptr,
+                               p.d_tot + (size_t)sl * ntasks * 3, p.d_task_base, p.d_blk_base, p.d_run, p.d_ps); if (rc) return rc;
+        if (!bins) launch_place(c, sB, kind, a, nblocks, ntasks);
+    }
+    prof_end(c, sp, sA); prof_end(c, pp, sB);
+    // the verdicts and the totals (sB is behind every scan: scanned events)
+    std::vector<u64> tot((size_t)nsl * ntasks * 3);
+    u64 *h_tot = (u64 *)((char *)c->pinned + (192u << 10));
+    const bool staged = (size_t)nsl * ntasks * 24 <= (64u << 10);
+    rc = read_parse_flags(c, sB, p.scan, true); if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(staged ? h_tot : tot.data(), p.d_tot, (size_t)nsl * ntasks * 24, hipMemcpyDeviceToHost, sB));
+    hipEvent_t placed = evs.get();
+    HIPCHK(c, hipEventRecord(placed, sB));
+    HIPCHK(c, hipStreamWaitEvent(sA, placed, 0));                          // the extraction (main stream) reads the store
+    HIPCHK(c, hsk_sync(c, sB));
+    if (staged) memcpy(tot.data(), h_tot, (size_t)nsl * ntasks * 24);
+    const ParseFlags &f = *parse_flags(c);
+    bool fallback = f.overflow != 0;                                        // a tile with more supermers than the record capacity
+    if (c->call.roff_check.valid() && !c->call.roff_check.get()) { fallback = true; c->call.roff_bad = true; }     // the reads do not lie back to back: the caller's offsets are needed
+    if (c->call.index_unchecked && (f.err & PARSE_ERR_INDEX)) fallback = true;          // (parse_count reports it)
+    if (bins && (f.err & PARSE_ERR_BINS)) { fallback = true; (void)hipMemsetAsync(c->d_err, 0, 4, sA); }      // (run_pipeline: the call again, without virtual tasks)
+    if (fallback) { HIPCHK(c, hsk_sync(c, sA)); pipe_release(c, p); free_store(c, st); return PARSE_FALLBACK; }      // (the main stream's wait first: its scans read the buffers)
+    if (p.scan.d_dropped) c->call.dropped_now = f.dropped;
+    if (bins) {
+        p.scan.bins.nchunks = std::min(f.chunks, p.scan.bins.cap);
+        rc = bins_to_store(c, p.scan.bins, st, ntasks, c->call.vt_shift, sA); if (rc) { pipe_release(c, p); return rc; }      // (main stream: behind the `placed` wait above)
+    }
+    c->call.index_unchecked = false;
+    pipe_segments(tot, nsl, bins, st, segs);
+    const u64 cap_sup = a.ntiles * (u64)a.rec_cap;
+    if (!bins && st.tot_sup > cap_sup) { pipe_release(c, p); free_store(c, st); return fail(c, HSK_ERR_INTERNAL, "supermer store overrun (%llu > %llu)", (unsigned long long)st.tot_sup, (unsigned long long)cap_sup); }
+    if ((c->cfg.flags & HSK_FLAG_PROFILE) && !c->ev_pending.empty()) c->ev_pending.back().keys = st.tot_sup;
+    pipe_release(c, p);                                                     // (stream-ordered reuse: later users are enqueued behind the kernels above)
     return HSK_OK;
 }
 

@@ -843,7 +843,7 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
         ParseJob job;
         int rc = parse_count(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, nvt, job);
         if (rc && nranks == 1) { parse_release(c, job); c->call.vt_shift = 0; return rc; }
-        if (vts && !job.d_tile_sub && !job.bins.items && !job.empty) { parse_release(c, job); c->call.vt_shift = 0; c->call.combine_veto = true; return retry_plan("the parse left its fast path: no items"); }   // (the parse left its fast path: no items)
+        if (vts && !job.scan.d_tile_sub && !job.scan.bins.items && !job.empty) { parse_release(c, job); c->call.vt_shift = 0; c->call.combine_veto = true; return retry_plan("the parse left its fast path: no items"); }   // (the parse left its fast path: no items)
         if (nranks > 1) {
             // Several ranks: a rank that fails must not return alone (its peers would wait for it in the next collective for
             // ever).  Every all-reduce below carries the ranks' status as one more element; a failed rank keeps taking part

@@ -25,16 +25,16 @@
 // the supermers of a task that go to one destination rank are contiguous for the all-to-all.
 #pragma once
 #include "hsk_device.h"
+#include "hsk_parseplan.h"      // the tiling, PARSE_TILE, the record capacities: what host and kernels must agree on
 
 namespace hsk {
 
 constexpr int PARSE_THREADS = 256;
 constexpr int PARSE_PPT = 8;                          // positions per thread
-constexpr int PARSE_TILE = PARSE_THREADS * PARSE_PPT; // 2048 positions = 512 bytes
+static_assert(PARSE_TILE == PARSE_THREADS * PARSE_PPT, "a tile is one pass of the workgroup: 2048 positions = 512 bytes");
 constexpr int SUPERMER_CUT = 128;                     // forced supermer boundary period (positions)
 constexpr int MAX_K = 95;
 constexpr int HSK_MAX_TASKS = 1024;
-constexpr int PARSE_WORDS = PARSE_TILE / 16 + 12;     // 128 tile words + halo (K-1 <= 94 bases = 6 words) + overread
 constexpr int PARSE_HMAX = PARSE_TILE + 96;           // hashes for TILE + (K-M) positions
 constexpr int PARSE_RWIN = 64;                        // reads looked at per tile by the wave-parallel index search
 static_assert(PARSE_RWIN + PARSE_WORDS <= PARSE_THREADS, "scan_kernel prefetches the next tile with one lane per read-index entry and per word");
@@ -597,8 +597,6 @@ __device__ __forceinline__ void bin_store(const BinTable &a, u64 slot, u64 w0, u
     a.subs[slot] = sub;
 }
 
-constexpr u32 SCAN_REC_CAP = 512;                     // default records kept per tile (expected ~270 at K=31, M=17)
-constexpr u32 PLACE_MAX_REC = 8192;                   // records of one placement step (rec_cap * place_group)
 // LDS layout of the tile's hashes: position p = 8*t + i lives at [i][t] (row stride SCAN_HSTRIDE), so that the 64
 // lanes of a wave, which all touch the same i of consecutive t, hit consecutive 8-byte words (a lane-major layout
 // puts them 64 bytes apart: 8-way bank conflicts on every access)
@@ -1049,13 +1047,6 @@ __global__ __launch_bounds__(PARSE_THREADS) void place_kernel(ParseArgs a)
 // (s_go) are written by wave 0 one phase earlier; s_go is read by the prefetch alone, so one array serves.  A prefetch reads exactly the
 // addresses that step's own loads would read (same guards), and the slots are what they were: blk_base, the step order, the in-step rank.
 // dynamic LDS: u64 cur[nt], u32 tcnt[nt], u32 tpre[nt], u64 srt[PLACE_ITEM_REC], u32 words[PLACE_ITEM_WORDS]
-constexpr int PLACE_ITEM_THREADS = 1024;
-#ifndef PLACE_ITEM_RPT
-#define PLACE_ITEM_RPT 16
-#endif
-constexpr u32 PLACE_ITEM_REC = PLACE_ITEM_RPT * 1024;  // records of one step (rec_cap * place_group)
-constexpr u32 PLACE_ITEM_TILES = PLACE_ITEM_REC / 512; // tiles per step at most
-constexpr u32 PLACE_ITEM_WORDS = PLACE_ITEM_TILES * (PARSE_TILE / 16) + 8;      // their packed words + the reach of the last supermer's second word
 struct PlaceItemStep { u32 sl, t0, ng; u64 tfirst; bool ok; };                  // a step of a workgroup's walk: slab, first tile (of the block, global), tiles
 __global__ __launch_bounds__(PLACE_ITEM_THREADS) void place_items_kernel(ParseArgs a)
 {
@@ -1227,10 +1218,6 @@ __global__ __launch_bounds__(PLACE_ITEM_THREADS) void place_items_kernel(ParseAr
 // dynamic LDS: u64 cur[nt], u64 curb[nt], u64 tbase[nt], u64 tc[nt], u32 tpre[nt], u32 pad[nt], u64 srt[PLACE_BYTES_REC], u32 words[...]
 // A step takes 8192 records (1024 threads, 16 tiles): with the 320 tasks of eight ranks a (step, task) run is ~25 supermers = 250 bytes (4096 records:
 // half that; measured in DESIGN.md 3.2f).
-constexpr int PLACE_BYTES_THREADS = 1024;
-constexpr u32 PLACE_BYTES_REC = 8192;                  // records of one step (rec_cap * place_group)
-constexpr u32 PLACE_BYTES_TILES = 16;                  // tiles per step at most (a record's tile: 4 bits)
-constexpr u32 PLACE_BYTES_WORDS = PLACE_BYTES_TILES * (PARSE_TILE / 16) + 24;   // their packed words + the overhang of the last supermer (<= 222 bases) + overread
 __global__ __launch_bounds__(PLACE_BYTES_THREADS) void place_bytes_kernel(ParseArgs a)
 {
     constexpr int PARSE_THREADS = PLACE_BYTES_THREADS;      // (this kernel's own width)

@@ -111,7 +111,10 @@ def test_slab_ingest_equals_reads_in_place(K, EXT):
     """Pinned input above 32 MB: the packed reads arrive as DMA copies slab by slab while the scan hashes the slabs before
     (h2d_slabs: 16 by default, 3 and 8 here as well; the last slab is short and a read straddles every slab edge); =0: the scan reads
     the host buffer in place as in round 2.  Same list, same histogram, and equal to the pageable path.  One context per setting, in this
-    process (the switches are per-context tuning names since round 4; rounds 2 - 3 started a process per setting)."""
+    process (the switches are per-context tuning names since round 4; rounds 2 - 3 started a process per setting).
+    Which way a setting went is asserted too, from the context's counters over its three calls: only the settings with a forced record capacity leave the
+    fast parse (hsk_stats::parse_fallbacks: once per call in parse_count, and once more per pinned call where the pipelined ingest had
+    to hand over first), and under the profile flag (K=31) every call scans once -- twice where the pipelined ingest handed over."""
     import hashlib
     import hysortk_amd as H
     from hysortk_amd import synth
@@ -120,16 +123,21 @@ def test_slab_ingest_equals_reads_in_place(K, EXT):
     packed, off, lens = synth.packed_reads(2000000, 150, n, 21)
     pp, po, pl = H.pinned_empty(packed.size, np.uint8), H.pinned_empty(off.size, np.uint64), H.pinned_empty(lens.size, np.uint32)
     pp[:] = packed; po[:] = off; pl[:] = lens
-    outs = []
+    outs, paths = [], []
     # ({}: ingest, scan and placement as one pipeline, the store laid out [slab][task]; ingest_pipeline=0: slab ingest, one placement;
-    #  a record capacity of 300 makes some tile overflow: both fall back to the general parse kernels with the reads already in HBM)
-    envs = ({}, {"HSK_H2D_SLABS": "3"}, {"HSK_H2D_SLABS": "0"}, {"HSK_H2D_SLABS": "8", "HSK_PARSE_REC_CAP": "300"}, {"HSK_INGEST_PIPELINE": "0"},
-            {"HSK_INGEST_PIPELINE": "0", "HSK_PARSE_REC_CAP": "300"})
+    #  a record capacity below the mean number of supermers per tile makes tiles overflow: both fall back to the general parse kernels with
+    #  the reads already in HBM.  150-base reads have k-mers at (151 - K) / 150 of their positions, a window of W = K - 16 k-mers starts a
+    #  supermer every (W + 1) / 2 of those, every 128 positions and at every read: ~230 per 2048-position tile at K=31, ~100 at K=51 -- the
+    #  capacity of 300 this test used until the counters below were read never overflowed)
+    cap = {31: "200", 51: "80"}[K]
+    envs = ({}, {"HSK_H2D_SLABS": "3"}, {"HSK_H2D_SLABS": "0"}, {"HSK_H2D_SLABS": "8", "HSK_PARSE_REC_CAP": cap}, {"HSK_INGEST_PIPELINE": "0"},
+            {"HSK_INGEST_PIPELINE": "0", "HSK_PARSE_REC_CAP": cap})
     if EXT:
         envs = envs[:1] + envs[2:3]                              # (payloads take the slab ingest without the placement pipeline: default and in-place suffice)
     try:
         for env in envs:
-            with H.Context(K=K, M=17, L=2, U=200, EXT=EXT, ntasks=16, tuning=util.tuning(env)) as c:
+            with H.Context(K=K, M=17, L=2, U=200, EXT=EXT, ntasks=16, profile=(K == 31), tuning=util.tuning(env)) as c:
+                c.stats()                                        # (counters from zero)
                 for src in ((pp, po, pl), (packed, off, lens), (pp, po, pl)):
                     r = c.count(src)
                     pay = b""
@@ -139,11 +147,19 @@ def test_slab_ingest_equals_reads_in_place(K, EXT):
                             pay = np.array([(x * np.uint64(0x9E3779B97F4A7C15)).sum(dtype=np.uint64), np.bitwise_xor.reduce(x), x.size], dtype=np.uint64).tobytes()
                     outs.append((hashlib.sha256(r.kmers.tobytes() + r.cnt.tobytes() + r.task_off.tobytes() + r.histo.tobytes() + pay).hexdigest(), len(r)))
                     del r
+                st = c.stats()
+                paths.append((env, int(st["parse_fallbacks"]), int(st["scan_launches"])))
     finally:
         for x in (pp, po, pl):
             H.pinned_free(x)
     assert len(outs) == 3 * len(envs) and len({o[0] for o in outs}) == 1, outs
     assert int(outs[0][1]) > 100000
+    print(paths)
+    for env, fallbacks, scans in paths:
+        overflow = "HSK_PARSE_REC_CAP" in env
+        handed_over = 2 if overflow and not EXT and env.get("HSK_INGEST_PIPELINE") != "0" else 0      # the two pinned calls went through the pipelined ingest first
+        assert fallbacks == ((3 + handed_over) if overflow else 0), paths
+        assert scans == ((3 + handed_over) if K == 31 else 0), paths
 
 
 def test_result_outlives_its_context():
