@@ -59,6 +59,14 @@ class Pairs(C.Structure):
     ]
 
 
+class PairsSlices(C.Structure):
+    """hsk_pairs_slices: what hsk_result_pairs_sliced says about its slices and merges."""
+    _fields_ = [
+        ("slices", C.c_uint64), ("peak_records", C.c_uint64), ("merges", C.c_uint64), ("merged_rows", C.c_uint64), ("ms_merge", C.c_double),
+        ("reserved", C.c_int64 * 4),
+    ]
+
+
 FLAG_PROFILE = 1
 FLAG_KEEP_DEVICE = 2
 FLAG_PLAIN_CLASSIFIER = 4
@@ -71,6 +79,7 @@ UNIQUE_ID_BYTES = 128
 SYMBOLS = [
     "hsk_abi_version", "hsk_device_count", "hsk_host_alloc", "hsk_host_free", "hsk_init", "hsk_destroy", "hsk_strerror", "hsk_last_error", "hsk_config_default",
     "hsk_count", "hsk_count_device", "hsk_count_loopback", "hsk_count_loopback_device", "hsk_result_free", "hsk_result_device_task", "hsk_result_pairs", "hsk_pairs_free", "hsk_format_entries", "hsk_get_stats",
+    "hsk_result_pairs_sliced", "hsk_pairs_merge",
     "hsk_stage_destinations", "hsk_stage_task_kmers", "hsk_stage_sort", "hsk_stage_count_sorted",
     "hsk_plan_tot_tasks", "hsk_plan_classify", "hsk_plan_dispatch", "hsk_plan_partition_reads", "hsk_plan_exchange",
     "hsk_comm_get_unique_id", "hsk_comm_init", "hsk_comm_destroy", "hsk_comm_selftest",
@@ -122,6 +131,8 @@ def load():
     L.hsk_result_free.restype = None
     L.hsk_result_device_task.argtypes = [C.POINTER(Result), C.c_int32] + [vp] * 7
     L.hsk_result_pairs.argtypes = [vp, C.POINTER(Result), C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(Pairs)]
+    L.hsk_result_pairs_sliced.argtypes = [vp, C.POINTER(Result), C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_uint64, C.POINTER(Pairs), C.POINTER(PairsSlices)]
+    L.hsk_pairs_merge.argtypes = [vp, C.POINTER(C.POINTER(Pairs)), C.c_int32, C.c_uint32, C.c_int32, C.POINTER(Pairs)]
     L.hsk_pairs_free.argtypes = [vp, C.POINTER(Pairs)]
     L.hsk_pairs_free.restype = None
     L.hsk_get_stats.argtypes = [vp, C.POINTER(Stats), C.c_int]

@@ -223,10 +223,14 @@ class ReadPairs:
         return cls(rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3], **kw)
 
     @staticmethod
-    def combine(parts, min_shared=1):
-        """The list of the union of disjoint task ranges, or of the ranks of a several-GPU run, from their lists (host side, numpy): rows
-        with equal keys join -- shared adds up, first is the minimum, last the maximum -- and min_shared is applied afterwards.  The
-        parts must have been computed with min_shared=1."""
+    def combine(parts, min_shared=1, ctx=None, on_device=False):
+        """The list of the union of disjoint task ranges, or of the ranks of a several-GPU run, from their lists: rows with equal keys
+        join -- shared adds up, first is the minimum, last the maximum -- and min_shared is applied afterwards.  The parts must have
+        been computed with min_shared=1.  Without ctx: on the host, in numpy (the parts' rows must be on the host).  With a Context:
+        hsk_pairs_merge on its GPU -- parts whose rows are on the device are read there, host rows are uploaded, and on_device=True
+        leaves the result in HBM as DeviceResult.pairs does."""
+        if ctx is not None:
+            return ReadPairs._combine_device(list(parts), min_shared, ctx, on_device)
         rows = [p.rows() for p in parts if len(p)]
         if not rows:
             return ReadPairs.from_rows(np.zeros((0, 4), np.uint64))
@@ -237,6 +241,39 @@ class ReadPairs:
         info = {k: sum(int(p.info.get(k, 0)) for p in parts) for k in ("records", "self_records")}
         info["keys"] = int(out.shape[0])
         return ReadPairs.from_rows(out[out[:, 1] >= np.uint64(min_shared)], info=info)
+
+    @staticmethod
+    def _combine_device(parts, min_shared, ctx, on_device):
+        structs, keep = [], []
+        for p in parts:
+            s = _lib.Pairs()
+            s.n = len(p)
+            s.records, s.self_records = int(p.info.get("records", 0)), int(p.info.get("self_records", 0))
+            if len(p) and p.rows_dev:
+                s.rows_dev = p.rows_dev
+            elif len(p):
+                r = np.ascontiguousarray(p.rows(), dtype=np.uint64)
+                keep.append(r)
+                s.rows = r.ctypes.data_as(C.POINTER(C.c_uint64))
+            structs.append(s)
+        arr = (C.POINTER(_lib.Pairs) * max(len(structs), 1))(*[C.pointer(s) for s in structs])
+        pr = _lib.Pairs()
+        ctx._check(ctx.lib.hsk_pairs_merge(ctx.h, arr, len(structs), min_shared, 1 if on_device else 0, C.byref(pr)))
+        return ReadPairs._wrap(ctx, pr, on_device)
+
+    @staticmethod
+    def _wrap(ctx, pr, on_device, extra=None):
+        """A ReadPairs from a filled hsk_pairs: the rows copied to numpy and the struct freed, or (on_device) left in HBM and owned."""
+        info = dict(records=int(pr.records), self_records=int(pr.self_records), keys=int(pr.keys), sort_passes=int(pr.sort_passes),
+                    ms_expand=pr.ms_expand, ms_sort=pr.ms_sort, ms_reduce=pr.ms_reduce, ms_d2h=pr.ms_d2h, ms_total=pr.ms_total)
+        info.update(extra or {})
+        n = int(pr.n)
+        if on_device:
+            z = np.zeros(0, np.uint64)
+            return ReadPairs(z, z, z, z, info=info, rows_dev=pr.rows_dev, n=n, owner=(ctx, pr))
+        rows = np.ctypeslib.as_array(pr.rows, shape=(n * 4,)).reshape(n, 4).copy() if n else np.zeros((0, 4), np.uint64)
+        ctx.lib.hsk_pairs_free(ctx.h, C.byref(pr))
+        return ReadPairs.from_rows(rows, info=info)
 
     def close(self):
         if self._owner is not None:
@@ -286,22 +323,21 @@ class DeviceResult:
             out["rid"] = self.ctx.d2h(d["rid"], d["npay"] * 4).view(np.int32)
         return out
 
-    def pairs(self, task_lo=0, task_hi=None, min_shared=1, on_device=False):
+    def pairs(self, task_lo=0, task_hi=None, min_shared=1, on_device=False, max_records=None):
         """hsk_result_pairs over tasks [task_lo, task_hi) (default: all): the read pairs that share at least min_shared k-mer
         occurrence pairs, as a ReadPairs.  on_device=True leaves the rows in HBM (ReadPairs.rows_dev, .n; close() it before the
-        context goes)."""
+        context goes).  max_records=N: hsk_result_pairs_sliced -- the same list, from at most N records expanded at a time (0: the
+        library chooses from the device memory that is left); info then has slices, peak_records, merges, merged_rows and ms_merge."""
         pr = _lib.Pairs()
         hi = self.ntasks if task_hi is None else task_hi
-        self.ctx._check(self.ctx.lib.hsk_result_pairs(self.ctx.h, C.byref(self.res), task_lo, hi, min_shared, 1 if on_device else 0, C.byref(pr)))
-        info = dict(records=int(pr.records), self_records=int(pr.self_records), keys=int(pr.keys), sort_passes=int(pr.sort_passes),
-                    ms_expand=pr.ms_expand, ms_sort=pr.ms_sort, ms_reduce=pr.ms_reduce, ms_d2h=pr.ms_d2h, ms_total=pr.ms_total)
-        n = int(pr.n)
-        if on_device:
-            z = np.zeros(0, np.uint64)
-            return ReadPairs(z, z, z, z, info=info, rows_dev=pr.rows_dev, n=n, owner=(self.ctx, pr))
-        rows = np.ctypeslib.as_array(pr.rows, shape=(n * 4,)).reshape(n, 4).copy() if n else np.zeros((0, 4), np.uint64)
-        self.ctx.lib.hsk_pairs_free(self.ctx.h, C.byref(pr))
-        return ReadPairs.from_rows(rows, info=info)
+        if max_records is None:
+            self.ctx._check(self.ctx.lib.hsk_result_pairs(self.ctx.h, C.byref(self.res), task_lo, hi, min_shared, 1 if on_device else 0, C.byref(pr)))
+            return ReadPairs._wrap(self.ctx, pr, on_device)
+        sl = _lib.PairsSlices()
+        self.ctx._check(self.ctx.lib.hsk_result_pairs_sliced(self.ctx.h, C.byref(self.res), task_lo, hi, min_shared, 1 if on_device else 0, int(max_records),
+                                                             C.byref(pr), C.byref(sl)))
+        extra = dict(slices=int(sl.slices), peak_records=int(sl.peak_records), merges=int(sl.merges), merged_rows=int(sl.merged_rows), ms_merge=sl.ms_merge)
+        return ReadPairs._wrap(self.ctx, pr, on_device, extra)
 
     def close(self):
         if self.res is not None:

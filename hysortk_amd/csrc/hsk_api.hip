@@ -38,6 +38,7 @@
 #include "hsk_combine.h"
 #include "hsk_heavy.h"
 #include "hsk_pairs.h"
+#include "hsk_pairmerge.h"
 #include "hsk_estimate.h"
 #include "hsk_synth.h"
 #include "hsk_plan.h"

@@ -1,74 +1,103 @@
-// hsk_host_pairs.h -- host side of hsk_result_pairs: read pairs that share k-mers, from the resident EXTENSION list (kernels: hsk_pairs.h).
+// hsk_host_pairs.h -- host side of hsk_result_pairs, hsk_result_pairs_sliced and hsk_pairs_merge: read pairs that share k-mers, from the
+// resident EXTENSION list (kernels: hsk_pairs.h, hsk_pairmerge.h).
 // Part of the single translation unit hsk_api.hip (included in this order; everything here is file-local).
 #pragma once
 
 struct PairsPriv { void *host_rows = nullptr; void *dev_rows = nullptr; };
 
-// The tasks of the range go through ONE launch per kernel over a device table of task descriptors (at most HSK_MAX_TASKS of them):
-// the records of the whole range are one array, sorted once.  Two waits before the large buffers exist (the record count), one per
-// sort (its histogram), one for the row count, one at the end.
-static int pairs_impl(hsk_ctx *c, const ResultPriv *rp, int nw, int32_t task_lo, int32_t task_hi, u32 min_shared, bool on_device, hsk_pairs *out, PairsPriv *pp)
-{
+// The phases of a call, summed over its slices and merges.  Every event pair is closed before the host waits, and taken behind the wait.
+enum { PT_EXPAND = 0, PT_SORT, PT_REDUCE, PT_MERGE, PT_D2H, PT_N };
+struct PairClock {
+    PhaseTimer t; double ms[PT_N] = {0, 0, 0, 0, 0};
+    explicit PairClock(hsk_ctx *c) : t(c) {}
+    void take() { for (int ph = 0; ph < PT_N; ++ph) ms[ph] += t.collect(ph); }
+    ~PairClock() { take(); }                             // (a call that failed: the events go back to the context)
+};
+
+// The tasks of a range that have entries, the record count of each entry and what the count pass leaves on the device for the expansion.
+struct PairRange {
     std::vector<PairTask> tk;
-    u64 nent = 0;
+    u64 nent = 0, records = 0;
+    PairTask *d_tasks = nullptr; u64 *d_off = nullptr, *d_loc = nullptr, *d_stat = nullptr;
+};
+
+static int pairs_range_tasks(hsk_ctx *c, const ResultPriv *rp, int32_t task_lo, int32_t task_hi, PairRange &r)
+{
     for (int32_t t = task_lo; t < task_hi; ++t) {
         const TaskOut &to = rp->dev_tasks[t];
         if (!to.n) continue;
         if (!to.entries || !to.payoff || !to.pos || !to.rid) return fail(c, HSK_ERR_INTERNAL, "task %d of the resident result has entries but no payload arrays", t);
         if (to.npay >> PAIR_LOC_SHIFT) return fail(c, HSK_ERR_UNSUPPORTED, "task %d holds %llu payloads (2^%d at most)", t, (unsigned long long)to.npay, PAIR_LOC_SHIFT);
-        PairTask p; p.entries = to.entries; p.payoff = to.payoff; p.pos = to.pos; p.rid = to.rid; p.ent_base = nent; p.n = to.n; p.npay = to.npay; p.pay_base = to.pay_base;
-        tk.push_back(p); nent += to.n;
+        PairTask p; p.entries = to.entries; p.payoff = to.payoff; p.pos = to.pos; p.rid = to.rid; p.ent_base = r.nent; p.n = to.n; p.npay = to.npay; p.pay_base = to.pay_base;
+        r.tk.push_back(p); r.nent += to.n;
     }
-    if (!nent) return HSK_OK;
-    EvList ev(c);
-    hipEvent_t e_start = ev.get(), e_expand = ev.get(), e_sort = ev.get(), e_reduce = ev.get(), e_end = ev.get();
-    HIPCHK(c, hipEventRecord(e_start, c->stream));
+    return HSK_OK;
+}
 
-    // ---- record counts: t_e per entry, exclusive 64-bit offsets, the total ---------------------------------------------------
-    const u64 ctiles = (nent + PC_TILE - 1) / PC_TILE;
-    PairTask *d_tasks; u64 *d_off, *d_loc, *d_ctile, *d_stat;
-    DALLOC(c, d_tasks, PairTask *, tk.size() * sizeof(PairTask));
-    DALLOC(c, d_off, u64 *, (nent + 1) * 8); DALLOC(c, d_loc, u64 *, nent * 8);
-    DALLOC(c, d_ctile, u64 *, ctiles * 8); DALLOC(c, d_stat, u64 *, PAIR_STAT_WORDS * 8);
-    HIPCHK(c, hipMemcpyAsync(d_tasks, tk.data(), tk.size() * sizeof(PairTask), hipMemcpyHostToDevice, c->stream));     // (tk lives until the waits below)
-    HIPCHK(c, hipMemsetAsync(d_stat, 0, PAIR_STAT_WORDS * 8, c->stream));
+// ---- record counts: t_e per entry, exclusive 64-bit offsets, the total: once for the range, whatever follows; two waits ------------
+static int pairs_count_records(hsk_ctx *c, int nw, PairRange &r, PairClock &ck)
+{
+    const u64 nent = r.nent, ctiles = (nent + PC_TILE - 1) / PC_TILE;
+    u64 *d_ctile;
+    DALLOC(c, r.d_tasks, PairTask *, r.tk.size() * sizeof(PairTask));
+    DALLOC(c, r.d_off, u64 *, (nent + 1) * 8); DALLOC(c, r.d_loc, u64 *, nent * 8);
+    DALLOC(c, d_ctile, u64 *, ctiles * 8); DALLOC(c, r.d_stat, u64 *, PAIR_STAT_WORDS * 8);
+    ck.t.begin(PT_EXPAND);
+    HIPCHK(c, hipMemcpyAsync(r.d_tasks, r.tk.data(), r.tk.size() * sizeof(PairTask), hipMemcpyHostToDevice, c->stream));     // (tk lives until the wait below)
+    HIPCHK(c, hipMemsetAsync(r.d_stat, 0, PAIR_STAT_WORDS * 8, c->stream));
     PairSumArgs sa; memset(&sa, 0, sizeof sa);
-    sa.tasks = d_tasks; sa.ntasks = (u32)tk.size(); sa.nw = nw; sa.nent = nent; sa.tile_sum = d_ctile; sa.off = d_off; sa.loc = d_loc; sa.err = (u32 *)(d_stat + PAIR_STAT_ERR);
+    sa.tasks = r.d_tasks; sa.ntasks = (u32)r.tk.size(); sa.nw = nw; sa.nent = nent; sa.tile_sum = d_ctile; sa.off = r.d_off; sa.loc = r.d_loc; sa.err = (u32 *)(r.d_stat + PAIR_STAT_ERR);
     hipLaunchKernelGGL(pair_tsum_kernel<false>, dim3((u32)ctiles), dim3(PAIR_THREADS), 0, c->stream, sa);
-    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_ctile, ctiles, d_stat + PAIR_STAT_RECORDS);
+    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_ctile, ctiles, r.d_stat + PAIR_STAT_RECORDS);
     hipLaunchKernelGGL(pair_tsum_kernel<true>, dim3((u32)ctiles), dim3(PAIR_THREADS), 0, c->stream, sa);
     HIPCHK(c, hipGetLastError());
+    ck.t.end(PT_EXPAND);
     u64 *st = staging(c)->read_pairs;
-    HIPCHK(c, hipMemcpyAsync(st, d_stat, PAIR_STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(st, r.d_stat, PAIR_STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hsk_sync(c, c->stream));
+    ck.take();
     if (st[PAIR_STAT_ERR]) return fail(c, HSK_ERR_INTERNAL, "the resident result is not a valid CSR (%s)", (st[PAIR_STAT_ERR] & PAIR_ERR_COUNT) ? "an entry's count is above 65535" : "an entry's payload slice lies outside its task's payload");
-    const u64 records = st[PAIR_STAT_RECORDS];
-    out->records = records;
+    r.records = st[PAIR_STAT_RECORDS];
     c->pool.release(d_ctile);
-    float f = 0;
-    if (!records) {
-        HIPCHK(c, hipEventRecord(e_end, c->stream)); HIPCHK(c, hsk_sync(c, c->stream));
-        if (hipEventElapsedTime(&f, e_start, e_end) == hipSuccess) out->ms_expand = out->ms_total = f;
-        c->pool.release(d_tasks); c->pool.release(d_off); c->pool.release(d_loc); c->pool.release(d_stat);
-        return HSK_OK;
-    }
+    return HSK_OK;
+}
 
+static void pairs_release_range(hsk_ctx *c, PairRange &r, bool stat)
+{
+    c->pool.release(r.d_tasks); c->pool.release(r.d_off); c->pool.release(r.d_loc); r.d_tasks = nullptr; r.d_off = r.d_loc = nullptr;
+    if (stat) { c->pool.release(r.d_stat); r.d_stat = nullptr; }
+}
+
+// a row list in HBM: a slice's, a caller's part, or a merge's
+struct PairList { u64 *rows = nullptr; u64 n = 0; int level = 0; bool owned = true; };
+struct PairWindow { u64 ent0, ent1, rec0, records; };   // entries [ent0, ent1) = records [rec0, rec0 + records) of the range; records > 0
+
+// Expand a record window, sort it, reduce it to rows that stay on the device.  The whole range is the window { 0, nent, 0, records }.
+// `last`: no window follows -- what the count pass left goes back as soon as the expansion is enqueued.  One wait per sort (its histogram)
+// and one for the row count.  The window's record buffers are released before the routine returns.
+static int pairs_window(hsk_ctx *c, PairRange &r, const PairWindow &w, bool last, u32 min_shared, int32_t task_lo, int32_t task_hi, PairClock &ck, hsk_pairs *acc, PairList *list)
+{
+    const u64 records = w.records;
+    u64 *st = staging(c)->read_pairs;
     // ---- expansion -------------------------------------------------------------------------------------------------------------
     // the working set: two key and two value buffers of `records` words (the sort's ping-pong), known before any of them is asked for
     u64 *kA = (u64 *)c->pool.alloc(records * 8 + 64), *kB = (u64 *)c->pool.alloc(records * 8 + 64), *vA = (u64 *)c->pool.alloc(records * 8 + 64), *vB = (u64 *)c->pool.alloc(records * 8 + 64);      // (+ 64: as every caller of the sort sizes them)
     if (!kA || !kB || !vA || !vB)
-        return fail(c, HSK_ERR_OOM, "read pairs of tasks [%d, %d): %llu records need %llu bytes of device memory (two key and two value buffers) and the rows on top; ask for a narrower task range and combine the lists",
+        return fail(c, HSK_ERR_OOM, "read pairs of tasks [%d, %d): %llu records need %llu bytes of device memory (two key and two value buffers) and the rows on top; ask for a narrower task range and combine the lists, or let hsk_result_pairs_sliced expand fewer records at a time",
                     task_lo, task_hi, (unsigned long long)records, (unsigned long long)(records * 32));
     PairExpandArgs xa; memset(&xa, 0, sizeof xa);
-    xa.tasks = d_tasks; xa.off = d_off; xa.loc = d_loc; xa.nent = nent; xa.records = records; xa.keys = kA; xa.vals = vA;
+    xa.tasks = r.d_tasks; xa.off = r.d_off; xa.loc = r.d_loc; xa.nent = w.ent1; xa.records = records; xa.keys = kA; xa.vals = vA; xa.rec0 = w.rec0; xa.ent0 = w.ent0;
     const u64 xtiles = (records + PX_TILE - 1) / PX_TILE;
-    if (xtiles > 0x7fffffffULL) return fail(c, HSK_ERR_UNSUPPORTED, "%llu records are more than one launch expands; ask for a narrower task range", (unsigned long long)records);
+    if (xtiles > 0x7fffffffULL) return fail(c, HSK_ERR_UNSUPPORTED, "%llu records are more than one launch expands; ask for a narrower task range, or let hsk_result_pairs_sliced expand fewer at a time", (unsigned long long)records);
+    ck.t.begin(PT_EXPAND);
+    if (w.rec0) HIPCHK(c, hipMemsetAsync(r.d_stat, 0, PAIR_STAT_WORDS * 8, c->stream));      // (self_records of the slice before)
     hipLaunchKernelGGL(pair_expand_kernel, dim3((u32)xtiles), dim3(PAIR_THREADS), 0, c->stream, xa);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(e_expand, c->stream));
-    c->pool.release(d_tasks); c->pool.release(d_off); c->pool.release(d_loc);
+    ck.t.end(PT_EXPAND);
+    if (last) pairs_release_range(c, r, false);
 
     // ---- sort: the library's key + payload radix sort over all 64 key bits; digits in which all records agree are skipped -----------
+    ck.t.begin(PT_SORT);
     SortScratch sc; int rc = alloc_sort_scratch(c, sc); if (rc) return rc;
     u64 *sk, *sv;
     rc = sort_task_device<1>(c, kA, kB, vA, vB, records, 32, sc, &sk, &sv, false); if (rc) return rc;
@@ -87,67 +116,331 @@ static int pairs_impl(hsk_ctx *c, const ResultPriv *rp, int nw, int32_t task_lo,
             for (int d = 0; d < 256; ++d) { sum += hh[p * 256 + d]; if (hh[p * 256 + d] == records) trivial = true; }
             if (sum != records) passes = -1; else if (!trivial) ++passes;
         }
-        out->sort_passes = npass < 0 ? -1 : passes;
+        if (npass < 0) passes = -1;
+        acc->sort_passes = (passes < 0 || acc->sort_passes < 0) ? -1 : std::max(acc->sort_passes, passes);      // (the most over the slices)
     }
     rc = check_device_error(c); if (rc) return rc;
     free_sort_scratch(c, sc);
-    HIPCHK(c, hipEventRecord(e_sort, c->stream));
+    ck.t.end(PT_SORT);
 
     // ---- run reducer: rows per tile, scan, write pass ------------------------------------------------------------------------------
     const u64 rtiles = (records + PR_TILE - 1) / PR_TILE;
     u64 *d_rtile, *d_rkeys; DALLOC(c, d_rtile, u64 *, rtiles * 8); DALLOC(c, d_rkeys, u64 *, rtiles * 8);
     PairReduceArgs ra; memset(&ra, 0, sizeof ra);
-    ra.keys = sk; ra.vals = sv; ra.n = records; ra.min_shared = min_shared; ra.tile_cnt = d_rtile; ra.tile_keys = d_rkeys; ra.stats = d_stat;
+    ra.keys = sk; ra.vals = sv; ra.n = records; ra.min_shared = min_shared; ra.tile_cnt = d_rtile; ra.tile_keys = d_rkeys; ra.stats = r.d_stat;
+    ck.t.begin(PT_REDUCE);
     hipLaunchKernelGGL(pair_reduce_kernel<false>, dim3((u32)rtiles), dim3(PAIR_THREADS), 0, c->stream, ra);
-    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_rtile, rtiles, d_stat + PAIR_STAT_ROWS);
-    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_rkeys, rtiles, d_stat + PAIR_STAT_KEYS);      // (only its total is used)
+    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_rtile, rtiles, r.d_stat + PAIR_STAT_ROWS);
+    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_rkeys, rtiles, r.d_stat + PAIR_STAT_KEYS);      // (only its total is used)
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(st, d_stat, PAIR_STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    ck.t.end(PT_REDUCE);
+    HIPCHK(c, hipMemcpyAsync(st, r.d_stat, PAIR_STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hsk_sync(c, c->stream));
+    ck.take();
     const u64 nrows = st[PAIR_STAT_ROWS];
-    out->n = nrows; out->self_records = st[PAIR_STAT_SELF]; out->keys = st[PAIR_STAT_KEYS];
+    acc->self_records += st[PAIR_STAT_SELF]; acc->keys = st[PAIR_STAT_KEYS];
     u64 *d_rows = nullptr;
     if (nrows) {
         DALLOC(c, d_rows, u64 *, nrows * 32);
         ra.rows = d_rows;
+        ck.t.begin(PT_REDUCE);
         hipLaunchKernelGGL(pair_reduce_kernel<true>, dim3((u32)rtiles), dim3(PAIR_THREADS), 0, c->stream, ra);
         HIPCHK(c, hipGetLastError());
+        ck.t.end(PT_REDUCE);
     }
-    HIPCHK(c, hipEventRecord(e_reduce, c->stream));
-    c->pool.release(kA); c->pool.release(kB); c->pool.release(vA); c->pool.release(vB); c->pool.release(d_rtile); c->pool.release(d_rkeys); c->pool.release(d_stat);
+    c->pool.release(kA); c->pool.release(kB); c->pool.release(vA); c->pool.release(vB); c->pool.release(d_rtile); c->pool.release(d_rkeys);
+    if (last) { c->pool.release(r.d_stat); r.d_stat = nullptr; }
+    list->rows = d_rows; list->n = nrows; list->level = 0; list->owned = true;
+    return HSK_OK;
+}
 
-    // ---- egress ----------------------------------------------------------------------------------------------------------------------
+// ---- merges ------------------------------------------------------------------------------------------------------------------------
+struct PairMergeStat { u64 merges = 0, merged_rows = 0; };
+
+// One merge launch (COUNT, the scans, EMIT) of two lists on the device into a block of its own; one wait, for the row count.  *keys: the
+// rows before min_shared.  The inputs are left to the caller.
+static int pairs_merge_two(hsk_ctx *c, const PairList &A, const PairList &B, u32 min_shared, PairClock &ck, PairMergeStat &ms, PairList *out, u64 *keys)
+{
+    out->rows = nullptr; out->n = 0; out->owned = true; out->level = std::max(A.level, B.level) + 1;
+    *keys = 0;
+    const u64 total = A.n + B.n;
+    if (!total) return HSK_OK;
+    const u64 tiles = (total + PM_TILE - 1) / PM_TILE;
+    if (tiles > 0x7fffffffULL) return fail(c, HSK_ERR_UNSUPPORTED, "%llu rows are more than one launch merges", (unsigned long long)total);
+    u64 *d_cnt, *d_keys, *d_tot;
+    DALLOC(c, d_cnt, u64 *, tiles * 8); DALLOC(c, d_keys, u64 *, tiles * 8); DALLOC(c, d_tot, u64 *, 2 * 8);
+    PairMergeArgs ma; memset(&ma, 0, sizeof ma);
+    ma.a = A.rows; ma.na = A.n; ma.b = B.rows; ma.nb = B.n; ma.min_shared = min_shared; ma.tile_cnt = d_cnt; ma.tile_keys = d_keys;
+    ck.t.begin(PT_MERGE);
+    hipLaunchKernelGGL(pair_merge_kernel<false>, dim3((u32)tiles), dim3(PM_THREADS), 0, c->stream, ma);
+    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_cnt, tiles, d_tot);
+    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_keys, tiles, d_tot + 1);      // (only its total is used)
+    HIPCHK(c, hipGetLastError());
+    ck.t.end(PT_MERGE);
+    u64 *st = staging(c)->read_pairs;
+    HIPCHK(c, hipMemcpyAsync(st, d_tot, 2 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hsk_sync(c, c->stream));
+    ck.take();
+    const u64 nrows = st[0];
+    *keys = st[1];
+    if (nrows > total || st[1] > total) return fail(c, HSK_ERR_INTERNAL, "the merge of %llu rows counted %llu", (unsigned long long)total, (unsigned long long)std::max(nrows, st[1]));
+    if (nrows) {
+        DALLOC(c, out->rows, u64 *, nrows * 32);
+        ma.rows = out->rows;
+        ck.t.begin(PT_MERGE);
+        hipLaunchKernelGGL(pair_merge_kernel<true>, dim3((u32)tiles), dim3(PM_THREADS), 0, c->stream, ma);
+        HIPCHK(c, hipGetLastError());
+        ck.t.end(PT_MERGE);
+    }
+    out->n = nrows;
+    c->pool.release(d_cnt); c->pool.release(d_keys); c->pool.release(d_tot);
+    ms.merges++; ms.merged_rows += total;
+    return HSK_OK;
+}
+
+// The lists of the slices (or the caller's parts) in the order of a binary counter: a list enters at level 0, and while the two lists
+// on top have the same level they become one list of the next level.  A row is read by at most ceil(log2(lists)) + 1 merges, and no
+// list grows by one slice at a time.  finish() merges what is left, top first; the LAST merge applies min_shared and counts the keys.
+struct PairStack {
+    std::vector<PairList> v;
+    PairMergeStat ms;
+    static void drop(hsk_ctx *c, PairList &l) { if (l.owned) c->pool.release(l.rows); l.rows = nullptr; l.n = 0; }
+    int merge_top(hsk_ctx *c, u32 min_shared, bool final, PairClock &ck, u64 *keys)
+    {
+        PairList B = v.back(); v.pop_back();
+        PairList A = v.back(); v.pop_back();
+        PairList o;
+        if (!final && (!A.n || !B.n)) {                 // nothing to join: the other list moves up as it is
+            o = A.n ? A : B; o.level = std::max(A.level, B.level) + 1;
+            drop(c, A.n ? B : A);
+        } else {
+            const int rc = pairs_merge_two(c, A, B, min_shared, ck, ms, &o, keys); if (rc) return rc;
+            drop(c, A); drop(c, B);                      // (behind the merge on the stream)
+        }
+        v.push_back(o);
+        return HSK_OK;
+    }
+    // `more`: lists follow (the last one is left to finish(), which knows that its merges end the list)
+    int push(hsk_ctx *c, const PairList &l, bool more, PairClock &ck)
+    {
+        v.push_back(l);
+        u64 keys;
+        while (more && v.size() >= 2 && v[v.size() - 1].level == v[v.size() - 2].level) { const int rc = merge_top(c, 1, false, ck, &keys); if (rc) return rc; }
+        return HSK_OK;
+    }
+    int finish(hsk_ctx *c, u32 min_shared, PairClock &ck, PairList *fin, u64 *keys)
+    {
+        *fin = PairList(); *keys = 0;
+        if (v.empty()) return HSK_OK;
+        if (v.size() == 1) {
+            if (min_shared > 1 && v[0].n) v.push_back(PairList());      // one list: the filter is a merge with nothing
+            else { *fin = v[0]; *keys = v[0].n; v.clear(); return HSK_OK; }
+        }
+        while (v.size() > 1) { const int rc = merge_top(c, v.size() == 2 ? min_shared : 1, v.size() == 2, ck, keys); if (rc) return rc; }
+        *fin = v[0]; v.clear();
+        return HSK_OK;
+    }
+};
+
+// ---- egress: the final list to pinned host memory, or left on the device in a block the result owns; the call's last wait ----------
+static int pairs_egress(hsk_ctx *c, PairList &fin, bool on_device, hipEvent_t e_end, PairClock &ck, hsk_pairs *out, PairsPriv *pp)
+{
+    const u64 nrows = fin.n;
+    u64 *d_rows = fin.rows;
     if (nrows && !on_device) {
         pp->host_rows = c->hpool.alloc(nrows * 32);
         if (!pp->host_rows) return fail(c, HSK_ERR_OOM, "pinned host allocation of %llu bytes failed", (unsigned long long)(nrows * 32));
+        ck.t.begin(PT_D2H);
         HIPCHK(c, hipMemcpyAsync(pp->host_rows, d_rows, nrows * 32, hipMemcpyDeviceToHost, c->stream));
+        ck.t.end(PT_D2H);
         c->stats.d2h_bytes += nrows * 32;
+    } else if (nrows && !fin.owned) {                   // a caller's list that came through as it is: the result gets a copy of its own
+        u64 *cp; DALLOC(c, cp, u64 *, nrows * 32);
+        HIPCHK(c, hipMemcpyAsync(cp, d_rows, nrows * 32, hipMemcpyDeviceToDevice, c->stream));
+        d_rows = cp; fin.owned = true;
     }
     HIPCHK(c, hipEventRecord(e_end, c->stream));
     HIPCHK(c, hsk_sync(c, c->stream));
-    if (nrows && !on_device) { c->pool.release(d_rows); d_rows = nullptr; }
+    ck.take();
+    if (!nrows || !on_device) { if (fin.owned) c->pool.release(d_rows); d_rows = nullptr; }
+    fin.rows = nullptr;
     pp->dev_rows = d_rows;
-    out->rows = (uint64_t *)pp->host_rows; out->rows_dev = d_rows;
-    if (hipEventElapsedTime(&f, e_start, e_expand) == hipSuccess) out->ms_expand = f;
-    if (hipEventElapsedTime(&f, e_expand, e_sort) == hipSuccess) out->ms_sort = f;
-    if (hipEventElapsedTime(&f, e_sort, e_reduce) == hipSuccess) out->ms_reduce = f;
-    if (hipEventElapsedTime(&f, e_reduce, e_end) == hipSuccess) out->ms_d2h = f;
+    out->n = nrows; out->rows = (uint64_t *)pp->host_rows; out->rows_dev = d_rows;
+    out->ms_expand = ck.ms[PT_EXPAND]; out->ms_sort = ck.ms[PT_SORT]; out->ms_reduce = ck.ms[PT_REDUCE]; out->ms_d2h = ck.ms[PT_D2H];
+    return HSK_OK;
+}
+
+// What hsk_result_pairs_sliced expands at a time when the caller leaves it to the library (include/hsk.h): 1/96 of the device memory the
+// context can still get -- what the runtime reports free plus what the context's pool holds unused -- in records: a third of it for the
+// 32 bytes a record takes, the rest for the row lists and the merges.
+static u64 pairs_auto_budget(hsk_ctx *c)
+{
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = 0; }
+    const u64 b = ((u64)fr + c->pool.bytes_cached) / 96;
+    return b ? b : 1;
+}
+
+// The tasks of the range go through ONE launch per kernel over a device table of task descriptors (at most HSK_MAX_TASKS of them).
+// sliced == false (hsk_result_pairs): the records of the whole range are one array, sorted once.  Two waits before the large buffers exist
+// (the record count), one per sort (its histogram), one for the row count, one at the end.
+// sliced == true (hsk_result_pairs_sliced): the same while the records fit the budget; else one more wait for the plan -- one lane cuts the
+// whole range on the device (pair_plan_kernel), since reading a cut back per slice would wait once per slice -- then every slice is a window
+// of its own, and the lists meet on a PairStack: one wait per merge, for its row count.
+static int pairs_impl(hsk_ctx *c, const ResultPriv *rp, int nw, int32_t task_lo, int32_t task_hi, u32 min_shared, bool on_device, bool sliced, u64 max_records,
+                      hsk_pairs *out, hsk_pairs_slices *info, PairsPriv *pp)
+{
+    PairRange r;
+    int rc = pairs_range_tasks(c, rp, task_lo, task_hi, r); if (rc) return rc;
+    info->slices = 1;
+    if (!r.nent) return HSK_OK;
+    EvList ev(c);
+    hipEvent_t e_start = ev.get(), e_end = ev.get();
+    PairClock ck(c);
+    HIPCHK(c, hipEventRecord(e_start, c->stream));
+    rc = pairs_count_records(c, nw, r, ck); if (rc) return rc;
+    const u64 records = r.records;
+    out->records = records;
+    float f = 0;
+    if (!records) {
+        HIPCHK(c, hipEventRecord(e_end, c->stream)); HIPCHK(c, hsk_sync(c, c->stream));
+        if (hipEventElapsedTime(&f, e_start, e_end) == hipSuccess) out->ms_expand = out->ms_total = f;
+        pairs_release_range(c, r, true);
+        return HSK_OK;
+    }
+    u64 budget = records;
+    if (sliced) budget = max_records ? max_records : pairs_auto_budget(c);
+    PairList fin;
+    if (budget >= records) {
+        const PairWindow w = {0, r.nent, 0, records};
+        rc = pairs_window(c, r, w, true, min_shared, task_lo, task_hi, ck, out, &fin); if (rc) return rc;
+        info->peak_records = records;
+    } else {
+        // ---- the plan: every cut and the record offset at it, in one launch and one wait ---------------------------------------------
+        const u64 cap = pair_plan_max_slices(r.nent, records, budget);
+        u64 *d_cut; DALLOC(c, d_cut, u64 *, (2 * cap + 1) * 8);
+        PairPlanArgs pa; memset(&pa, 0, sizeof pa);
+        pa.off = r.d_off; pa.nent = r.nent; pa.max_records = budget; pa.cut = d_cut; pa.cap = cap; pa.ncut = d_cut + 2 * cap;
+        hipLaunchKernelGGL(pair_plan_kernel, dim3(1), dim3(1), 0, c->stream, pa);
+        HIPCHK(c, hipGetLastError());
+        std::vector<u64> cut(2 * cap + 1);
+        HIPCHK(c, hipMemcpyAsync(cut.data(), d_cut, cut.size() * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hsk_sync(c, c->stream));
+        c->pool.release(d_cut);
+        const u64 ncut = cut[2 * cap];
+        if (ncut == 0 || ncut > cap || cut[2 * (ncut - 1)] != r.nent || cut[2 * (ncut - 1) + 1] != records)
+            return fail(c, HSK_ERR_INTERNAL, "the slice plan of %llu entries does not end at the last one", (unsigned long long)r.nent);
+        std::vector<PairWindow> win;                     // the slices that hold records (a run of entries without any in front of a large entry is none)
+        u64 e0 = 0, r0 = 0;
+        for (u64 i = 0; i < ncut; ++i) {
+            const u64 e1 = cut[2 * i], r1 = cut[2 * i + 1];
+            if (e1 <= e0 || r1 < r0) return fail(c, HSK_ERR_INTERNAL, "the slice plan does not advance at entry %llu", (unsigned long long)e0);
+            if (r1 > r0) { const PairWindow w = {e0, e1, r0, r1 - r0}; win.push_back(w); }
+            e0 = e1; r0 = r1;
+        }
+        PairStack stk;
+        hsk_pairs acc; memset(&acc, 0, sizeof acc);
+        for (size_t i = 0; i < win.size(); ++i) {
+            const bool last = i + 1 == win.size();
+            PairList l;
+            rc = pairs_window(c, r, win[i], last, 1, task_lo, task_hi, ck, &acc, &l); if (rc) return rc;
+            info->peak_records = std::max<u64>(info->peak_records, win[i].records);
+            rc = stk.push(c, l, !last, ck); if (rc) return rc;
+        }
+        u64 keys = 0;
+        rc = stk.finish(c, min_shared, ck, &fin, &keys); if (rc) return rc;
+        out->self_records = acc.self_records; out->sort_passes = acc.sort_passes; out->keys = keys;
+        info->slices = win.size(); info->merges = stk.ms.merges; info->merged_rows = stk.ms.merged_rows;
+    }
+    rc = pairs_egress(c, fin, on_device, e_end, ck, out, pp); if (rc) return rc;
+    info->ms_merge = ck.ms[PT_MERGE];
     if (hipEventElapsedTime(&f, e_start, e_end) == hipSuccess) out->ms_total = f;
+    return HSK_OK;
+}
+
+static int pairs_entry(hsk_ctx *c, const hsk_result *res, int32_t task_lo, int32_t task_hi, uint32_t min_shared, int32_t on_device, bool sliced, uint64_t max_records,
+                       hsk_pairs *out, hsk_pairs_slices *info, const char *name)
+{
+    if (!c || !res || !out) return HSK_ERR_INVALID_ARG;
+    memset(out, 0, sizeof *out);
+    hsk_pairs_slices local; if (!info) info = &local;
+    memset(info, 0, sizeof *info);
+    if (!c->cfg.extension) return fail(c, HSK_ERR_INVALID_ARG, "%s needs a context with EXTENSION: without it the list carries no (ReadId, PosInRead)", name);
+    const ResultPriv *rp = (const ResultPriv *)res->priv;
+    if (!(c->cfg.flags & HSK_FLAG_KEEP_DEVICE) || !rp || res->ntasks <= 0 || rp->dev_tasks.size() != (size_t)res->ntasks)
+        return fail(c, HSK_ERR_INVALID_ARG, "%s needs a result that was left on the device (HSK_FLAG_KEEP_DEVICE)", name);
+    if (task_lo < 0 || task_hi < task_lo || task_hi > res->ntasks) return fail(c, HSK_ERR_INVALID_ARG, "task range [%d, %d) outside [0, %d]", task_lo, task_hi, res->ntasks);
+    if (min_shared == 0) return fail(c, HSK_ERR_INVALID_ARG, "min_shared must be at least 1");
+    PairsPriv *pp = new PairsPriv();
+    const int rc = ApiCall(c, name).run([&] { return pairs_impl(c, rp, res->nw, task_lo, task_hi, min_shared, on_device != 0, sliced, max_records, out, info, pp); });
+    if (rc != HSK_OK) {                                   // (the device blocks went back with the call's rollback)
+        if (pp->host_rows) c->hpool.release(pp->host_rows);
+        delete pp;
+        memset(out, 0, sizeof *out); memset(info, 0, sizeof *info);
+        return rc;
+    }
+    out->priv = pp;
     return HSK_OK;
 }
 
 extern "C" int hsk_result_pairs(hsk_ctx *c, const hsk_result *res, int32_t task_lo, int32_t task_hi, uint32_t min_shared, int32_t on_device, hsk_pairs *out)
 {
-    if (!c || !res || !out) return HSK_ERR_INVALID_ARG;
+    return pairs_entry(c, res, task_lo, task_hi, min_shared, on_device, false, 0, out, nullptr, "hsk_result_pairs");
+}
+
+extern "C" int hsk_result_pairs_sliced(hsk_ctx *c, const hsk_result *res, int32_t task_lo, int32_t task_hi, uint32_t min_shared, int32_t on_device, uint64_t max_records,
+                                       hsk_pairs *out, hsk_pairs_slices *info)
+{
+    return pairs_entry(c, res, task_lo, task_hi, min_shared, on_device, true, max_records, out, info, "hsk_result_pairs_sliced");
+}
+
+// The several-list contract on the GPU: host lists go up, device lists are read where they are, and all meet on a PairStack.
+static int pairs_merge_impl(hsk_ctx *c, const hsk_pairs *const *parts, int32_t nparts, u32 min_shared, bool on_device, hsk_pairs *out, PairsPriv *pp)
+{
+    EvList ev(c);
+    hipEvent_t e_start = ev.get(), e_end = ev.get();
+    PairClock ck(c);
+    HIPCHK(c, hipEventRecord(e_start, c->stream));
+    int32_t last = -1;
+    for (int32_t i = 0; i < nparts; ++i) { out->records += parts[i]->records; out->self_records += parts[i]->self_records; if (parts[i]->n) last = i; }
+    PairStack stk;
+    for (int32_t i = 0; i <= last; ++i) {
+        const hsk_pairs *p = parts[i];
+        if (!p->n) continue;
+        PairList l; l.n = p->n;
+        if (p->rows_dev) { l.rows = (u64 *)p->rows_dev; l.owned = false; }
+        else {
+            DALLOC(c, l.rows, u64 *, p->n * 32);
+            HIPCHK(c, hipMemcpyAsync(l.rows, p->rows, p->n * 32, hipMemcpyHostToDevice, c->stream));      // (pageable or pinned: the part outlives the call's last wait)
+            c->stats.h2d_bytes += p->n * 32;
+        }
+        const int rc = stk.push(c, l, i != last, ck); if (rc) return rc;
+    }
+    PairList fin; u64 keys = 0;
+    int rc = stk.finish(c, min_shared, ck, &fin, &keys); if (rc) return rc;
+    out->keys = keys;
+    rc = pairs_egress(c, fin, on_device, e_end, ck, out, pp); if (rc) return rc;
+    out->ms_reduce = ck.ms[PT_MERGE];                    // (the merges are this call's reduction)
+    float f = 0;
+    if (hipEventElapsedTime(&f, e_start, e_end) == hipSuccess) out->ms_total = f;
+    return HSK_OK;
+}
+
+extern "C" int hsk_pairs_merge(hsk_ctx *c, const hsk_pairs *const *parts, int32_t nparts, uint32_t min_shared, int32_t on_device, hsk_pairs *out)
+{
+    if (!c || !out) return HSK_ERR_INVALID_ARG;
     memset(out, 0, sizeof *out);
-    if (!c->cfg.extension) return fail(c, HSK_ERR_INVALID_ARG, "hsk_result_pairs needs a context with EXTENSION: without it the list carries no (ReadId, PosInRead)");
-    const ResultPriv *rp = (const ResultPriv *)res->priv;
-    if (!(c->cfg.flags & HSK_FLAG_KEEP_DEVICE) || !rp || res->ntasks <= 0 || rp->dev_tasks.size() != (size_t)res->ntasks)
-        return fail(c, HSK_ERR_INVALID_ARG, "hsk_result_pairs needs a result that was left on the device (HSK_FLAG_KEEP_DEVICE)");
-    if (task_lo < 0 || task_hi < task_lo || task_hi > res->ntasks) return fail(c, HSK_ERR_INVALID_ARG, "task range [%d, %d) outside [0, %d]", task_lo, task_hi, res->ntasks);
+    if (nparts < 0) return fail(c, HSK_ERR_INVALID_ARG, "hsk_pairs_merge: %d parts", nparts);
+    if (nparts > 0 && !parts) return fail(c, HSK_ERR_INVALID_ARG, "hsk_pairs_merge: %d parts and no array of them", nparts);
     if (min_shared == 0) return fail(c, HSK_ERR_INVALID_ARG, "min_shared must be at least 1");
+    for (int32_t i = 0; i < nparts; ++i) {
+        if (!parts[i]) return fail(c, HSK_ERR_INVALID_ARG, "hsk_pairs_merge: part %d is NULL", i);
+        if (parts[i]->n && !parts[i]->rows_dev && !parts[i]->rows) return fail(c, HSK_ERR_INVALID_ARG, "hsk_pairs_merge: part %d has %llu rows and neither rows nor rows_dev", i, (unsigned long long)parts[i]->n);
+        if (parts[i]->n && ((uintptr_t)parts[i]->rows_dev & 15)) return fail(c, HSK_ERR_INVALID_ARG, "hsk_pairs_merge: rows_dev of part %d is not 16-byte aligned", i);
+        if (parts[i]->n >> 58) return fail(c, HSK_ERR_INVALID_ARG, "hsk_pairs_merge: part %d claims %llu rows", i, (unsigned long long)parts[i]->n);
+    }
     PairsPriv *pp = new PairsPriv();
-    const int rc = ApiCall(c, "hsk_result_pairs").run([&] { return pairs_impl(c, rp, res->nw, task_lo, task_hi, min_shared, on_device != 0, out, pp); });
+    const int rc = ApiCall(c, "hsk_pairs_merge").run([&] { return pairs_merge_impl(c, parts, nparts, min_shared, on_device != 0, out, pp); });
     if (rc != HSK_OK) {                                   // (the device blocks went back with the call's rollback)
         if (pp->host_rows) c->hpool.release(pp->host_rows);
         delete pp;

@@ -17,6 +17,8 @@
 //                       and loads rid / pos at slice + i and slice + j: consecutive lanes walk i.  Key and value leave as full
 //                       8-byte words per lane.  A pair inside one read is written as key 0 -- no record has it (rid_b >= 1) --
 //                       so that it sorts to the front, leaves every digit as trivial as it was, and is counted by the reducer.
+//                       The launch covers a WINDOW of the range's records, [rec0, rec0 + records) = entries [ent0, nent): the whole
+//                       range for hsk_result_pairs, one slice of it for hsk_result_pairs_sliced (hsk_pairplan.h).
 //   pair_reduce_kernel  the shape of count_kernel: run heads of a tile as a bit mask, rows per tile, count_scan_kernel, write pass.
 //                       A run belongs to the tile it starts in.  The last run of a tile may go on for any number of tiles: the
 //                       whole workgroup reads ahead to its end (count, min, max reduced over the workgroup); tiles inside a run
@@ -98,8 +100,9 @@ constexpr int PX_STAGE = 1024;                                       // entry of
 struct PairExpandArgs {
     const PairTask *tasks;
     const u64 *off, *loc;    // nent + 1, nent
-    u64 nent, records;
-    u64 *keys, *vals;        // records each
+    u64 nent, records;       // the window: entries [ent0, nent), records [rec0, rec0 + records) of the range -- off[ent0] == rec0, off[nent] == rec0 + records
+    u64 *keys, *vals;        // records each: the window's record rec0 + i at [i]
+    u64 rec0, ent0;          // both 0: the whole range (hsk_result_pairs); a slice otherwise (hsk_result_pairs_sliced)
 };
 
 __global__ __launch_bounds__(PAIR_THREADS) void pair_expand_kernel(PairExpandArgs a)
@@ -107,10 +110,11 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_expand_kernel(PairExpandArg
     __shared__ u64 s_off[PX_STAGE + 1];
     __shared__ u64 s_e0;
     const int tid = threadIdx.x;
-    const u64 base = (u64)blockIdx.x * PX_TILE;
-    const u64 end = base + PX_TILE < a.records ? base + PX_TILE : a.records;
-    if (tid == 0) {                                      // the last entry whose offset is <= base (off[0] = 0 <= base < records = off[nent])
-        u64 lo = 0, hi = a.nent;
+    const u64 base = a.rec0 + (u64)blockIdx.x * PX_TILE;     // (record numbers are the range's; only the stores are relative to the window)
+    const u64 last = a.rec0 + a.records;
+    const u64 end = base + PX_TILE < last ? base + PX_TILE : last;
+    if (tid == 0) {                                      // the last entry whose offset is <= base (off[ent0] = rec0 <= base < rec0 + records = off[nent])
+        u64 lo = a.ent0, hi = a.nent;
         while (hi - lo > 1) { const u64 mid = (lo + hi) >> 1; if (a.off[mid] <= base) lo = mid; else hi = mid; }
         s_e0 = lo;
     }
@@ -160,8 +164,8 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_expand_kernel(PairExpandArg
         u32 pa = tk.pos[first + i], pb = tk.pos[first + j];
         if (ra > rb) { const u32 x = ra; ra = rb; rb = x; const u32 y = pa; pa = pb; pb = y; }
         const bool self = ra == rb;
-        a.keys[idx] = self ? 0ULL : ((u64)ra << 32) | rb;
-        a.vals[idx] = self ? 0ULL : ((u64)pa << 32) | pb;
+        a.keys[idx - a.rec0] = self ? 0ULL : ((u64)ra << 32) | rb;
+        a.vals[idx - a.rec0] = self ? 0ULL : ((u64)pa << 32) | pb;
     }
 }
 

@@ -249,7 +249,8 @@ int hsk_result_device_task(const hsk_result *res, int32_t task, const void **ent
  * min_shared = 1).  The call itself is rank-local and not collective; nothing is exchanged between the ranks here.
  *
  * Memory: two key and two value buffers of `records` 8-byte words plus the rows.  `records` is known after one counting pass and
- * before any of them is allocated: HSK_ERR_OOM then says how many records and bytes, and a narrower task range is the way out.
+ * before any of them is allocated: HSK_ERR_OOM then says how many records and bytes, and a narrower task range is the way out --
+ * or hsk_result_pairs_sliced (below), which computes the same list from as many records at a time as the caller allows.
  * HSK_ERR_INVALID_ARG: a NULL pointer, a result that was not left on the device, a context without EXTENSION, a task range outside
  * [0, ntasks], min_shared == 0.  An empty range is no error (n = 0).  hsk_pairs_free before hsk_destroy of the context.
  */
@@ -268,6 +269,49 @@ typedef struct {
 int  hsk_result_pairs(hsk_ctx *ctx, const hsk_result *res, int32_t task_lo, int32_t task_hi,
                       uint32_t min_shared, int32_t on_device, hsk_pairs *out);
 void hsk_pairs_free(hsk_ctx *ctx, hsk_pairs *p);
+/*
+ * The same list within a memory budget.  hsk_result_pairs_sliced has the definition, the row order and the refusals of
+ * hsk_result_pairs, and expands at most max_records records at a time: the record array of the task range is cut at entry boundaries
+ * into SLICES of at most max_records records, every slice is expanded, sorted and reduced to a row list of its own (32 bytes per
+ * record of the slice while that runs), and the lists are merged on the device (rows with equal keys join, as in the several-list
+ * contract above; min_shared is applied by the last merge).  The memory at the peak is 32 bytes x the largest slice plus the row
+ * lists: up to three times 32 bytes x the rows of the result while the last merge runs.
+ *   max_records  the budget.  A slice holds at least one entry: an entry with more records than the budget (cnt (cnt - 1) / 2 of them,
+ *                2 147 385 345 at most) is a slice of its own, and info->peak_records says how large the largest slice was.  When that
+ *                allocation fails the error is the HSK_ERR_OOM of hsk_result_pairs.  A budget of at least `records` runs
+ *                hsk_result_pairs' single pass (info->slices == 1).
+ *                0 = the library chooses: 1/96 of the device memory the context can still get when the record count is known (what the
+ *                runtime reports free plus what the context's pool holds unused), in records -- a third of that memory for the 32 bytes
+ *                per record, the rest for the row lists and the merges.
+ *   out          records and self_records are the sums over the slices, keys the distinct keys of the merged list before min_shared,
+ *                sort_passes the most any slice's sort took, ms_expand / ms_sort / ms_reduce the sums over the slices, ms_total the call.
+ *   info         may be NULL.
+ * The limit of 2^31 expansion tiles holds per slice, not per range.
+ */
+typedef struct {
+    uint64_t slices;        /* record windows expanded (1 = the unsliced path ran) */
+    uint64_t peak_records;  /* largest window: max(max_records, the largest single entry's records) at most */
+    uint64_t merges;        /* merge launches (COUNT + EMIT = one) */
+    uint64_t merged_rows;   /* input rows read by all merges */
+    double   ms_merge;      /* HIP events around the merges */
+    int64_t  reserved[4];
+} hsk_pairs_slices;
+
+int  hsk_result_pairs_sliced(hsk_ctx *ctx, const hsk_result *res, int32_t task_lo, int32_t task_hi, uint32_t min_shared,
+                             int32_t on_device, uint64_t max_records, hsk_pairs *out, hsk_pairs_slices *info);
+/*
+ * The several-list contract on the GPU: the list of the union of `nparts` lists that were computed with min_shared = 1 (disjoint task
+ * ranges, or the ranks of a several-GPU run).  Of each part the call reads n, rows_dev if set or else rows (host memory, pageable or
+ * pinned), records and self_records; its priv may be NULL, so a part may be a struct the caller filled in for rows of its own.
+ * rows_dev must be 16-byte aligned (every list of this library is).  Host lists are uploaded, the lists are merged two at a time on the
+ * device -- ascending keys, a key at most once per list: a two-way merge that reads and writes every row once per merge, in the order
+ * of a binary counter, so that no row goes through more than ceil(log2(nparts)) + 1 merges -- and min_shared is applied by the last
+ * merge.  out is an ordinary hsk_pairs (host rows, or device rows with on_device), freed by hsk_pairs_free: n, rows, records and
+ * self_records (the sums), keys (before min_shared), ms_reduce (the merges), ms_d2h, ms_total.  The parts are left as they are.
+ * Needs neither EXTENSION nor a resident result.  HSK_ERR_INVALID_ARG: a NULL pointer, nparts < 0, min_shared == 0, a part with n > 0
+ * and no rows.  nparts == 0, or parts that are all empty, give an empty list.
+ */
+int  hsk_pairs_merge(hsk_ctx *ctx, const hsk_pairs *const *parts, int32_t nparts, uint32_t min_shared, int32_t on_device, hsk_pairs *out);
 /* Result egress (write_output_file, reference src/hysortk.cpp:138-164): the lines "KMERSTRING\tcount\n" of `n` entries
  * ((nw + 1)-word records: host memory, or device memory when `on_device`), formatted on the GPU into `text` (host, capacity
  * bytes); *nbytes = bytes needed (call with capacity 0 to size the buffer: K + 2 + up to 20 digits per entry). */

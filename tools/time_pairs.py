@@ -1,4 +1,5 @@
-"""Timing of hsk_result_pairs (read pairs that share k-mers, from the resident EXTENSION list).
+"""Timing of hsk_result_pairs, hsk_result_pairs_sliced and hsk_pairs_merge (read pairs that share k-mers, from the resident EXTENSION list;
+DESIGN sections 6.7 and 6.7b).
 
 Workload: reads of a random genome generated in HBM (hsk_synth_reads): G = 8 Mbp, 150-bp reads, 20x, K = 31, L = 2, U = 50, EXTENSION,
 KEEP_DEVICE.  Counted once; then hsk_result_pairs over all tasks, 2 warm-up calls and 5 timed ones (rows left on the device, so that the
@@ -7,7 +8,13 @@ algorithmic bytes (expansion: 16 B written per record; sort: 32 B per record and
 reducer: 16 B read per record) and the GB/s they make, against hsk_copy_peak measured in the same process.  For context, what a client
 has to do without the stage before it can start pairing: DeviceResult.fetch of every task (wall clock).
 
-usage: python tools/time_pairs.py [--gbp 0.008] [--coverage 20] [--out profiles/pairs_8mbp.json]"""
+--max-records N (repeatable; N a number of records, a fraction of the range's records such as 1/4, or 0 for the library's choice): the
+same timing of hsk_result_pairs_sliced with that budget, its slices and merges, the ratio of its time to the unsliced call's, and its rows
+compared with the unsliced rows.  Where the unsliced call does not fit the device its error is recorded and the sliced runs stand alone.
+--merge-only: the lists of the two halves of the task range, left on the device, merged by hsk_pairs_merge: the merge kernels' time and
+GB/s (32 B read per input row, 32 B written per output row) against hsk_copy_peak.
+
+usage: python tools/time_pairs.py [--gbp 0.008] [--coverage 20] [--max-records N ...] [--merge-only] [--out profiles/pairs_8mbp.json]"""
 import argparse, json, os, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,12 +26,34 @@ def median(v):
     return s[len(s) // 2]
 
 
+def timed(call, warmup=WARMUP, reps=REPS):
+    """info dicts of `reps` calls after `warmup` calls; the rows stay on the device and go back after every call."""
+    runs = []
+    for i in range(warmup + reps):
+        t0 = time.perf_counter()
+        with call() as rp:
+            info = dict(rp.info, rows=rp.n, wall_ms=(time.perf_counter() - t0) * 1e3)
+        if i >= warmup:
+            runs.append(info)
+    return runs
+
+
+def budget(text, records):
+    if "/" in text:
+        p, q = text.split("/")
+        return max(1, records * int(p) // int(q))
+    return int(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gbp", type=float, default=0.008); ap.add_argument("--coverage", type=float, default=20.0)
+    ap.add_argument("--max-records", action="append", default=[]); ap.add_argument("--merge-only", action="store_true")
+    ap.add_argument("--reps", type=int, default=REPS)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pairs_8mbp.json"))
     a = ap.parse_args()
     sys.path.insert(0, ROOT)
+    import numpy as np
     import hysortk_amd as H
     RL = 150
     G = int(a.gbp * 1e9)
@@ -36,38 +65,77 @@ def main():
     t0 = time.perf_counter()
     dev = dna.count_resident_device()
     count_ms = (time.perf_counter() - t0) * 1e3
-    runs = []
-    for i in range(WARMUP + REPS):
-        t0 = time.perf_counter()
-        with dev.pairs(on_device=True) as rp:
-            info = dict(rp.info, rows=rp.n, wall_ms=(time.perf_counter() - t0) * 1e3)
-        if i >= WARMUP:
-            runs.append(info)
-    host = dev.pairs()
-    last = runs[-1]
-    rec, passes = last["records"], last["sort_passes"]
-    nbytes = {"expand": 16 * rec, "sort": 32 * rec * passes + 8 * rec, "reduce": 16 * rec}
-    phases = {}
-    for ph in ("expand", "sort", "reduce"):
-        ms = [r["ms_" + ph] for r in runs]
-        m = median(ms)
-        phases[ph] = {"ms": ms, "median_ms": m, "bytes": nbytes[ph], "gbs": nbytes[ph] / (m * 1e-3) / 1e9 if m > 0 else 0.0,
-                      "of_copy_peak": nbytes[ph] / (m * 1e-3) / 1e9 / peak if m > 0 and peak > 0 else 0.0}
-    # the parent commit's way to the payload: every task's CSR across PCIe
-    t0 = time.perf_counter()
-    fetched = 0
-    for t in range(dev.ntasks):
-        d = dev.fetch(t)
-        fetched += d["n"] * (dev.nw + 1) * 8 + d["n"] * 8 + d["npay"] * 8
-    fetch_ms = (time.perf_counter() - t0) * 1e3
     out = {"what": "tools/time_pairs.py: hsk_result_pairs over all tasks of a resident EXTENSION result",
            "workload": {"genome_bp": G, "read_len": RL, "reads": n, "K": 31, "M": 17, "L": 2, "U": 50, "ntasks": dev.ntasks, "entries": dev.n, "count_call_wall_ms": count_ms},
-           "records": rec, "self_records": last["self_records"], "keys": last["keys"], "rows": last["rows"], "sort_passes": passes,
-           "copy_peak_gbs": peak, "phases": phases,
-           "ms_total": {"ms": [r["ms_total"] for r in runs], "median_ms": median([r["ms_total"] for r in runs])},
-           "wall_ms": {"ms": [r["wall_ms"] for r in runs], "median_ms": median([r["wall_ms"] for r in runs])},
-           "rows_to_host": {"ms_d2h": host.info["ms_d2h"], "ms_total": host.info["ms_total"], "bytes": len(host) * 32},
-           "fetch_every_task": {"wall_ms": fetch_ms, "bytes": fetched}}
+           "copy_peak_gbs": peak}
+
+    if a.merge_only:
+        half = dev.ntasks // 2
+        with dev.pairs(0, half, on_device=True) as pa, dev.pairs(half, dev.ntasks, on_device=True) as pb:
+            runs = timed(lambda: H.ReadPairs.combine([pa, pb], ctx=ctx, on_device=True), reps=a.reps)
+            na, nbr, no = pa.n, pb.n, runs[-1]["rows"]
+        nbytes = 32 * (na + nbr) + 32 * no
+        m = median([r["ms_reduce"] for r in runs])
+        out["what"] = "tools/time_pairs.py --merge-only: hsk_pairs_merge of the row lists of the two halves of the task range, all three lists in HBM"
+        out["merge"] = {"rows_a": na, "rows_b": nbr, "rows_out": no, "keys": runs[-1]["keys"], "bytes": nbytes,
+                        "ms_merge": [r["ms_reduce"] for r in runs], "median_ms": m, "gbs": nbytes / (m * 1e-3) / 1e9 if m > 0 else 0.0,
+                        "of_copy_peak": nbytes / (m * 1e-3) / 1e9 / peak if m > 0 and peak > 0 else 0.0,
+                        "ms_total": [r["ms_total"] for r in runs], "wall_ms": [r["wall_ms"] for r in runs]}
+    else:
+        base_rows, base_ms, records = None, None, None
+        try:
+            runs = timed(lambda: dev.pairs(on_device=True), reps=a.reps)
+            host = dev.pairs()
+            base_rows = host.rows() if a.max_records else None
+            last = runs[-1]
+            records = rec = last["records"]; passes = last["sort_passes"]
+            nbytes = {"expand": 16 * rec, "sort": 32 * rec * passes + 8 * rec, "reduce": 16 * rec}
+            phases = {}
+            for ph in ("expand", "sort", "reduce"):
+                ms = [r["ms_" + ph] for r in runs]
+                m = median(ms)
+                phases[ph] = {"ms": ms, "median_ms": m, "bytes": nbytes[ph], "gbs": nbytes[ph] / (m * 1e-3) / 1e9 if m > 0 else 0.0,
+                              "of_copy_peak": nbytes[ph] / (m * 1e-3) / 1e9 / peak if m > 0 and peak > 0 else 0.0}
+            base_ms = median([r["ms_total"] for r in runs])
+            out.update({"records": rec, "self_records": last["self_records"], "keys": last["keys"], "rows": last["rows"], "sort_passes": passes, "phases": phases,
+                        "ms_total": {"ms": [r["ms_total"] for r in runs], "median_ms": base_ms},
+                        "wall_ms": {"ms": [r["wall_ms"] for r in runs], "median_ms": median([r["wall_ms"] for r in runs])},
+                        "rows_to_host": {"ms_d2h": host.info["ms_d2h"], "ms_total": host.info["ms_total"], "bytes": len(host) * 32}})
+            del host
+        except H.HskError as e:
+            out["unsliced"] = {"status": e.status, "error": str(e)}
+        if not a.max_records:
+            # the parent commit's way to the payload: every task's CSR across PCIe
+            t0 = time.perf_counter()
+            fetched = 0
+            for t in range(dev.ntasks):
+                d = dev.fetch(t)
+                fetched += d["n"] * (dev.nw + 1) * 8 + d["n"] * 8 + d["npay"] * 8
+            out["fetch_every_task"] = {"wall_ms": (time.perf_counter() - t0) * 1e3, "bytes": fetched}
+        sliced = []
+        for text in a.max_records:
+            if records is None:                          # the unsliced call did not fit: the record count comes from a sliced call of 2^29 records at a time
+                with dev.pairs(on_device=True, max_records=1 << 29) as rp:
+                    records = rp.info["records"]
+            m = budget(text, records)
+            runs = timed(lambda: dev.pairs(on_device=True, max_records=m), reps=a.reps)
+            last = runs[-1]
+            tot, mrg = median([r["ms_total"] for r in runs]), median([r["ms_merge"] for r in runs])
+            s = {"max_records": m, "asked": text, "records": last["records"], "rows": last["rows"], "keys": last["keys"], "slices": last["slices"],
+                 "peak_records": last["peak_records"], "merges": last["merges"], "merged_rows": last["merged_rows"], "sort_passes": last["sort_passes"],
+                 "ms_total": [r["ms_total"] for r in runs], "median_ms": tot, "ms_merge": [r["ms_merge"] for r in runs], "median_ms_merge": mrg,
+                 "median_ms_expand": median([r["ms_expand"] for r in runs]), "median_ms_sort": median([r["ms_sort"] for r in runs]),
+                 "median_ms_reduce": median([r["ms_reduce"] for r in runs]),
+                 # the merges read 32 B per input row; their output rows (at most as many) are not counted here: a lower bound of the kernels' GB/s
+                 "merge_read_gbs": 32 * last["merged_rows"] / (mrg * 1e-3) / 1e9 if mrg > 0 else 0.0,
+                 "ratio_to_unsliced": tot / base_ms if base_ms else None}
+            if base_rows is not None:
+                got = dev.pairs(max_records=m)
+                s["rows_equal_unsliced"] = bool(np.array_equal(got.rows(), base_rows))
+                del got
+            sliced.append(s)
+        if sliced:
+            out["sliced"] = sliced
     dev.close()
     ctx.synth_free(dp, do, dl)
     ctx.close()
