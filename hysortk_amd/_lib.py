@@ -67,6 +67,14 @@ class PairsSlices(C.Structure):
     ]
 
 
+class Strands(C.Structure):
+    """hsk_strands: the strand bits of a resident EXTENSION result's payload slots (hsk_result_strands)."""
+    _fields_ = [
+        ("ntasks", C.c_int32), ("payloads", C.c_uint64), ("reverse", C.c_uint64), ("palindromes", C.c_uint64), ("ms_total", C.c_double),
+        ("reserved", C.c_int64 * 4), ("priv", C.c_void_p),
+    ]
+
+
 FLAG_PROFILE = 1
 FLAG_KEEP_DEVICE = 2
 FLAG_PLAIN_CLASSIFIER = 4
@@ -80,6 +88,7 @@ SYMBOLS = [
     "hsk_abi_version", "hsk_device_count", "hsk_host_alloc", "hsk_host_free", "hsk_init", "hsk_destroy", "hsk_strerror", "hsk_last_error", "hsk_config_default",
     "hsk_count", "hsk_count_device", "hsk_count_loopback", "hsk_count_loopback_device", "hsk_result_free", "hsk_result_device_task", "hsk_result_pairs", "hsk_pairs_free", "hsk_format_entries", "hsk_get_stats",
     "hsk_result_pairs_sliced", "hsk_pairs_merge",
+    "hsk_result_strands", "hsk_strands_task", "hsk_strands_free", "hsk_result_pairs_oriented",
     "hsk_stage_destinations", "hsk_stage_task_kmers", "hsk_stage_sort", "hsk_stage_count_sorted",
     "hsk_plan_tot_tasks", "hsk_plan_classify", "hsk_plan_dispatch", "hsk_plan_partition_reads", "hsk_plan_exchange",
     "hsk_comm_get_unique_id", "hsk_comm_init", "hsk_comm_destroy", "hsk_comm_selftest",
@@ -133,6 +142,12 @@ def load():
     L.hsk_result_pairs.argtypes = [vp, C.POINTER(Result), C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(Pairs)]
     L.hsk_result_pairs_sliced.argtypes = [vp, C.POINTER(Result), C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_uint64, C.POINTER(Pairs), C.POINTER(PairsSlices)]
     L.hsk_pairs_merge.argtypes = [vp, C.POINTER(C.POINTER(Pairs)), C.c_int32, C.c_uint32, C.c_int32, C.POINTER(Pairs)]
+    L.hsk_result_strands.argtypes = [vp, C.POINTER(Result), vp, C.c_uint64, vp, vp, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(Strands)]
+    L.hsk_strands_task.argtypes = [C.POINTER(Strands), C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.hsk_strands_free.argtypes = [vp, C.POINTER(Strands)]
+    L.hsk_strands_free.restype = None
+    L.hsk_result_pairs_oriented.argtypes = [vp, C.POINTER(Result), C.POINTER(Strands), C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_uint64,
+                                            C.POINTER(Pairs), C.POINTER(PairsSlices)]
     L.hsk_pairs_free.argtypes = [vp, C.POINTER(Pairs)]
     L.hsk_pairs_free.restype = None
     L.hsk_get_stats.argtypes = [vp, C.POINTER(Stats), C.c_int]

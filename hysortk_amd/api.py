@@ -197,12 +197,20 @@ class ReadPairs:
     """The read pairs that share k-mers (hsk_result_pairs, include/hsk.h): one row per pair of reads rid_a < rid_b (unsigned) with
     `shared` common k-mer occurrence pairs; first_pos_* / last_pos_* are the smallest / largest (pos_a, pos_b) among them.  Rows are
     in ascending (rid_a, rid_b).  With on_device the rows stay in HBM: rows_dev (n rows of four uint64 words { rid_a << 32 | rid_b,
-    shared, first, last }) and n; close() gives them back to the context.  There is no strand."""
+    shared, first, last }) and n; close() gives them back to the context.  There is no strand -- unless the list is oriented
+    (hsk_result_pairs_oriented, DeviceResult.pairs(strands=...)): bit 63 of the key is then the relative strand of the two occurrences,
+    `opposite` is that bit as a bool array and rid_a is the key's upper half without it; a read pair has up to two rows, all same-strand
+    rows first.  fold() gives the unoriented list."""
 
-    def __init__(self, key, shared, first, last, info=None, rows_dev=None, n=None, owner=None):
+    def __init__(self, key, shared, first, last, info=None, rows_dev=None, n=None, owner=None, oriented=False):
         self.key, self.shared, self.first, self.last = (np.ascontiguousarray(x, dtype=np.uint64) for x in (key, shared, first, last))
         lo = np.uint64(0xFFFFFFFF)
+        self.oriented = bool(oriented)
         self.rid_a, self.rid_b = (self.key >> np.uint64(32)).astype(np.uint32), (self.key & lo).astype(np.uint32)
+        self.opposite = None
+        if self.oriented:                        # (an unoriented list may have bit 31 of rid_a set: read ids are unsigned 32-bit numbers there)
+            self.opposite = (self.key >> np.uint64(63)).astype(bool)
+            self.rid_a = self.rid_a & np.uint32(0x7FFFFFFF)
         self.first_pos_a, self.first_pos_b = (self.first >> np.uint64(32)).astype(np.uint32), (self.first & lo).astype(np.uint32)
         self.last_pos_a, self.last_pos_b = (self.last >> np.uint64(32)).astype(np.uint32), (self.last & lo).astype(np.uint32)
         self.info = info or {}
@@ -228,22 +236,39 @@ class ReadPairs:
         join -- shared adds up, first is the minimum, last the maximum -- and min_shared is applied afterwards.  The parts must have
         been computed with min_shared=1.  Without ctx: on the host, in numpy (the parts' rows must be on the host).  With a Context:
         hsk_pairs_merge on its GPU -- parts whose rows are on the device are read there, host rows are uploaded, and on_device=True
-        leaves the result in HBM as DeviceResult.pairs does."""
+        leaves the result in HBM as DeviceResult.pairs does.  Oriented parts give an oriented list (bit 63 is part of the key); oriented
+        and unoriented parts do not combine (ValueError)."""
+        parts = list(parts)
+        flags = {bool(p.oriented) for p in parts}
+        if len(flags) > 1:
+            raise ValueError("oriented and unoriented read pair lists do not combine: fold() the oriented ones first")
+        oriented = bool(flags) and flags.pop()
         if ctx is not None:
-            return ReadPairs._combine_device(list(parts), min_shared, ctx, on_device)
+            return ReadPairs._combine_device(parts, min_shared, ctx, on_device, oriented)
         rows = [p.rows() for p in parts if len(p)]
         if not rows:
-            return ReadPairs.from_rows(np.zeros((0, 4), np.uint64))
+            return ReadPairs.from_rows(np.zeros((0, 4), np.uint64), oriented=oriented)
         r = np.concatenate(rows)
         r = r[np.argsort(r[:, 0], kind="stable")]
         start = np.flatnonzero(np.concatenate([[True], r[1:, 0] != r[:-1, 0]]))
         out = np.stack([r[start, 0], np.add.reduceat(r[:, 1], start), np.minimum.reduceat(r[:, 2], start), np.maximum.reduceat(r[:, 3], start)], axis=1)
         info = {k: sum(int(p.info.get(k, 0)) for p in parts) for k in ("records", "self_records")}
         info["keys"] = int(out.shape[0])
-        return ReadPairs.from_rows(out[out[:, 1] >= np.uint64(min_shared)], info=info)
+        return ReadPairs.from_rows(out[out[:, 1] >= np.uint64(min_shared)], info=info, oriented=oriented)
+
+    def fold(self, min_shared=1):
+        """The unoriented list of an oriented one, on the host (the folding property, include/hsk.h): bit 63 of every key cleared, rows
+        with equal keys joined -- shared adds up, first is the minimum, last the maximum -- and min_shared applied afterwards: the list
+        DeviceResult.pairs gives without strands for the same task range (from an oriented list computed with min_shared=1)."""
+        if not self.oriented:
+            raise ValueError("fold() is for an oriented list")
+        r = self.rows().copy()
+        r[:, 0] &= np.uint64(0x7FFFFFFFFFFFFFFF)
+        info = {k: v for k, v in self.info.items() if k in ("records", "self_records")}
+        return ReadPairs.combine([ReadPairs.from_rows(r, info=info)], min_shared=min_shared)
 
     @staticmethod
-    def _combine_device(parts, min_shared, ctx, on_device):
+    def _combine_device(parts, min_shared, ctx, on_device, oriented=False):
         structs, keep = [], []
         for p in parts:
             s = _lib.Pairs()
@@ -259,10 +284,10 @@ class ReadPairs:
         arr = (C.POINTER(_lib.Pairs) * max(len(structs), 1))(*[C.pointer(s) for s in structs])
         pr = _lib.Pairs()
         ctx._check(ctx.lib.hsk_pairs_merge(ctx.h, arr, len(structs), min_shared, 1 if on_device else 0, C.byref(pr)))
-        return ReadPairs._wrap(ctx, pr, on_device)
+        return ReadPairs._wrap(ctx, pr, on_device, oriented=oriented)
 
     @staticmethod
-    def _wrap(ctx, pr, on_device, extra=None):
+    def _wrap(ctx, pr, on_device, extra=None, oriented=False):
         """A ReadPairs from a filled hsk_pairs: the rows copied to numpy and the struct freed, or (on_device) left in HBM and owned."""
         info = dict(records=int(pr.records), self_records=int(pr.self_records), keys=int(pr.keys), sort_passes=int(pr.sort_passes),
                     ms_expand=pr.ms_expand, ms_sort=pr.ms_sort, ms_reduce=pr.ms_reduce, ms_d2h=pr.ms_d2h, ms_total=pr.ms_total)
@@ -270,10 +295,10 @@ class ReadPairs:
         n = int(pr.n)
         if on_device:
             z = np.zeros(0, np.uint64)
-            return ReadPairs(z, z, z, z, info=info, rows_dev=pr.rows_dev, n=n, owner=(ctx, pr))
+            return ReadPairs(z, z, z, z, info=info, rows_dev=pr.rows_dev, n=n, owner=(ctx, pr), oriented=oriented)
         rows = np.ctypeslib.as_array(pr.rows, shape=(n * 4,)).reshape(n, 4).copy() if n else np.zeros((0, 4), np.uint64)
         ctx.lib.hsk_pairs_free(ctx.h, C.byref(pr))
-        return ReadPairs.from_rows(rows, info=info)
+        return ReadPairs.from_rows(rows, info=info, oriented=oriented)
 
     def close(self):
         if self._owner is not None:
@@ -285,6 +310,48 @@ class ReadPairs:
     def __del__(self):
         try:
             self.close()                 # (rows left on the device go back while the context is alive; after hsk_destroy there is nothing to free)
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Strands:
+    """The strand bits of a resident EXTENSION result (hsk_result_strands, include/hsk.h): one bit per payload slot, in HBM.  info has
+    ntasks, payloads, reverse, palindromes and ms_total; task_bits(t) copies task t's bits to the host.  close() gives the arrays back
+    to the context (before the context goes)."""
+
+    def __init__(self, ctx, st):
+        self.ctx, self.st = ctx, st
+        self.info = dict(ntasks=int(st.ntasks), payloads=int(st.payloads), reverse=int(st.reverse), palindromes=int(st.palindromes), ms_total=st.ms_total)
+
+    def task(self, t):
+        """(device address of task t's bit words or None, number of its payload slots)"""
+        bits, npay = C.c_void_p(), C.c_uint64()
+        self.ctx._check(self.ctx.lib.hsk_strands_task(C.byref(self.st), t, C.byref(bits), C.byref(npay)))
+        return bits.value, int(npay.value)
+
+    def task_bits(self, t):
+        """numpy bool array of npay: the strand of every payload slot of task t (False for the gaps of filtered k-mers)."""
+        bits, npay = self.task(t)
+        if not npay:
+            return np.zeros(0, dtype=bool)
+        words = self.ctx.d2h(bits, (npay + 63) // 64 * 8)
+        return np.unpackbits(words, bitorder="little")[:npay].astype(bool)
+
+    def close(self):
+        if self.st is not None:
+            if getattr(self.ctx, "h", None):
+                self.ctx.lib.hsk_strands_free(self.ctx.h, C.byref(self.st))
+            self.st = None
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 
@@ -323,13 +390,41 @@ class DeviceResult:
             out["rid"] = self.ctx.d2h(d["rid"], d["npay"] * 4).view(np.int32)
         return out
 
-    def pairs(self, task_lo=0, task_hi=None, min_shared=1, on_device=False, max_records=None):
+    def strands(self, reads, rid_base=None):
+        """hsk_result_strands: the strand of every payload slot of the result, recovered from the reads it was counted from -- a
+        DeviceDna (read where it lies in HBM), a DnaBuffer or a (packed, off, lens) tuple of host arrays (uploaded for the call).
+        rid_base: the id of read 0, as it was given to the count (default: the buffer's first_read_id, else 0).  Returns a Strands;
+        close() it before the context goes."""
+        st = _lib.Strands()
+        if isinstance(reads, DeviceDna):
+            base = reads.first_read_id if rid_base is None else rid_base
+            rc = self.ctx.lib.hsk_result_strands(self.ctx.h, C.byref(self.res), reads.dp, reads.nbytes, reads.do, reads.dl, reads.nreads, base, 1, C.byref(st))
+        else:
+            base = getattr(reads, "first_read_id", 0) if rid_base is None else rid_base
+            packed, off, lens = reads.arrays() if isinstance(reads, DnaBuffer) else reads
+            packed = np.ascontiguousarray(packed, dtype=np.uint8)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+            lens = np.ascontiguousarray(lens, dtype=np.uint32)
+            rc = self.ctx.lib.hsk_result_strands(self.ctx.h, C.byref(self.res), _p(packed), packed.size, _p(off), _p(lens), lens.size, base, 0, C.byref(st))
+        self.ctx._check(rc)
+        return Strands(self.ctx, st)
+
+    def pairs(self, task_lo=0, task_hi=None, min_shared=1, on_device=False, max_records=None, strands=None):
         """hsk_result_pairs over tasks [task_lo, task_hi) (default: all): the read pairs that share at least min_shared k-mer
         occurrence pairs, as a ReadPairs.  on_device=True leaves the rows in HBM (ReadPairs.rows_dev, .n; close() it before the
         context goes).  max_records=N: hsk_result_pairs_sliced -- the same list, from at most N records expanded at a time (0: the
-        library chooses from the device memory that is left); info then has slices, peak_records, merges, merged_rows and ms_merge."""
+        library chooses from the device memory that is left); info then has slices, peak_records, merges, merged_rows and ms_merge.
+        strands=Strands (of this result): hsk_result_pairs_oriented -- the rows split by the relative strand of the two occurrences, an
+        oriented ReadPairs (max_records=None: the single pass)."""
         pr = _lib.Pairs()
         hi = self.ntasks if task_hi is None else task_hi
+        if strands is not None:
+            sl = _lib.PairsSlices()
+            budget = 0xFFFFFFFFFFFFFFFF if max_records is None else int(max_records)
+            self.ctx._check(self.ctx.lib.hsk_result_pairs_oriented(self.ctx.h, C.byref(self.res), C.byref(strands.st), task_lo, hi, min_shared, 1 if on_device else 0,
+                                                                   budget, C.byref(pr), C.byref(sl)))
+            extra = dict(slices=int(sl.slices), peak_records=int(sl.peak_records), merges=int(sl.merges), merged_rows=int(sl.merged_rows), ms_merge=sl.ms_merge)
+            return ReadPairs._wrap(self.ctx, pr, on_device, extra, oriented=True)
         if max_records is None:
             self.ctx._check(self.ctx.lib.hsk_result_pairs(self.ctx.h, C.byref(self.res), task_lo, hi, min_shared, 1 if on_device else 0, C.byref(pr)))
             return ReadPairs._wrap(self.ctx, pr, on_device)

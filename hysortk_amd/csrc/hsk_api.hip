@@ -39,6 +39,7 @@
 #include "hsk_heavy.h"
 #include "hsk_pairs.h"
 #include "hsk_pairmerge.h"
+#include "hsk_strand.h"
 #include "hsk_estimate.h"
 #include "hsk_synth.h"
 #include "hsk_plan.h"
@@ -450,6 +451,8 @@ extern "C" int hsk_result_device_task(const hsk_result *r, int32_t task, const v
 
 // read pairs that share k-mers, from a resident EXTENSION result: hsk_result_pairs, hsk_pairs_free
 #include "hsk_host_pairs.h"
+// the strand of every occurrence of such a result, one bit per payload slot: hsk_result_strands, hsk_strands_task, hsk_strands_free
+#include "hsk_host_strand.h"
 
 // Uploads the DnaBuffer description; returns device arrays with nreads+1 offsets.
 

@@ -1,9 +1,11 @@
-// hsk_host_pairs.h -- host side of hsk_result_pairs, hsk_result_pairs_sliced and hsk_pairs_merge: read pairs that share k-mers, from the
-// resident EXTENSION list (kernels: hsk_pairs.h, hsk_pairmerge.h).
+// hsk_host_pairs.h -- host side of hsk_result_pairs, hsk_result_pairs_sliced, hsk_result_pairs_oriented and hsk_pairs_merge: read pairs that
+// share k-mers, from the resident EXTENSION list (kernels: hsk_pairs.h, hsk_pairmerge.h).
 // Part of the single translation unit hsk_api.hip (included in this order; everything here is file-local).
 #pragma once
 
 struct PairsPriv { void *host_rows = nullptr; void *dev_rows = nullptr; };
+// hsk_strands (hsk_host_strand.h): one block of bit words for all tasks of the result; task t's npay[t] bits start at word word0[t]
+struct StrandsPriv { u64 *bits = nullptr; std::vector<u64> word0, npay; };
 
 // The phases of a call, summed over its slices and merges.  Every event pair is closed before the host waits, and taken behind the wait.
 enum { PT_EXPAND = 0, PT_SORT, PT_REDUCE, PT_MERGE, PT_D2H, PT_N };
@@ -21,7 +23,8 @@ struct PairRange {
     PairTask *d_tasks = nullptr; u64 *d_off = nullptr, *d_loc = nullptr, *d_stat = nullptr;
 };
 
-static int pairs_range_tasks(hsk_ctx *c, const ResultPriv *rp, int32_t task_lo, int32_t task_hi, PairRange &r)
+// sp: the strand bits of the result's payload slots (hsk_result_pairs_oriented), or NULL
+static int pairs_range_tasks(hsk_ctx *c, const ResultPriv *rp, int32_t task_lo, int32_t task_hi, PairRange &r, const StrandsPriv *sp = nullptr)
 {
     for (int32_t t = task_lo; t < task_hi; ++t) {
         const TaskOut &to = rp->dev_tasks[t];
@@ -29,6 +32,7 @@ static int pairs_range_tasks(hsk_ctx *c, const ResultPriv *rp, int32_t task_lo, 
         if (!to.entries || !to.payoff || !to.pos || !to.rid) return fail(c, HSK_ERR_INTERNAL, "task %d of the resident result has entries but no payload arrays", t);
         if (to.npay >> PAIR_LOC_SHIFT) return fail(c, HSK_ERR_UNSUPPORTED, "task %d holds %llu payloads (2^%d at most)", t, (unsigned long long)to.npay, PAIR_LOC_SHIFT);
         PairTask p; p.entries = to.entries; p.payoff = to.payoff; p.pos = to.pos; p.rid = to.rid; p.ent_base = r.nent; p.n = to.n; p.npay = to.npay; p.pay_base = to.pay_base;
+        p.strand = sp ? sp->bits + sp->word0[t] : nullptr;
         r.tk.push_back(p); r.nent += to.n;
     }
     return HSK_OK;
@@ -75,7 +79,7 @@ struct PairWindow { u64 ent0, ent1, rec0, records; };   // entries [ent0, ent1) 
 // Expand a record window, sort it, reduce it to rows that stay on the device.  The whole range is the window { 0, nent, 0, records }.
 // `last`: no window follows -- what the count pass left goes back as soon as the expansion is enqueued.  One wait per sort (its histogram)
 // and one for the row count.  The window's record buffers are released before the routine returns.
-static int pairs_window(hsk_ctx *c, PairRange &r, const PairWindow &w, bool last, u32 min_shared, int32_t task_lo, int32_t task_hi, PairClock &ck, hsk_pairs *acc, PairList *list)
+static int pairs_window(hsk_ctx *c, PairRange &r, const PairWindow &w, bool last, bool oriented, u32 min_shared, int32_t task_lo, int32_t task_hi, PairClock &ck, hsk_pairs *acc, PairList *list)
 {
     const u64 records = w.records;
     u64 *st = staging(c)->read_pairs;
@@ -91,7 +95,8 @@ static int pairs_window(hsk_ctx *c, PairRange &r, const PairWindow &w, bool last
     if (xtiles > 0x7fffffffULL) return fail(c, HSK_ERR_UNSUPPORTED, "%llu records are more than one launch expands; ask for a narrower task range, or let hsk_result_pairs_sliced expand fewer at a time", (unsigned long long)records);
     ck.t.begin(PT_EXPAND);
     if (w.rec0) HIPCHK(c, hipMemsetAsync(r.d_stat, 0, PAIR_STAT_WORDS * 8, c->stream));      // (self_records of the slice before)
-    hipLaunchKernelGGL(pair_expand_kernel, dim3((u32)xtiles), dim3(PAIR_THREADS), 0, c->stream, xa);
+    if (oriented) hipLaunchKernelGGL(pair_expand_kernel<true>, dim3((u32)xtiles), dim3(PAIR_THREADS), 0, c->stream, xa);      // (bit 63 of the key: the strands' XOR)
+    else hipLaunchKernelGGL(pair_expand_kernel<false>, dim3((u32)xtiles), dim3(PAIR_THREADS), 0, c->stream, xa);
     HIPCHK(c, hipGetLastError());
     ck.t.end(PT_EXPAND);
     if (last) pairs_release_range(c, r, false);
@@ -287,11 +292,12 @@ static u64 pairs_auto_budget(hsk_ctx *c)
 // sliced == true (hsk_result_pairs_sliced): the same while the records fit the budget; else one more wait for the plan -- one lane cuts the
 // whole range on the device (pair_plan_kernel), since reading a cut back per slice would wait once per slice -- then every slice is a window
 // of its own, and the lists meet on a PairStack: one wait per merge, for its row count.
-static int pairs_impl(hsk_ctx *c, const ResultPriv *rp, int nw, int32_t task_lo, int32_t task_hi, u32 min_shared, bool on_device, bool sliced, u64 max_records,
+static int pairs_impl(hsk_ctx *c, const ResultPriv *rp, const StrandsPriv *sp, int nw, int32_t task_lo, int32_t task_hi, u32 min_shared, bool on_device, bool sliced, u64 max_records,
                       hsk_pairs *out, hsk_pairs_slices *info, PairsPriv *pp)
 {
     PairRange r;
-    int rc = pairs_range_tasks(c, rp, task_lo, task_hi, r); if (rc) return rc;
+    const bool oriented = sp != nullptr;               // (hsk_result_pairs_oriented: only the key of a record differs)
+    int rc = pairs_range_tasks(c, rp, task_lo, task_hi, r, sp); if (rc) return rc;
     info->slices = 1;
     if (!r.nent) return HSK_OK;
     EvList ev(c);
@@ -313,7 +319,7 @@ static int pairs_impl(hsk_ctx *c, const ResultPriv *rp, int nw, int32_t task_lo,
     PairList fin;
     if (budget >= records) {
         const PairWindow w = {0, r.nent, 0, records};
-        rc = pairs_window(c, r, w, true, min_shared, task_lo, task_hi, ck, out, &fin); if (rc) return rc;
+        rc = pairs_window(c, r, w, true, oriented, min_shared, task_lo, task_hi, ck, out, &fin); if (rc) return rc;
         info->peak_records = records;
     } else {
         // ---- the plan: every cut and the record offset at it, in one launch and one wait ---------------------------------------------
@@ -343,7 +349,7 @@ static int pairs_impl(hsk_ctx *c, const ResultPriv *rp, int nw, int32_t task_lo,
         for (size_t i = 0; i < win.size(); ++i) {
             const bool last = i + 1 == win.size();
             PairList l;
-            rc = pairs_window(c, r, win[i], last, 1, task_lo, task_hi, ck, &acc, &l); if (rc) return rc;
+            rc = pairs_window(c, r, win[i], last, oriented, 1, task_lo, task_hi, ck, &acc, &l); if (rc) return rc;
             info->peak_records = std::max<u64>(info->peak_records, win[i].records);
             rc = stk.push(c, l, !last, ck); if (rc) return rc;
         }
@@ -358,7 +364,7 @@ static int pairs_impl(hsk_ctx *c, const ResultPriv *rp, int nw, int32_t task_lo,
     return HSK_OK;
 }
 
-static int pairs_entry(hsk_ctx *c, const hsk_result *res, int32_t task_lo, int32_t task_hi, uint32_t min_shared, int32_t on_device, bool sliced, uint64_t max_records,
+static int pairs_entry(hsk_ctx *c, const hsk_result *res, const hsk_strands *strands, int32_t task_lo, int32_t task_hi, uint32_t min_shared, int32_t on_device, bool sliced, uint64_t max_records,
                        hsk_pairs *out, hsk_pairs_slices *info, const char *name)
 {
     if (!c || !res || !out) return HSK_ERR_INVALID_ARG;
@@ -371,8 +377,17 @@ static int pairs_entry(hsk_ctx *c, const hsk_result *res, int32_t task_lo, int32
         return fail(c, HSK_ERR_INVALID_ARG, "%s needs a result that was left on the device (HSK_FLAG_KEEP_DEVICE)", name);
     if (task_lo < 0 || task_hi < task_lo || task_hi > res->ntasks) return fail(c, HSK_ERR_INVALID_ARG, "task range [%d, %d) outside [0, %d]", task_lo, task_hi, res->ntasks);
     if (min_shared == 0) return fail(c, HSK_ERR_INVALID_ARG, "min_shared must be at least 1");
+    const StrandsPriv *sp = strands ? (const StrandsPriv *)strands->priv : nullptr;
+    if (strands) {                                        // do the bits belong to this result?
+        if (!sp || strands->ntasks != res->ntasks || sp->npay.size() != (size_t)res->ntasks)
+            return fail(c, HSK_ERR_INVALID_ARG, "%s: the strands are of %d tasks, the result has %d", name, sp ? strands->ntasks : 0, res->ntasks);
+        for (int32_t t = 0; t < res->ntasks; ++t)
+            if (sp->npay[t] != rp->dev_tasks[t].npay)
+                return fail(c, HSK_ERR_INVALID_ARG, "%s: the strands do not belong to this result (task %d: %llu payload slots, the result has %llu)", name, t,
+                            (unsigned long long)sp->npay[t], (unsigned long long)rp->dev_tasks[t].npay);
+    }
     PairsPriv *pp = new PairsPriv();
-    const int rc = ApiCall(c, name).run([&] { return pairs_impl(c, rp, res->nw, task_lo, task_hi, min_shared, on_device != 0, sliced, max_records, out, info, pp); });
+    const int rc = ApiCall(c, name).run([&] { return pairs_impl(c, rp, sp, res->nw, task_lo, task_hi, min_shared, on_device != 0, sliced, max_records, out, info, pp); });
     if (rc != HSK_OK) {                                   // (the device blocks went back with the call's rollback)
         if (pp->host_rows) c->hpool.release(pp->host_rows);
         delete pp;
@@ -385,13 +400,22 @@ static int pairs_entry(hsk_ctx *c, const hsk_result *res, int32_t task_lo, int32
 
 extern "C" int hsk_result_pairs(hsk_ctx *c, const hsk_result *res, int32_t task_lo, int32_t task_hi, uint32_t min_shared, int32_t on_device, hsk_pairs *out)
 {
-    return pairs_entry(c, res, task_lo, task_hi, min_shared, on_device, false, 0, out, nullptr, "hsk_result_pairs");
+    return pairs_entry(c, res, nullptr, task_lo, task_hi, min_shared, on_device, false, 0, out, nullptr, "hsk_result_pairs");
 }
 
 extern "C" int hsk_result_pairs_sliced(hsk_ctx *c, const hsk_result *res, int32_t task_lo, int32_t task_hi, uint32_t min_shared, int32_t on_device, uint64_t max_records,
                                        hsk_pairs *out, hsk_pairs_slices *info)
 {
-    return pairs_entry(c, res, task_lo, task_hi, min_shared, on_device, true, max_records, out, info, "hsk_result_pairs_sliced");
+    return pairs_entry(c, res, nullptr, task_lo, task_hi, min_shared, on_device, true, max_records, out, info, "hsk_result_pairs_sliced");
+}
+
+// hsk_result_pairs_sliced with the relative strand of the two occurrences in bit 63 of every record's key: the sort, the reducer, the
+// slices and the merges see a key like any other
+extern "C" int hsk_result_pairs_oriented(hsk_ctx *c, const hsk_result *res, const hsk_strands *strands, int32_t task_lo, int32_t task_hi, uint32_t min_shared,
+                                         int32_t on_device, uint64_t max_records, hsk_pairs *out, hsk_pairs_slices *info)
+{
+    if (!strands) { if (c && out) memset(out, 0, sizeof *out); return c ? fail(c, HSK_ERR_INVALID_ARG, "hsk_result_pairs_oriented: strands is NULL") : HSK_ERR_INVALID_ARG; }
+    return pairs_entry(c, res, strands, task_lo, task_hi, min_shared, on_device, true, max_records, out, info, "hsk_result_pairs_oriented");
 }
 
 // The several-list contract on the GPU: host lists go up, device lists are read where they are, and all meet on a PairStack.

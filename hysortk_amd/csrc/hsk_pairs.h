@@ -19,6 +19,8 @@
 //                       so that it sorts to the front, leaves every digit as trivial as it was, and is counted by the reducer.
 //                       The launch covers a WINDOW of the range's records, [rec0, rec0 + records) = entries [ent0, nent): the whole
 //                       range for hsk_result_pairs, one slice of it for hsk_result_pairs_sliced (hsk_pairplan.h).
+//                       ORIENTED (hsk_result_pairs_oriented): the XOR of the two occurrences' strand bits (hsk_strand.h) is bit 63 of the
+//                       key; everything behind the expansion sees a key like any other.
 //   pair_reduce_kernel  the shape of count_kernel: run heads of a tile as a bit mask, rows per tile, count_scan_kernel, write pass.
 //                       A run belongs to the tile it starts in.  The last run of a tile may go on for any number of tiles: the
 //                       whole workgroup reads ahead to its end (count, min, max reduced over the workgroup); tiles inside a run
@@ -30,14 +32,15 @@
 
 namespace hsk {
 
-// one task of the range that has entries (host: hsk_host_pairs.h)
-struct PairTask {
+// one task of the range that has entries (host: hsk_host_pairs.h).  128 bytes, a power of two: the kernels address the table with a shift
+struct alignas(128) PairTask {
     const u64 *entries;      // n records of nw + 1 words, the count last
     const u64 *payoff;       // n: first payload of the entry in the rank's numbering
     const u32 *pos;          // npay
     const int32_t *rid;      // npay
     u64 ent_base;            // entries of the range's tasks before this one
     u64 n, npay, pay_base;   // entry i owns pos / rid[payoff[i] - pay_base ...][0 .. cnt_i)
+    const u64 *strand;       // hsk_result_pairs_oriented: bit s & 63 of word s >> 6 = the strand of payload slot s (hsk_strand.h); NULL otherwise
 };
 
 constexpr int PAIR_THREADS = 256;
@@ -105,6 +108,8 @@ struct PairExpandArgs {
     u64 rec0, ent0;          // both 0: the whole range (hsk_result_pairs); a slice otherwise (hsk_result_pairs_sliced)
 };
 
+// ORIENTED (hsk_result_pairs_oriented): bit 63 of the key is the XOR of the two occurrences' strands -- read ids are below 2^31 there
+template <bool ORIENTED>
 __global__ __launch_bounds__(PAIR_THREADS) void pair_expand_kernel(PairExpandArgs a)
 {
     __shared__ u64 s_off[PX_STAGE + 1];
@@ -164,7 +169,9 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_expand_kernel(PairExpandArg
         u32 pa = tk.pos[first + i], pb = tk.pos[first + j];
         if (ra > rb) { const u32 x = ra; ra = rb; rb = x; const u32 y = pa; pa = pb; pb = y; }
         const bool self = ra == rb;
-        a.keys[idx - a.rec0] = self ? 0ULL : ((u64)ra << 32) | rb;
+        u64 o = 0;
+        if (ORIENTED) { const u64 si = first + i, sj = first + j; o = ((tk.strand[si >> 6] >> (si & 63)) ^ (tk.strand[sj >> 6] >> (sj & 63))) << 63; }
+        a.keys[idx - a.rec0] = self ? 0ULL : o | ((u64)ra << 32) | rb;
         a.vals[idx - a.rec0] = self ? 0ULL : ((u64)pa << 32) | pb;
     }
 }

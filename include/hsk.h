@@ -241,7 +241,8 @@ int hsk_result_device_task(const hsk_result *res, int32_t task, const void **ent
  *     { key, shared, first, last }     shared = records with that key, first / last = the smallest / largest value of the run
  * (as 64-bit numbers: ordered by pos_a, then pos_b).  Minimum and maximum do not depend on the order of the payload inside an
  * entry, which is unspecified.  There is NO STRAND in a row: the payload carries none, so a pair of reads that overlap on opposite
- * strands is told from one on the same strand only by the way pos_b runs against pos_a, which first and last bracket.
+ * strands is told from one on the same strand only by the way pos_b runs against pos_a, which first and last bracket
+ * (hsk_result_strands and hsk_result_pairs_oriented, below, recover the strand from the reads and split the rows by it).
  *
  * Several lists (the multi-rank contract).  The lists of disjoint task ranges combine to the list of their union, and so do the
  * lists of the ranks of a several-GPU run (every k-mer belongs to one task and every task to one rank): rows with equal keys
@@ -312,6 +313,66 @@ int  hsk_result_pairs_sliced(hsk_ctx *ctx, const hsk_result *res, int32_t task_l
  * and no rows.  nparts == 0, or parts that are all empty, give an empty list.
  */
 int  hsk_pairs_merge(hsk_ctx *ctx, const hsk_pairs *const *parts, int32_t nparts, uint32_t min_shared, int32_t on_device, hsk_pairs *out);
+/*
+ * The strand of every k-mer occurrence of a result that was left on the device (HSK_FLAG_KEEP_DEVICE and EXTENSION), recovered from the
+ * reads the result was counted from: the payload (ReadId, PosInRead) carries no strand, but the entry holds the canonical k-mer, and the
+ * read's K bases at the position spell either it or its reverse complement.
+ *
+ * Definition.  For entry e of task t and each of its cnt_e payload slots s (indices into the task's pos / rid arrays, as
+ * hsk_result_device_task describes them: s = payload_off[e] - payload_base + 0 .. cnt_e - 1), the read rid[s] - rid_base has K bases at
+ * pos[s], in the packed bytes exactly as hsk_count reads them: base i of a read in byte i / 4 of the read at shift 6 - 2 (i % 4).  Put into
+ * the layout of the entry's k-mer words (base i in word i / 32 at shift 2 (31 - i % 32)) they are the word f.  f equals the entry's k-mer:
+ * strand 0; else the reverse complement of f (Kmer::GetTwin, kmer.hpp:266-296) equals it: strand 1.  Equality with the entry is tested
+ * first, so a k-mer that is its own reverse complement (even K only) has strand 0; such occurrences are counted in `palindromes`.
+ *
+ * Output.  One device array of (npay + 63) / 64 uint64 words per task (hsk_strands_task): bit s & 63 of word s >> 6 is the strand of slot
+ * s.  Slots that belong to no entry -- the gaps that filtered k-mers leave -- have bit 0 and are never read as (rid, pos).  The arrays
+ * belong to the hsk_strands: hsk_strands_free before hsk_destroy of the context.
+ *
+ *   packed, read_byte_off, read_len, nreads, rid_base   the reads as hsk_count / hsk_count_device took them; reads_on_device != 0: the
+ *                three arrays are device memory (what hsk_count_device, hsk_pack_fasta and hsk_synth_reads leave in HBM; packed 4-byte
+ *                aligned), else host memory that is uploaded for the call.  No byte at or beyond packed_bytes is read.
+ * The call is rank-local: a rank of a several-GPU run is given the reads its payload names (a payload that names another read is the
+ * out-of-range refusal below).
+ * HSK_ERR_INVALID_ARG, with a hsk_last_error text that names the case, the context usable afterwards: a NULL pointer; a context without
+ * EXTENSION; a result that was not left on the device; rid_base + nreads > 2^31; an owned slot whose rid lies outside
+ * [rid_base, rid_base + nreads); an owned slot with pos + K > read_len; a read of the index outside the packed bytes; an owned slot whose
+ * bases are neither the entry's k-mer nor its reverse complement ("these are not the reads the result was counted from").
+ */
+typedef struct {
+    int32_t  ntasks;
+    uint64_t payloads;     /* payload slots owned by entries of the result (sum of cnt) */
+    uint64_t reverse;      /* of which strand 1 */
+    uint64_t palindromes;  /* occurrences whose k-mer is its own reverse complement (even K only); strand 0 */
+    double   ms_total;     /* HIP events */
+    int64_t  reserved[4];
+    void    *priv;
+} hsk_strands;
+
+int  hsk_result_strands(hsk_ctx *ctx, const hsk_result *res,
+                        const void *packed, uint64_t packed_bytes, const void *read_byte_off, const void *read_len,
+                        uint64_t nreads, int64_t rid_base, int32_t reads_on_device, hsk_strands *out);
+/* task `task`'s bit words in HBM (NULL when the task has no payload) and the number of its payload slots */
+int  hsk_strands_task(const hsk_strands *s, int32_t task, const void **bits_dev, uint64_t *npay);
+void hsk_strands_free(hsk_ctx *ctx, hsk_strands *s);
+/*
+ * Read pairs split by relative strand.  hsk_result_pairs_oriented has the definition, the refusals, the memory rules and the slicing of
+ * hsk_result_pairs_sliced (max_records: 0 lets the library choose, a budget of at least `records` -- UINT64_MAX -- is the single pass), with
+ * one difference: the record of an occurrence pair (i, j) of two different reads has
+ *     key = o << 63 | rid_a << 32 | rid_b        o = strand_i XOR strand_j   (`strands`: hsk_result_strands of the same result)
+ * Read ids are below 2^31 here (hsk_result_strands has refused anything else), so bit 63 is free.  The list has all same-strand rows first
+ * and all opposite-strand rows behind them, each half in ascending (rid_a, rid_b); key & ~(1 << 63) is the key hsk_result_pairs gives.
+ * A pair inside one read is still key 0 and counted in self_records, whatever its strands; keys counts distinct (read pair, orientation).
+ * Seeds of a same-strand overlap and of a reverse-complement overlap of two reads thus arrive as two rows, each with its own shared count
+ * and first / last bracket.
+ * Folding property.  Clearing bit 63 and joining equal keys -- shared adds up, first is the minimum, last the maximum, min_shared applied
+ * afterwards -- gives exactly the list of hsk_result_pairs for the same task range.
+ * Oriented lists of disjoint task ranges or of several ranks combine through hsk_pairs_merge as they are: bit 63 is part of the key.
+ * HSK_ERR_INVALID_ARG also for a NULL `strands` and for one that does not belong to `res` (ntasks and every task's payload slots are compared).
+ */
+int  hsk_result_pairs_oriented(hsk_ctx *ctx, const hsk_result *res, const hsk_strands *strands,
+                               int32_t task_lo, int32_t task_hi, uint32_t min_shared, int32_t on_device,
+                               uint64_t max_records, hsk_pairs *out, hsk_pairs_slices *info);
 /* Result egress (write_output_file, reference src/hysortk.cpp:138-164): the lines "KMERSTRING\tcount\n" of `n` entries
  * ((nw + 1)-word records: host memory, or device memory when `on_device`), formatted on the GPU into `text` (host, capacity
  * bytes); *nbytes = bytes needed (call with capacity 0 to size the buffer: K + 2 + up to 20 digits per entry). */

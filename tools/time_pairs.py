@@ -14,7 +14,12 @@ compared with the unsliced rows.  Where the unsliced call does not fit the devic
 --merge-only: the lists of the two halves of the task range, left on the device, merged by hsk_pairs_merge: the merge kernels' time and
 GB/s (32 B read per input row, 32 B written per output row) against hsk_copy_peak.
 
-usage: python tools/time_pairs.py [--gbp 0.008] [--coverage 20] [--max-records N ...] [--merge-only] [--out profiles/pairs_8mbp.json]"""
+--oriented: hsk_result_strands (the strand of every payload slot, from the reads in HBM), then hsk_result_pairs and
+hsk_result_pairs_oriented on the same resident result: the ms of each, the sort passes of both pair calls, the ratio of the oriented call
+to the plain one, and the oriented rows folded and compared with the plain rows.  --strands-only (with --oriented): the strand pass alone --
+with --gbp it shows how the pass scales with the size of the packed reads it gathers from (the entry lookup per payload slot is the same).
+
+usage: python tools/time_pairs.py [--gbp 0.008] [--coverage 20] [--max-records N ...] [--merge-only] [--oriented [--strands-only]] [--out profiles/pairs_8mbp.json]"""
 import argparse, json, os, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -49,6 +54,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gbp", type=float, default=0.008); ap.add_argument("--coverage", type=float, default=20.0)
     ap.add_argument("--max-records", action="append", default=[]); ap.add_argument("--merge-only", action="store_true")
+    ap.add_argument("--oriented", action="store_true"); ap.add_argument("--strands-only", action="store_true")
     ap.add_argument("--reps", type=int, default=REPS)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pairs_8mbp.json"))
     a = ap.parse_args()
@@ -69,7 +75,40 @@ def main():
            "workload": {"genome_bp": G, "read_len": RL, "reads": n, "K": 31, "M": 17, "L": 2, "U": 50, "ntasks": dev.ntasks, "entries": dev.n, "count_call_wall_ms": count_ms},
            "copy_peak_gbs": peak}
 
-    if a.merge_only:
+    if a.oriented:
+        # the strand pass, then both pair calls on the same resident result: what the strand bit costs the sort (its top digit is no longer trivial)
+        sruns = []
+        for i in range(WARMUP + a.reps):
+            t0 = time.perf_counter()
+            with dev.strands(dna) as st:
+                info = dict(st.info, wall_ms=(time.perf_counter() - t0) * 1e3)
+            if i >= WARMUP:
+                sruns.append(info)
+        sms = median([r["ms_total"] for r in sruns])
+        npay = sum(dev.task(t)["npay"] for t in range(dev.ntasks))
+        out["what"] = "tools/time_pairs.py --oriented: hsk_result_strands, hsk_result_pairs and hsk_result_pairs_oriented on the same resident EXTENSION result"
+        out["strands"] = {"payloads": sruns[-1]["payloads"], "reverse": sruns[-1]["reverse"], "palindromes": sruns[-1]["palindromes"], "payload_slots": npay,
+                          "packed_read_bytes": nb, "ms_total": [r["ms_total"] for r in sruns], "median_ms": sms, "wall_ms": [r["wall_ms"] for r in sruns],
+                          "payloads_per_us": sruns[-1]["payloads"] / (sms * 1e3) if sms > 0 else 0.0}
+        if not a.strands_only:
+            def summary(runs):
+                last = runs[-1]
+                s = {"records": last["records"], "self_records": last["self_records"], "keys": last["keys"], "rows": last["rows"], "sort_passes": last["sort_passes"],
+                     "ms_total": [r["ms_total"] for r in runs], "median_ms": median([r["ms_total"] for r in runs])}
+                for ph in ("expand", "sort", "reduce"):
+                    s["median_ms_" + ph] = median([r["ms_" + ph] for r in runs])
+                return s
+            with dev.strands(dna) as st:
+                plain = summary(timed(lambda: dev.pairs(on_device=True), reps=a.reps))
+                ori = summary(timed(lambda: dev.pairs(on_device=True, strands=st), reps=a.reps))
+                folded = dev.pairs(strands=st).fold()
+                ori["folded_rows_equal_plain"] = bool(np.array_equal(folded.rows(), dev.pairs().rows()))
+                del folded
+            out["pairs"] = plain
+            out["pairs_oriented"] = ori
+            out["oriented_over_plain"] = ori["median_ms"] / plain["median_ms"] if plain["median_ms"] > 0 else None
+            out["strands_plus_oriented_over_plain"] = (sms + ori["median_ms"]) / plain["median_ms"] if plain["median_ms"] > 0 else None
+    elif a.merge_only:
         half = dev.ntasks // 2
         with dev.pairs(0, half, on_device=True) as pa, dev.pairs(half, dev.ntasks, on_device=True) as pb:
             runs = timed(lambda: H.ReadPairs.combine([pa, pb], ctx=ctx, on_device=True), reps=a.reps)
