@@ -75,6 +75,16 @@ class Strands(C.Structure):
     ]
 
 
+class PairDiags(C.Structure):
+    """hsk_pair_diags: the diagonal bins of the oriented read pairs of a resident EXTENSION result (hsk_result_pair_diagonals)."""
+    _fields_ = [
+        ("n", C.c_uint64), ("rows", C.POINTER(C.c_uint64)), ("rows_dev", C.c_void_p),
+        ("records", C.c_uint64), ("self_records", C.c_uint64), ("keys", C.c_uint64), ("bins", C.c_uint64), ("sort_passes", C.c_int32),
+        ("ms_expand", C.c_double), ("ms_sort", C.c_double), ("ms_reduce", C.c_double), ("ms_d2h", C.c_double), ("ms_total", C.c_double),
+        ("reserved", C.c_int64 * 4), ("priv", C.c_void_p),
+    ]
+
+
 FLAG_PROFILE = 1
 FLAG_KEEP_DEVICE = 2
 FLAG_PLAIN_CLASSIFIER = 4
@@ -89,6 +99,7 @@ SYMBOLS = [
     "hsk_count", "hsk_count_device", "hsk_count_loopback", "hsk_count_loopback_device", "hsk_result_free", "hsk_result_device_task", "hsk_result_pairs", "hsk_pairs_free", "hsk_format_entries", "hsk_get_stats",
     "hsk_result_pairs_sliced", "hsk_pairs_merge",
     "hsk_result_strands", "hsk_strands_task", "hsk_strands_free", "hsk_result_pairs_oriented",
+    "hsk_result_pair_diagonals", "hsk_pair_diags_free",
     "hsk_stage_destinations", "hsk_stage_task_kmers", "hsk_stage_sort", "hsk_stage_count_sorted",
     "hsk_plan_tot_tasks", "hsk_plan_classify", "hsk_plan_dispatch", "hsk_plan_partition_reads", "hsk_plan_exchange",
     "hsk_comm_get_unique_id", "hsk_comm_init", "hsk_comm_destroy", "hsk_comm_selftest",
@@ -148,6 +159,10 @@ def load():
     L.hsk_strands_free.restype = None
     L.hsk_result_pairs_oriented.argtypes = [vp, C.POINTER(Result), C.POINTER(Strands), C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_uint64,
                                             C.POINTER(Pairs), C.POINTER(PairsSlices)]
+    L.hsk_result_pair_diagonals.argtypes = [vp, C.POINTER(Result), C.POINTER(Strands), C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32,
+                                            C.POINTER(PairDiags)]
+    L.hsk_pair_diags_free.argtypes = [vp, C.POINTER(PairDiags)]
+    L.hsk_pair_diags_free.restype = None
     L.hsk_pairs_free.argtypes = [vp, C.POINTER(Pairs)]
     L.hsk_pairs_free.restype = None
     L.hsk_get_stats.argtypes = [vp, C.POINTER(Stats), C.c_int]

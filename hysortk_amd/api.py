@@ -320,6 +320,133 @@ class ReadPairs:
         self.close()
 
 
+class PairDiagonals:
+    """The oriented read pairs by diagonal (hsk_result_pair_diagonals, include/hsk.h): rows { key, shared, bin, support, first, last } with
+    key = o << 63 | rid_a << 32 | rid_b.  A record's diagonal number is D = pos_a - pos_b + 2^32 on the same strand (o = 0) and pos_a + pos_b
+    on opposite strands (o = 1), its bin D // diag_bin.  all_bins=False: one row per key -- the bin with the most records (the smallest such
+    bin on a tie), `support` its records, `shared` the records of the key over all bins, first_pos_* / last_pos_* the smallest / largest
+    (pos_a, pos_b) of that bin only.  all_bins=True: one row per (key, bin), ascending, shared == support.  With on_device the rows stay in
+    HBM (rows_dev: n rows of six uint64 words; close() gives them back).  select() and combine() work on all-bins lists, on the host."""
+
+    COLS = 6
+
+    def __init__(self, key, shared, bin, support, first, last, diag_bin=None, all_bins=False, info=None, rows_dev=None, n=None, owner=None):
+        self.key, self.shared, self.bin, self.support, self.first, self.last = (np.ascontiguousarray(x, dtype=np.uint64) for x in (key, shared, bin, support, first, last))
+        lo = np.uint64(0xFFFFFFFF)
+        self.diag_bin = None if diag_bin is None else int(diag_bin)
+        self.all_bins = bool(all_bins)
+        self.opposite = (self.key >> np.uint64(63)).astype(bool)
+        self.rid_a, self.rid_b = ((self.key >> np.uint64(32)) & np.uint64(0x7FFFFFFF)).astype(np.uint32), (self.key & lo).astype(np.uint32)
+        self.first_pos_a, self.first_pos_b = (self.first >> np.uint64(32)).astype(np.uint32), (self.first & lo).astype(np.uint32)
+        self.last_pos_a, self.last_pos_b = (self.last >> np.uint64(32)).astype(np.uint32), (self.last & lo).astype(np.uint32)
+        self.info = info or {}
+        self.rows_dev = rows_dev
+        self.n = int(self.key.size) if n is None else int(n)
+        self._owner = owner                      # (ctx, hsk_pair_diags) of rows that live on the device
+
+    def __len__(self):
+        return self.n
+
+    def rows(self):
+        """[n, 6] uint64: { key, shared, bin, support, first, last }, the C ABI's layout."""
+        return np.stack([self.key, self.shared, self.bin, self.support, self.first, self.last], axis=1) if self.key.size else np.zeros((0, 6), np.uint64)
+
+    @classmethod
+    def from_rows(cls, rows, **kw):
+        rows = np.asarray(rows, dtype=np.uint64).reshape(-1, 6)
+        return cls(*(rows[:, i] for i in range(6)), **kw)
+
+    def diagonal(self):
+        """(lo, hi), two int64 arrays: the range a row's bin covers -- of pos_a - pos_b (signed) for a same-strand row, of pos_a + pos_b for an
+        opposite-strand row.  Needs diag_bin."""
+        if self.diag_bin is None:
+            raise ValueError("diagonal() needs the bin width: give diag_bin to from_rows()")
+        w = self.diag_bin
+        lo = self.bin.astype(np.int64) * w - np.where(self.opposite, 0, 1 << 32)
+        return lo, lo + (w - 1)
+
+    def select(self, min_support=1):
+        """The selection property (include/hsk.h), on the host: the list by best bin of an all-bins list that was computed with
+        min_support=1 -- per key shared is the sum of support, the row with the largest support is kept (the smallest bin on a tie), and
+        min_support is applied afterwards."""
+        if not self.all_bins:
+            raise ValueError("select() is for an all-bins list")
+        r = self.rows()
+        info = dict(self.info)
+        if not r.shape[0]:
+            return PairDiagonals.from_rows(r, diag_bin=self.diag_bin, all_bins=False, info=info)
+        start = np.flatnonzero(np.concatenate([[True], r[1:, 0] != r[:-1, 0]]))
+        shared = np.add.reduceat(r[:, 3], start)
+        grp = np.cumsum(np.concatenate([[False], r[1:, 0] != r[:-1, 0]]))
+        # rows are in ascending (key, bin): the first row of a key that reaches the key's largest support is the one with the smallest bin
+        top = np.maximum.reduceat(r[:, 3], start)
+        is_top = r[:, 3] == top[grp]
+        idx = np.arange(r.shape[0])
+        pick = np.minimum.reduceat(np.where(is_top, idx, r.shape[0]), start)
+        out = r[pick].copy()
+        out[:, 1] = shared
+        info["keys"] = int(start.size)
+        return PairDiagonals.from_rows(out[out[:, 3] >= np.uint64(min_support)], diag_bin=self.diag_bin, all_bins=False, info=info)
+
+    @staticmethod
+    def combine(parts):
+        """The several-list contract, on the host: the all-bins list of the union of disjoint task ranges, or of the ranks of a several-GPU
+        run, from their all-bins lists (computed with min_support=1, same diag_bin): rows with equal (key, bin) join -- support and shared
+        add up, first is the minimum, last the maximum.  Best-bin lists do not combine (ValueError): select() the joined list."""
+        parts = list(parts)
+        if any(not p.all_bins for p in parts):
+            raise ValueError("lists by best bin do not combine: combine the all-bins lists, then select()")
+        widths = {p.diag_bin for p in parts}
+        if len(widths) > 1:
+            raise ValueError("lists of different diag_bin do not combine")
+        w = widths.pop() if widths else None
+        info = {k: sum(int(p.info.get(k, 0)) for p in parts) for k in ("records", "self_records")}
+        rows = [p.rows() for p in parts if len(p)]
+        if not rows:
+            info.update(keys=0, bins=0)
+            return PairDiagonals.from_rows(np.zeros((0, 6), np.uint64), diag_bin=w, all_bins=True, info=info)
+        r = np.concatenate(rows)
+        r = r[np.lexsort((r[:, 2], r[:, 0]))]
+        new = np.concatenate([[True], (r[1:, 0] != r[:-1, 0]) | (r[1:, 2] != r[:-1, 2])])
+        start = np.flatnonzero(new)
+        sup = np.add.reduceat(r[:, 3], start)
+        out = np.stack([r[start, 0], sup, r[start, 2], sup, np.minimum.reduceat(r[:, 4], start), np.maximum.reduceat(r[:, 5], start)], axis=1)
+        info.update(keys=int(np.unique(out[:, 0]).size), bins=int(out.shape[0]))
+        return PairDiagonals.from_rows(out, diag_bin=w, all_bins=True, info=info)
+
+    @staticmethod
+    def _wrap(ctx, pd, on_device, diag_bin, all_bins):
+        """A PairDiagonals from a filled hsk_pair_diags: the rows copied to numpy and the struct freed, or (on_device) left in HBM and owned."""
+        info = dict(records=int(pd.records), self_records=int(pd.self_records), keys=int(pd.keys), bins=int(pd.bins), sort_passes=int(pd.sort_passes),
+                    ms_expand=pd.ms_expand, ms_sort=pd.ms_sort, ms_reduce=pd.ms_reduce, ms_d2h=pd.ms_d2h, ms_total=pd.ms_total)
+        n = int(pd.n)
+        if on_device:
+            z = np.zeros(0, np.uint64)
+            return PairDiagonals(z, z, z, z, z, z, diag_bin=diag_bin, all_bins=all_bins, info=info, rows_dev=pd.rows_dev, n=n, owner=(ctx, pd))
+        rows = np.ctypeslib.as_array(pd.rows, shape=(n * 6,)).reshape(n, 6).copy() if n else np.zeros((0, 6), np.uint64)
+        ctx.lib.hsk_pair_diags_free(ctx.h, C.byref(pd))
+        return PairDiagonals.from_rows(rows, diag_bin=diag_bin, all_bins=all_bins, info=info)
+
+    def close(self):
+        if self._owner is not None:
+            ctx, pd = self._owner
+            if getattr(ctx, "h", None):
+                ctx.lib.hsk_pair_diags_free(ctx.h, C.byref(pd))
+            self._owner, self.rows_dev = None, None
+
+    def __del__(self):
+        try:
+            self.close()                 # (rows left on the device go back while the context is alive; after hsk_destroy there is nothing to free)
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 class Strands:
     """The strand bits of a resident EXTENSION result (hsk_result_strands, include/hsk.h): one bit per payload slot, in HBM.  info has
     ntasks, payloads, reverse, palindromes and ms_total; task_bits(t) copies task t's bits to the host.  close() gives the arrays back
@@ -433,6 +560,17 @@ class DeviceResult:
                                                              C.byref(pr), C.byref(sl)))
         extra = dict(slices=int(sl.slices), peak_records=int(sl.peak_records), merges=int(sl.merges), merged_rows=int(sl.merged_rows), ms_merge=sl.ms_merge)
         return ReadPairs._wrap(self.ctx, pr, on_device, extra)
+
+    def pair_diagonals(self, strands, diag_bin, task_lo=0, task_hi=None, min_support=1, all_bins=False, on_device=False):
+        """hsk_result_pair_diagonals over tasks [task_lo, task_hi) (default: all): the records of pairs(strands=...) binned by diagonal
+        (bins of diag_bin diagonals), as a PairDiagonals -- per oriented read pair the bin with the most records (all_bins=False), or every
+        (pair, bin) (all_bins=True: what disjoint task ranges and ranks combine through, PairDiagonals.combine and .select).  strands: the
+        Strands of this result.  on_device=True leaves the rows in HBM (close() it before the context goes)."""
+        pd = _lib.PairDiags()
+        hi = self.ntasks if task_hi is None else task_hi
+        self.ctx._check(self.ctx.lib.hsk_result_pair_diagonals(self.ctx.h, C.byref(self.res), C.byref(strands.st) if strands is not None else None, task_lo, hi,
+                                                               int(diag_bin), int(min_support), 1 if all_bins else 0, 1 if on_device else 0, C.byref(pd)))
+        return PairDiagonals._wrap(self.ctx, pd, on_device, int(diag_bin), bool(all_bins))
 
     def close(self):
         if self.res is not None:

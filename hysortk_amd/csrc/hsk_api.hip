@@ -39,6 +39,7 @@
 #include "hsk_heavy.h"
 #include "hsk_pairs.h"
 #include "hsk_pairmerge.h"
+#include "hsk_pairdiag.h"
 #include "hsk_strand.h"
 #include "hsk_estimate.h"
 #include "hsk_synth.h"
@@ -453,6 +454,8 @@ extern "C" int hsk_result_device_task(const hsk_result *r, int32_t task, const v
 #include "hsk_host_pairs.h"
 // the strand of every occurrence of such a result, one bit per payload slot: hsk_result_strands, hsk_strands_task, hsk_strands_free
 #include "hsk_host_strand.h"
+// the oriented pairs by diagonal, and the best-supported bin of each: hsk_result_pair_diagonals, hsk_pair_diags_free
+#include "hsk_host_pairdiag.h"
 
 // Uploads the DnaBuffer description; returns device arrays with nreads+1 offsets.
 

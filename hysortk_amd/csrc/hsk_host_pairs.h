@@ -364,19 +364,14 @@ static int pairs_impl(hsk_ctx *c, const ResultPriv *rp, const StrandsPriv *sp, i
     return HSK_OK;
 }
 
-static int pairs_entry(hsk_ctx *c, const hsk_result *res, const hsk_strands *strands, int32_t task_lo, int32_t task_hi, uint32_t min_shared, int32_t on_device, bool sliced, uint64_t max_records,
-                       hsk_pairs *out, hsk_pairs_slices *info, const char *name)
+// What every call that reads a resident EXTENSION result checks before it opens its scope; *rp, *sp: the private parts (sp NULL without strands).
+static int pairs_check_args(hsk_ctx *c, const hsk_result *res, const hsk_strands *strands, int32_t task_lo, int32_t task_hi, const char *name, const ResultPriv **rpo, const StrandsPriv **spo)
 {
-    if (!c || !res || !out) return HSK_ERR_INVALID_ARG;
-    memset(out, 0, sizeof *out);
-    hsk_pairs_slices local; if (!info) info = &local;
-    memset(info, 0, sizeof *info);
     if (!c->cfg.extension) return fail(c, HSK_ERR_INVALID_ARG, "%s needs a context with EXTENSION: without it the list carries no (ReadId, PosInRead)", name);
     const ResultPriv *rp = (const ResultPriv *)res->priv;
     if (!(c->cfg.flags & HSK_FLAG_KEEP_DEVICE) || !rp || res->ntasks <= 0 || rp->dev_tasks.size() != (size_t)res->ntasks)
         return fail(c, HSK_ERR_INVALID_ARG, "%s needs a result that was left on the device (HSK_FLAG_KEEP_DEVICE)", name);
     if (task_lo < 0 || task_hi < task_lo || task_hi > res->ntasks) return fail(c, HSK_ERR_INVALID_ARG, "task range [%d, %d) outside [0, %d]", task_lo, task_hi, res->ntasks);
-    if (min_shared == 0) return fail(c, HSK_ERR_INVALID_ARG, "min_shared must be at least 1");
     const StrandsPriv *sp = strands ? (const StrandsPriv *)strands->priv : nullptr;
     if (strands) {                                        // do the bits belong to this result?
         if (!sp || strands->ntasks != res->ntasks || sp->npay.size() != (size_t)res->ntasks)
@@ -386,6 +381,20 @@ static int pairs_entry(hsk_ctx *c, const hsk_result *res, const hsk_strands *str
                 return fail(c, HSK_ERR_INVALID_ARG, "%s: the strands do not belong to this result (task %d: %llu payload slots, the result has %llu)", name, t,
                             (unsigned long long)sp->npay[t], (unsigned long long)rp->dev_tasks[t].npay);
     }
+    *rpo = rp; *spo = sp;
+    return HSK_OK;
+}
+
+static int pairs_entry(hsk_ctx *c, const hsk_result *res, const hsk_strands *strands, int32_t task_lo, int32_t task_hi, uint32_t min_shared, int32_t on_device, bool sliced, uint64_t max_records,
+                       hsk_pairs *out, hsk_pairs_slices *info, const char *name)
+{
+    if (!c || !res || !out) return HSK_ERR_INVALID_ARG;
+    memset(out, 0, sizeof *out);
+    hsk_pairs_slices local; if (!info) info = &local;
+    memset(info, 0, sizeof *info);
+    const ResultPriv *rp; const StrandsPriv *sp;
+    const int chk = pairs_check_args(c, res, strands, task_lo, task_hi, name, &rp, &sp); if (chk) return chk;
+    if (min_shared == 0) return fail(c, HSK_ERR_INVALID_ARG, "min_shared must be at least 1");
     PairsPriv *pp = new PairsPriv();
     const int rc = ApiCall(c, name).run([&] { return pairs_impl(c, rp, sp, res->nw, task_lo, task_hi, min_shared, on_device != 0, sliced, max_records, out, info, pp); });
     if (rc != HSK_OK) {                                   // (the device blocks went back with the call's rollback)

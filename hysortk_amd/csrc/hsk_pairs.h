@@ -21,6 +21,8 @@
 //                       range for hsk_result_pairs, one slice of it for hsk_result_pairs_sliced (hsk_pairplan.h).
 //                       ORIENTED (hsk_result_pairs_oriented): the XOR of the two occurrences' strand bits (hsk_strand.h) is bit 63 of the
 //                       key; everything behind the expansion sees a key like any other.
+//                       DIAG (hsk_result_pair_diagonals, hsk_pairdiag.h): the key has two words, the oriented key in the more significant
+//                       word 1 and the sort word of the record's diagonal bin (hsk_diagbin.h) in word 0; a pair inside one read has both 0.
 //   pair_reduce_kernel  the shape of count_kernel: run heads of a tile as a bit mask, rows per tile, count_scan_kernel, write pass.
 //                       A run belongs to the tile it starts in.  The last run of a tile may go on for any number of tiles: the
 //                       whole workgroup reads ahead to its end (count, min, max reduced over the workgroup); tiles inside a run
@@ -29,6 +31,7 @@
 #include "hsk_device.h"
 #include "hsk_count.h"
 #include "hsk_pairdecode.h"
+#include "hsk_diagbin.h"
 
 namespace hsk {
 
@@ -106,12 +109,16 @@ struct PairExpandArgs {
     u64 nent, records;       // the window: entries [ent0, nent), records [rec0, rec0 + records) of the range -- off[ent0] == rec0, off[nent] == rec0 + records
     u64 *keys, *vals;        // records each: the window's record rec0 + i at [i]
     u64 rec0, ent0;          // both 0: the whole range (hsk_result_pairs); a slice otherwise (hsk_result_pairs_sliced)
+    u64 diag_w;              // DIAG: the bin width, and a word that holds a bound of every position of the range (diag_maxpos_kernel); keys: 2 * records words
+    const u64 *maxpos;
 };
 
 // ORIENTED (hsk_result_pairs_oriented): bit 63 of the key is the XOR of the two occurrences' strands -- read ids are below 2^31 there
-template <bool ORIENTED>
+// DIAG (hsk_result_pair_diagonals; with ORIENTED): record i's key is the 16 bytes { sort word of its bin, oriented key } at keys[2 i]
+template <bool ORIENTED, bool DIAG = false>
 __global__ __launch_bounds__(PAIR_THREADS) void pair_expand_kernel(PairExpandArgs a)
 {
+    static_assert(ORIENTED || !DIAG, "a diagonal needs the relative strand");
     __shared__ u64 s_off[PX_STAGE + 1];
     __shared__ u64 s_e0;
     const int tid = threadIdx.x;
@@ -128,6 +135,7 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_expand_kernel(PairExpandArg
     u64 ent[PX_SLOTS]; u32 r[PX_SLOTS]; bool found[PX_SLOTS];
 #pragma unroll
     for (int s = 0; s < PX_SLOTS; ++s) { ent[s] = 0; r[s] = 0; found[s] = false; }
+    const u32 maxpos = DIAG ? (u32)a.maxpos[0] : 0;
     for (;;) {
         // entries e_cur .. e_cur + m - 1 and the offset behind them; a record not found yet lies at or behind s_off[0]
         const u32 m = (u32)(a.nent - e_cur < (u64)PX_STAGE ? a.nent - e_cur : (u64)PX_STAGE);
@@ -171,7 +179,12 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_expand_kernel(PairExpandArg
         const bool self = ra == rb;
         u64 o = 0;
         if (ORIENTED) { const u64 si = first + i, sj = first + j; o = ((tk.strand[si >> 6] >> (si & 63)) ^ (tk.strand[sj >> 6] >> (sj & 63))) << 63; }
-        a.keys[idx - a.rec0] = self ? 0ULL : o | ((u64)ra << 32) | rb;
+        const u64 key = self ? 0ULL : o | ((u64)ra << 32) | rb;
+        if (DIAG) {
+            typedef unsigned long long v2u64x __attribute__((ext_vector_type(2)));
+            const v2u64x kk = {self ? 0ULL : diag_sort_word(o >> 63, pa, pb, maxpos, a.diag_w), key};
+            *(v2u64x *)(a.keys + 2 * (idx - a.rec0)) = kk;
+        } else a.keys[idx - a.rec0] = key;
         a.vals[idx - a.rec0] = self ? 0ULL : ((u64)pa << 32) | pb;
     }
 }

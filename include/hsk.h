@@ -373,6 +373,64 @@ void hsk_strands_free(hsk_ctx *ctx, hsk_strands *s);
 int  hsk_result_pairs_oriented(hsk_ctx *ctx, const hsk_result *res, const hsk_strands *strands,
                                int32_t task_lo, int32_t task_hi, uint32_t min_shared, int32_t on_device,
                                uint64_t max_records, hsk_pairs *out, hsk_pairs_slices *info);
+/*
+ * Read pairs by diagonal: the seed bins of every oriented read pair, and the best-supported one (what a client of the BELLA kind does
+ * next with the oriented rows: bin a pair's seeds by diagonal, keep the bin with the most seeds, start the alignment from a seed of it).
+ *
+ * Definition.  The RECORDS are exactly those of hsk_result_pairs_oriented for the same result, strands and task range:
+ *     key   = o << 63 | rid_a << 32 | rid_b        value = pos_a << 32 | pos_b
+ * a pair inside one read is no record and counted in self_records.  Every record has a diagonal number
+ *     D = pos_a - pos_b + 2^32   (o = 0)           D = pos_a + pos_b   (o = 1)
+ * in 64-bit arithmetic, never negative -- seeds of a same-strand overlap keep the difference of their positions, seeds of a
+ * reverse-complement overlap keep the sum; no read length is needed -- and a bin
+ *     bin = D / diag_bin                           (unsigned integer division).
+ * The records of a key fall into bins.  A ROW has six uint64 words (48 bytes; the lists are 16-byte aligned):
+ *     { key, shared, bin, support, first, last }
+ *   all_bins == 0   the list by best bin, one row per key: shared = the records of the key over all its bins (the `shared` of the oriented
+ *                   list); bin = the bin with the most records, among equal counts the smallest bin; support = its records; first / last =
+ *                   the smallest / largest value among the records of THAT bin only.  Rows with support < min_support are dropped after
+ *                   the selection.  The row order is that of the oriented list.
+ *   all_bins != 0   the list before the selection, one row per (key, bin) in ascending (key, bin): shared = support = the records of the
+ *                   bin, first / last over the bin; min_support is applied per row.
+ * Selection property.  The first list is a pure function of the second (computed with min_support = 1): per key, shared is the sum of
+ * support, the row with the largest support is kept -- on a tie the one with the smallest bin -- and min_support is applied afterwards.
+ *
+ * Several lists.  The ALL-BINS lists of disjoint task ranges, or of the ranks of a several-GPU run, join on (key, bin): support (and
+ * shared) add up, first is the minimum, last the maximum; the selection then runs on the joined list.  Compute the parts with
+ * min_support = 1.  The best-bin lists themselves DO NOT combine: the best bin of a part need not be the best bin of the union.
+ * There is no slicing and no merge on the device for these lists yet: a narrower task range plus the join on the host is the way out.
+ *
+ *   diag_bin      the bin width W, 1 .. 2^31
+ *   out           records, self_records as hsk_result_pairs_oriented; keys = distinct (read pair, orientation) before min_support; bins =
+ *                 distinct (key, bin) before min_support; sort_passes = scatter passes of the sort over the two-word key (pair key, bin)
+ *                 (-1: not known); ms_* HIP events (ms_expand includes the record count, ms_reduce both reducers).
+ * Memory: 48 bytes per record while the sort runs (two buffers of two-word keys and two of values); then 48 bytes per distinct (key, bin)
+ * for the bin rows, beside the record buffers while they are written, and 48 bytes per row of the result.  `records` is known after one
+ * counting pass and before the record buffers are asked for: HSK_ERR_OOM then says how many records and bytes.  `bins` is known after
+ * the reducer's count pass, before the bin rows are asked for.
+ * HSK_ERR_INVALID_ARG, with a hsk_last_error text, the context usable afterwards: everything hsk_result_pairs_oriented refuses (a NULL
+ * pointer, `strands` NULL or not of `res`, a result that was not left on the device, a context without EXTENSION, a task range outside
+ * [0, ntasks]); diag_bin == 0 or diag_bin > 2^31; min_support == 0.  An empty range is no error (n = 0).
+ * hsk_pair_diags_free before hsk_destroy of the context.
+ */
+typedef struct {
+    uint64_t n;             /* rows */
+    uint64_t *rows;         /* host (pinned), n * 6 words; NULL when left on the device */
+    void     *rows_dev;     /* device copy when asked for */
+    uint64_t records;       /* occurrence pairs expanded, same-read ones included */
+    uint64_t self_records;  /* of which dropped: both occurrences in one read */
+    uint64_t keys;          /* distinct (read pair, orientation) before min_support */
+    uint64_t bins;          /* distinct (key, bin) before min_support */
+    int32_t  sort_passes;   /* scatter passes the sort took (-1: not known) */
+    double   ms_expand, ms_sort, ms_reduce, ms_d2h, ms_total;   /* HIP events */
+    int64_t  reserved[4];
+    void    *priv;
+} hsk_pair_diags;
+
+int  hsk_result_pair_diagonals(hsk_ctx *ctx, const hsk_result *res, const hsk_strands *strands,
+                               int32_t task_lo, int32_t task_hi, uint64_t diag_bin, uint32_t min_support,
+                               int32_t all_bins, int32_t on_device, hsk_pair_diags *out);
+void hsk_pair_diags_free(hsk_ctx *ctx, hsk_pair_diags *d);
 /* Result egress (write_output_file, reference src/hysortk.cpp:138-164): the lines "KMERSTRING\tcount\n" of `n` entries
  * ((nw + 1)-word records: host memory, or device memory when `on_device`), formatted on the GPU into `text` (host, capacity
  * bytes); *nbytes = bytes needed (call with capacity 0 to size the buffer: K + 2 + up to 20 digits per entry). */

@@ -19,7 +19,13 @@ hsk_result_pairs_oriented on the same resident result: the ms of each, the sort 
 to the plain one, and the oriented rows folded and compared with the plain rows.  --strands-only (with --oriented): the strand pass alone --
 with --gbp it shows how the pass scales with the size of the packed reads it gathers from (the entry lookup per payload slot is the same).
 
-usage: python tools/time_pairs.py [--gbp 0.008] [--coverage 20] [--max-records N ...] [--merge-only] [--oriented [--strands-only]] [--out profiles/pairs_8mbp.json]"""
+--diagonals [--diag-bin W]: on the input of --oriented, hsk_result_pairs_oriented (single pass) and hsk_result_pair_diagonals (best bin and
+all bins, W diagonals per bin) on the same resident result, side by side: the ms of each call and phase, the sort passes, the ratio to the
+oriented call, and the rows compared -- the selection of the all-bins list with the best-bin list, the all-bins list folded by key with the
+oriented list.  The oriented call is the yardstick: per record and scatter pass the sort moves 48 bytes (two key words and the value) where
+it moves 32.  Writes profiles/pairs_diagonals_8mbp.json unless --out says otherwise.
+
+usage: python tools/time_pairs.py [--gbp 0.008] [--coverage 20] [--max-records N ...] [--merge-only] [--oriented [--strands-only]] [--diagonals [--diag-bin W]] [--out profiles/pairs_8mbp.json]"""
 import argparse, json, os, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -43,6 +49,18 @@ def timed(call, warmup=WARMUP, reps=REPS):
     return runs
 
 
+def summary(runs):
+    """what the timed calls of one kind say: the counts of the last one, the medians of the call and of its phases"""
+    last = runs[-1]
+    s = {"records": last["records"], "self_records": last["self_records"], "keys": last["keys"], "rows": last["rows"], "sort_passes": last["sort_passes"],
+         "ms_total": [r["ms_total"] for r in runs], "median_ms": median([r["ms_total"] for r in runs])}
+    if "bins" in last:
+        s["bins"] = last["bins"]
+    for ph in ("expand", "sort", "reduce"):
+        s["median_ms_" + ph] = median([r["ms_" + ph] for r in runs])
+    return s
+
+
 def budget(text, records):
     if "/" in text:
         p, q = text.split("/")
@@ -55,9 +73,12 @@ def main():
     ap.add_argument("--gbp", type=float, default=0.008); ap.add_argument("--coverage", type=float, default=20.0)
     ap.add_argument("--max-records", action="append", default=[]); ap.add_argument("--merge-only", action="store_true")
     ap.add_argument("--oriented", action="store_true"); ap.add_argument("--strands-only", action="store_true")
+    ap.add_argument("--diagonals", action="store_true"); ap.add_argument("--diag-bin", type=int, default=64)
     ap.add_argument("--reps", type=int, default=REPS)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pairs_8mbp.json"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "pairs_diagonals_8mbp.json" if a.diagonals else "pairs_8mbp.json")
     sys.path.insert(0, ROOT)
     import numpy as np
     import hysortk_amd as H
@@ -75,7 +96,32 @@ def main():
            "workload": {"genome_bp": G, "read_len": RL, "reads": n, "K": 31, "M": 17, "L": 2, "U": 50, "ntasks": dev.ntasks, "entries": dev.n, "count_call_wall_ms": count_ms},
            "copy_peak_gbs": peak}
 
-    if a.oriented:
+    if a.diagonals:
+        # the oriented single pass and the diagonal call on the same resident result and strands: what the second key word and the second reducer cost
+        W = a.diag_bin
+        with dev.strands(dna) as st:
+            ori = summary(timed(lambda: dev.pairs(on_device=True, strands=st), reps=a.reps))
+            best = summary(timed(lambda: dev.pair_diagonals(st, W, on_device=True), reps=a.reps))
+            allb = summary(timed(lambda: dev.pair_diagonals(st, W, all_bins=True, on_device=True), reps=a.reps))
+            hb, ha, ho = dev.pair_diagonals(st, W), dev.pair_diagonals(st, W, all_bins=True), dev.pairs(strands=st)
+            best["equals_selection_of_all_bins"] = bool(np.array_equal(ha.select().rows(), hb.rows()))
+            k = ha.rows()
+            start = np.flatnonzero(np.concatenate([[True], k[1:, 0] != k[:-1, 0]])) if k.shape[0] else np.zeros(0, np.int64)
+            folded = np.stack([k[start, 0], np.add.reduceat(k[:, 3], start), np.minimum.reduceat(k[:, 4], start), np.maximum.reduceat(k[:, 5], start)], axis=1) if k.shape[0] else np.zeros((0, 4), np.uint64)
+            allb["folded_by_key_equals_oriented"] = bool(np.array_equal(folded, ho.rows()))
+            best["rows_to_host"] = {"ms_d2h": hb.info["ms_d2h"], "ms_total": hb.info["ms_total"], "bytes": len(hb) * 48}
+            del hb, ha, ho
+        out["what"] = "tools/time_pairs.py --diagonals: hsk_result_pairs_oriented (single pass) and hsk_result_pair_diagonals on the same resident EXTENSION result and strands"
+        out["diag_bin"] = W
+        out["pairs_oriented"], out["pair_diagonals"], out["pair_diagonals_all_bins"] = ori, best, allb
+        for name, s in (("pair_diagonals", best), ("pair_diagonals_all_bins", allb)):
+            s["over_oriented"] = s["median_ms"] / ori["median_ms"] if ori["median_ms"] > 0 else None
+            # sort traffic per record and scatter pass: 32 bytes (key + value, read and written) for the oriented call, 48 for the two-word key
+            s["sort_bytes_over_oriented"] = (48.0 * s["sort_passes"]) / (32.0 * ori["sort_passes"]) if ori["sort_passes"] > 0 and s["sort_passes"] > 0 else None
+        print("%-28s %10s %10s %10s %10s %6s %10s" % ("call (median ms)", "total", "expand", "sort", "reduce", "passes", "rows"))
+        for name, s in (("hsk_result_pairs_oriented", ori), ("hsk_result_pair_diagonals", best), ("  ... all_bins", allb)):
+            print("%-28s %10.3f %10.3f %10.3f %10.3f %6d %10d" % (name, s["median_ms"], s["median_ms_expand"], s["median_ms_sort"], s["median_ms_reduce"], s["sort_passes"], s["rows"]))
+    elif a.oriented:
         # the strand pass, then both pair calls on the same resident result: what the strand bit costs the sort (its top digit is no longer trivial)
         sruns = []
         for i in range(WARMUP + a.reps):
@@ -91,13 +137,6 @@ def main():
                           "packed_read_bytes": nb, "ms_total": [r["ms_total"] for r in sruns], "median_ms": sms, "wall_ms": [r["wall_ms"] for r in sruns],
                           "payloads_per_us": sruns[-1]["payloads"] / (sms * 1e3) if sms > 0 else 0.0}
         if not a.strands_only:
-            def summary(runs):
-                last = runs[-1]
-                s = {"records": last["records"], "self_records": last["self_records"], "keys": last["keys"], "rows": last["rows"], "sort_passes": last["sort_passes"],
-                     "ms_total": [r["ms_total"] for r in runs], "median_ms": median([r["ms_total"] for r in runs])}
-                for ph in ("expand", "sort", "reduce"):
-                    s["median_ms_" + ph] = median([r["ms_" + ph] for r in runs])
-                return s
             with dev.strands(dna) as st:
                 plain = summary(timed(lambda: dev.pairs(on_device=True), reps=a.reps))
                 ori = summary(timed(lambda: dev.pairs(on_device=True, strands=st), reps=a.reps))
