@@ -16,6 +16,15 @@ struct PairClock {
     ~PairClock() { take(); }                             // (a call that failed: the events go back to the context)
 };
 
+// The events and the phase clock of a call; start() when there is work, finish() is the call's last wait.
+struct PairCall {
+    EvList ev; hipEvent_t e_start = nullptr, e_end = nullptr; PairClock ck;
+    explicit PairCall(hsk_ctx *c) : ev(c), ck(c) {}
+    int start(hsk_ctx *c) { e_start = ev.get(); e_end = ev.get(); HIPCHK(c, hipEventRecord(e_start, c->stream)); return HSK_OK; }
+    int finish(hsk_ctx *c) { HIPCHK(c, hipEventRecord(e_end, c->stream)); HIPCHK(c, hsk_sync(c, c->stream)); ck.take(); return HSK_OK; }
+    float total() const { float f = 0; return hipEventElapsedTime(&f, e_start, e_end) == hipSuccess ? f : 0; }
+};
+
 // The tasks of a range that have entries, the record count of each entry and what the count pass leaves on the device for the expansion.
 struct PairRange {
     std::vector<PairTask> tk;
@@ -72,88 +81,142 @@ static void pairs_release_range(hsk_ctx *c, PairRange &r, bool stat)
     if (stat) { c->pool.release(r.d_stat); r.d_stat = nullptr; }
 }
 
+// What every call over a task range starts with: the tasks, the call's events, the record count.  *go: there are records to expand; else
+// `out` is complete (no entry in the range, or no pair among its entries) and nothing of the range is left on the device.
+template <typename Out>
+static int pairs_begin(hsk_ctx *c, const ResultPriv *rp, const StrandsPriv *sp, int nw, int32_t task_lo, int32_t task_hi, PairRange &r, PairCall &pc, Out *out, bool *go)
+{
+    *go = false;
+    int rc = pairs_range_tasks(c, rp, task_lo, task_hi, r, sp); if (rc) return rc;
+    if (!r.nent) return HSK_OK;
+    rc = pc.start(c); if (rc) return rc;
+    rc = pairs_count_records(c, nw, r, pc.ck); if (rc) return rc;
+    out->records = r.records;
+    if (r.records) { *go = true; return HSK_OK; }
+    rc = pc.finish(c); if (rc) return rc;
+    out->ms_expand = out->ms_total = pc.total();
+    pairs_release_range(c, r, true);
+    return HSK_OK;
+}
+
+// ---- one pass over records: the sort's ping-pong buffers, the expansion, the sort ---------------------------------------------------
+struct RecordPass {
+    u64 *kA = nullptr, *kB = nullptr, *vA = nullptr, *vB = nullptr;      // NW * records key words and records value words each
+    u64 *keys = nullptr, *vals = nullptr;                // the sorted side
+    int passes = 0;                                      // scatter passes of the sort
+    void release(hsk_ctx *c) { c->pool.release(kA); c->pool.release(kB); c->pool.release(vA); c->pool.release(vB); }
+};
+struct PassTexts { const char *what, *need, *launch; };  // where the refusals of the two calls differ
+
+// Keys of NW words.  expand(xtiles) enqueues the expansion into kA / vA (PT_EXPAND); `release_range`: no pass follows -- what the count
+// pass left goes back as soon as the expansion is enqueued.  Then the library's key + payload radix sort over all key bits (PT_SORT);
+// digits in which all records agree are skipped.  One wait (the sort's histogram).  The caller releases the buffers behind its reducer.
+template <int NW, typename Expand>
+static int pairs_record_pass(hsk_ctx *c, PairRange &r, u64 records, bool release_range, int32_t task_lo, int32_t task_hi, const PassTexts &tx, PairClock &ck, RecordPass &p, Expand &&expand)
+{
+    const u64 xtiles = (records + PX_TILE - 1) / PX_TILE;
+    const bool launch = xtiles <= 0x7fffffffULL;         // (refused in front of the buffers for two-word keys, behind them for one: as each call always did)
+    if (NW == 2 && !launch) return fail(c, HSK_ERR_UNSUPPORTED, "%llu records are more than one launch expands; ask for a narrower task range%s", (unsigned long long)records, tx.launch);
+    // the working set, known before any of it is asked for (+ 64: as every caller of the sort sizes them)
+    p.kA = (u64 *)c->pool.alloc(records * 8 * NW + 64); p.kB = (u64 *)c->pool.alloc(records * 8 * NW + 64); p.vA = (u64 *)c->pool.alloc(records * 8 + 64); p.vB = (u64 *)c->pool.alloc(records * 8 + 64);
+    if (!p.kA || !p.kB || !p.vA || !p.vB)
+        return fail(c, HSK_ERR_OOM, "%s of tasks [%d, %d): %llu records need %llu bytes of device memory %s", tx.what, task_lo, task_hi, (unsigned long long)records, (unsigned long long)(records * (16 * NW + 16)), tx.need);
+    if (!launch) return fail(c, HSK_ERR_UNSUPPORTED, "%llu records are more than one launch expands; ask for a narrower task range%s", (unsigned long long)records, tx.launch);
+    ck.t.begin(PT_EXPAND);
+    int rc = expand((u32)xtiles); if (rc) return rc;
+    HIPCHK(c, hipGetLastError());
+    ck.t.end(PT_EXPAND);
+    if (release_range) pairs_release_range(c, r, false);
+    ck.t.begin(PT_SORT);
+    SortScratch sc; rc = alloc_sort_scratch(c, sc); if (rc) return rc;
+    rc = sort_task_device<NW>(c, p.kA, p.kB, p.vA, p.vB, records, 32 * NW, sc, &p.keys, &p.vals, false, &p.passes); if (rc) return rc;
+    rc = check_device_error(c); if (rc) return rc;
+    free_sort_scratch(c, sc);
+    ck.t.end(PT_SORT);
+    return HSK_OK;
+}
+
+// ---- count tiles, scan, read the totals, (the caller: check them, allocate the rows), emit ---------------------------------------------
+// k tile arrays of ntiles words.  count(): the caller's COUNT launch, one count_scan_kernel per array -- array i's total into word
+// word[i] of the caller's block d_tot -- the block's first nwords words to the staging word, ONE wait; *tot is read on the spot.
+// emit(): the caller's EMIT launch (if there are rows) in the same phase, and the tile arrays go back behind it on the stream.
+struct CountEmit {
+    hsk_ctx *c; PairClock &ck; int phase; u64 ntiles; int k;
+    u64 *tile[3] = {nullptr, nullptr, nullptr};
+    CountEmit(hsk_ctx *c_, PairClock &ck_, int phase_, u64 ntiles_, int k_) : c(c_), ck(ck_), phase(phase_), ntiles(ntiles_), k(k_) {}
+    template <typename Launch>
+    int count(u64 *d_tot, int nwords, const int *word, const u64 **tot, Launch &&launch)
+    {
+        for (int i = 0; i < k; ++i) DALLOC(c, tile[i], u64 *, ntiles * 8);
+        ck.t.begin(phase);
+        launch();
+        for (int i = 0; i < k; ++i) hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, tile[i], ntiles, d_tot + word[i]);      // (of all but the first, only the total is used)
+        HIPCHK(c, hipGetLastError());
+        ck.t.end(phase);
+        u64 *st = staging(c)->read_pairs;
+        HIPCHK(c, hipMemcpyAsync(st, d_tot, (size_t)nwords * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hsk_sync(c, c->stream));
+        ck.take();
+        *tot = st;
+        return HSK_OK;
+    }
+    template <typename Launch>
+    int emit(bool rows, Launch &&launch)
+    {
+        if (rows) {
+            ck.t.begin(phase);
+            launch();
+            HIPCHK(c, hipGetLastError());
+            ck.t.end(phase);
+        }
+        for (int i = 0; i < k; ++i) { c->pool.release(tile[i]); tile[i] = nullptr; }
+        return HSK_OK;
+    }
+};
+
 // a row list in HBM: a slice's, a caller's part, or a merge's
 struct PairList { u64 *rows = nullptr; u64 n = 0; int level = 0; bool owned = true; };
 struct PairWindow { u64 ent0, ent1, rec0, records; };   // entries [ent0, ent1) = records [rec0, rec0 + records) of the range; records > 0
 
 // Expand a record window, sort it, reduce it to rows that stay on the device.  The whole range is the window { 0, nent, 0, records }.
-// `last`: no window follows -- what the count pass left goes back as soon as the expansion is enqueued.  One wait per sort (its histogram)
-// and one for the row count.  The window's record buffers are released before the routine returns.
+// `last`: no window follows.  One wait per sort (its histogram) and one for the row count.  The window's record buffers are released
+// before the routine returns.
 static int pairs_window(hsk_ctx *c, PairRange &r, const PairWindow &w, bool last, bool oriented, u32 min_shared, int32_t task_lo, int32_t task_hi, PairClock &ck, hsk_pairs *acc, PairList *list)
 {
+    static const PassTexts tx = {"read pairs", "(two key and two value buffers) and the rows on top; ask for a narrower task range and combine the lists, or let hsk_result_pairs_sliced expand fewer records at a time",
+                                 ", or let hsk_result_pairs_sliced expand fewer at a time"};
     const u64 records = w.records;
-    u64 *st = staging(c)->read_pairs;
-    // ---- expansion -------------------------------------------------------------------------------------------------------------
-    // the working set: two key and two value buffers of `records` words (the sort's ping-pong), known before any of them is asked for
-    u64 *kA = (u64 *)c->pool.alloc(records * 8 + 64), *kB = (u64 *)c->pool.alloc(records * 8 + 64), *vA = (u64 *)c->pool.alloc(records * 8 + 64), *vB = (u64 *)c->pool.alloc(records * 8 + 64);      // (+ 64: as every caller of the sort sizes them)
-    if (!kA || !kB || !vA || !vB)
-        return fail(c, HSK_ERR_OOM, "read pairs of tasks [%d, %d): %llu records need %llu bytes of device memory (two key and two value buffers) and the rows on top; ask for a narrower task range and combine the lists, or let hsk_result_pairs_sliced expand fewer records at a time",
-                    task_lo, task_hi, (unsigned long long)records, (unsigned long long)(records * 32));
-    PairExpandArgs xa; memset(&xa, 0, sizeof xa);
-    xa.tasks = r.d_tasks; xa.off = r.d_off; xa.loc = r.d_loc; xa.nent = w.ent1; xa.records = records; xa.keys = kA; xa.vals = vA; xa.rec0 = w.rec0; xa.ent0 = w.ent0;
-    const u64 xtiles = (records + PX_TILE - 1) / PX_TILE;
-    if (xtiles > 0x7fffffffULL) return fail(c, HSK_ERR_UNSUPPORTED, "%llu records are more than one launch expands; ask for a narrower task range, or let hsk_result_pairs_sliced expand fewer at a time", (unsigned long long)records);
-    ck.t.begin(PT_EXPAND);
-    if (w.rec0) HIPCHK(c, hipMemsetAsync(r.d_stat, 0, PAIR_STAT_WORDS * 8, c->stream));      // (self_records of the slice before)
-    if (oriented) hipLaunchKernelGGL(pair_expand_kernel<true>, dim3((u32)xtiles), dim3(PAIR_THREADS), 0, c->stream, xa);      // (bit 63 of the key: the strands' XOR)
-    else hipLaunchKernelGGL(pair_expand_kernel<false>, dim3((u32)xtiles), dim3(PAIR_THREADS), 0, c->stream, xa);
-    HIPCHK(c, hipGetLastError());
-    ck.t.end(PT_EXPAND);
-    if (last) pairs_release_range(c, r, false);
-
-    // ---- sort: the library's key + payload radix sort over all 64 key bits; digits in which all records agree are skipped -----------
-    ck.t.begin(PT_SORT);
-    SortScratch sc; int rc = alloc_sort_scratch(c, sc); if (rc) return rc;
-    u64 *sk, *sv;
-    rc = sort_task_device<1>(c, kA, kB, vA, vB, records, 32, sc, &sk, &sv, false); if (rc) return rc;
-    if (records >= 2) {
-        // The scatter passes the sort took.  sort_task_device (hsk_host_sort.h, which this stage leaves as it is) does not say; it reads the digit
-        // histograms of its plan back to the start of the pinned staging block -- hh[p * 256 + d], the bases behind them at MAX_PASSES * 256 -- and
-        // scatters by every digit p in which no value holds all n records.  The same plan and the same test on the same words give the number.
-        // Should the sort ever stage its histograms elsewhere, the rows found here no longer add up to `records`: then -1 (not known) is
-        // reported, not a wrong count.
-        PassDesc plan[MAX_PASSES];
-        const int npass = make_pass_plan(32, 1, c->cfg.radix_bits, plan, MAX_PASSES);
-        const u64 *hh = (const u64 *)c->pinned;
-        int passes = 0;
-        for (int p = 0; p < npass && passes >= 0; ++p) {
-            bool trivial = false; u64 sum = 0;
-            for (int d = 0; d < 256; ++d) { sum += hh[p * 256 + d]; if (hh[p * 256 + d] == records) trivial = true; }
-            if (sum != records) passes = -1; else if (!trivial) ++passes;
-        }
-        if (npass < 0) passes = -1;
-        acc->sort_passes = (passes < 0 || acc->sort_passes < 0) ? -1 : std::max(acc->sort_passes, passes);      // (the most over the slices)
-    }
-    rc = check_device_error(c); if (rc) return rc;
-    free_sort_scratch(c, sc);
-    ck.t.end(PT_SORT);
+    RecordPass p;
+    int rc = pairs_record_pass<1>(c, r, records, last, task_lo, task_hi, tx, ck, p, [&](u32 xtiles) -> int {
+        PairExpandArgs xa; memset(&xa, 0, sizeof xa);
+        xa.tasks = r.d_tasks; xa.off = r.d_off; xa.loc = r.d_loc; xa.nent = w.ent1; xa.records = records; xa.keys = p.kA; xa.vals = p.vA; xa.rec0 = w.rec0; xa.ent0 = w.ent0;
+        if (w.rec0) HIPCHK(c, hipMemsetAsync(r.d_stat, 0, PAIR_STAT_WORDS * 8, c->stream));      // (self_records of the slice before)
+        if (oriented) hipLaunchKernelGGL(pair_expand_kernel<true>, dim3(xtiles), dim3(PAIR_THREADS), 0, c->stream, xa);      // (bit 63 of the key: the strands' XOR)
+        else hipLaunchKernelGGL(pair_expand_kernel<false>, dim3(xtiles), dim3(PAIR_THREADS), 0, c->stream, xa);
+        return HSK_OK;
+    });
+    if (rc) return rc;
+    acc->sort_passes = std::max<int32_t>(acc->sort_passes, p.passes);      // (the most over the slices)
 
     // ---- run reducer: rows per tile, scan, write pass ------------------------------------------------------------------------------
     const u64 rtiles = (records + PR_TILE - 1) / PR_TILE;
-    u64 *d_rtile, *d_rkeys; DALLOC(c, d_rtile, u64 *, rtiles * 8); DALLOC(c, d_rkeys, u64 *, rtiles * 8);
     PairReduceArgs ra; memset(&ra, 0, sizeof ra);
-    ra.keys = sk; ra.vals = sv; ra.n = records; ra.min_shared = min_shared; ra.tile_cnt = d_rtile; ra.tile_keys = d_rkeys; ra.stats = r.d_stat;
-    ck.t.begin(PT_REDUCE);
-    hipLaunchKernelGGL(pair_reduce_kernel<false>, dim3((u32)rtiles), dim3(PAIR_THREADS), 0, c->stream, ra);
-    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_rtile, rtiles, r.d_stat + PAIR_STAT_ROWS);
-    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_rkeys, rtiles, r.d_stat + PAIR_STAT_KEYS);      // (only its total is used)
-    HIPCHK(c, hipGetLastError());
-    ck.t.end(PT_REDUCE);
-    HIPCHK(c, hipMemcpyAsync(st, r.d_stat, PAIR_STAT_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hsk_sync(c, c->stream));
-    ck.take();
+    ra.keys = p.keys; ra.vals = p.vals; ra.n = records; ra.min_shared = min_shared; ra.stats = r.d_stat;
+    CountEmit ce(c, ck, PT_REDUCE, rtiles, 2);
+    static const int word[2] = {PAIR_STAT_ROWS, PAIR_STAT_KEYS};
+    const u64 *st;
+    rc = ce.count(r.d_stat, PAIR_STAT_WORDS, word, &st, [&] {
+        ra.tile_cnt = ce.tile[0]; ra.tile_keys = ce.tile[1];
+        hipLaunchKernelGGL(pair_reduce_kernel<false>, dim3((u32)rtiles), dim3(PAIR_THREADS), 0, c->stream, ra);
+    });
+    if (rc) return rc;
     const u64 nrows = st[PAIR_STAT_ROWS];
     acc->self_records += st[PAIR_STAT_SELF]; acc->keys = st[PAIR_STAT_KEYS];
     u64 *d_rows = nullptr;
-    if (nrows) {
-        DALLOC(c, d_rows, u64 *, nrows * 32);
-        ra.rows = d_rows;
-        ck.t.begin(PT_REDUCE);
-        hipLaunchKernelGGL(pair_reduce_kernel<true>, dim3((u32)rtiles), dim3(PAIR_THREADS), 0, c->stream, ra);
-        HIPCHK(c, hipGetLastError());
-        ck.t.end(PT_REDUCE);
-    }
-    c->pool.release(kA); c->pool.release(kB); c->pool.release(vA); c->pool.release(vB); c->pool.release(d_rtile); c->pool.release(d_rkeys);
+    if (nrows) { DALLOC(c, d_rows, u64 *, nrows * 32); ra.rows = d_rows; }
+    rc = ce.emit(nrows != 0, [&] { hipLaunchKernelGGL(pair_reduce_kernel<true>, dim3((u32)rtiles), dim3(PAIR_THREADS), 0, c->stream, ra); });
+    if (rc) return rc;
+    p.release(c);
     if (last) { c->pool.release(r.d_stat); r.d_stat = nullptr; }
     list->rows = d_rows; list->n = nrows; list->level = 0; list->owned = true;
     return HSK_OK;
@@ -162,7 +225,7 @@ static int pairs_window(hsk_ctx *c, PairRange &r, const PairWindow &w, bool last
 // ---- merges ------------------------------------------------------------------------------------------------------------------------
 struct PairMergeStat { u64 merges = 0, merged_rows = 0; };
 
-// One merge launch (COUNT, the scans, EMIT) of two lists on the device into a block of its own; one wait, for the row count.  *keys: the
+// One merge (CountEmit: COUNT, the scans, EMIT) of two lists on the device into a block of its own; one wait, for the row count.  *keys: the
 // rows before min_shared.  The inputs are left to the caller.
 static int pairs_merge_two(hsk_ctx *c, const PairList &A, const PairList &B, u32 min_shared, PairClock &ck, PairMergeStat &ms, PairList *out, u64 *keys)
 {
@@ -172,33 +235,25 @@ static int pairs_merge_two(hsk_ctx *c, const PairList &A, const PairList &B, u32
     if (!total) return HSK_OK;
     const u64 tiles = (total + PM_TILE - 1) / PM_TILE;
     if (tiles > 0x7fffffffULL) return fail(c, HSK_ERR_UNSUPPORTED, "%llu rows are more than one launch merges", (unsigned long long)total);
-    u64 *d_cnt, *d_keys, *d_tot;
-    DALLOC(c, d_cnt, u64 *, tiles * 8); DALLOC(c, d_keys, u64 *, tiles * 8); DALLOC(c, d_tot, u64 *, 2 * 8);
+    u64 *d_tot; DALLOC(c, d_tot, u64 *, 2 * 8);
     PairMergeArgs ma; memset(&ma, 0, sizeof ma);
-    ma.a = A.rows; ma.na = A.n; ma.b = B.rows; ma.nb = B.n; ma.min_shared = min_shared; ma.tile_cnt = d_cnt; ma.tile_keys = d_keys;
-    ck.t.begin(PT_MERGE);
-    hipLaunchKernelGGL(pair_merge_kernel<false>, dim3((u32)tiles), dim3(PM_THREADS), 0, c->stream, ma);
-    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_cnt, tiles, d_tot);
-    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(CNT_THREADS), 0, c->stream, d_keys, tiles, d_tot + 1);      // (only its total is used)
-    HIPCHK(c, hipGetLastError());
-    ck.t.end(PT_MERGE);
-    u64 *st = staging(c)->read_pairs;
-    HIPCHK(c, hipMemcpyAsync(st, d_tot, 2 * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hsk_sync(c, c->stream));
-    ck.take();
+    ma.a = A.rows; ma.na = A.n; ma.b = B.rows; ma.nb = B.n; ma.min_shared = min_shared;
+    CountEmit ce(c, ck, PT_MERGE, tiles, 2);
+    static const int word[2] = {0, 1};
+    const u64 *st;
+    int rc = ce.count(d_tot, 2, word, &st, [&] {
+        ma.tile_cnt = ce.tile[0]; ma.tile_keys = ce.tile[1];
+        hipLaunchKernelGGL(pair_merge_kernel<false>, dim3((u32)tiles), dim3(PM_THREADS), 0, c->stream, ma);
+    });
+    if (rc) return rc;
     const u64 nrows = st[0];
     *keys = st[1];
     if (nrows > total || st[1] > total) return fail(c, HSK_ERR_INTERNAL, "the merge of %llu rows counted %llu", (unsigned long long)total, (unsigned long long)std::max(nrows, st[1]));
-    if (nrows) {
-        DALLOC(c, out->rows, u64 *, nrows * 32);
-        ma.rows = out->rows;
-        ck.t.begin(PT_MERGE);
-        hipLaunchKernelGGL(pair_merge_kernel<true>, dim3((u32)tiles), dim3(PM_THREADS), 0, c->stream, ma);
-        HIPCHK(c, hipGetLastError());
-        ck.t.end(PT_MERGE);
-    }
+    if (nrows) { DALLOC(c, out->rows, u64 *, nrows * 32); ma.rows = out->rows; }
+    rc = ce.emit(nrows != 0, [&] { hipLaunchKernelGGL(pair_merge_kernel<true>, dim3((u32)tiles), dim3(PM_THREADS), 0, c->stream, ma); });
+    if (rc) return rc;
     out->n = nrows;
-    c->pool.release(d_cnt); c->pool.release(d_keys); c->pool.release(d_tot);
+    c->pool.release(d_tot);
     ms.merges++; ms.merged_rows += total;
     return HSK_OK;
 }
@@ -247,32 +302,37 @@ struct PairStack {
     }
 };
 
-// ---- egress: the final list to pinned host memory, or left on the device in a block the result owns; the call's last wait ----------
-static int pairs_egress(hsk_ctx *c, PairList &fin, bool on_device, hipEvent_t e_end, PairClock &ck, hsk_pairs *out, PairsPriv *pp)
+// ---- egress: the final list (rows of row_bytes bytes) to pinned host memory, or left on the device in a block the result owns; the
+// call's last wait.  pp holds the two pointers; pairs_store() puts them and the call's times into the ABI struct.
+static int pairs_egress(hsk_ctx *c, PairList &fin, u64 row_bytes, bool on_device, PairCall &pc, PairsPriv *pp)
 {
-    const u64 nrows = fin.n;
+    const u64 bytes = fin.n * row_bytes;
     u64 *d_rows = fin.rows;
-    if (nrows && !on_device) {
-        pp->host_rows = c->hpool.alloc(nrows * 32);
-        if (!pp->host_rows) return fail(c, HSK_ERR_OOM, "pinned host allocation of %llu bytes failed", (unsigned long long)(nrows * 32));
-        ck.t.begin(PT_D2H);
-        HIPCHK(c, hipMemcpyAsync(pp->host_rows, d_rows, nrows * 32, hipMemcpyDeviceToHost, c->stream));
-        ck.t.end(PT_D2H);
-        c->stats.d2h_bytes += nrows * 32;
-    } else if (nrows && !fin.owned) {                   // a caller's list that came through as it is: the result gets a copy of its own
-        u64 *cp; DALLOC(c, cp, u64 *, nrows * 32);
-        HIPCHK(c, hipMemcpyAsync(cp, d_rows, nrows * 32, hipMemcpyDeviceToDevice, c->stream));
+    if (bytes && !on_device) {
+        pp->host_rows = c->hpool.alloc(bytes);
+        if (!pp->host_rows) return fail(c, HSK_ERR_OOM, "pinned host allocation of %llu bytes failed", (unsigned long long)bytes);
+        pc.ck.t.begin(PT_D2H);
+        HIPCHK(c, hipMemcpyAsync(pp->host_rows, d_rows, bytes, hipMemcpyDeviceToHost, c->stream));
+        pc.ck.t.end(PT_D2H);
+        c->stats.d2h_bytes += bytes;
+    } else if (bytes && !fin.owned) {                    // a caller's list that came through hsk_pairs_merge as it is: the result gets a copy of its own
+        u64 *cp; DALLOC(c, cp, u64 *, bytes);
+        HIPCHK(c, hipMemcpyAsync(cp, d_rows, bytes, hipMemcpyDeviceToDevice, c->stream));
         d_rows = cp; fin.owned = true;
     }
-    HIPCHK(c, hipEventRecord(e_end, c->stream));
-    HIPCHK(c, hsk_sync(c, c->stream));
-    ck.take();
-    if (!nrows || !on_device) { if (fin.owned) c->pool.release(d_rows); d_rows = nullptr; }
+    const int rc = pc.finish(c); if (rc) return rc;
+    if (!bytes || !on_device) { if (fin.owned) c->pool.release(d_rows); d_rows = nullptr; }
     fin.rows = nullptr;
     pp->dev_rows = d_rows;
-    out->n = nrows; out->rows = (uint64_t *)pp->host_rows; out->rows_dev = d_rows;
-    out->ms_expand = ck.ms[PT_EXPAND]; out->ms_sort = ck.ms[PT_SORT]; out->ms_reduce = ck.ms[PT_REDUCE]; out->ms_d2h = ck.ms[PT_D2H];
     return HSK_OK;
+}
+
+template <typename Out>
+static void pairs_store(Out *out, u64 nrows, const PairsPriv *pp, const PairCall &pc)
+{
+    out->n = nrows; out->rows = (uint64_t *)pp->host_rows; out->rows_dev = pp->dev_rows;
+    out->ms_expand = pc.ck.ms[PT_EXPAND]; out->ms_sort = pc.ck.ms[PT_SORT]; out->ms_reduce = pc.ck.ms[PT_REDUCE]; out->ms_d2h = pc.ck.ms[PT_D2H];
+    out->ms_total = pc.total();
 }
 
 // What hsk_result_pairs_sliced expands at a time when the caller leaves it to the library (include/hsk.h): 1/96 of the device memory the
@@ -295,25 +355,12 @@ static u64 pairs_auto_budget(hsk_ctx *c)
 static int pairs_impl(hsk_ctx *c, const ResultPriv *rp, const StrandsPriv *sp, int nw, int32_t task_lo, int32_t task_hi, u32 min_shared, bool on_device, bool sliced, u64 max_records,
                       hsk_pairs *out, hsk_pairs_slices *info, PairsPriv *pp)
 {
-    PairRange r;
+    PairRange r; PairCall pc(c); bool go;
+    PairClock &ck = pc.ck;
     const bool oriented = sp != nullptr;               // (hsk_result_pairs_oriented: only the key of a record differs)
-    int rc = pairs_range_tasks(c, rp, task_lo, task_hi, r, sp); if (rc) return rc;
     info->slices = 1;
-    if (!r.nent) return HSK_OK;
-    EvList ev(c);
-    hipEvent_t e_start = ev.get(), e_end = ev.get();
-    PairClock ck(c);
-    HIPCHK(c, hipEventRecord(e_start, c->stream));
-    rc = pairs_count_records(c, nw, r, ck); if (rc) return rc;
+    int rc = pairs_begin(c, rp, sp, nw, task_lo, task_hi, r, pc, out, &go); if (rc || !go) return rc;
     const u64 records = r.records;
-    out->records = records;
-    float f = 0;
-    if (!records) {
-        HIPCHK(c, hipEventRecord(e_end, c->stream)); HIPCHK(c, hsk_sync(c, c->stream));
-        if (hipEventElapsedTime(&f, e_start, e_end) == hipSuccess) out->ms_expand = out->ms_total = f;
-        pairs_release_range(c, r, true);
-        return HSK_OK;
-    }
     u64 budget = records;
     if (sliced) budget = max_records ? max_records : pairs_auto_budget(c);
     PairList fin;
@@ -358,19 +405,28 @@ static int pairs_impl(hsk_ctx *c, const ResultPriv *rp, const StrandsPriv *sp, i
         out->self_records = acc.self_records; out->sort_passes = acc.sort_passes; out->keys = keys;
         info->slices = win.size(); info->merges = stk.ms.merges; info->merged_rows = stk.ms.merged_rows;
     }
-    rc = pairs_egress(c, fin, on_device, e_end, ck, out, pp); if (rc) return rc;
+    rc = pairs_egress(c, fin, 32, on_device, pc, pp); if (rc) return rc;
+    pairs_store(out, fin.n, pp, pc);
     info->ms_merge = ck.ms[PT_MERGE];
-    if (hipEventElapsedTime(&f, e_start, e_end) == hipSuccess) out->ms_total = f;
     return HSK_OK;
 }
 
-// What every call that reads a resident EXTENSION result checks before it opens its scope; *rp, *sp: the private parts (sp NULL without strands).
-static int pairs_check_args(hsk_ctx *c, const hsk_result *res, const hsk_strands *strands, int32_t task_lo, int32_t task_hi, const char *name, const ResultPriv **rpo, const StrandsPriv **spo)
+// What every call that reads a resident EXTENSION result checks before it opens its scope; *rpo: the result's private part.
+static int pairs_check_resident(hsk_ctx *c, const hsk_result *res, const char *name, const ResultPriv **rpo)
 {
     if (!c->cfg.extension) return fail(c, HSK_ERR_INVALID_ARG, "%s needs a context with EXTENSION: without it the list carries no (ReadId, PosInRead)", name);
     const ResultPriv *rp = (const ResultPriv *)res->priv;
     if (!(c->cfg.flags & HSK_FLAG_KEEP_DEVICE) || !rp || res->ntasks <= 0 || rp->dev_tasks.size() != (size_t)res->ntasks)
         return fail(c, HSK_ERR_INVALID_ARG, "%s needs a result that was left on the device (HSK_FLAG_KEEP_DEVICE)", name);
+    *rpo = rp;
+    return HSK_OK;
+}
+
+// ... and a task range of it, with or without the strands of its payload slots (*spo NULL without)
+static int pairs_check_args(hsk_ctx *c, const hsk_result *res, const hsk_strands *strands, int32_t task_lo, int32_t task_hi, const char *name, const ResultPriv **rpo, const StrandsPriv **spo)
+{
+    const ResultPriv *rp;
+    const int rc = pairs_check_resident(c, res, name, &rp); if (rc) return rc;
     if (task_lo < 0 || task_hi < task_lo || task_hi > res->ntasks) return fail(c, HSK_ERR_INVALID_ARG, "task range [%d, %d) outside [0, %d]", task_lo, task_hi, res->ntasks);
     const StrandsPriv *sp = strands ? (const StrandsPriv *)strands->priv : nullptr;
     if (strands) {                                        // do the bits belong to this result?
@@ -385,6 +441,31 @@ static int pairs_check_args(hsk_ctx *c, const hsk_result *res, const hsk_strands
     return HSK_OK;
 }
 
+// A call that returns a row list: the list's private part, the call's scope (ApiCall), and nothing left behind when it fails.
+template <typename Out, typename Impl>
+static int pairs_api_call(hsk_ctx *c, const char *name, Out *out, Impl &&impl)
+{
+    PairsPriv *pp = new PairsPriv();
+    const int rc = ApiCall(c, name).run([&] { return impl(pp); });
+    if (rc != HSK_OK) {                                   // (the device blocks went back with the call's rollback)
+        if (pp->host_rows) c->hpool.release(pp->host_rows);
+        delete pp;
+        memset(out, 0, sizeof *out);
+        return rc;
+    }
+    out->priv = pp;
+    return HSK_OK;
+}
+
+static void pairs_priv_free(hsk_ctx *c, void *priv)
+{
+    PairsPriv *pp = (PairsPriv *)priv;
+    if (!pp) return;
+    if (c) { if (pp->host_rows) c->hpool.release(pp->host_rows); c->pool.release(pp->dev_rows); }
+    else if (pp->host_rows) (void)hipHostFree(pp->host_rows);
+    delete pp;
+}
+
 static int pairs_entry(hsk_ctx *c, const hsk_result *res, const hsk_strands *strands, int32_t task_lo, int32_t task_hi, uint32_t min_shared, int32_t on_device, bool sliced, uint64_t max_records,
                        hsk_pairs *out, hsk_pairs_slices *info, const char *name)
 {
@@ -395,16 +476,9 @@ static int pairs_entry(hsk_ctx *c, const hsk_result *res, const hsk_strands *str
     const ResultPriv *rp; const StrandsPriv *sp;
     const int chk = pairs_check_args(c, res, strands, task_lo, task_hi, name, &rp, &sp); if (chk) return chk;
     if (min_shared == 0) return fail(c, HSK_ERR_INVALID_ARG, "min_shared must be at least 1");
-    PairsPriv *pp = new PairsPriv();
-    const int rc = ApiCall(c, name).run([&] { return pairs_impl(c, rp, sp, res->nw, task_lo, task_hi, min_shared, on_device != 0, sliced, max_records, out, info, pp); });
-    if (rc != HSK_OK) {                                   // (the device blocks went back with the call's rollback)
-        if (pp->host_rows) c->hpool.release(pp->host_rows);
-        delete pp;
-        memset(out, 0, sizeof *out); memset(info, 0, sizeof *info);
-        return rc;
-    }
-    out->priv = pp;
-    return HSK_OK;
+    const int rc = pairs_api_call(c, name, out, [&](PairsPriv *pp) { return pairs_impl(c, rp, sp, res->nw, task_lo, task_hi, min_shared, on_device != 0, sliced, max_records, out, info, pp); });
+    if (rc != HSK_OK) memset(info, 0, sizeof *info);
+    return rc;
 }
 
 extern "C" int hsk_result_pairs(hsk_ctx *c, const hsk_result *res, int32_t task_lo, int32_t task_hi, uint32_t min_shared, int32_t on_device, hsk_pairs *out)
@@ -430,10 +504,9 @@ extern "C" int hsk_result_pairs_oriented(hsk_ctx *c, const hsk_result *res, cons
 // The several-list contract on the GPU: host lists go up, device lists are read where they are, and all meet on a PairStack.
 static int pairs_merge_impl(hsk_ctx *c, const hsk_pairs *const *parts, int32_t nparts, u32 min_shared, bool on_device, hsk_pairs *out, PairsPriv *pp)
 {
-    EvList ev(c);
-    hipEvent_t e_start = ev.get(), e_end = ev.get();
-    PairClock ck(c);
-    HIPCHK(c, hipEventRecord(e_start, c->stream));
+    PairCall pc(c);
+    PairClock &ck = pc.ck;
+    int rc = pc.start(c); if (rc) return rc;
     int32_t last = -1;
     for (int32_t i = 0; i < nparts; ++i) { out->records += parts[i]->records; out->self_records += parts[i]->self_records; if (parts[i]->n) last = i; }
     PairStack stk;
@@ -447,15 +520,14 @@ static int pairs_merge_impl(hsk_ctx *c, const hsk_pairs *const *parts, int32_t n
             HIPCHK(c, hipMemcpyAsync(l.rows, p->rows, p->n * 32, hipMemcpyHostToDevice, c->stream));      // (pageable or pinned: the part outlives the call's last wait)
             c->stats.h2d_bytes += p->n * 32;
         }
-        const int rc = stk.push(c, l, i != last, ck); if (rc) return rc;
+        rc = stk.push(c, l, i != last, ck); if (rc) return rc;
     }
     PairList fin; u64 keys = 0;
-    int rc = stk.finish(c, min_shared, ck, &fin, &keys); if (rc) return rc;
+    rc = stk.finish(c, min_shared, ck, &fin, &keys); if (rc) return rc;
     out->keys = keys;
-    rc = pairs_egress(c, fin, on_device, e_end, ck, out, pp); if (rc) return rc;
+    rc = pairs_egress(c, fin, 32, on_device, pc, pp); if (rc) return rc;
+    pairs_store(out, fin.n, pp, pc);
     out->ms_reduce = ck.ms[PT_MERGE];                    // (the merges are this call's reduction)
-    float f = 0;
-    if (hipEventElapsedTime(&f, e_start, e_end) == hipSuccess) out->ms_total = f;
     return HSK_OK;
 }
 
@@ -472,26 +544,12 @@ extern "C" int hsk_pairs_merge(hsk_ctx *c, const hsk_pairs *const *parts, int32_
         if (parts[i]->n && ((uintptr_t)parts[i]->rows_dev & 15)) return fail(c, HSK_ERR_INVALID_ARG, "hsk_pairs_merge: rows_dev of part %d is not 16-byte aligned", i);
         if (parts[i]->n >> 58) return fail(c, HSK_ERR_INVALID_ARG, "hsk_pairs_merge: part %d claims %llu rows", i, (unsigned long long)parts[i]->n);
     }
-    PairsPriv *pp = new PairsPriv();
-    const int rc = ApiCall(c, "hsk_pairs_merge").run([&] { return pairs_merge_impl(c, parts, nparts, min_shared, on_device != 0, out, pp); });
-    if (rc != HSK_OK) {                                   // (the device blocks went back with the call's rollback)
-        if (pp->host_rows) c->hpool.release(pp->host_rows);
-        delete pp;
-        memset(out, 0, sizeof *out);
-        return rc;
-    }
-    out->priv = pp;
-    return HSK_OK;
+    return pairs_api_call(c, "hsk_pairs_merge", out, [&](PairsPriv *pp) { return pairs_merge_impl(c, parts, nparts, min_shared, on_device != 0, out, pp); });
 }
 
 extern "C" void hsk_pairs_free(hsk_ctx *c, hsk_pairs *p)
 {
     if (!p) return;
-    PairsPriv *pp = (PairsPriv *)p->priv;
-    if (pp) {
-        if (c) { if (pp->host_rows) c->hpool.release(pp->host_rows); c->pool.release(pp->dev_rows); }
-        else if (pp->host_rows) (void)hipHostFree(pp->host_rows);
-        delete pp;
-    }
+    pairs_priv_free(c, p->priv);
     memset(p, 0, sizeof *p);
 }

@@ -64,12 +64,14 @@ static void launch_onesweep(hsk_ctx *c, const SortArgs &a, u32 ntiles)
 }
 
 // Sorts n records in bufA (keys) / valA using bufB / valB as the ping-pong buffer.  On return
-// *out_keys / *out_vals point at whichever buffer holds the sorted data.
+// *out_keys / *out_vals point at whichever buffer holds the sorted data.  *scatter_passes (where asked for): the onesweep launches
+// the call enqueued -- 0 for n < 2 or when every digit is trivial; with the hybrid path's full-width redo, those of both legs.
 template <int NW>
 static int sort_task_device(hsk_ctx *c, u64 *keysA, u64 *keysB, u64 *valsA, u64 *valsB, u64 n, int K, SortScratch &sc,
-                            u64 **out_keys, u64 **out_vals, bool allow_hybrid = true)
+                            u64 **out_keys, u64 **out_vals, bool allow_hybrid = true, int *scatter_passes = nullptr)
 {
     *out_keys = keysA; *out_vals = valsA;
+    if (scatter_passes) *scatter_passes = 0;
     if (n < 2) return HSK_OK;
     const bool has_val = valsA != nullptr;
     const bool hybrid = allow_hybrid && NW == 1 && hybrid_enabled();
@@ -89,6 +91,7 @@ static int sort_task_device(hsk_ctx *c, u64 *keysA, u64 *keysB, u64 *valsA, u64 
         for (int d = 0; d < 256; ++d) { if (hh[p * 256 + d] == n) trivial = true; hb[p * 256 + d] = run; run += hh[p * 256 + d]; }
         if (!trivial) todo.push_back(p);
     }
+    if (scatter_passes) *scatter_passes = (int)todo.size();
     if (todo.empty() && !hybrid) return HSK_OK;
     u64 *kin = keysA, *kout = keysB, *vin = valsA, *vout = valsB;
     if (!todo.empty()) {
@@ -137,7 +140,10 @@ static int sort_task_device(hsk_ctx *c, u64 *keysA, u64 *keysB, u64 *valsA, u64 
             c->stats.redone_tasks++;
             u64 *other = (kin == keysA) ? keysB : keysA;
             u64 *vother = has_val ? ((vin == valsA) ? valsB : valsA) : nullptr;
-            return sort_task_device<NW>(c, kin, other, vin, vother, n, K, sc, out_keys, out_vals, false);
+            int redo = 0;
+            const int rc = sort_task_device<NW>(c, kin, other, vin, vother, n, K, sc, out_keys, out_vals, false, &redo);
+            if (scatter_passes) *scatter_passes += redo;
+            return rc;
         }
     }
     *out_keys = kin; *out_vals = vin;

@@ -86,10 +86,8 @@ extern "C" int hsk_result_strands(hsk_ctx *c, const hsk_result *res, const void 
     memset(out, 0, sizeof *out);
     if ((nreads && (!roff || !rlen)) || (packed_bytes && !packed)) return fail(c, HSK_ERR_INVALID_ARG, "hsk_result_strands: %llu reads in %llu packed bytes and a NULL pointer among packed, read_byte_off and read_len",
                                                                                (unsigned long long)nreads, (unsigned long long)packed_bytes);
-    if (!c->cfg.extension) return fail(c, HSK_ERR_INVALID_ARG, "hsk_result_strands needs a context with EXTENSION: without it the list carries no (ReadId, PosInRead)");
-    const ResultPriv *rp = (const ResultPriv *)res->priv;
-    if (!(c->cfg.flags & HSK_FLAG_KEEP_DEVICE) || !rp || res->ntasks <= 0 || rp->dev_tasks.size() != (size_t)res->ntasks)
-        return fail(c, HSK_ERR_INVALID_ARG, "hsk_result_strands needs a result that was left on the device (HSK_FLAG_KEEP_DEVICE)");
+    const ResultPriv *rp;
+    const int chk = pairs_check_resident(c, res, "hsk_result_strands", &rp); if (chk) return chk;
     if (rid_base < 0 || nreads > (1ULL << 31) || (u64)rid_base + nreads > (1ULL << 31))
         return fail(c, HSK_ERR_INVALID_ARG, "hsk_result_strands: read ids [%lld, %lld + %llu) do not lie below 2^31 (bit 63 of an oriented key must be free)", (long long)rid_base, (long long)rid_base, (unsigned long long)nreads);
     if (reads_on_device && ((uintptr_t)packed & 3) != 0) return fail(c, HSK_ERR_INVALID_ARG, "hsk_result_strands: packed must be 4-byte aligned on the device");

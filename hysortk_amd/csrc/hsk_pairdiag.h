@@ -8,20 +8,19 @@
 //                        that have records (the gap slots of filtered k-mers are not read: nothing says what they hold).  One lane per
 //                        entry walks its slice; one atomicMax per workgroup.  The sort word is taken relative to this bound.
 //   diag_reduce_kernel   level 1: runs of equal (key, word 0) become BIN ROWS of six words { key, support, bin, support, first, last },
-//                        the all-bins row of the ABI.  The shape of pair_reduce_kernel: run heads as bit masks, the tile's last run
-//                        followed to its end by the whole workgroup, a count pass, count_scan_kernel, an emit pass; the compare is on two
-//                        words, which every lane holds in registers (its record and the one before it: neighbouring 16-byte loads), so
-//                        that LDS holds the values only.  The zero-key run is self_records.  Per tile it also counts the key heads
-//                        (`keys`) and the runs before min_support (`bins`).
+//                        the all-bins row of the ABI.  The steps of pair_reduce_kernel (hsk_runmask.h), a count pass, count_scan_kernel,
+//                        an emit pass; the compare is on two words, which every lane holds in registers (its record and the one before
+//                        it: neighbouring 16-byte loads), so that LDS holds the values only.  The zero-key run is self_records.  Per
+//                        tile it also counts the key heads (`keys`) and the runs before min_support (`bins`).
 //   diag_select_kernel   level 2: runs of equal key over the bin rows become one row { key, sum of support, bin, support, first, last }
-//                        of the bin with the largest support, the smallest such bin on a tie (diag_better).  A key's bin rows may span
-//                        any number of tiles: the run belongs to the tile it starts in, whose workgroup follows it to its end -- every
-//                        lane keeps (sum, best support, best bin, row of the best), reduced over the workgroup -- and tiles inside a run
-//                        do nothing.  No atomics.  first / last are read from the winning bin row.  Rows leave as three 16-byte stores,
-//                        in key order by popcount prefix; min_support is applied after the selection.
+//                        of the bin with the largest support, the smallest such bin on a tie (diag_better).  The same steps; what a
+//                        lane keeps of a run is (sum, best support, best bin, row of the best), reduced over the workgroup for the
+//                        tile's last key.  No atomics.  first / last are read from the winning bin row.  Rows leave as three 16-byte
+//                        stores, in key order by popcount prefix; min_support is applied after the selection.
 #pragma once
 #include "hsk_device.h"
 #include "hsk_count.h"
+#include "hsk_runmask.h"
 #include "hsk_pairs.h"
 #include "hsk_diagbin.h"
 
@@ -104,17 +103,15 @@ __global__ __launch_bounds__(PAIR_THREADS) void diag_reduce_kernel(DiagReduceArg
             else { const v2u64d prev = kk[base + p - 1]; khead[j] = prev.y != cur.y; head[j] = khead[j] || prev.x != cur.x; }
             if (EMIT) s_v[p] = a.vals[base + p];
         }
-        const u64 m = __ballot(head[j]);
-        if (lane == 0) s_head[j * 4 + wave] = m;
+        rm_publish(s_head, j, __ballot(head[j]));
     }
     __syncthreads();
-    int lw = DR_WORDS - 1;
-    while (lw >= 0 && s_head[lw] == 0) --lw;
-    if (lw < 0) { if (!EMIT && tid == 0) { a.tile_cnt[blockIdx.x] = 0; a.tile_keys[blockIdx.x] = 0; a.tile_bins[blockIdx.x] = 0; } return; }      // the tile lies inside a run that started before it
-    const u32 p_last = (u32)lw * 64 + 63 - (u32)__builtin_clzll(s_head[lw]);
+    const int p_last = rm_last_head<DR_WORDS>(s_head);
+    if (p_last < 0) { if (!EMIT && tid == 0) { a.tile_cnt[blockIdx.x] = 0; a.tile_keys[blockIdx.x] = 0; a.tile_bins[blockIdx.x] = 0; } return; }      // the tile lies inside a run that started before it
 
     // ---- the tile's last run: the workgroup follows it to its end --------------------------------------------------
     const v2u64d key_last = kk[base + p_last];
+    // (scalars and the loop in the kernel's own text, not RunAcc and rm_follow: 64 VGPRs and occupancy 8 that way, 66 and 7 the other)
     u64 lc = 0, lmn = ~0ULL, lmx = 0;
     for (u32 i = p_last + tid; i < tn; i += PAIR_THREADS) {
         ++lc;
@@ -136,16 +133,8 @@ __global__ __launch_bounds__(PAIR_THREADS) void diag_reduce_kernel(DiagReduceArg
         }
         if (__syncthreads_or(stop)) break;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lc += __shfl_xor(lc, o, WAVE);
-        if (EMIT) { const u64 n1 = __shfl_xor(lmn, o, WAVE), x1 = __shfl_xor(lmx, o, WAVE); lmn = n1 < lmn ? n1 : lmn; lmx = x1 > lmx ? x1 : lmx; }
-    }
-    if (lane == 0) { s_red[wave][0] = lc; s_red[wave][1] = lmn; s_red[wave][2] = lmx; }
-    __syncthreads();
-    lc = 0; lmn = ~0ULL; lmx = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { lc += s_red[w][0]; lmn = s_red[w][1] < lmn ? s_red[w][1] : lmn; lmx = s_red[w][2] > lmx ? s_red[w][2] : lmx; }
+    RunAcc L; L.n = lc; L.mn = lmn; L.mx = lmx;
+    rm_reduce_run<EMIT>(L, s_red);
 
     // ---- run lengths, the min_support filter --------------------------------------------------------------------------
     u64 runlen[DR_PPT];
@@ -155,31 +144,19 @@ __global__ __launch_bounds__(PAIR_THREADS) void diag_reduce_kernel(DiagReduceArg
         const u32 p = j * PAIR_THREADS + tid;
         u64 c = 0; bool real = false;
         if (head[j]) {
-            if (p == p_last) c = lc;
-            else {                                        // the next head is inside the tile
-                u32 w = p >> 6;
-                u64 m = s_head[w] & ((p & 63) == 63 ? 0ULL : (~0ULL << ((p & 63) + 1)));
-                while (m == 0) m = s_head[++w];
-                c = (w << 6) + (u32)__builtin_ctzll(m) - p;
-            }
+            c = p == (u32)p_last ? L.n : rm_next_head(s_head, p) - p;
             real = k1[j] != 0;
             if (!EMIT && !real) a.stats[PAIR_STAT_SELF] = c;
         }
         const bool keep = real && c >= a.min_support;
         runlen[j] = keep ? c : 0;
-        const u64 km = __ballot(keep);
-        if (lane == 0) s_keep[j * 4 + wave] = km;
+        rm_publish(s_keep, j, __ballot(keep));
         if (!EMIT) { nbins += (u32)__popcll(__ballot(real)); nkeys += (u32)__popcll(__ballot(real && khead[j])); }
     }
     __syncthreads();                                      // (s_red has been read by every wave)
     if (!EMIT && lane == 0) { s_red[wave][0] = nkeys; s_red[wave][1] = nbins; }
     __syncthreads();
-    if (tid < 64) {
-        const u32 v = tid < DR_WORDS ? (u32)__popcll(s_keep[tid]) : 0;
-        const u32 inc = wave_incl_scan<u32>(v);
-        if (tid < DR_WORDS) s_pre[tid] = inc - v;
-        if (tid == DR_WORDS - 1) s_pre[DR_WORDS] = inc;
-    }
+    rm_prefix<DR_WORDS>(s_keep, s_pre);
     __syncthreads();
     if (!EMIT) {
         if (tid == 0) {
@@ -197,15 +174,10 @@ __global__ __launch_bounds__(PAIR_THREADS) void diag_reduce_kernel(DiagReduceArg
         const u64 c = runlen[j];
         if (!c) continue;
         const u32 p = j * PAIR_THREADS + tid;
-        const u32 w = j * 4 + wave;
-        const u32 slot = s_pre[w] + (u32)__popcll(s_keep[w] & ((1ULL << lane) - 1));
-        u64 mn = lmn, mx = lmx;
-        if (p != p_last) {
-            mn = ~0ULL; mx = 0;
-            for (u32 q = p; q < p + (u32)c; ++q) { const u64 v = s_v[EMIT ? q : 0]; mn = v < mn ? v : mn; mx = v > mx ? v : mx; }
-        }
-        v2u64d *row = (v2u64d *)(a.rows + (obase + slot) * DIAG_ROW_WORDS);
-        const v2u64d r0 = {k1[j], c}, r1 = {k0[j] + ((k1[j] >> 63) ? lo_opp : lo_same), c}, r2 = {mn, mx};
+        RunAcc r = L;
+        if (p != (u32)p_last) r.span(s_v, p, (u32)c);
+        v2u64d *row = (v2u64d *)(a.rows + (obase + rm_slot(s_keep, s_pre, j)) * DIAG_ROW_WORDS);
+        const v2u64d r0 = {k1[j], c}, r1 = {k0[j] + ((k1[j] >> 63) ? lo_opp : lo_same), c}, r2 = {r.mn, r.mx};
         row[0] = r0; row[1] = r1; row[2] = r2;
     }
 }
@@ -253,34 +225,23 @@ __global__ __launch_bounds__(PAIR_THREADS) void diag_select_kernel(DiagSelectArg
             key[j] = r0.x; s_bin[p] = r1.x; s_sup[p] = r1.y;
             head[j] = base + p == 0 || a.bins[(base + p - 1) * DIAG_ROW_WORDS] != r0.x;
         }
-        const u64 m = __ballot(head[j]);
-        if (lane == 0) s_head[j * 4 + wave] = m;
+        rm_publish(s_head, j, __ballot(head[j]));
     }
     __syncthreads();
-    int lw = DS_WORDS - 1;
-    while (lw >= 0 && s_head[lw] == 0) --lw;
-    if (lw < 0) { if (!EMIT && tid == 0) a.tile_cnt[blockIdx.x] = 0; return; }      // the tile lies inside a key's bins: the tile of the key's first bin row reads them
-    const u32 p_last = (u32)lw * 64 + 63 - (u32)__builtin_clzll(s_head[lw]);
+    const int p_last = rm_last_head<DS_WORDS>(s_head);
+    if (p_last < 0) { if (!EMIT && tid == 0) a.tile_cnt[blockIdx.x] = 0; return; }      // the tile lies inside a key's bins: the tile of the key's first bin row reads them
 
     // ---- the tile's last key: the workgroup follows its bin rows to their end, over as many tiles as they take -----------
     const u64 key_last = a.bins[(base + p_last) * DIAG_ROW_WORDS];
     DiagBest L; L.clear();
     for (u32 i = p_last + tid; i < tn; i += PAIR_THREADS) L.take(s_sup[i], s_bin[i], base + i);
-    for (u64 g = base + tn;; g += (u64)PAIR_THREADS * DS_AHEAD) {
-        int stop = g >= a.n;
-        if (!stop) {
-#pragma unroll
-            for (int s = 0; s < DS_AHEAD; ++s) {
-                const u64 gi = g + (u64)s * PAIR_THREADS + tid;
-                if (gi >= a.n) { stop = 1; continue; }
-                const v2u64d *r = (const v2u64d *)(a.bins + gi * DIAG_ROW_WORDS);
-                const v2u64d r0 = r[0], r1 = r[1];
-                if (r0.x != key_last) { stop = 1; continue; }
-                L.take(r1.y, r1.x, gi);
-            }
-        }
-        if (__syncthreads_or(stop)) break;
-    }
+    rm_follow<DS_AHEAD>(base + tn, a.n, [&](u64 gi) {
+        const v2u64d *r = (const v2u64d *)(a.bins + gi * DIAG_ROW_WORDS);
+        const v2u64d r0 = r[0], r1 = r[1];
+        if (r0.x != key_last) return false;
+        L.take(r1.y, r1.x, gi);
+        return true;
+    });
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const u64 osum = __shfl_xor(L.sum, o, WAVE), os = __shfl_xor(L.sup, o, WAVE), ob = __shfl_xor(L.bin, o, WAVE), orow = __shfl_xor(L.row, o, WAVE);
@@ -299,37 +260,22 @@ __global__ __launch_bounds__(PAIR_THREADS) void diag_select_kernel(DiagSelectArg
         const u32 p = j * PAIR_THREADS + tid;
         best[j].clear();
         if (head[j]) {
-            if (p == p_last) best[j] = L;
-            else {                                        // the next head is inside the tile
-                u32 w = p >> 6;
-                u64 m = s_head[w] & ((p & 63) == 63 ? 0ULL : (~0ULL << ((p & 63) + 1)));
-                while (m == 0) m = s_head[++w];
-                const u32 e = (w << 6) + (u32)__builtin_ctzll(m);
-                for (u32 q = p; q < e; ++q) best[j].take(s_sup[q], s_bin[q], base + q);
-            }
+            if (p == (u32)p_last) best[j] = L;
+            else for (u32 q = p, e = rm_next_head(s_head, p); q < e; ++q) best[j].take(s_sup[q], s_bin[q], base + q);
         }
-        const bool keep = head[j] && best[j].sup >= a.min_support;
-        const u64 km = __ballot(keep);
-        if (lane == 0) s_keep[j * 4 + wave] = km;
+        rm_publish(s_keep, j, __ballot(head[j] && best[j].sup >= a.min_support));
     }
     __syncthreads();
-    if (tid < 64) {
-        const u32 v = tid < DS_WORDS ? (u32)__popcll(s_keep[tid]) : 0;
-        const u32 inc = wave_incl_scan<u32>(v);
-        if (tid < DS_WORDS) s_pre[tid] = inc - v;
-        if (tid == DS_WORDS - 1) s_pre[DS_WORDS] = inc;
-    }
+    rm_prefix<DS_WORDS>(s_keep, s_pre);
     __syncthreads();
     if (!EMIT) { if (tid == 0) a.tile_cnt[blockIdx.x] = s_pre[DS_WORDS]; return; }
 
     // ---- rows: slot = popcount prefix of the kept heads, so the list stays in key order ------------------------------------
 #pragma unroll
     for (int j = 0; j < DS_PPT; ++j) {
-        const u32 w = j * 4 + wave;
-        if (!((s_keep[w] >> lane) & 1)) continue;
-        const u32 slot = s_pre[w] + (u32)__popcll(s_keep[w] & ((1ULL << lane) - 1));
+        if (!((s_keep[j * RM_WAVES + wave] >> lane) & 1)) continue;
         const v2u64d fl = ((const v2u64d *)(a.bins + best[j].row * DIAG_ROW_WORDS))[2];
-        v2u64d *row = (v2u64d *)(a.rows + (obase + slot) * DIAG_ROW_WORDS);
+        v2u64d *row = (v2u64d *)(a.rows + (obase + rm_slot(s_keep, s_pre, j)) * DIAG_ROW_WORDS);
         const v2u64d r0 = {key[j], best[j].sum}, r1 = {best[j].bin, best[j].sup};
         row[0] = r0; row[1] = r1; row[2] = fl;
     }

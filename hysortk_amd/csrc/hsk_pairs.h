@@ -23,13 +23,14 @@
 //                       key; everything behind the expansion sees a key like any other.
 //                       DIAG (hsk_result_pair_diagonals, hsk_pairdiag.h): the key has two words, the oriented key in the more significant
 //                       word 1 and the sort word of the record's diagonal bin (hsk_diagbin.h) in word 0; a pair inside one read has both 0.
-//   pair_reduce_kernel  the shape of count_kernel: run heads of a tile as a bit mask, rows per tile, count_scan_kernel, write pass.
-//                       A run belongs to the tile it starts in.  The last run of a tile may go on for any number of tiles: the
-//                       whole workgroup reads ahead to its end (count, min, max reduced over the workgroup); tiles inside a run
-//                       have no head and nothing to do.  The zero-key run is self_records and no row.
+//   pair_reduce_kernel  the steps of hsk_runmask.h over keys staged in LDS: run heads of a tile as a bit mask, rows per tile,
+//                       count_scan_kernel, write pass.  The last run of a tile may go on for any number of tiles (count, min, max
+//                       reduced over the workgroup); tiles inside a run have no head and nothing to do.  The zero-key run is
+//                       self_records and no row.
 #pragma once
 #include "hsk_device.h"
 #include "hsk_count.h"
+#include "hsk_runmask.h"
 #include "hsk_pairdecode.h"
 #include "hsk_diagbin.h"
 
@@ -46,7 +47,7 @@ struct alignas(128) PairTask {
     const u64 *strand;       // hsk_result_pairs_oriented: bit s & 63 of word s >> 6 = the strand of payload slot s (hsk_strand.h); NULL otherwise
 };
 
-constexpr int PAIR_THREADS = 256;
+constexpr int PAIR_THREADS = RM_THREADS;
 constexpr int PC_EPT = 8, PC_TILE = PAIR_THREADS * PC_EPT;          // entries per thread / tile of pair_tsum_kernel
 constexpr int PAIR_LOC_SHIFT = 40;                                  // loc = task slot << 40 | first payload inside the task (npay < 2^40)
 constexpr u32 PAIR_ERR_COUNT = 1, PAIR_ERR_SLICE = 2;               // an entry's count above 65535 / its slice outside the task's payload
@@ -223,48 +224,24 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_reduce_kernel(PairReduceArg
     for (int j = 0; j < PR_PPT; ++j) {
         const u32 p = j * PAIR_THREADS + tid;
         head[j] = p < tn && ((base + p == 0) || s_k[p + 1] != s_k[p]);
-        const u64 m = __ballot(head[j]);
-        if (lane == 0) s_head[j * 4 + wave] = m;
+        rm_publish(s_head, j, __ballot(head[j]));
     }
     __syncthreads();
-    int lw = PR_WORDS - 1;
-    while (lw >= 0 && s_head[lw] == 0) --lw;
-    if (lw < 0) { if (!EMIT && tid == 0) { a.tile_cnt[blockIdx.x] = 0; a.tile_keys[blockIdx.x] = 0; } return; }      // the tile lies inside a run that started before it
-    const u32 p_last = (u32)lw * 64 + 63 - (u32)__builtin_clzll(s_head[lw]);
+    const int p_last = rm_last_head<PR_WORDS>(s_head);
+    if (p_last < 0) { if (!EMIT && tid == 0) { a.tile_cnt[blockIdx.x] = 0; a.tile_keys[blockIdx.x] = 0; } return; }      // the tile lies inside a run that started before it
 
     // ---- the tile's last run: the workgroup follows it to its end --------------------------------------------------
     const u64 key_last = s_k[p_last + 1];
-    u64 lc = 0, lmn = ~0ULL, lmx = 0;
-    for (u32 i = p_last + tid; i < tn; i += PAIR_THREADS) {
-        ++lc;
-        if (EMIT) { const u64 v = s_v[i]; lmn = v < lmn ? v : lmn; lmx = v > lmx ? v : lmx; }
-    }
-    for (u64 g = base + tn;; g += (u64)PAIR_THREADS * PR_AHEAD) {
-        int stop = g >= a.n;
-        if (!stop) {
-#pragma unroll
-            for (int s = 0; s < PR_AHEAD; ++s) {
-                const u64 gi = g + (u64)s * PAIR_THREADS + tid;
-                if (gi >= a.n) { stop = 1; continue; }
-                const u64 k = a.keys[gi];
-                const u64 v = EMIT ? a.vals[gi] : 0;
-                if (k != key_last) { stop = 1; continue; }
-                ++lc;
-                if (EMIT) { lmn = v < lmn ? v : lmn; lmx = v > lmx ? v : lmx; }
-            }
-        }
-        if (__syncthreads_or(stop)) break;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        lc += __shfl_xor(lc, o, WAVE);
-        if (EMIT) { const u64 n1 = __shfl_xor(lmn, o, WAVE), x1 = __shfl_xor(lmx, o, WAVE); lmn = n1 < lmn ? n1 : lmn; lmx = x1 > lmx ? x1 : lmx; }
-    }
-    if (lane == 0) { s_red[wave][0] = lc; s_red[wave][1] = lmn; s_red[wave][2] = lmx; }
-    __syncthreads();
-    lc = 0; lmn = ~0ULL; lmx = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { lc += s_red[w][0]; lmn = s_red[w][1] < lmn ? s_red[w][1] : lmn; lmx = s_red[w][2] > lmx ? s_red[w][2] : lmx; }
+    RunAcc L;
+    for (u32 i = p_last + tid; i < tn; i += PAIR_THREADS) L.take<EMIT>(EMIT ? s_v[i] : 0);
+    rm_follow<PR_AHEAD>(base + tn, a.n, [&](u64 gi) {
+        const u64 k = a.keys[gi];
+        const u64 v = EMIT ? a.vals[gi] : 0;
+        if (k != key_last) return false;
+        L.take<EMIT>(v);
+        return true;
+    });
+    rm_reduce_run<EMIT>(L, s_red);
 
     // ---- run lengths, the min_shared filter ----------------------------------------------------------------------------
     u64 runlen[PR_PPT];
@@ -274,31 +251,19 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_reduce_kernel(PairReduceArg
         const u32 p = j * PAIR_THREADS + tid;
         u64 c = 0; bool real = false;
         if (head[j]) {
-            if (p == p_last) c = lc;
-            else {                                        // the next head is inside the tile
-                u32 w = p >> 6;
-                u64 m = s_head[w] & ((p & 63) == 63 ? 0ULL : (~0ULL << ((p & 63) + 1)));
-                while (m == 0) m = s_head[++w];
-                c = (w << 6) + (u32)__builtin_ctzll(m) - p;
-            }
+            c = p == (u32)p_last ? L.n : rm_next_head(s_head, p) - p;
             real = s_k[p + 1] != 0;
             if (!EMIT && !real) a.stats[PAIR_STAT_SELF] = c;
         }
         const bool keep = real && c >= a.min_shared;
         runlen[j] = keep ? c : 0;
-        const u64 km = __ballot(keep);
-        if (lane == 0) s_keep[j * 4 + wave] = km;
+        rm_publish(s_keep, j, __ballot(keep));
         if (!EMIT) nkeys += (u32)__popcll(__ballot(real));
     }
     __syncthreads();                                      // (s_red has been read by every wave)
     if (!EMIT && lane == 0) s_red[wave][0] = nkeys;
     __syncthreads();
-    if (tid < 64) {
-        const u32 v = tid < PR_WORDS ? (u32)__popcll(s_keep[tid]) : 0;
-        const u32 inc = wave_incl_scan<u32>(v);
-        if (tid < PR_WORDS) s_pre[tid] = inc - v;
-        if (tid == PR_WORDS - 1) s_pre[PR_WORDS] = inc;
-    }
+    rm_prefix<PR_WORDS>(s_keep, s_pre);
     __syncthreads();
     if (!EMIT) { if (tid == 0) { a.tile_cnt[blockIdx.x] = s_pre[PR_WORDS]; a.tile_keys[blockIdx.x] = s_red[0][0] + s_red[1][0] + s_red[2][0] + s_red[3][0]; } return; }
 
@@ -308,16 +273,11 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_reduce_kernel(PairReduceArg
         const u64 c = runlen[j];
         if (!c) continue;
         const u32 p = j * PAIR_THREADS + tid;
-        const u32 w = j * 4 + wave;
-        const u32 slot = s_pre[w] + (u32)__popcll(s_keep[w] & ((1ULL << lane) - 1));
-        u64 mn = lmn, mx = lmx;
-        if (p != p_last) {
-            mn = ~0ULL; mx = 0;
-            for (u32 q = p; q < p + (u32)c; ++q) { const u64 v = s_v[EMIT ? q : 0]; mn = v < mn ? v : mn; mx = v > mx ? v : mx; }
-        }
+        RunAcc r = L;
+        if (p != (u32)p_last) r.span(s_v, p, (u32)c);
         typedef unsigned long long v2u64r __attribute__((ext_vector_type(2)));
-        v2u64r *row = (v2u64r *)(a.rows + (obase + slot) * 4);
-        const v2u64r r0 = {s_k[p + 1], c}, r1 = {mn, mx};
+        v2u64r *row = (v2u64r *)(a.rows + (obase + rm_slot(s_keep, s_pre, j)) * 4);
+        const v2u64r r0 = {s_k[p + 1], c}, r1 = {r.mn, r.mx};
         row[0] = r0; row[1] = r1;
     }
 }

@@ -9,6 +9,7 @@ import pytest
 
 from tests import diagonal_ref as D
 from tests import oriented_ref as R
+from tests.test_gpu_pairs import sort_passes_of
 from tests.test_gpu_strands import _case, _open, _revcomp, _seqs
 
 pytestmark = pytest.mark.gpu
@@ -317,5 +318,16 @@ def test_sort_passes(H, O, clean):
     ori = r.dev.pairs(strands=r.st)
     pd = r.dev.pair_diagonals(r.st, 16)
     print("sort passes: oriented %d, diagonals %d" % (ori.info["sort_passes"], pd.info["sort_passes"]))
-    if ori.info["sort_passes"] >= 0 and pd.info["sort_passes"] >= 0:      # (-1: the sort did not say)
-        assert pd.info["sort_passes"] <= ori.info["sort_passes"] + 2
+    assert ori.info["sort_passes"] >= 0 and pd.info["sort_passes"] >= 0
+    assert pd.info["sort_passes"] <= ori.info["sort_passes"] + 2
+    # The two-word record keys by their definition (hsk_diagbin.h): word 1 the pair key, word 0 the bin less the smallest bin a record of that
+    # orientation can have under the largest position among the payload slots of the entries that have records; a pair inside one read is { 0, 0 }.
+    o, ref = r.case["o"], _ref(r.case, 16)
+    ent = np.flatnonzero(o.cnt >= 2)
+    maxpos = max(int(o.pos[int(p):int(p) + int(n)].max()) for p, n in zip(o.payoff[ent], o.cnt[ent]))
+    key, bins = ref["all_bins"][:, 0], ref["all_bins"][:, 2]
+    word0 = bins - np.where((key & TOP) != 0, 0, ((1 << 32) - maxpos) // 16).astype(np.uint64)
+    words = np.stack([word0, key], axis=1)
+    if ref["self_records"]:
+        words = np.concatenate([np.zeros((1, 2), np.uint64), words])
+    assert pd.info["sort_passes"] == sort_passes_of(words)

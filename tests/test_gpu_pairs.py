@@ -56,6 +56,30 @@ def reference(o, task_lo=0, task_hi=None, min_shared=1):
     return rows[rows[:, 1] >= np.uint64(min_shared)], records, records - int(k.size), int(uk.size)
 
 
+def distinct_keys(ref):
+    """The distinct record keys of a reference computed with min_shared = 1; a pair inside one read is a record with the key 0."""
+    rows, records, self_records, keys = ref
+    assert rows.shape[0] == keys
+    return np.concatenate([np.zeros(1 if self_records else 0, np.uint64), rows[:, 0]])
+
+
+def sort_passes_of(words, radix_bits=8):
+    """The scatter passes of the key sort, from the distinct record keys ([n] or [n, NW] uint64, word 0 first): the digits of
+    make_pass_plan(32 NW, NW, radix_bits) (hsk_passplan.h: every word from bit 0 up in digits of radix_bits bits, the last digit of a word
+    the narrower one) in which the records do not all hold the same value.  No record or one key: 0."""
+    w = np.asarray(words, np.uint64)
+    w = w.reshape(w.shape[0], -1)
+    passes = 0
+    for col in w.T:
+        lo = 0
+        while lo < 64:
+            bits = min(radix_bits, 64 - lo)
+            d = (col >> np.uint64(lo)) & np.uint64((1 << bits) - 1)
+            passes += int(d.size > 0 and bool(np.any(d != d[0])))
+            lo += bits
+    return passes
+
+
 def _check(rp, ref):
     rows, records, self_records, keys = ref
     assert rp.info["records"] == records and rp.info["self_records"] == self_records and rp.info["keys"] == keys
@@ -128,6 +152,7 @@ def test_clean_reads(H, O, clean):
     rp = dev.pairs()
     _check(rp, ref)
     assert 1 <= rp.info["sort_passes"] <= 8 and rp.info["ms_total"] > 0
+    assert rp.info["sort_passes"] == sort_passes_of(distinct_keys(ref))
     assert np.array_equal(rp.rid_a.astype(np.uint64) << np.uint64(32) | rp.rid_b.astype(np.uint64), rp.key) and np.all(rp.rid_a < rp.rid_b)
     assert np.array_equal(rp.first_pos_a.astype(np.uint64) << np.uint64(32) | rp.first_pos_b.astype(np.uint64), rp.first)
     assert np.array_equal(rp.last_pos_a.astype(np.uint64) << np.uint64(32) | rp.last_pos_b.astype(np.uint64), rp.last)
@@ -194,6 +219,7 @@ def test_high_read_ids(H, O):
     rp = _pairs(H, dna, par)
     _check(rp, ref)
     assert int(rp.rid_a.min()) >= 2_000_000_000
+    assert rp.info["sort_passes"] == sort_passes_of(distinct_keys(ref))
 
 
 def test_task_ranges_combine(H, O, clean):

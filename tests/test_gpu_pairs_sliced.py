@@ -5,7 +5,7 @@ is integer work and compared exactly, whatever the budget."""
 import numpy as np
 import pytest
 
-from tests.test_gpu_pairs import _case, _check, reference
+from tests.test_gpu_pairs import U32, _case, _check, _triu, reference, sort_passes_of
 
 pytestmark = pytest.mark.gpu
 
@@ -48,9 +48,43 @@ def _open(H, par, tuning=None):
     return H.Context(K=par["K"], M=par["M"], L=par["L"], U=par["U"], EXT=1, ntasks=par["ntasks"], keep_device=True, tuning=tuning)
 
 
-def _check_sliced(rp, ref, m, largest):
+def entry_records(o, strand=None):
+    """The record keys of the whole range in the order of the expansion, entry by entry (a pair inside one read is the key 0; with the strand of
+    every payload slot, bit 63 is the relative strand), and the record offset of every entry that has records, the total last."""
+    rid = o.rid.astype(np.int64).astype(np.uint64) & U32
+    sb = None if strand is None else strand.astype(np.uint64)
+    ks, off = [np.zeros(0, np.uint64)], [0]
+    for e in np.flatnonzero(o.cnt >= 2):
+        i, j = _triu(int(o.cnt[e]))
+        si, sj = int(o.payoff[e]) + i, int(o.payoff[e]) + j
+        ra, rb = np.minimum(rid[si], rid[sj]), np.maximum(rid[si], rid[sj])
+        k = (ra << np.uint64(32)) | rb
+        if sb is not None:
+            k |= (sb[si] ^ sb[sj]) << np.uint64(63)
+        ks.append(np.where(ra == rb, np.uint64(0), k)); off.append(off[-1] + i.size)
+    return np.concatenate(ks), np.array(off, np.int64)
+
+
+def slice_plan(recs, budget):
+    """(slices that hold records, the most scatter passes any slice's sort takes) under the planner's rule (hsk_pairplan.h): a slice takes
+    entries while its records stay within the budget, and an entry above the budget is a slice of its own.  Entries without records join
+    a neighbour and change no record set."""
+    keys, off = recs
+    slices, passes, a = 0, 0, 0
+    while a + 1 < off.size:
+        b = max(int(np.searchsorted(off, off[a] + budget, side="right")) - 1, a + 1)
+        slices += 1; passes = max(passes, sort_passes_of(keys[off[a]:off[b]]))
+        a = b
+    return slices, passes
+
+
+def _check_sliced(rp, ref, m, largest, recs=None):
+    """recs: entry_records() of the range.  sort_passes is the most over the slices' sorts, each over the records of its cut."""
     _check(rp, ref)                                       # rows, n, records, self_records, keys
     records, info = ref[1], rp.info
+    budget = m if m >= 1 else (records if info["slices"] == 1 else None)      # (m = 0: the library's choice, known only where it took everything)
+    if recs is not None and budget is not None:
+        assert (info["slices"], info["sort_passes"]) == slice_plan(recs, budget), (m, info)
     if m >= 1:
         assert (info["slices"] == 1) == (m >= records), (m, info)
         assert info["peak_records"] <= max(m, largest), (m, info)
@@ -68,23 +102,23 @@ def test_every_budget_gives_the_list(H, O, name):
     sparse: the cuts fall into long runs of entries without records."""
     dna, par, o = _case(H, O, name)
     ref = _ref(o, name)
-    records, largest = ref[1], _largest_entry(o)
+    records, largest, recs = ref[1], _largest_entry(o), entry_records(o)
     assert records > 1000 and largest < records
     with _open(H, par) as c:
         with c.count_resident(dna, rid_base=par["rid_base"]) as dev:
             for m in (_prime_near(records / 7), records - 1, records, 10 * records, 0):
                 rp = dev.pairs(max_records=m)
-                _check_sliced(rp, ref, m, largest)
+                _check_sliced(rp, ref, m, largest, recs)
                 if m == records - 1:
                     assert rp.info["slices"] == 2
             if name == "wide_entry":                     # budgets below one entry: every entry is a slice of its own
                 for m in (1, 44849, 44850, 2 * 44850 - 1):
                     rp = dev.pairs(max_records=m)
-                    _check_sliced(rp, ref, m, largest)
+                    _check_sliced(rp, ref, m, largest, recs)
                     assert rp.info["slices"] == 30 and rp.info["peak_records"] == 44850
                 # two entries per slice: 15 lists of the same 44 850 keys, 14 merges of two such lists each
                 rp = dev.pairs(max_records=2 * 44850)
-                _check_sliced(rp, ref, 2 * 44850, largest)
+                _check_sliced(rp, ref, 2 * 44850, largest, recs)
                 assert rp.info["slices"] == 15 and rp.info["peak_records"] == 2 * 44850
                 assert rp.info["merges"] == 14 and rp.info["merged_rows"] == 14 * 2 * 44850
 
@@ -96,7 +130,7 @@ def test_one_record_at_a_time_short_reads(H, O):
     with _open(H, par) as c:
         with c.count_resident(dna, rid_base=par["rid_base"]) as dev:
             rp = dev.pairs(max_records=1)
-            _check_sliced(rp, ref, 1, _largest_entry(o))
+            _check_sliced(rp, ref, 1, _largest_entry(o), entry_records(o))
             assert rp.info["slices"] == int((o.cnt >= 2).sum())
 
 
@@ -113,7 +147,7 @@ def test_one_record_at_a_time_few_reads(H, O):
         with c.count_resident(dna, rid_base=par["rid_base"]) as dev:
             for m in (1, 2, 3):
                 rp = dev.pairs(max_records=m)
-                _check_sliced(rp, ref, m, _largest_entry(o))
+                _check_sliced(rp, ref, m, _largest_entry(o), entry_records(o))
             assert dev.pairs(max_records=1).info["slices"] == int((o.cnt >= 2).sum())
 
 

@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 
 from tests import oriented_ref as R
+from tests.test_gpu_pairs import distinct_keys, sort_passes_of
+from tests.test_gpu_pairs_sliced import entry_records, slice_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -297,9 +299,12 @@ def test_sliced_equals_unsliced(H, O):
                 one = dev.pairs(strands=st)
                 _check_rows(one, ref)
                 assert one.info["slices"] == 1 and one.info["records"] > 1000
+                assert one.info["sort_passes"] == sort_passes_of(distinct_keys(ref))
+                recs = entry_records(case["o"], case["strand"])
                 for m in (one.info["records"] // 7, 1):
                     rp = dev.pairs(strands=st, max_records=m)
                     _check_rows(rp, ref)
+                    assert (rp.info["slices"], rp.info["sort_passes"]) == slice_plan(recs, m)
                     assert rp.info["slices"] > 1 and np.array_equal(rp.rows(), one.rows())
 
 
