@@ -156,16 +156,6 @@ struct Comm {
     template <typename Pool> int allreduce_max_u64(uint64_t *h, size_t n, hipStream_t s, Pool &p) { return allreduce_u64(h, n, RCCL_MAX, s, p); }
 };
 
-struct ExchangeBuffers {
-    uint8_t *len = nullptr; uint8_t *bytes = nullptr; uint32_t *pos = nullptr; int32_t *rid = nullptr; uint64_t nbytes = 0;
-    unsigned short *sub16 = nullptr;      // the supermers' top 16 minimizer bits (combining extraction on the owner's side), beside len
-    template <typename Pool> void release(Pool &pool)
-    {
-        pool.release(len); pool.release(bytes); pool.release(pos); pool.release(rid); pool.release(sub16);
-        len = bytes = nullptr; pos = nullptr; rid = nullptr; sub16 = nullptr;
-    }
-};
-
 // Host-side plan of the all-to-all-v (pure arithmetic; also used by the CPU multi-rank tests
 // through hsk_plan_exchange): given the full size matrix M[src][task] = {supermers, bytes, kmers}
 // and the owner table, computes what `rank` sends to / receives from every peer and where the
@@ -174,6 +164,25 @@ struct ExchangePlan {
     std::vector<uint64_t> send_sup, send_bytes, send_sup_off, send_byte_off;   // per peer
     std::vector<uint64_t> recv_sup, recv_bytes, recv_sup_off, recv_byte_off;   // per peer
     uint64_t recv_tot_sup = 0, recv_tot_bytes = 0;
+};
+
+// the receive arrays of one plan
+struct ExchangeBuffers {
+    uint8_t *len = nullptr; uint8_t *bytes = nullptr; uint32_t *pos = nullptr; int32_t *rid = nullptr; uint64_t nbytes = 0;
+    unsigned short *sub16 = nullptr;      // the supermers' top 16 minimizer bits (combining extraction on the owner's side), beside len
+    // pos / rid with payloads only, sub16 only where asked for; false: the pool is out of memory (what it did hand out stays here for release)
+    template <typename Pool> bool alloc(Pool &pool, const ExchangePlan &pl, bool ext, bool with_sub = false)
+    {
+        len = (uint8_t *)pool.alloc(pl.recv_tot_sup + 64); bytes = (uint8_t *)pool.alloc(pl.recv_tot_bytes + 64); nbytes = pl.recv_tot_bytes;
+        if (ext) { pos = (uint32_t *)pool.alloc(pl.recv_tot_sup * 4 + 64); rid = (int32_t *)pool.alloc(pl.recv_tot_sup * 4 + 64); }
+        if (with_sub) sub16 = (unsigned short *)pool.alloc(pl.recv_tot_sup * 2 + 64);
+        return len && bytes && (!ext || (pos && rid)) && (!with_sub || sub16);
+    }
+    template <typename Pool> void release(Pool &pool)
+    {
+        pool.release(len); pool.release(bytes); pool.release(pos); pool.release(rid); pool.release(sub16);
+        len = bytes = nullptr; pos = nullptr; rid = nullptr; sub16 = nullptr;
+    }
 };
 
 // group_of / g: restrict the plan to the tasks t with (*group_of)[t] == g (the exchange proceeds in groups of
@@ -312,11 +321,8 @@ inline int exchange_supermers(Comm &cm, hipStream_t s, Pool &pool, bool ext, int
     if (rc) { if (rc > 0) cm.last_error = "a rank failed before the supermer exchange"; return rc; }
     ExchangePlan pl;
     plan_exchange(nr, me, ntasks, owner, order, M, task_base, pl, segs);
-    xb.len = (uint8_t *)pool.alloc(pl.recv_tot_sup + 64);
-    xb.bytes = (uint8_t *)pool.alloc(pl.recv_tot_bytes + 64); xb.nbytes = pl.recv_tot_bytes;
-    if (ext) { xb.pos = (uint32_t *)pool.alloc(pl.recv_tot_sup * 4 + 64); xb.rid = (int32_t *)pool.alloc(pl.recv_tot_sup * 4 + 64); }
     {   // every rank must have its receive arrays before anybody sends
-        const bool oom = !xb.len || !xb.bytes || (ext && (!xb.pos || !xb.rid));
+        const bool oom = !xb.alloc(pool, pl, ext);
         std::vector<uint64_t> none;
         rc = cm.allreduce_with_status(none, RCCL_MAX, oom, s, pool);
         if (oom) { cm.last_error = "oom"; return -1; }

@@ -15,15 +15,33 @@ static u32 certain_drop_mask(hsk_ctx *c);                                       
 
 struct TaskInput { const u8 *len; BaseSource src; const u32 *pos; const int32_t *rid; const unsigned short *sub16 = nullptr; };
 
-// HSK_TEST_FAIL="<rank>:<site>" (tests/test_gpu_rccl.py, read at every call): the named step of that rank fails as if an
-// allocation had returned null.  Sites: sortbuf (before the first task group travels), group1 (the exchange buffers of the
-// second group: peers are already inside the exchange), late (the second batch: everything is in flight).
+// HSK_TEST_FAIL="<rank>:<site>" (tests/test_gpu_rccl.py, read at every call): the named step of that rank fails as if an allocation had returned null.
+// Sites: sortbuf (before the first task group travels), group1 (the exchange buffers of the second group: peers are already inside the exchange), late
+// (the second batch: everything is in flight); and, in front of the status-carrying all-reduces before the exchange: parse (parse_count's result, several
+// ranks only), place (parse_place's result), heavy (heavy_preaggregate's result), heavybuf (the owner's receive buffers of the heavy lists).
 static bool test_fail(hsk_ctx *c, const char *site)
 {
     const char *e = getenv("HSK_TEST_FAIL");
     if (!e || !*e) return false;
     const char *colon = strchr(e, ':');
     return colon && atoi(e) == c->comm.rank && strcmp(colon + 1, site) == 0;
+}
+
+// virtual ranks: the share that rank `src` sends to rank `dst` under their plans sp and p, from src's store into dst's receive arrays, by device copies
+static int copy_share(hsk_ctx *c, const SupermerStore &ss, const ExchangePlan &sp, int src, const ExchangeBuffers &b, const ExchangePlan &p, int dst, bool ext, bool with_sub, hipStream_t s, int g = -1)
+{
+    const u64 n = sp.send_sup[dst], nb = sp.send_bytes[dst];
+    if (n != p.recv_sup[src] || nb != p.recv_bytes[src])
+        return g < 0 ? fail(c, HSK_ERR_INTERNAL, "exchange plan mismatch %d->%d", src, dst) : fail(c, HSK_ERR_INTERNAL, "exchange plan mismatch %d->%d (group %d)", src, dst, g);
+    if (!n) return HSK_OK;
+    HIPCHK(c, hipMemcpyAsync(b.len + p.recv_sup_off[src], ss.sm_len + sp.send_sup_off[dst], n, hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(b.bytes + p.recv_byte_off[src], ss.sm_bytes + sp.send_byte_off[dst], nb, hipMemcpyDeviceToDevice, s));
+    if (with_sub) HIPCHK(c, hipMemcpyAsync(b.sub16 + p.recv_sup_off[src], ss.sm_sub16 + sp.send_sup_off[dst], n * 2, hipMemcpyDeviceToDevice, s));
+    if (ext) {
+        HIPCHK(c, hipMemcpyAsync(b.pos + p.recv_sup_off[src], ss.sm_pos + sp.send_sup_off[dst], n * 4, hipMemcpyDeviceToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(b.rid + p.recv_sup_off[src], ss.sm_rid + sp.send_sup_off[dst], n * 4, hipMemcpyDeviceToDevice, s));
+    }
+    return HSK_OK;
 }
 
 struct GroupFeeder {
@@ -59,10 +77,7 @@ struct GroupFeeder {
     {
         ExchangeBuffers &b = xb[g]; const ExchangePlan &p = pl[g];
         if (g == 1 && !draining && test_fail(c, "group1")) return fail(c, HSK_ERR_OOM, "exchange buffers of group %d (injected)", g);
-        b.len = (u8 *)c->pool.alloc(p.recv_tot_sup + 64); b.bytes = (u8 *)c->pool.alloc(p.recv_tot_bytes + 64); b.nbytes = p.recv_tot_bytes;
-        if (ext) { b.pos = (u32 *)c->pool.alloc(p.recv_tot_sup * 4 + 64); b.rid = (int32_t *)c->pool.alloc(p.recv_tot_sup * 4 + 64); }
-        if (with_sub) b.sub16 = (unsigned short *)c->pool.alloc(p.recv_tot_sup * 2 + 64);
-        if (!b.len || !b.bytes || (ext && (!b.pos || !b.rid)) || (with_sub && !b.sub16)) return fail(c, HSK_ERR_OOM, "exchange buffers of group %d", g);
+        if (!b.alloc(c->pool, p, ext, with_sub)) return fail(c, HSK_ERR_OOM, "exchange buffers of group %d", g);
         // the bytes this group sends are packed now, on the communication stream (RCCL: this rank's store; virtual ranks:
         // the store of every source that has not produced group g yet)
         std::vector<SupermerStore *> to_pack;
@@ -84,19 +99,7 @@ struct GroupFeeder {
         hipStream_t s = c->comm_stream;
         for (size_t i = 0; i < to_pack.size(); ++i) { int rc = pack_group_launch(c, *to_pack[i], packs[g][i], s); if (rc) return rc; to_pack[i]->group_packed[g] = 1; }
         if (st_all) {
-            for (int src = 0; src < nranks; ++src) {
-                const ExchangePlan &sp = (*pl_all)[src][g]; const SupermerStore &ss = (*st_all)[src];
-                const u64 n = sp.send_sup[rank], nb = sp.send_bytes[rank];
-                if (n != p.recv_sup[src] || nb != p.recv_bytes[src]) return fail(c, HSK_ERR_INTERNAL, "exchange plan mismatch %d->%d (group %d)", src, rank, g);
-                if (!n) continue;
-                HIPCHK(c, hipMemcpyAsync(b.len + p.recv_sup_off[src], ss.sm_len + sp.send_sup_off[rank], n, hipMemcpyDeviceToDevice, s));
-                HIPCHK(c, hipMemcpyAsync(b.bytes + p.recv_byte_off[src], ss.sm_bytes + sp.send_byte_off[rank], nb, hipMemcpyDeviceToDevice, s));
-                if (with_sub) HIPCHK(c, hipMemcpyAsync(b.sub16 + p.recv_sup_off[src], ss.sm_sub16 + sp.send_sup_off[rank], n * 2, hipMemcpyDeviceToDevice, s));
-                if (ext) {
-                    HIPCHK(c, hipMemcpyAsync(b.pos + p.recv_sup_off[src], ss.sm_pos + sp.send_sup_off[rank], n * 4, hipMemcpyDeviceToDevice, s));
-                    HIPCHK(c, hipMemcpyAsync(b.rid + p.recv_sup_off[src], ss.sm_rid + sp.send_sup_off[rank], n * 4, hipMemcpyDeviceToDevice, s));
-                }
-            }
+            for (int src = 0; src < nranks; ++src) { int rc = copy_share(c, (*st_all)[src], (*pl_all)[src][g], src, b, p, rank, ext, with_sub, s, g); if (rc) return rc; }
         } else {
             int rc = post_exchange(c->comm, s, ext, p, st->sm_len, st->sm_bytes, st->sm_pos, st->sm_rid, b, with_sub ? st->sm_sub16 : nullptr);
             if (rc) return fail(c, HSK_ERR_COMM, "supermer exchange (group %d) failed: %d (%s)", g, rc, c->comm.last_error.c_str());
@@ -117,18 +120,20 @@ struct GroupFeeder {
     // the main stream has launched its last reader of every group below g
     void release_below(int g)
     {
-        for (; released < g && released < posted; ++released) {
-            xb[released].release(c->pool);         // next user is ordered after the readers by post()'s fence (or is on the main stream)
-            for (auto &pj : packs[released]) expand_release(c, pj.x);
-            packs[released].clear();
-            if (arrived[released]) { ev_put(c, arrived[released]); arrived[released] = nullptr; }
-        }
+        for (; released < g && released < posted; ++released) drop_group(released);      // next user is ordered after the readers by post()'s fence (or is on the main stream)
+    }
+    void drop_group(int g)
+    {
+        xb[g].release(c->pool);
+        for (auto &pj : packs[g]) expand_release(c, pj.x);
+        packs[g].clear();
+        if (arrived[g]) { ev_put(c, arrived[g]); arrived[g] = nullptr; }
     }
     // This rank's count has failed after the exchange began (RCCL only).  Its peers still expect its supermers and still send
     // it theirs: a rank that simply returned would leave them blocked in ncclRecv for ever (the reference dies together there:
     // MPI_Abort, src/kmerops.cpp:1477).  So the rank drains its own work, hands every device block the failed count allocated
     // (since `mark`: the supermer store stays) back to the pool -- a failed allocation is the usual reason to be here -- and posts
-    // the remaining groups one by one, receiving into buffers it drops at once.  The ranks then agree on the outcome (run_pipeline)
+    // the remaining groups one by one, receiving into buffers it drops at once.  The ranks then agree on the outcome (agree_on_outcome)
     // and all return an error.
     bool draining = false;
     int drain_after_failure(unsigned long long mark)
@@ -142,10 +147,7 @@ struct GroupFeeder {
             const int g = posted;
             int rc = post(g); if (rc) return rc;
             HIPCHK(c, hipStreamSynchronize(c->comm_stream));
-            xb[g].release(c->pool);
-            for (auto &pj : packs[g]) expand_release(c, pj.x);
-            packs[g].clear();
-            if (arrived[g]) { ev_put(c, arrived[g]); arrived[g] = nullptr; }
+            drop_group(g);
             released = g + 1;
         }
         return HSK_OK;
@@ -166,10 +168,7 @@ struct GroupFeeder {
     }
 };
 
-static bool overlap_enabled()
-{
-    return tune("overlap", 1) != 0;
-}
+static bool overlap_enabled() { return tune("overlap", 1) != 0; }
 
 // ---- heavy-hitter tasks (a8): the owner's side --------------------------------------------------------------
 // d_entries: the {k-mer, count} lists of all ranks for one task, concatenated (n entries, each list key-ordered,
@@ -194,6 +193,7 @@ static int heavy_merge_task(hsk_ctx *c, const u64 *d_entries, u64 n, u64 *d_hist
 }
 
 struct HeavyIn { u32 task; u64 *d_entries; u64 n; };       // a heavy task this rank owns: concatenated lists of all ranks
+static void free_heavy_in(hsk_ctx *c, std::vector<HeavyIn> &hin) { for (auto &h : hin) c->pool.release(h.d_entries); hin.clear(); }
 struct ProcExtra {
     bool force_batch = false;                              // every task through the batch kernels (partial batches padded)
     const std::vector<HeavyIn> *heavy_in = nullptr;        // merged and filtered here (they have no supermers)
@@ -698,59 +698,102 @@ static bool combine_allowed(const hsk_ctx *c, int nranks, u64 bytes)
            (nranks == 1 || (overlap_enabled() && place_bytes_enabled(true)));
 }
 static ResultPriv *begin_result(hsk_result *out, int nw) { memset(out, 0, sizeof *out); ResultPriv *rp = new ResultPriv(); out->priv = rp; out->nw = nw; return rp; }
-// the k-mers of the input that did not arrive as supermers: the instances the scan left out, and the heavy tasks this rank owns (they arrived as lists)
-static void add_unsent_kmers(hsk_ctx *c, hsk_result *out, u64 dropped, const std::vector<u8> &is_heavy, const std::vector<u64> &heavy_kmers, const std::vector<int32_t> &owner, int rank)
-{
-    out->total_kmers += dropped; c->stats.dropped_kmers += (int64_t)dropped;
-    for (size_t t = 0; t < is_heavy.size(); ++t) if (is_heavy[t] && owner[t] == rank) out->total_kmers += heavy_kmers[t];
-}
 // virtual ranks: a rank's parse was timed on its own, its total is the sum of its phases
 static void sum_phases(hsk_result &o, double ms_parse) { o.ms_parse = ms_parse; o.ms_total = o.ms_parse + o.ms_exchange + o.ms_extract + o.ms_sort + o.ms_count + o.ms_d2h; }
+
+// ---- steps both drivers take (run_pipeline: one GPU or one rank over RCCL; run_loopback: virtual ranks) ------------------------------
+struct CallInput { const u8 *d_packed; u64 packed_bytes; const u64 *d_roff; const u32 *d_rlen; u64 nreads; int64_t rid_base; };      // one rank's reads, in HBM
+static std::vector<u32> identity_order(u32 n) { std::vector<u32> o(n); for (u32 i = 0; i < n; ++i) o[i] = i; return o; }
+
+// Where the supermers of every task (`only`: of these alone) live in a store that is read in place: one segment per task from the store's totals and bases.
+// vt_shift: the store's tasks are virtual ones, 2^vt_shift per task; a task's segments are those of its virtual tasks (which one: ExpSeg::byte_off, unused in item mode).
+static void segs_from_store(const SupermerStore &st, u32 ntasks, u32 vt_shift, const std::vector<u8> *only, std::vector<TaskSegs> &segs)
+{
+    for (u32 v = 0; v < (ntasks << vt_shift); ++v) {
+        const u32 t = v >> vt_shift;
+        if (only && !(*only)[t]) continue;
+        segs[t].nkmers += st.task_tot[3 * v + 2];
+        if (st.task_tot[3 * v] == 0) continue;
+        ExpSeg sg; sg.sup_off = st.task_base[3 * v]; sg.n_sup = st.task_tot[3 * v]; sg.kmer_off = 0; sg.tile_start = 0;
+        sg.byte_off = vt_shift ? v & ((1u << vt_shift) - 1u) : st.task_base[3 * v + 1];
+        segs[t].segs.push_back(sg);
+    }
+}
 
 // ---- heavy-hitter tasks (a8): the sending side ----------------------------------------------------------------
 // HeavyHitterClassifier (reference src/kmerops.cpp:1157-1199) on the GLOBAL k-mer counts, for every key width (the
 // reference's ScatteredKmerList is generic over TKmer, kmerops.cpp:363-401); forced plain with EXTENSION or
 // PLAIN_CLASSIFIER (kmerops.cpp:109-113).
-static bool heavy_enabled(hsk_ctx *c, int nranks)
+static bool heavy_enabled(hsk_ctx *c, int nranks) { return nranks > 1 && c->cfg.extension == 0 && (c->cfg.flags & HSK_FLAG_PLAIN_CLASSIFIER) == 0; }
+struct HeavySet {
+    std::vector<u8> is_heavy; bool any = false;
+    std::vector<u64> kmers;                              // k-mer instances of a heavy task over all ranks (they travel as lists: its owner counts them into total_kmers)
+    explicit HeavySet(u32 ntasks) : is_heavy(ntasks, 0), kmers(ntasks, 0) {}
+    void classify(const hsk_ctx *c, const std::vector<u64> &kg)      // kg[t]: the k-mer instances of task t over all ranks
+    {
+        std::vector<int32_t> types(kg.size(), 0);
+        plan_classify(kg.data(), (int)kg.size(), c->cfg.unbalanced_ratio, types.data());
+        for (size_t t = 0; t < kg.size(); ++t) if (types[t] == 1) { is_heavy[t] = 1; any = true; kmers[t] = kg[t]; }
+    }
+    // After the pre-aggregation.  bad[t]: some rank could not aggregate task t -- it travels as supermers after all, on every rank.  The others stay
+    // heavy, and what they weigh in the dispatch (bytes[t]) is the size of their lists.  lists[0 .. nlists): [task] lists of the ranks this process holds.
+    void settle(hsk_ctx *c, const std::vector<u64> &bad, std::vector<TaskOut> *lists, int nlists, u64 entry_bytes, std::vector<u64> &bytes)
+    {
+        any = false;
+        for (size_t t = 0; t < is_heavy.size(); ++t) {
+            if (!is_heavy[t]) continue;
+            if (bad[t]) { is_heavy[t] = 0; for (int r = 0; r < nlists; ++r) free_task_out(c, lists[r][t]); continue; }
+            any = true; c->stats.heavy_tasks++; bytes[t] = 0;
+            for (int r = 0; r < nlists; ++r) bytes[t] += lists[r][t].n * entry_bytes;                   // ScatteredKmerList::get_size_bytes
+        }
+    }
+};
+// An owner's buffer of a heavy task: the ranks' lists in rank order.  n[p * stride]: entries of rank p's list; -> where it begins (p == nranks: the total)
+static u64 heavy_list_off(const u64 *n, size_t stride, int p) { u64 o = 0; for (int q = 0; q < p; ++q) o += n[(size_t)q * stride]; return o; }
+
+// the k-mers of the input that did not arrive as supermers: the instances the scan left out, and the heavy tasks this rank owns (they arrived as lists)
+static void add_unsent_kmers(hsk_ctx *c, hsk_result *out, u64 dropped, const HeavySet &hv, const std::vector<int32_t> &owner, int rank)
 {
-    return nranks > 1 && c->cfg.extension == 0 && (c->cfg.flags & HSK_FLAG_PLAIN_CLASSIFIER) == 0;
+    out->total_kmers += dropped; c->stats.dropped_kmers += (int64_t)dropped;
+    for (size_t t = 0; t < hv.is_heavy.size(); ++t) if (hv.is_heavy[t] && owner[t] == rank) out->total_kmers += hv.kmers[t];
+}
+
+// the dispatcher on the global task sizes; `order`: the storage order of a rank's supermers, tasks grouped by owner
+static int dispatch_owners(hsk_ctx *c, const std::vector<u64> &bytes, int nranks, std::vector<int32_t> &owner, std::vector<u32> &order)
+{
+    if (plan_dispatch(bytes.data(), (int)bytes.size(), nranks, c->cfg.plain_dispatcher != 0, c->cfg.dispatch_upper_coe, c->cfg.dispatch_step, owner.data()))
+        return fail(c, HSK_ERR_DISPATCH, "%s", hsk_strerror(HSK_ERR_DISPATCH));      // (same input on every rank: all of them fail here; a failed call's blocks go back with its scope: ApiCall)
+    std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) { return owner[x] < owner[y]; });
+    return HSK_OK;
 }
 
 // Every rank turns its OWN supermers of the heavy tasks into unfiltered {k-mer, count} lists (ScatteredKmerList,
 // kmerops.cpp:363-398): only the heavy tasks are placed, then the ordinary expand / sort / aggregate kernels run with
-// L = 1, U = max.  lists[t] stays in HBM; failed[t] = the aggregating finish could not handle the task (it is then
+// L = 1, U = max.  lists[t] stays in HBM; bad[t] is set where the aggregating finish could not handle the task (it is then
 // sent as supermers like any other task -- on every rank, the flags are combined by the caller).
 template <int NW>
-static int heavy_preaggregate(hsk_ctx *c, ParseJob &job, const u8 *d_packed, u64 packed_bytes, const std::vector<u8> &is_heavy,
-                              std::vector<TaskOut> &lists, std::vector<u8> &failed)
+static int heavy_preaggregate(hsk_ctx *c, ParseJob &job, const u8 *d_packed, u64 packed_bytes, const std::vector<u8> &is_heavy, std::vector<TaskOut> &lists, std::vector<u64> &bad)
 {
     const u32 ntasks = job.ntasks;
-    lists.assign(ntasks, TaskOut()); failed.assign(ntasks, 0);
+    lists.assign(ntasks, TaskOut());
     std::vector<u32> order; std::vector<u8> skip(ntasks, 0);
     for (u32 t = 0; t < ntasks; ++t) if (is_heavy[t]) order.push_back(t);
     for (u32 t = 0; t < ntasks; ++t) if (!is_heavy[t]) { order.push_back(t); skip[t] = 1; }
     SupermerStore sth;
     int rc = parse_place(c, job, order, sth, &skip); if (rc) return rc;
     std::vector<TaskSegs> segs(ntasks);
-    std::vector<int32_t> own(ntasks, -1);
-    for (u32 t = 0; t < ntasks; ++t) {
-        if (!is_heavy[t]) continue;
-        own[t] = 0;
-        if (sth.task_tot[3 * t] == 0) continue;
-        ExpSeg sg; sg.sup_off = sth.task_base[3 * t]; sg.n_sup = sth.task_tot[3 * t]; sg.byte_off = sth.task_base[3 * t + 1]; sg.kmer_off = 0; sg.tile_start = 0;
-        segs[t].segs.push_back(sg); segs[t].nkmers = sth.task_tot[3 * t + 2];
-    }
+    std::vector<int32_t> own(ntasks, -1); for (u32 t = 0; t < ntasks; ++t) if (is_heavy[t]) own[t] = 0;
+    segs_from_store(sth, ntasks, 0, &is_heavy, segs);
     const hsk_config keep = c->cfg;
     c->cfg.lower_freq = 1; c->cfg.upper_freq = INT32_MAX; c->cfg.flags |= HSK_FLAG_KEEP_DEVICE;
     c->forbid_long_way = true;
-    hsk_result tmp; memset(&tmp, 0, sizeof tmp);
-    ResultPriv *rp = new ResultPriv(); tmp.priv = rp; tmp.nw = NW;
+    hsk_result tmp; ResultPriv *rp = begin_result(&tmp, NW);
     PhaseTimer pt(c);
     ProcExtra ex; ex.force_batch = true;
     rc = process_rank<NW>(c, ntasks, own, 0, segs, sth.sm_len, source_from_store(sth, d_packed, packed_bytes), nullptr, nullptr, &tmp, rp, pt, false, nullptr, &ex);
     c->cfg = keep; c->forbid_long_way = false;
     if (rc == HSK_OK) {
-        for (u32 t = 0; t < ntasks; ++t) if (is_heavy[t] && t < rp->dev_tasks.size()) { lists[t] = rp->dev_tasks[t]; failed[t] = lists[t].failed ? 1 : 0; }
+        for (u32 t = 0; t < ntasks; ++t) if (is_heavy[t] && t < rp->dev_tasks.size()) { lists[t] = rp->dev_tasks[t]; if (lists[t].failed) bad[t] = 1; }
         rp->dev_tasks.clear();                              // the lists are ours now
     }
     hsk_result_free(c, &tmp);
@@ -758,15 +801,12 @@ static int heavy_preaggregate(hsk_ctx *c, ParseJob &job, const u8 *d_packed, u64
     return rc;
 }
 
+// ---- the steps of run_pipeline ------------------------------------------------------------------------------------------------------
+// The plan of the call, in hsk_ctx::call (read by the parse and by process_rank): the context's periodic second looks, the combining extraction or
+// not, the task count, the virtual-task shift, the certain drops.  Several ranks agree on all of it in one all-reduce.
 template <int NW>
-static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u64 *d_roff, const u32 *d_rlen, u64 nreads,
-                        int64_t rid_base, hsk_result *out)
+static int plan_call(hsk_ctx *c, int nranks, u64 packed_bytes, u32 &ntasks)
 {
-    const bool ext = c->cfg.extension != 0;
-    const int K = c->cfg.kmer_size;
-    const int nranks = c->comm.active() ? c->comm.nranks : 1;
-    const int rank = c->comm.active() ? c->comm.rank : 0;
-    ResultPriv *rp = begin_result(out, NW);
     if ((c->agg_off || c->agg_off_wide) && ++c->agg_off_calls >= 8) { c->agg_off = c->agg_off_wide = false; c->agg_off_calls = 0; }      // (another look every eighth call: the input may have changed)
     if (c->combine_off && ++c->combine_off_calls >= c->combine_off_period) { c->combine_off = false; c->combine_off_calls = 0; c->combine_prefix_floor = 0; }      // (another look: the bin width starts from the default again as well)
     if (c->call.est.valid && c->agg_off && c->call.plan_attempt == 0) { c->agg_off = false; c->agg_off_calls = 0; }      // (process_rank decides again, from the estimate and the task sizes)
@@ -775,10 +815,7 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
     // the combining extraction wants buckets of ~12 k k-mers: the parse itself splits every task by the top minimizer bits (virtual
     // tasks, up to 16 per task and HSK_MAX_TASKS in all: ParseArgs::vt_shift), the bucket order does the rest (hsk_combine.h)
     c->call.vt_shift = 0;
-    PhaseTimer pt(c);
-    pt.begin(PH_TOTAL);
-
-    u32 ntasks = c->cfg.ntasks ? (u32)c->cfg.ntasks : auto_ntasks(c, packed_bytes, nranks);
+    ntasks = c->cfg.ntasks ? (u32)c->cfg.ntasks : auto_ntasks(c, packed_bytes, nranks);
     if (c->comm.active()) {
         // every rank must use the same task count (the maximum of the local proposals) and the same plan (the combining extraction only if
         // every rank's own estimate says its input pays for it: the minimizer bits either travel from all ranks or from none)
@@ -789,7 +826,6 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
         if (v[1]) c->call.combine_now = false;
         c->call.drop_mask_now = (v[2] ? 1u : 0u) | (v[3] ? 2u : 0u);
     }
-    out->ntasks = (int32_t)ntasks;
     // (at most 768 virtual tasks: the item placement's LDS holds 16 bytes for each beside its 16384 records; more real tasks than that: the instance path)
     if (ntasks > 768 && nranks == 1) c->call.combine_now = false;
     if (c->call.combine_now && nranks == 1) { u32 sh = 0; while (sh < 4 && ((u64)ntasks << (sh + 1)) <= 768) ++sh; c->call.vt_shift = sh; }
@@ -801,223 +837,229 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
         if (per_bucket > (double)combine_bucket_kmers() && c->call.est.distinct_per_kmer * per_bucket > 1400.0) { c->call.combine_now = false; c->call.vt_shift = 0; }
     }
     c->call.item_mode_now = c->call.combine_now && nranks == 1;      // one GPU: the store holds items (several ranks: byte runs + minimizer bits, the owners build the items)
+    return HSK_OK;
+}
+
+// One GPU, reads arriving from pinned host memory, no payload: ingest, scan and placement as one pipeline over slabs.  done = false: not this
+// call's way, or the pipeline fell back with the packed reads in HBM -- the two-step parse takes it from there.
+static int parse_pipelined(hsk_ctx *c, const CallInput &in, int nranks, u32 ntasks, SupermerStore &st, std::vector<TaskSegs> &segs, bool &done)
+{
     const u32 vts = c->call.vt_shift, nvt = ntasks << vts;       // what the parse calls tasks
-    std::vector<int32_t> owner(ntasks, 0);
-    std::vector<u32> order(ntasks);
-    for (u32 t = 0; t < ntasks; ++t) order[t] = t;
+    const bool pipe_enabled = tune("ingest_pipeline", 1) != 0;
+    done = false;
+    if (nranks != 1 || c->cfg.extension || !c->call.h2d_src || !pipe_enabled || !parse_fast_enabled() || c->cfg.minimizer_size > SCAN_MAX_M) return HSK_OK;
+    const u8 *src = c->call.h2d_src; c->call.h2d_src = nullptr;
+    std::vector<TaskSegs> segs_v;
+    const int prc = parse_ingest_pipelined(c, src, in.d_packed, in.packed_bytes, in.d_roff, in.d_rlen, in.nreads, in.rid_base, nvt, st, vts ? segs_v : segs);
+    if (prc == HSK_OK) {
+        done = true;
+        for (u32 v = 0; v < (u32)segs_v.size(); ++v) {          // a task's segments: those of its virtual tasks, as in segs_from_store (the ingest hands back one per slab)
+            TaskSegs &ts = segs[v >> vts];
+            for (ExpSeg sg : segs_v[v].segs) { sg.byte_off = v & ((1u << vts) - 1u); sg.kmer_off = 0; ts.segs.push_back(sg); }
+            ts.nkmers += segs_v[v].nkmers;
+        }
+    }
+    else if (prc == PARSE_FALLBACK && vts) { c->call.vt_shift = 0; c->call.combine_veto = true; return retry_plan("the pipelined ingest fell back"); }      // (the fallback parse knows no virtual tasks: the call again, without them)
+    else if (prc != PARSE_FALLBACK) { c->call.vt_shift = 0; return prc; }
+    else c->stats.parse_fallbacks++;
+    return HSK_OK;
+}
+
+// Several ranks, between parse_count and parse_place: the ranks agree on the tasks' global sizes, on which tasks are heavy (a8: classified on the
+// global k-mer counts, every rank pre-aggregates its own share into `hlists`), and from the sizes on owners and storage order.  A rank that fails
+// must not return alone (its peers would wait for it in the next collective for ever).  Every all-reduce here carries the ranks' status as one more
+// element; a failed rank (parse_rc: its parse_count) keeps taking part, with zeros, until the next one, then all ranks return together.
+template <int NW>
+static int agree_on_tasks(hsk_ctx *c, ParseJob &job, const CallInput &in, int nranks, u32 ntasks, int parse_rc, HeavySet &hv, std::vector<TaskOut> &hlists, std::vector<int32_t> &owner, std::vector<u32> &order)
+{
+    Comm &cm = c->comm;
+    int local_rc = parse_rc;                             // first local failure since the last collective
+    auto together = [&](int st_, const char *what) { return left_together(c, st_, what, local_rc, "another rank failed before the all-reduce of %s"); };
+    std::vector<u64> bytes(ntasks, 0); int rc;
+    if (!local_rc) for (u32 t = 0; t < ntasks; ++t) bytes[t] = job.task_tot[3 * t + 1] + job.task_tot[3 * t] * (c->cfg.extension ? 9 : 1);
+    if (heavy_enabled(c, nranks)) {
+        std::vector<u64> kg(ntasks, 0);
+        if (!local_rc) for (u32 t = 0; t < ntasks; ++t) kg[t] = job.task_tot[3 * t + 2];
+        rc = together(cm.allreduce_with_status(kg, RCCL_SUM, local_rc != 0, c->stream, c->pool), "task k-mers"); if (rc) return rc;
+        hv.classify(c, kg);
+    }
+    if (hv.any) {
+        std::vector<u64> bad(ntasks, 0);
+        local_rc = heavy_preaggregate<NW>(c, job, in.d_packed, in.packed_bytes, hv.is_heavy, hlists, bad);
+        if (!local_rc && test_fail(c, "heavy")) { local_rc = fail(c, HSK_ERR_OOM, "heavy-hitter lists (injected)"); bad.assign(ntasks, 0); }
+        rc = together(cm.allreduce_with_status(bad, RCCL_MAX, local_rc != 0, c->stream, c->pool), "heavy flags"); if (rc) return rc;     // a task one rank could not aggregate travels as supermers everywhere
+        hv.settle(c, bad, &hlists, 1, (u64)(NW + 1) * 8, bytes);
+    }
+    rc = together(cm.allreduce_with_status(bytes, RCCL_SUM, local_rc != 0, c->stream, c->pool), "task sizes"); if (rc) return rc;
+    return dispatch_owners(c, bytes, nranks, owner, order);
+}
+
+// The reads are hashed once (parse_count); several ranks: the dispatcher needs the global task sizes before the storage order (tasks grouped
+// by owner rank) is known (agree_on_tasks), then parse_place lays the supermers out.
+template <int NW>
+static int parse_two_steps(hsk_ctx *c, const CallInput &in, int nranks, u32 ntasks, HeavySet &hv, std::vector<TaskOut> &hlists, std::vector<int32_t> &owner, std::vector<u32> &order, SupermerStore &st, int &place_rc)
+{
+    const u32 vts = c->call.vt_shift, nvt = ntasks << vts;
+    ParseJob job;
+    struct Release { hsk_ctx *c; ParseJob &j; ~Release() { parse_release(c, j); } } release{c, job};      // (on every way out)
+    int rc = parse_count(c, in.d_packed, in.packed_bytes, in.d_roff, in.d_rlen, in.nreads, in.rid_base, nvt, job);
+    if (!rc && nranks > 1 && test_fail(c, "parse")) rc = fail(c, HSK_ERR_OOM, "parse tables (injected)");
+    if (rc && nranks == 1) { c->call.vt_shift = 0; return rc; }
+    if (vts && !job.scan.d_tile_sub && !job.scan.bins.items && !job.empty) { c->call.vt_shift = 0; c->call.combine_veto = true; return retry_plan("the parse left its fast path: no items"); }
+    if (nranks > 1) { rc = agree_on_tasks<NW>(c, job, in, nranks, ntasks, rc, hv, hlists, owner, order); if (rc) return rc; }
+    if (vts) rc = parse_place(c, job, identity_order(nvt), st, nullptr, false);
+    else rc = parse_place(c, job, order, st, hv.any ? &hv.is_heavy : nullptr, nranks > 1);
+    if (!rc && nranks > 1 && test_fail(c, "place")) rc = fail(c, HSK_ERR_OOM, "supermer store (injected)");
+    if (rc && nranks == 1) return rc;
+    place_rc = rc;                                           // several ranks: carried into the size-matrix all-reduce (exchange_or_feed)
+    return HSK_OK;
+}
+
+// Several ranks, after the placement: the byte runs are packed (src: the store's bases), then either the feeder is planned from the size matrix --
+// fed: the task groups travel while process_rank counts -- or, HSK_OVERLAP=0, everything travels now: `xb` holds the owned tasks' supermers and
+// the store is freed.  Afterwards segs[t] lists where the supermers of owned task t live.
+static int exchange_or_feed(hsk_ctx *c, int place_rc, u32 ntasks, const std::vector<int32_t> &owner, const std::vector<u32> &order, SupermerStore &st, const BaseSource &src, GroupFeeder &feeder, bool &fed, ExchangeBuffers &xb, std::vector<TaskSegs> &segs)
+{
+    const int nranks = c->comm.nranks, rank = c->comm.rank;
+    const int local_rc = place_rc ? place_rc : pack_store_bytes(c, st, src, !overlap_enabled());
+    if (!overlap_enabled()) {
+        const int rc = exchange_supermers(c->comm, c->stream, c->pool, c->cfg.extension != 0, c->cfg.kmer_size, ntasks, owner, order, st.task_tot, st.task_base, st.sm_len, st.sm_bytes, st.sm_pos, st.sm_rid, xb, segs, local_rc != 0);
+        if (rc > 0 && local_rc) return local_rc;
+        if (rc) return fail(c, HSK_ERR_COMM, "supermer exchange failed: %d (%s)", rc, c->comm.last_error.c_str());
+        free_store(c, st);
+        return HSK_OK;
+    }
+    // size matrix: every rank contributes its row, the sum is the full matrix (+ the ranks' status: a rank whose placement or byte packing failed leaves together with its peers)
+    std::vector<u64> M((size_t)nranks * ntasks * 3, 0);
+    if (!local_rc) std::copy_n(st.task_tot.begin(), (size_t)ntasks * 3, M.begin() + (size_t)rank * ntasks * 3);
+    M.push_back((!local_rc && (st.sm_sub16 != nullptr || st.tot_sup == 0)) ? 1 : 0);      // this rank's supermers carry their minimizer bits (or it has none to send)
+    const int st_ = c->comm.allreduce_with_status(M, RCCL_SUM, local_rc != 0, c->stream, c->pool);
+    if (st_) return left_together(c, st_, "size matrix", local_rc, "another rank failed before the supermer exchange");
+    const bool all_sub = M.back() == (u64)nranks && c->call.combine_now; M.pop_back();
+    const int rc = feeder.plan(c, nranks, rank, ntasks, owner, order, M, st.task_base, segs); if (rc) return rc;
+    feeder.st = &st; feeder.lazy_pack = true; feeder.with_sub = all_sub; fed = true;
+    return HSK_OK;
+}
+
+// The k-mer lists of the heavy tasks go to their owners: sizes by all-reduce, one grouped send/recv, the own share by device copy.  hin: the
+// heavy tasks this rank owns, the lists of all ranks; hlists (this rank's lists) are freed.
+template <int NW>
+static int exchange_heavy_lists(hsk_ctx *c, const HeavySet &hv, const std::vector<int32_t> &owner, std::vector<TaskOut> &hlists, std::vector<HeavyIn> &hin)
+{
+    Comm &cm = c->comm;
+    const int nranks = cm.nranks, rank = cm.rank;
+    std::vector<u32> hv_tasks; for (u32 t = 0; t < (u32)hv.is_heavy.size(); ++t) if (hv.is_heavy[t]) hv_tasks.push_back(t);
+    const size_t nh = hv_tasks.size();
+    std::vector<u64> Hn((size_t)nranks * nh, 0);         // [rank][heavy task] entries of the rank's list
+    for (size_t i = 0; i < nh; ++i) Hn[(size_t)rank * nh + i] = hlists[hv_tasks[i]].n;
+    int rc = cm.allreduce_sum_u64(Hn.data(), Hn.size(), c->stream, c->pool);
+    if (rc) return fail(c, HSK_ERR_COMM, "allreduce(heavy list sizes) failed: %d (%s)", rc, cm.last_error.c_str());
+    const size_t ew = (size_t)(NW + 1) * 8;
+    const bool injected = test_fail(c, "heavybuf");
+    bool oom = injected;
+    std::vector<char *> buf(nh, nullptr);                // [heavy task] the owner's buffer, on its owner
+    for (size_t i = 0; i < nh; ++i) {
+        if (owner[hv_tasks[i]] != rank) continue;
+        HeavyIn h; h.task = hv_tasks[i]; h.n = heavy_list_off(&Hn[i], nh, nranks); h.d_entries = nullptr;
+        if (h.n && !oom) { h.d_entries = (u64 *)c->pool.alloc(h.n * ew); if (!h.d_entries) oom = true; }
+        hin.push_back(h); buf[i] = (char *)h.d_entries;
+    }
+    {   // every owner must have its receive buffers before anybody sends
+        std::vector<u64> none;
+        const int st_ = cm.allreduce_with_status(none, RCCL_MAX, oom, c->stream, c->pool);
+        if (st_ > 0) free_heavy_in(c, hin);
+        if (st_) return left_together(c, st_, "status", oom ? fail(c, HSK_ERR_OOM, injected ? "heavy-hitter receive buffers (injected)" : "heavy-hitter receive buffers") : 0, "another rank ran out of memory before the heavy-hitter exchange");
+    }
+    {
+        P2PGroup grp(cm);
+        for (size_t i = 0; i < nh && !grp.rc; ++i) {
+            const TaskOut &l = hlists[hv_tasks[i]]; const int o = owner[hv_tasks[i]];
+            if (o != rank) { if (l.n) grp.send(l.entries, l.n * ew, o, c->stream, "ncclSend(heavy list)"); continue; }
+            for (int p = 0; p < nranks; ++p) {
+                const u64 n = Hn[(size_t)p * nh + i];
+                if (n && p != rank) grp.recv(buf[i] + heavy_list_off(&Hn[i], nh, p) * ew, n * ew, p, c->stream, "ncclRecv(heavy list)");
+            }
+        }
+        if (grp.end()) return fail(c, HSK_ERR_COMM, "heavy-hitter list exchange failed: %s", cm.last_error.c_str());
+    }
+    for (size_t i = 0; i < nh; ++i) {                                   // own share: device copy
+        const TaskOut &l = hlists[hv_tasks[i]];
+        if (owner[hv_tasks[i]] == rank && l.n) HIPCHK(c, hipMemcpyAsync(buf[i] + heavy_list_off(&Hn[i], nh, rank) * ew, l.entries, l.n * ew, hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIPCHK(c, hsk_sync(c, c->stream));
+    for (auto &to : hlists) free_task_out(c, to);
+    return HSK_OK;
+}
+
+// Leaving together, part two (part one: the all-reduces with status up to the first task group: agree_on_tasks, exchange_or_feed, exchange_heavy_lists).
+// A rank whose count failed while the groups were travelling keeps its side of the exchange going (drain_after_failure); then the ranks tell each other how it went, and if one
+// of them failed they all return an error -- the failed rank its own, the others HSK_ERR_COMM.  rc: process_rank's on entry, the call's afterwards; false: the transport itself is broken.
+static bool agree_on_outcome(hsk_ctx *c, GroupFeeder &feeder, unsigned long long before_rank, hsk_result *out, int &rc)
+{
+    if (rc != HSK_OK) {
+        char keep_msg[sizeof c->err]; memcpy(keep_msg, c->err, sizeof keep_msg);
+        hsk_result_free(c, out);                                               // (its blocks are the rollback's: dropped first)
+        const int drc = feeder.drain_after_failure(before_rank);
+        if (drc) { rc = drc; return false; }
+        memcpy(c->err, keep_msg, sizeof keep_msg);
+    }
+    std::vector<u64> none;
+    const int st_ = c->comm.allreduce_with_status(none, RCCL_MAX, rc != HSK_OK, c->stream, c->pool);
+    const int trc = left_together(c, st_, "final status", rc, "another rank failed while the supermers were travelling; this rank's result is dropped");
+    if (st_) rc = trc;
+    return st_ >= 0;
+}
+
+template <int NW>
+static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u64 *d_roff, const u32 *d_rlen, u64 nreads, int64_t rid_base, hsk_result *out)
+{
+    const bool ext = c->cfg.extension != 0;
+    const int nranks = c->comm.active() ? c->comm.nranks : 1;
+    const int rank = c->comm.active() ? c->comm.rank : 0;
+    const CallInput in{d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base};
+    ResultPriv *rp = begin_result(out, NW);
+    PhaseTimer pt(c);
+    pt.begin(PH_TOTAL);
+    u32 ntasks = 0;
+    int rc = plan_call<NW>(c, nranks, packed_bytes, ntasks); if (rc) return rc;
+    out->ntasks = (int32_t)ntasks;
+    const u32 vts = c->call.vt_shift;
+    std::vector<int32_t> owner(ntasks, 0); std::vector<u32> order = identity_order(ntasks);
 
     // ---- parse ------------------------------------------------------------------------------------
     SupermerStore st;
-    std::vector<u8> is_heavy(ntasks, 0);
-    std::vector<u64> heavy_kmers(ntasks, 0);             // k-mer instances of a heavy task over all ranks (they travel as lists: its owner counts them into total_kmers)
+    HeavySet hv(ntasks);
     std::vector<TaskOut> hlists;                         // this rank's {k-mer, count} lists of the heavy tasks
     std::vector<HeavyIn> hin;                            // heavy tasks this rank owns: the lists of all ranks
-    bool any_heavy = false;
-    int place_rc = HSK_OK;
     std::vector<TaskSegs> segs(ntasks);
-    bool pipelined = false;
+    int place_rc = HSK_OK; bool pipelined = false;
     pt.begin(PH_PARSE);
-    // one GPU, reads arriving from pinned host memory, no payload: ingest, scan and placement as one pipeline over slabs
-    const bool pipe_enabled = tune("ingest_pipeline", 1) != 0;
-    if (nranks == 1 && !ext && c->call.h2d_src && pipe_enabled && parse_fast_enabled() && c->cfg.minimizer_size <= SCAN_MAX_M) {
-        const u8 *src = c->call.h2d_src; c->call.h2d_src = nullptr;
-        std::vector<TaskSegs> segs_v;
-        const int prc = parse_ingest_pipelined(c, src, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, nvt, st, vts ? segs_v : segs);
-        if (prc == HSK_OK) {
-            pipelined = true;
-            if (vts) {                                          // a task's segments: those of its virtual tasks (which one: ExpSeg::byte_off, unused in item mode)
-                for (u32 v = 0; v < nvt; ++v) {
-                    TaskSegs &ts = segs[v >> vts];
-                    for (ExpSeg sg : segs_v[v].segs) { sg.byte_off = v & ((1u << vts) - 1u); sg.kmer_off = 0; ts.segs.push_back(sg); }
-                    ts.nkmers += segs_v[v].nkmers;
-                }
-            }
-        }
-        else if (prc == PARSE_FALLBACK && vts) { c->call.vt_shift = 0; c->call.combine_veto = true; return retry_plan("the pipelined ingest fell back"); }      // (the fallback parse knows no virtual tasks: the call again, without them)
-        else if (prc != PARSE_FALLBACK) { c->call.vt_shift = 0; return prc; }
-        else c->stats.parse_fallbacks++;                        // (the packed reads are in HBM now: the two-step parse below takes it from there)
-    }
-    if (!pipelined) {
-        // the reads are hashed once (parse_count); multi-GPU: the dispatcher needs the global task sizes
-        // before the storage order (tasks grouped by owner rank) is known, then parse_place lays the supermers out
-        ParseJob job;
-        int rc = parse_count(c, d_packed, packed_bytes, d_roff, d_rlen, nreads, rid_base, nvt, job);
-        if (rc && nranks == 1) { parse_release(c, job); c->call.vt_shift = 0; return rc; }
-        if (vts && !job.scan.d_tile_sub && !job.scan.bins.items && !job.empty) { parse_release(c, job); c->call.vt_shift = 0; c->call.combine_veto = true; return retry_plan("the parse left its fast path: no items"); }   // (the parse left its fast path: no items)
-        if (nranks > 1) {
-            // Several ranks: a rank that fails must not return alone (its peers would wait for it in the next collective for
-            // ever).  Every all-reduce below carries the ranks' status as one more element; a failed rank keeps taking part
-            // (with zeros) until the next one, then all ranks return together.
-            Comm &cm = c->comm;
-            int local_rc = rc;                                   // first local failure since the last collective
-            auto together = [&](int st_, const char *what) { return left_together(c, st_, what, local_rc, "another rank failed before the all-reduce of %s"); };
-            std::vector<u64> bytes(ntasks, 0);
-            if (!local_rc) for (u32 t = 0; t < ntasks; ++t) bytes[t] = job.task_tot[3 * t + 1] + job.task_tot[3 * t] * (ext ? 9 : 1);
-            // heavy-hitter tasks (a8): classified on the global k-mer counts; every rank pre-aggregates its own share
-            if (heavy_enabled(c, nranks)) {
-                std::vector<u64> kg(ntasks, 0); std::vector<int32_t> types(ntasks, 0);
-                if (!local_rc) for (u32 t = 0; t < ntasks; ++t) kg[t] = job.task_tot[3 * t + 2];
-                rc = together(cm.allreduce_with_status(kg, RCCL_SUM, local_rc != 0, c->stream, c->pool), "task k-mers");
-                if (rc) { parse_release(c, job); return rc; }
-                plan_classify(kg.data(), (int)ntasks, c->cfg.unbalanced_ratio, types.data());
-                for (u32 t = 0; t < ntasks; ++t) if (types[t] == 1) { is_heavy[t] = 1; any_heavy = true; heavy_kmers[t] = kg[t]; }
-            }
-            if (any_heavy) {
-                std::vector<u8> failed(ntasks, 0);
-                local_rc = heavy_preaggregate<NW>(c, job, d_packed, packed_bytes, is_heavy, hlists, failed);
-                std::vector<u64> bad(ntasks, 0);
-                if (!local_rc) for (u32 t = 0; t < ntasks; ++t) bad[t] = failed[t];
-                rc = together(cm.allreduce_with_status(bad, RCCL_MAX, local_rc != 0, c->stream, c->pool), "heavy flags");     // a task one rank could not aggregate travels as supermers everywhere
-                if (rc) { parse_release(c, job); return rc; }
-                any_heavy = false;
-                for (u32 t = 0; t < ntasks; ++t) {
-                    if (!is_heavy[t]) continue;
-                    if (bad[t]) { is_heavy[t] = 0; free_task_out(c, hlists[t]); continue; }
-                    any_heavy = true; c->stats.heavy_tasks++;
-                    bytes[t] = hlists[t].n * (u64)(NW + 1) * 8;                               // ScatteredKmerList::get_size_bytes
-                }
-            }
-            rc = together(cm.allreduce_with_status(bytes, RCCL_SUM, local_rc != 0, c->stream, c->pool), "task sizes");
-            if (rc) { parse_release(c, job); return rc; }
-            rc = plan_dispatch(bytes.data(), (int)ntasks, nranks, c->cfg.plain_dispatcher != 0, c->cfg.dispatch_upper_coe, c->cfg.dispatch_step, owner.data());
-            if (rc) { parse_release(c, job); return fail(c, HSK_ERR_DISPATCH, "%s", hsk_strerror(HSK_ERR_DISPATCH)); }      // (same input on every rank: all of them fail here)
-            std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) { return owner[x] < owner[y]; });
-        }
-        if (vts) { std::vector<u32> order_v(nvt); for (u32 v = 0; v < nvt; ++v) order_v[v] = v; rc = parse_place(c, job, order_v, st, nullptr, false); }
-        else rc = parse_place(c, job, order, st, any_heavy ? &is_heavy : nullptr, nranks > 1);
-        parse_release(c, job);
-        if (rc && nranks == 1) return rc;
-        place_rc = rc;                                           // several ranks: carried into the size-matrix all-reduce below
-    }
+    rc = parse_pipelined(c, in, nranks, ntasks, st, segs, pipelined); if (rc) return rc;
+    if (!pipelined) { rc = parse_two_steps<NW>(c, in, nranks, ntasks, hv, hlists, owner, order, st, place_rc); if (rc) return rc; }
     pt.end(PH_PARSE);
     c->call.vt_shift = 0;
     tmark("parse enqueued (task totals read)");
     out->total_supermers = st.tot_sup; out->total_supermer_bytes = st.tot_bytes + st.tot_sup * (ext ? 9 : 1);
 
     // ---- exchange (multi-GPU) ---------------------------------------------------------------------
-    // After this block `segs[t]` lists where the supermers of owned task t live.
-    const u8 *x_len = st.sm_len; const u32 *x_pos = st.sm_pos; const int32_t *x_rid = st.sm_rid;
-    BaseSource x_src = source_from_store(st, d_packed, packed_bytes);
+    // After this block `segs[t]` lists where the supermers of owned task t live, and `x` says in which arrays.
+    TaskInput x{st.sm_len, source_from_store(st, d_packed, packed_bytes), st.sm_pos, st.sm_rid};
     ExchangeBuffers xb;
     GroupFeeder feeder; bool fed = false;
     pt.begin(PH_EXCH);
     if (nranks > 1) {
-        int local_rc = place_rc ? place_rc : pack_store_bytes(c, st, x_src, !overlap_enabled());
-        int rc;
-        if (overlap_enabled()) {
-            // size matrix: every rank contributes its row, the sum is the full matrix (+ the ranks' status: a rank whose
-            // placement or byte packing failed leaves together with its peers)
-            std::vector<u64> M((size_t)nranks * ntasks * 3, 0);
-            if (!local_rc) for (size_t i = 0; i < (size_t)ntasks * 3; ++i) M[(size_t)rank * ntasks * 3 + i] = st.task_tot[i];
-            M.push_back((!local_rc && (st.sm_sub16 != nullptr || st.tot_sup == 0)) ? 1 : 0);      // this rank's supermers carry their minimizer bits (or it has none to send)
-            const int st_ = c->comm.allreduce_with_status(M, RCCL_SUM, local_rc != 0, c->stream, c->pool);
-            if (st_) return left_together(c, st_, "size matrix", local_rc, "another rank failed before the supermer exchange");
-            const bool all_sub = M.back() == (u64)nranks && c->call.combine_now;
-            M.pop_back();
-            rc = feeder.plan(c, nranks, rank, ntasks, owner, order, M, st.task_base, segs); if (rc) return rc;
-            feeder.st = &st; feeder.lazy_pack = true; feeder.with_sub = all_sub; fed = true;
-        } else {
-            rc = exchange_supermers(c->comm, c->stream, c->pool, ext, K, ntasks, owner, order, st.task_tot, st.task_base,
-                                    st.sm_len, st.sm_bytes, st.sm_pos, st.sm_rid, xb, segs, local_rc != 0);
-            if (rc > 0 && local_rc) return local_rc;
-            if (rc) return fail(c, HSK_ERR_COMM, "supermer exchange failed: %d (%s)", rc, c->comm.last_error.c_str());
-            x_len = xb.len; x_pos = xb.pos; x_rid = xb.rid;
-            x_src = source_from_bytes(xb.bytes, xb.nbytes);
-            free_store(c, st);
-        }
-    } else if (!pipelined && vts) {
-        for (u32 v = 0; v < nvt; ++v) {
-            TaskSegs &ts = segs[v >> vts];
-            ts.nkmers += st.task_tot[3 * v + 2];
-            if (st.task_tot[3 * v] == 0) continue;
-            ExpSeg sg; sg.sup_off = st.task_base[3 * v]; sg.n_sup = st.task_tot[3 * v]; sg.byte_off = v & ((1u << vts) - 1u); sg.kmer_off = 0; sg.tile_start = 0;
-            ts.segs.push_back(sg);
-        }
-    } else if (!pipelined) {
-        for (u32 t = 0; t < ntasks; ++t) {
-            if (st.task_tot[3 * t] == 0) continue;
-            ExpSeg s; s.sup_off = st.task_base[3 * t]; s.n_sup = st.task_tot[3 * t]; s.byte_off = st.task_base[3 * t + 1]; s.kmer_off = 0; s.tile_start = 0;
-            segs[t].segs.push_back(s); segs[t].nkmers = st.task_tot[3 * t + 2];
-        }
-    }
-    if (any_heavy) {
-        // the k-mer lists of the heavy tasks go to their owners: counts by all-reduce, one grouped send/recv
-        std::vector<u32> hv_tasks; for (u32 t = 0; t < ntasks; ++t) if (is_heavy[t]) hv_tasks.push_back(t);
-        const size_t nh = hv_tasks.size();
-        std::vector<u64> Hn((size_t)nranks * nh, 0);
-        for (size_t i = 0; i < nh; ++i) Hn[(size_t)rank * nh + i] = hlists[hv_tasks[i]].n;
-        int rc = c->comm.allreduce_sum_u64(Hn.data(), Hn.size(), c->stream, c->pool);
-        if (rc) return fail(c, HSK_ERR_COMM, "allreduce(heavy list sizes) failed: %d (%s)", rc, c->comm.last_error.c_str());
-        const size_t ew = (size_t)(NW + 1) * 8;
-        bool oom = false;
-        for (size_t i = 0; i < nh; ++i) {
-            const u32 t = hv_tasks[i];
-            if (owner[t] != rank) continue;
-            HeavyIn hv; hv.task = t; hv.n = 0; hv.d_entries = nullptr;
-            for (int p = 0; p < nranks; ++p) hv.n += Hn[(size_t)p * nh + i];
-            if (hv.n && !oom) { hv.d_entries = (u64 *)c->pool.alloc(hv.n * ew); if (!hv.d_entries) oom = true; }
-            hin.push_back(hv);
-        }
-        {   // every owner must have its receive buffers before anybody sends
-            std::vector<u64> none;
-            const int st_ = c->comm.allreduce_with_status(none, RCCL_MAX, oom, c->stream, c->pool);
-            if (st_ > 0) { for (auto &hv : hin) c->pool.release(hv.d_entries); hin.clear(); }
-            if (st_) return left_together(c, st_, "status", oom ? fail(c, HSK_ERR_OOM, "heavy-hitter receive buffers") : 0, "another rank ran out of memory before the heavy-hitter exchange");
-        }
-        Comm &cm = c->comm;
-        size_t hi = 0;
-        {
-            P2PGroup grp(cm);
-            for (size_t i = 0; i < nh && !grp.rc; ++i) {
-                const u32 t = hv_tasks[i];
-                if (owner[t] == rank) {
-                    HeavyIn &hv = hin[hi++];
-                    u64 o = 0;
-                    for (int p = 0; p < nranks; ++p) {
-                        const u64 n = Hn[(size_t)p * nh + i];
-                        if (n && p != rank) grp.recv((char *)hv.d_entries + o * ew, n * ew, p, c->stream, "ncclRecv(heavy list)");
-                        o += n;
-                    }
-                } else if (hlists[t].n) {
-                    grp.send(hlists[t].entries, hlists[t].n * ew, owner[t], c->stream, "ncclSend(heavy list)");
-                }
-            }
-            if (grp.end()) return fail(c, HSK_ERR_COMM, "heavy-hitter list exchange failed: %s", cm.last_error.c_str());
-        }
-        hi = 0;
-        for (size_t i = 0; i < nh; ++i) {                                   // own share: device copy
-            const u32 t = hv_tasks[i];
-            if (owner[t] != rank) continue;
-            HeavyIn &hv = hin[hi++];
-            u64 o = 0; for (int p = 0; p < rank; ++p) o += Hn[(size_t)p * nh + i];
-            if (hlists[t].n) HIPCHK(c, hipMemcpyAsync((char *)hv.d_entries + o * ew, hlists[t].entries, hlists[t].n * ew, hipMemcpyDeviceToDevice, c->stream));
-        }
-        HIPCHK(c, hsk_sync(c, c->stream));
-        for (auto &to : hlists) free_task_out(c, to);
-    }
+        rc = exchange_or_feed(c, place_rc, ntasks, owner, order, st, x.src, feeder, fed, xb, segs); if (rc) return rc;
+        if (!fed) x = TaskInput{xb.len, source_from_bytes(xb.bytes, xb.nbytes), xb.pos, xb.rid};
+    } else if (!pipelined) segs_from_store(st, ntasks, vts, nullptr, segs);
+    if (hv.any) { rc = exchange_heavy_lists<NW>(c, hv, owner, hlists, hin); if (rc) return rc; }
     pt.end(PH_EXCH);
+
     ProcExtra ex; ex.heavy_in = &hin; ex.vt_shift = vts; if (nranks == 1 && st.sm_item) ex.items_store = &st;
     const unsigned long long before_rank = c->pool.mark();
-    int rc = process_rank<NW>(c, ntasks, owner, rank, segs, x_len, x_src, x_pos, x_rid, out, rp, pt, true, fed ? &feeder : nullptr, &ex);
-    if (rc == HSK_OK) add_unsent_kmers(c, out, c->call.dropped_now, is_heavy, heavy_kmers, owner, rank);      // (one GPU: no task is heavy)
-    if (fed && feeder.live) {
-        // Leaving together, part two (part one: the all-reduces with status up to the first task group).  A rank whose count failed
-        // while the groups were travelling has kept its side of the exchange going (drain_after_failure); now the ranks tell each
-        // other how it went, and if one of them failed they all return an error -- the failed rank its own, the others HSK_ERR_COMM.
-        if (rc != HSK_OK) {
-            char keep_msg[sizeof c->err]; memcpy(keep_msg, c->err, sizeof keep_msg);
-            hsk_result_free(c, out);                                               // (its blocks are the rollback's: dropped first)
-            const int drc = feeder.drain_after_failure(before_rank);
-            if (drc) return drc;                                                   // the transport itself is broken: nothing more to agree on
-            memcpy(c->err, keep_msg, sizeof keep_msg);
-        }
-        std::vector<u64> none;
-        const int st_ = c->comm.allreduce_with_status(none, RCCL_MAX, rc != HSK_OK, c->stream, c->pool);
-        const int trc = left_together(c, st_, "final status", rc, "another rank failed while the supermers were travelling; this rank's result is dropped");
-        if (st_ < 0) return trc;
-        if (st_ > 0) rc = trc;
-    }
-    for (auto &hv : hin) c->pool.release(hv.d_entries);
+    rc = process_rank<NW>(c, ntasks, owner, rank, segs, x.len, x.src, x.pos, x.rid, out, rp, pt, true, fed ? &feeder : nullptr, &ex);
+    if (rc == HSK_OK) add_unsent_kmers(c, out, c->call.dropped_now, hv, owner, rank);      // (one GPU: no task is heavy)
+    if (fed && feeder.live && !agree_on_outcome(c, feeder, before_rank, out, rc)) return rc;
+    free_heavy_in(c, hin);
     if (nranks > 1 && !fed) xb.release(c->pool); else free_store(c, st);
     return rc;
 }
@@ -1028,6 +1070,16 @@ static int run_pipeline(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const 
 // This is how the exchange logic is exercised on a single-GPU box (tests/test_gpu_multirank.py).
 // ------------------------------------------------------------------------------------------------
 struct DevInput { u8 *packed = nullptr; u64 *roff = nullptr; u32 *rlen = nullptr; };
+// what run_pipeline does for its rank from process_rank on, for virtual rank r: its supermers come from the feeder's groups or lie in `x`
+template <int NW, class ParseMs>
+static int count_virtual_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owner, int r, std::vector<TaskSegs> &segs, const TaskInput &x, GroupFeeder *feeder, const std::vector<HeavyIn> &hin, const HeavySet &hv, u64 dropped, const ParseMs &parse_ms, hsk_result *out)
+{
+    ResultPriv *rp = begin_result(out, NW); out->ntasks = (int32_t)ntasks;
+    PhaseTimer pt(c); ProcExtra ex; ex.heavy_in = &hin;
+    const int rc = process_rank<NW>(c, ntasks, owner, r, segs, x.len, x.src, x.pos, x.rid, out, rp, pt, false, feeder, &ex);
+    if (rc == HSK_OK) { add_unsent_kmers(c, out, dropped, hv, owner, r); sum_phases(*out, parse_ms(r)); }
+    return rc;
+}
 
 template <int NW>
 static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed_bytes, const u64 *nreads, hsk_result *outs, int32_t *owner_out, u32 *ntasks_out)
@@ -1038,8 +1090,7 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
     *ntasks_out = ntasks;
     std::vector<int64_t> rid_base(R, 0);
     for (int r = 1; r < R; ++r) rid_base[r] = rid_base[r - 1] + (int64_t)nreads[r - 1];      // MPI_Exscan of the read counts
-    std::vector<u32> order(ntasks); for (u32 t = 0; t < ntasks; ++t) order[t] = t;
-    // the plan, as run_pipeline chooses it with several ranks: the sketch of a rank's reads (here: of the first virtual rank that has some)
+    // the plan, as plan_call chooses it with several ranks: the sketch of a rank's reads (here: of the first virtual rank that has some)
     const bool scan_ok = parse_fast_enabled() && c->cfg.minimizer_size <= SCAN_MAX_M;
     if (R > 1 && scan_ok && c->cfg.kmer_size <= 57) {          // (without a plan to choose, the sketch still says which k-mers are certain to be dropped)
         int r0 = 0; while (r0 + 1 < R && nreads[r0] == 0) ++r0;
@@ -1047,8 +1098,8 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
         c->call.drop_mask_now = certain_drop_mask(c);              // (a rank that is certain is right for all: the virtual ranks share the first one's)
         c->call.combine_now = combine_allowed<NW>(c, R, tot_bytes / (u64)R);
     }
-    // 1. hash every rank's reads once (parse_count), sum the task sizes, dispatch
-    std::vector<u64> bytes(ntasks, 0), dropped(R, 0);
+    // 1. hash every rank's reads once (parse_count), sum the task sizes
+    std::vector<u64> bytes(ntasks, 0), kg(ntasks, 0), dropped(R, 0);
     std::vector<ParseJob> jobs(R);
     // per-rank device time of the parse (hash + count, then placement + byte store): outs[r].ms_parse
     EvList tev(c);
@@ -1061,128 +1112,77 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
         dropped[r] = c->call.dropped_now;
         (void)hipEventRecord(e1[r], c->stream);
         if (rc) return rc;
-        for (u32 t = 0; t < ntasks; ++t) bytes[t] += jobs[r].task_tot[3 * t + 1] + jobs[r].task_tot[3 * t] * (ext ? 9 : 1);
+        for (u32 t = 0; t < ntasks; ++t) { bytes[t] += jobs[r].task_tot[3 * t + 1] + jobs[r].task_tot[3 * t] * (ext ? 9 : 1); kg[t] += jobs[r].task_tot[3 * t + 2]; }
     }
-    // 1b. heavy-hitter tasks: classify on the global k-mer counts, every rank pre-aggregates its share
-    std::vector<u8> is_heavy(ntasks, 0);
-    std::vector<u64> heavy_kmers(ntasks, 0);             // k-mer instances of a heavy task over all ranks: its owner counts them into total_kmers
+    // 1b. heavy-hitter tasks: classify on the global k-mer counts, every rank pre-aggregates its share; then the dispatch
+    HeavySet hv(ntasks);
     std::vector<std::vector<TaskOut>> hlists(R);
-    bool any_heavy = false;
-    if (heavy_enabled(c, R)) {
-        std::vector<u64> kg(ntasks, 0); std::vector<int32_t> types(ntasks, 0);
-        for (int r = 0; r < R; ++r) for (u32 t = 0; t < ntasks; ++t) kg[t] += jobs[r].task_tot[3 * t + 2];
-        plan_classify(kg.data(), (int)ntasks, c->cfg.unbalanced_ratio, types.data());
-        for (u32 t = 0; t < ntasks; ++t) if (types[t] == 1) { is_heavy[t] = 1; any_heavy = true; heavy_kmers[t] = kg[t]; }
+    if (heavy_enabled(c, R)) hv.classify(c, kg);
+    if (hv.any) {
+        std::vector<u64> bad(ntasks, 0);
+        for (int r = 0; r < R; ++r) { int rc = heavy_preaggregate<NW>(c, jobs[r], in[r].packed, packed_bytes[r], hv.is_heavy, hlists[r], bad); if (rc) return rc; }
+        hv.settle(c, bad, hlists.data(), R, (u64)(NW + 1) * 8, bytes);
     }
-    if (any_heavy) {
-        std::vector<u8> bad(ntasks, 0);
-        for (int r = 0; r < R; ++r) {
-            std::vector<u8> failed;
-            int rc = heavy_preaggregate<NW>(c, jobs[r], in[r].packed, packed_bytes[r], is_heavy, hlists[r], failed);
-            if (rc) return rc;
-            for (u32 t = 0; t < ntasks; ++t) bad[t] |= failed[t];
-        }
-        any_heavy = false;
-        for (u32 t = 0; t < ntasks; ++t) {
-            if (!is_heavy[t]) continue;
-            if (bad[t]) { is_heavy[t] = 0; for (int r = 0; r < R; ++r) free_task_out(c, hlists[r][t]); continue; }   // travels as supermers after all
-            any_heavy = true; c->stats.heavy_tasks++;
-            bytes[t] = 0;
-            for (int r = 0; r < R; ++r) bytes[t] += hlists[r][t].n * (u64)(NW + 1) * 8;       // ScatteredKmerList::get_size_bytes
-        }
-    }
-    std::vector<int32_t> owner(ntasks, 0);
-    if (plan_dispatch(bytes.data(), (int)ntasks, R, c->cfg.plain_dispatcher != 0, c->cfg.dispatch_upper_coe, c->cfg.dispatch_step, owner.data()))
-        return fail(c, HSK_ERR_DISPATCH, "%s", hsk_strerror(HSK_ERR_DISPATCH));      // (a failed call's blocks go back with its scope: ApiCall)
+    std::vector<int32_t> owner(ntasks, 0); std::vector<u32> order = identity_order(ntasks);
+    { int rc = dispatch_owners(c, bytes, R, owner, order); if (rc) return rc; }
     if (owner_out) memcpy(owner_out, owner.data(), sizeof(int32_t) * ntasks);
-    std::stable_sort(order.begin(), order.end(), [&](u32 x, u32 y) { return owner[x] < owner[y]; });
     // 2. owner-grouped placement + byte materialisation on every rank
     std::vector<SupermerStore> st(R);
     std::vector<u64> M((size_t)R * ntasks * 3, 0);
     for (int r = 0; r < R; ++r) {
         (void)hipEventRecord(e2[r], c->stream);
-        int rc = parse_place(c, jobs[r], order, st[r], any_heavy ? &is_heavy : nullptr, R > 1);
+        int rc = parse_place(c, jobs[r], order, st[r], hv.any ? &hv.is_heavy : nullptr, R > 1);
         parse_release(c, jobs[r]);
         if (rc) return rc;
         rc = pack_store_bytes(c, st[r], source_from_packed(in[r].packed, packed_bytes[r], st[r].sm_gpos), !overlap_enabled()); if (rc) return rc;
         (void)hipEventRecord(e3[r], c->stream);
-        for (size_t i = 0; i < (size_t)ntasks * 3; ++i) M[(size_t)r * ntasks * 3 + i] = st[r].task_tot[i];
+        std::copy_n(st[r].task_tot.begin(), (size_t)ntasks * 3, M.begin() + (size_t)r * ntasks * 3);
     }
-    // 2b. the k-mer lists of the heavy tasks go to their owners (device copies here, send/recv in run_pipeline)
+    // 2b. the k-mer lists of the heavy tasks go to their owners (device copies here, send/recv in exchange_heavy_lists)
     std::vector<std::vector<HeavyIn>> hin(R);
-    if (any_heavy) {
+    if (hv.any) {
+        std::vector<u64> n(R);
         for (u32 t = 0; t < ntasks; ++t) {
-            if (!is_heavy[t]) continue;
-            HeavyIn hv; hv.task = t; hv.n = 0; hv.d_entries = nullptr;
-            for (int r = 0; r < R; ++r) hv.n += hlists[r][t].n;
-            if (hv.n) {
-                DALLOC(c, hv.d_entries, u64 *, hv.n * (NW + 1) * 8);
-                u64 o = 0;
-                for (int r = 0; r < R; ++r) {
-                    if (hlists[r][t].n) HIPCHK(c, hipMemcpyAsync(hv.d_entries + o * (NW + 1), hlists[r][t].entries, hlists[r][t].n * (NW + 1) * 8, hipMemcpyDeviceToDevice, c->stream));
-                    o += hlists[r][t].n;
-                }
-            }
-            hin[owner[t]].push_back(hv);
+            if (!hv.is_heavy[t]) continue;
+            for (int r = 0; r < R; ++r) n[r] = hlists[r][t].n;
+            HeavyIn h; h.task = t; h.n = heavy_list_off(n.data(), 1, R); h.d_entries = nullptr;
+            if (h.n) DALLOC(c, h.d_entries, u64 *, h.n * (NW + 1) * 8);
+            for (int r = 0; r < R; ++r) if (n[r]) HIPCHK(c, hipMemcpyAsync(h.d_entries + heavy_list_off(n.data(), 1, r) * (NW + 1), hlists[r][t].entries, n[r] * (NW + 1) * 8, hipMemcpyDeviceToDevice, c->stream));
+            hin[owner[t]].push_back(h);
         }
         HIPCHK(c, hsk_sync(c, c->stream));
         for (auto &v : hlists) for (auto &to : v) free_task_out(c, to);
     }
-    auto free_hin = [&]() { for (auto &v : hin) for (auto &hv : v) c->pool.release(hv.d_entries); };
     // 3. the exchange: same plans as the RCCL path (hsk_comm.h), device copies instead of send/recv
+    std::vector<std::vector<TaskSegs>> segs(R);
+    int rc_all = HSK_OK;
     if (overlap_enabled()) {
-        // grouped exchange overlapped with the sort, exactly as run_pipeline drives it
-        std::vector<GroupFeeder> fd(R);
-        std::vector<std::vector<ExchangePlan>> pl_all(R);
-        std::vector<std::vector<TaskSegs>> segs(R);
+        // grouped exchange overlapped with the sort, driven as run_pipeline drives it; 4. every rank finishes its own tasks while its groups travel
+        std::vector<GroupFeeder> fd(R); std::vector<std::vector<ExchangePlan>> pl_all(R);
         bool all_sub = c->call.combine_now;
         for (int r = 0; r < R; ++r) if (st[r].tot_sup && !st[r].sm_sub16) all_sub = false;
         for (int d = 0; d < R; ++d) { int rc = fd[d].plan(c, R, d, ntasks, owner, order, M, st[d].task_base, segs[d]); if (rc) return rc; pl_all[d] = fd[d].pl; fd[d].with_sub = all_sub; }
-        int rc_all = HSK_OK;
         for (int r = 0; r < R && rc_all == HSK_OK; ++r) {
             fd[r].st_all = &st; fd[r].pl_all = &pl_all; fd[r].lazy_pack = true;
-            ResultPriv *rp = begin_result(&outs[r], NW); outs[r].ntasks = (int32_t)ntasks;
-            PhaseTimer pt(c);
-            ProcExtra ex; ex.heavy_in = &hin[r];
-            rc_all = process_rank<NW>(c, ntasks, owner, r, segs[r], nullptr, BaseSource(), nullptr, nullptr, &outs[r], rp, pt, false, &fd[r], &ex);
-            if (rc_all == HSK_OK) { add_unsent_kmers(c, &outs[r], dropped[r], is_heavy, heavy_kmers, owner, r); sum_phases(outs[r], parse_ms(r)); }
+            rc_all = count_virtual_rank<NW>(c, ntasks, owner, r, segs[r], TaskInput{nullptr, BaseSource(), nullptr, nullptr}, &fd[r], hin[r], hv, dropped[r], parse_ms, &outs[r]);
         }
         for (int r = 0; r < R; ++r) free_store(c, st[r]);
-        free_hin();
-        return rc_all;
-    }
-    std::vector<ExchangePlan> pl(R);
-    std::vector<std::vector<TaskSegs>> segs(R);
-    std::vector<ExchangeBuffers> xb(R);
-    for (int d = 0; d < R; ++d) {
-        plan_exchange(R, d, ntasks, owner, order, M, st[d].task_base, pl[d], segs[d]);
-        xb[d].len = (u8 *)c->pool.alloc(pl[d].recv_tot_sup + 64); xb[d].bytes = (u8 *)c->pool.alloc(pl[d].recv_tot_bytes + 64); xb[d].nbytes = pl[d].recv_tot_bytes;
-        if (ext) { xb[d].pos = (u32 *)c->pool.alloc(pl[d].recv_tot_sup * 4 + 64); xb[d].rid = (int32_t *)c->pool.alloc(pl[d].recv_tot_sup * 4 + 64); }
-        if (!xb[d].len || !xb[d].bytes || (ext && (!xb[d].pos || !xb[d].rid))) return fail(c, HSK_ERR_OOM, "exchange buffers");
-    }
-    for (int d = 0; d < R; ++d) for (int sidx = 0; sidx < R; ++sidx) {
-        const u64 n = pl[sidx].send_sup[d], nb = pl[sidx].send_bytes[d];
-        if (n != pl[d].recv_sup[sidx] || nb != pl[d].recv_bytes[sidx]) return fail(c, HSK_ERR_INTERNAL, "exchange plan mismatch %d->%d", sidx, d);
-        if (!n) continue;
-        HIPCHK(c, hipMemcpyAsync(xb[d].len + pl[d].recv_sup_off[sidx], st[sidx].sm_len + pl[sidx].send_sup_off[d], n, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(xb[d].bytes + pl[d].recv_byte_off[sidx], st[sidx].sm_bytes + pl[sidx].send_byte_off[d], nb, hipMemcpyDeviceToDevice, c->stream));
-        if (ext) {
-            HIPCHK(c, hipMemcpyAsync(xb[d].pos + pl[d].recv_sup_off[sidx], st[sidx].sm_pos + pl[sidx].send_sup_off[d], n * 4, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(xb[d].rid + pl[d].recv_sup_off[sidx], st[sidx].sm_rid + pl[sidx].send_sup_off[d], n * 4, hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        std::vector<ExchangePlan> pl(R); std::vector<ExchangeBuffers> xb(R);
+        for (int d = 0; d < R; ++d) {
+            plan_exchange(R, d, ntasks, owner, order, M, st[d].task_base, pl[d], segs[d]);
+            if (!xb[d].alloc(c->pool, pl[d], ext)) return fail(c, HSK_ERR_OOM, "exchange buffers");
         }
+        for (int d = 0; d < R; ++d) for (int sidx = 0; sidx < R; ++sidx) { int rc = copy_share(c, st[sidx], pl[sidx], sidx, xb[d], pl[d], d, ext, false, c->stream); if (rc) return rc; }
+        HIPCHK(c, hsk_sync(c, c->stream));
+        for (int r = 0; r < R; ++r) free_store(c, st[r]);
+        // 4. every rank finishes its own tasks
+        for (int r = 0; r < R && rc_all == HSK_OK; ++r) {
+            rc_all = count_virtual_rank<NW>(c, ntasks, owner, r, segs[r], TaskInput{xb[r].len, source_from_bytes(xb[r].bytes, xb[r].nbytes), xb[r].pos, xb[r].rid}, nullptr, hin[r], hv, dropped[r], parse_ms, &outs[r]);
+            xb[r].release(c->pool);
+        }
+        if (rc_all) return rc_all;
     }
-    HIPCHK(c, hsk_sync(c, c->stream));
-    for (int r = 0; r < R; ++r) free_store(c, st[r]);
-    // 4. every rank finishes its own tasks
-    for (int r = 0; r < R; ++r) {
-        ResultPriv *rp = begin_result(&outs[r], NW); outs[r].ntasks = (int32_t)ntasks;
-        PhaseTimer pt(c);
-        ProcExtra ex; ex.heavy_in = &hin[r];
-        int rc = process_rank<NW>(c, ntasks, owner, r, segs[r], xb[r].len, source_from_bytes(xb[r].bytes, xb[r].nbytes), xb[r].pos, xb[r].rid, &outs[r], rp, pt, false, nullptr, &ex);
-        xb[r].release(c->pool);
-        if (rc) return rc;
-        sum_phases(outs[r], parse_ms(r));
-    }
-    free_hin();
-    return HSK_OK;
+    for (auto &v : hin) free_heavy_in(c, v);
+    return rc_all;
 }

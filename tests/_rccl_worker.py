@@ -42,8 +42,12 @@ def main():
             failure = dict(code=int(e.status), msg=str(e), seconds=time.time() - t0)
         del os.environ["HSK_TEST_FAIL"]
         comm.barrier()
+    if spec.get("expect_heavy"):
+        ctx.stats()                                                        # (reads and resets: what the failed call counted is not this call's)
     res = ctx.count(dna, rid_base=rid_base)                                # (after a failure: same context, same communicator)
     st = ctx.stats()
+    if spec.get("expect_heavy"):
+        assert st["heavy_tasks"] > 0, "no heavy task: the failure was injected on a path this input does not take"
     out = dict(kmers=res.kmers, cnt=res.cnt, task_off=res.task_off, histo=res.histo, heavy=np.array([st["heavy_tasks"]]), combine_pairs=np.array([st["combine_pairs"]]),
                dropped=np.array([st["dropped_kmers"]]), total_kmers=np.array([res.info["total_kmers"]]))
     if failure is not None:

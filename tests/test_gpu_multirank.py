@@ -101,13 +101,14 @@ def test_overlap_switch_gives_identical_lists():
             "res, owner = c.count_loopback([H.DnaBuffer.from_sequences(p) for p in parts])\n"
             "h = hashlib.sha256(owner.tobytes())\n"
             "for kl in res: h.update(kl.kmers.tobytes() + kl.cnt.tobytes() + kl.task_off.tobytes() + kl.histo.tobytes())\n"
-            "print(h.hexdigest(), sum(len(k) for k in res))\n") % util.ROOT
+            "print(h.hexdigest(), sum(len(k) for k in res), sum(int(kl.info['total_kmers']) for kl in res), sum(len(s) - 30 for s in seqs if len(s) >= 31))\n") % util.ROOT
     outs = []
     # ... and so do the two supermer stores: bytes written by the placement (default when supermers travel) or positions + pack_kernel
     for env in ({"HSK_OVERLAP": "1"}, {"HSK_OVERLAP": "0"}, {"HSK_PLACE_BYTES": "0"}, {"HSK_PLACE_BYTES": "0", "HSK_OVERLAP": "0"}):
         outs.append(subprocess.check_output([sys.executable, "-c", code], env=dict(os.environ, **util.tune_env(env))).decode().split())
     assert all(o == outs[0] for o in outs), outs
     assert int(outs[0][1]) > 10000
+    assert int(outs[0][2]) == int(outs[0][3])          # total_kmers of the virtual ranks: every k-mer instance of the reads, with either exchange
 
 
 @pytest.mark.gpu

@@ -133,16 +133,28 @@ def _small_case(tmp_path):
     return seqs, reads_json
 
 
-@pytest.mark.parametrize("site", ["sortbuf", "group1", "late"])
+FAIL_SITES = ["sortbuf", "group1", "late", "parse", "place", "heavy", "heavybuf"]
+
+
+@pytest.mark.parametrize("site", FAIL_SITES)
 def test_failing_together(site, tmp_path):
     """One rank's allocation fails -- before the first task group travels (sortbuf), after it (group1: the exchange buffers of
-    the second group) or in the middle of the batches (late).  BOTH ranks must return an error, quickly, nobody hangs, and the
-    same contexts and communicator count correctly afterwards (reference: the ranks die together, src/kmerops.cpp:1477)."""
+    the second group) or in the middle of the batches (late); or earlier still, in front of one of the status-carrying all-reduces
+    that come before the exchange: the parse (parse), the placement (place), the heavy tasks' pre-aggregation (heavy) and the
+    owners' receive buffers of the heavy lists (heavybuf; the last two on reads that do have heavy tasks).  BOTH ranks must return
+    an error, quickly, nobody hangs, and the same contexts and communicator count correctly afterwards (reference: the ranks die
+    together, src/kmerops.cpp:1477)."""
     import hysortk_amd as H
-    cfg = dict(K=31, M=17, L=2, U=50, EXT=0, ntasks=40)          # 20 tasks per rank: three task groups, three batches
-    seqs, reads_json = _small_case(tmp_path)
-    spec = dict(cfg, reads=reads_json, out=str(tmp_path / "rank%d.npz"), fail="1:" + site)
-    got = _run_ranks(2, spec, tmp_path, 29650 + ["sortbuf", "group1", "late"].index(site))
+    if site.startswith("heavy"):
+        cfg = {k: v for k, v in CASES["heavy_k31"].items()}
+        seqs = _heavy_reads()
+        reads_json = str(tmp_path / "reads.json")
+        json.dump(seqs, open(reads_json, "w"))
+    else:
+        cfg = dict(K=31, M=17, L=2, U=50, EXT=0, ntasks=40)          # 20 tasks per rank: three task groups, three batches
+        seqs, reads_json = _small_case(tmp_path)
+    spec = dict(cfg, reads=reads_json, out=str(tmp_path / "rank%d.npz"), fail="1:" + site, expect_heavy=site.startswith("heavy"))
+    got = _run_ranks(2, spec, tmp_path, 29650 + FAIL_SITES.index(site))
     assert int(got[1]["fail_code"][0]) == 4, str(got[1]["fail_msg"])                                   # HSK_ERR_OOM: its own error
     assert "injected" in str(got[1]["fail_msg"][0])
     assert int(got[0]["fail_code"][0]) == 7 and "another rank" in str(got[0]["fail_msg"][0]), str(got[0]["fail_msg"])     # HSK_ERR_COMM
