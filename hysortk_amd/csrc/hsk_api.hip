@@ -44,6 +44,7 @@
 #include "hsk_estimate.h"
 #include "hsk_synth.h"
 #include "hsk_plan.h"
+#include "hsk_tuning.h"
 #include "hsk_comm.h"
 
 using namespace hsk;
@@ -139,12 +140,12 @@ static size_t roll_back(hsk_ctx *c, unsigned long long mark, hsk_result *outs, i
     return n;
 }
 
-// What every entry point that takes a context and allocates or launches does first and last.  Open: the context's device, its
-// tuning and plan flags for this thread (enter_ctx), a fresh CallState, a mark of the device pool.  end(): a failed call is rolled
-// back (roll_back); with red zones (tuning pool_redzone), every zone of a live or quarantined block is compared with the pattern
-// after the last sync -- a zone that was written fails the call -- and the quarantined blocks go back to the pool; then the
-// CallState is reset and the thread forgets the context.  An entry point validates its arguments, opens the scope and returns
-// end(impl()) through run(): the impl may return early on any path (it does not run where the device could not be selected).
+// What every entry point that takes a context and allocates or launches does first and last.  Open: the context's device, a fresh
+// CallState, a mark of the device pool.  end(): a failed call is rolled back (roll_back); with red zones (tuning pool_redzone), every
+// zone of a live or quarantined block is compared with the pattern after the last sync -- a zone that was written fails the call --
+// and the quarantined blocks go back to the pool; then the CallState is reset.  An entry point validates its arguments, opens the
+// scope and returns end(impl()) through run(): the impl may return early on any path (it does not run where the device could not be
+// selected).  The tuning table and the plan flags are the context's (c->tune, c->cfg.flags): whoever reads them is handed the context.
 // HSK_TIMING: one line per call on stderr.
 struct ApiCall {
     hsk_ctx *c; const char *name; bool ok; unsigned long long mark; size_t live_open;
@@ -152,7 +153,6 @@ struct ApiCall {
     {
         ok = hipSetDevice(c->cfg.device) == hipSuccess;
         if (!ok) { (void)hipGetLastError(); fail(c, HSK_ERR_HIP, "hipSetDevice(%d) failed", c->cfg.device); }
-        enter_ctx(c);
         c->call = CallState();
         mark = c->pool.mark(); live_open = c->pool.bytes_live;
     }
@@ -174,7 +174,6 @@ struct ApiCall {
                     c->pool.bytes_live, rolled, c->pool.bytes_cached, c->pool.bytes_mapped(), c->pool.peak);
         if (c->call.roff_check.valid()) (void)c->call.roff_check.get();      // (a call that failed before the pipeline collected the verdict)
         c->call = CallState();
-        g_tune = nullptr; g_plan_flags = 0;
         return rc;
     }
 };
@@ -216,7 +215,7 @@ extern "C" int hsk_init(const hsk_config *cfg, hsk_ctx **out)
     c->pool.be_fill = pool_hip_fill; c->pool.be_check = pool_hip_check; c->pool.be_arg = c;
     const int rc = ApiCall(c, "hsk_init").run([&]() -> int {
         // (tests) red zones behind every device block, checked when every entry point's scope ends (ApiCall::end)
-        c->pool.redzone = (size_t)std::min<long long>(std::max<long long>(tune("pool_redzone", 0), 0), 1 << 20);
+        c->pool.redzone = (size_t)std::min<long long>(std::max<long long>(c->tune.pool_redzone, 0), 1 << 20);
         if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking) != hipSuccess ||
             hipStreamCreateWithFlags(&c->d2h_stream, hipStreamNonBlocking) != hipSuccess) return HSK_ERR_HIP;
         c->pinned_bytes = 1 << 20;
@@ -235,7 +234,7 @@ extern "C" int hsk_init(const hsk_config *cfg, hsk_ctx **out)
         for (int i = 8; i < 16; ++i) if (h_cnt[i]) seen = -100;
         // every XCD must get a fair share of a round-robin launch (4096 workgroups: 512 each)
         c->xcd_batch_ok = seen == 8 && lo >= 256;
-        if (c->tune.get("force_no_xcd", 0)) c->xcd_batch_ok = false;      // test hook
+        if (c->tune.force_no_xcd) c->xcd_batch_ok = false;      // test hook
         return HSK_OK;
     });
     if (rc != HSK_OK) { hsk_destroy(c); return rc; }
@@ -318,10 +317,11 @@ extern "C" int hsk_get_stats(hsk_ctx *c, hsk_stats *out, int reset)
 static int estimate_plan(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u64 *d_roff, const u32 *d_rlen, u64 nreads, int nranks)
 {
     c->call.est = PlanEstimate();
-    const bool enabled = tune("plan_sample", 1) != 0;
     constexpr u64 MIN_INPUT = 32ULL << 20, MIN_SAMPLE = 4ULL << 20, MAX_SAMPLE = 64ULL << 20;
+    static_assert(Tuning().plan_min_input == (long long)MIN_INPUT, "the table's default of plan_min_input (hsk_tuning.h) is MIN_INPUT");
+    const u64 min_input = (u64)c->tune.plan_min_input;
     // who would use it: one-word keys without payload on one GPU (combining extraction or not, first table, aggregation or not)
-    if (!enabled || c->cfg.kmer_size >= 64 || packed_bytes < (u64)tune("plan_min_input", (long long)MIN_INPUT) || nreads < 4096) return HSK_OK;       // (several ranks: every rank sketches its own reads, run_pipeline makes them agree)
+    if (c->tune.plan_sample == 0 || c->cfg.kmer_size >= 64 || packed_bytes < min_input || nreads < 4096) return HSK_OK;       // (several ranks: every rank sketches its own reads, run_pipeline makes them agree)
     // (payloads, three-word keys, pinned plans: nothing to choose -- the sketch still says which k-mers are certain to be dropped, `valid` stays false)
     const bool plan_wanted = c->nw <= 2 && !c->cfg.extension && !(c->cfg.flags & (HSK_FLAG_NO_AGGREGATION | HSK_FLAG_FULL_SORT));
     if (!plan_wanted && c->cfg.kmer_size > 57) return HSK_OK;
@@ -341,7 +341,7 @@ static int estimate_plan(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const
         HIPCHK(c, hipMemcpyAsync(h_out + 8, d_out + 8, 16, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hsk_sync(c, c->stream));
         const u64 s_reads = h_out[8]; s_bytes = h_out[9];
-        if (s_reads < 2048 || s_bytes < std::min<u64>(MIN_SAMPLE / 2, (u64)tune("plan_min_input", (long long)MIN_INPUT)) || s_bytes > packed_bytes || s_bytes > want + (1u << 20)) { release(); return HSK_OK; }      // (very long reads, a strange index: no estimate, the context's memory decides)
+        if (s_reads < 2048 || s_bytes < std::min<u64>(MIN_SAMPLE / 2, min_input) || s_bytes > packed_bytes || s_bytes > want + (1u << 20)) { release(); return HSK_OK; }      // (very long reads, a strange index: no estimate, the context's memory decides)
         // host input: the sample's bytes first (the main run copies them again with its first slab)
         if (c->call.h2d_src || c->call.zc_src) HIPCHK(c, hipMemcpyAsync(const_cast<u8 *>(d_packed), c->call.h2d_src ? c->call.h2d_src : c->call.zc_src, s_bytes, hipMemcpyDefault, c->stream));
         EstimateArgs ea; memset(&ea, 0, sizeof ea);
@@ -388,7 +388,7 @@ static int estimate_plan(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const
 // which homopolymer k-mers this call's sketch has found more than U (and at least 2^16) copies of: bit 0 all-A, bit 1 all-C
 static u32 certain_drop_mask(hsk_ctx *c)
 {
-    if (tune("drop_certain", 1) == 0 || c->cfg.kmer_size > 57 || !parse_fast_enabled() || c->cfg.minimizer_size > SCAN_MAX_M) return 0;
+    if (c->tune.drop_certain == 0 || c->cfg.kmer_size > 57 || c->tune.parse_fast == 0 || c->cfg.minimizer_size > SCAN_MAX_M) return 0;
     const u64 dmin = std::max<u64>((u64)std::max(c->cfg.upper_freq, 0), 1ULL << 16);
     return (c->call.est.homo_at > dmin ? 1u : 0u) | (c->call.est.homo_cg > dmin ? 2u : 0u);
 }
@@ -528,11 +528,7 @@ static bool offsets_back_to_back(const uint64_t *off, const uint32_t *len, uint6
 // Inputs in pinned host memory (hsk_host_alloc, hipHostMalloc, hipHostRegister) are not copied first: scan_kernel reads the
 // packed reads in place over PCIe -- once, while it hashes them -- and leaves the copy the later stages need in HBM, so the
 // transfer hides behind the VALU-bound scan; only the read index (12 bytes per read) travels ahead of it.  Pageable inputs
-// take staged copies.  HSK_ZERO_COPY=0 always copies.
-static bool zero_copy_enabled()
-{
-    return tune("zero_copy", 1) != 0;
-}
+// take staged copies.  tuning "zero_copy=0" always copies (hsk_count).
 
 // hsk_count() with a pinned DnaBuffer: only the read lengths travel ahead of the scan, the byte offsets are their prefix sums
 // (roff_*_kernel); the caller's offsets are compared with that layout by host threads while the GPU scans.  Returns a status
@@ -550,8 +546,7 @@ static int derive_input(hsk_ctx *c, uint64_t packed_bytes, const uint64_t *off, 
     // Fixed-length reads (sequencer output): three samples say so, the device fills in the lengths, and the host threads that
     // compare the offsets anyway verify EVERY length while the GPU scans -- 4 bytes per read less on the link (267 MB of 2.8 GB at
     // 10 Gbp of 150-bp reads).  A single read of another length sends the call down the same road as a buffer with gaps.
-    const bool uniform_enabled = tune("uniform_len", 1) != 0;
-    const uint32_t ulen = (uniform_enabled && len[0] != 0 && len[0] == len[nreads / 2] && len[0] == len[nreads - 1]) ? len[0] : 0;
+    const uint32_t ulen = (c->tune.uniform_len != 0 && len[0] != 0 && len[0] == len[nreads / 2] && len[0] == len[nreads - 1]) ? len[0] : 0;
     if (ulen) { hipLaunchKernelGGL(rlen_fill_kernel, dim3(2048), dim3(256), 0, c->stream, d.rlen, nreads, ulen); c->call.rlen_host = len; c->stats.h2d_bytes -= nreads * 4; }
     else HIPCHK(c, hipMemcpyAsync(d.rlen, len, nreads * 4, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(roff_tilesum_kernel, dim3((u32)ntl), dim3(PARSE_THREADS), 0, c->stream, d.rlen, nreads, d_tsum);
@@ -574,22 +569,21 @@ extern "C" int hsk_count(hsk_ctx *c, const uint8_t *packed, uint64_t packed_byte
         const bool device_check = nreads >= (1u << 20);          // a serial host loop over 10^8 reads costs more than the whole count
         int rc = device_check ? HSK_OK : check_host_index(c, packed_bytes, off, len, nreads); if (rc) return rc;
         const u8 *zc = nullptr;
-        if (zero_copy_enabled() && packed_bytes >= (16u << 20)) {
+        if (c->tune.zero_copy != 0 && packed_bytes >= (16u << 20)) {
             hipPointerAttribute_t at; memset(&at, 0, sizeof at);
             if (hipPointerGetAttributes(&at, packed) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer) zc = (const u8 *)at.devicePointer;
             else (void)hipGetLastError();
         }
         // pinned input of some size: slab ingest (DMA copies pipelined with the scan: enqueue_slab_copies, for parse_ingest_pipelined or
         // parse_count's fast scan) instead of reads over PCIe in place;
-        // HSK_H2D_SLABS=0: in place as in round 2, =n: n slabs
-        const int slabs_env = (int)tune("h2d_slabs", 16);
-        const bool slab_ingest = zc != nullptr && slabs_env > 1 && packed_bytes >= (32u << 20);
+        // tuning "h2d_slabs=0": in place, =n: n slabs
+        const int slabs = (int)c->tune.h2d_slabs;
+        const bool slab_ingest = zc != nullptr && slabs > 1 && packed_bytes >= (32u << 20);
         const bool profile = (c->cfg.flags & HSK_FLAG_PROFILE) != 0;
-        const bool derive_enabled = tune("derive_offsets", 1) != 0;
         // only the read lengths travel ahead of the scan (see roff_tilesum_kernel).  The host threads' verdict on the derived index is read by the
-        // fast parse (count_verdict for parse_count, parse_ingest_pipelined): with the general parse kernels from the start (M > SCAN_MAX_M, HSK_PARSE_FAST=0)
+        // fast parse (count_verdict for parse_count, parse_ingest_pipelined): with the general parse kernels from the start (M > SCAN_MAX_M, tuning "parse_fast=0")
         // the caller's index travels and is checked on the device like a pageable one
-        const bool derive = zc != nullptr && device_check && derive_enabled && parse_fast_enabled() && c->cfg.minimizer_size <= SCAN_MAX_M;
+        const bool derive = zc != nullptr && device_check && c->tune.derive_offsets != 0 && c->tune.parse_fast != 0 && c->cfg.minimizer_size <= SCAN_MAX_M;
         DevInput d;
         u64 *d_given = nullptr, *d_tsum = nullptr;
         EvPair ep{}; if (profile) { ep.a = ev_get(c); ep.b = ev_get(c); ep.kind = 5; (void)hipEventRecord(ep.a, c->stream); }
@@ -603,7 +597,7 @@ extern "C" int hsk_count(hsk_ctx *c, const uint8_t *packed, uint64_t packed_byte
             c->call.index_unchecked = true;
         }
         c->call.zc_src = slab_ingest ? nullptr : zc;
-        c->call.h2d_src = slab_ingest ? packed : nullptr; c->call.h2d_slabs = slabs_env;
+        c->call.h2d_src = slab_ingest ? packed : nullptr; c->call.h2d_slabs = slabs;
         tmark(zc ? (derive ? "input enqueued (zero-copy packed, offsets derived from the lengths)" : "input enqueued (zero-copy packed)") : "input enqueued (copies)");
         rc = dispatch_pipeline(c, d.packed, packed_bytes, d.roff, d.rlen, nreads, rid_base, out);
         tmark("pipeline returned");

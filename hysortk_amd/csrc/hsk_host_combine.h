@@ -2,26 +2,24 @@
 // Part of the single translation unit hsk_api.hip (included in this order; everything here is file-local).
 #pragma once
 
-// HSK_COMBINE=0: the instance path (expand_scatter2_kernel ...) always
-static bool combine_enabled()
+// tuning "combine=0": the instance path (expand_scatter2_kernel ...) always
+static bool combine_enabled(const hsk_ctx *c)
 {
-    return tune("combine", 1) != 0 && !(g_plan_flags & (HSK_FLAG_NO_AGGREGATION | HSK_FLAG_FULL_SORT | HSK_FLAG_NO_COMBINE));
+    return c->tune.combine != 0 && !(c->cfg.flags & (HSK_FLAG_NO_AGGREGATION | HSK_FLAG_FULL_SORT | HSK_FLAG_NO_COMBINE));
 }
-// k-mers per bucket the bucket order aims at (a table of CB_CAP slots takes the ~400 distinct k-mers of such a bucket at 32x coverage
-// with room to spare, and still most of them at 5x)
 // bins of the weighted finish: the top combine_prefix_bits() key bits (8 < bits <= 16).  A bin of the instance path's 16 bits would hold
 // ~120 pairs at 32x coverage and its workgroup would mostly wait for its own start-up; 14 bits: ~480 pairs on the 2048-slot table
 // More pairs per task than ~900 per bin (larger genomes, lower coverage) widen the prefix for the batches that follow, up to the instance
-// path's 16 bits; a bin that beats the last table before that has happened sends the call round again with 16.  HSK_COMBINE_PREFIX pins it.
+// path's 16 bits; a bin that beats the last table before that has happened sends the call round again with 16.  tuning "combine_prefix" pins it.
 constexpr int COMBINE_PREFIX_DEFAULT = 14, COMBINE_PREFIX_MAX = 16;
-static int combine_prefix_forced()
+static int combine_prefix_forced(const hsk_ctx *c)
 {
-    const long long v = tune("combine_prefix", 0);
+    const long long v = c->tune.combine_prefix;
     return v ? (int)std::min<long long>(16, std::max<long long>(9, v)) : 0;
 }
 static int combine_prefix_bits(const hsk_ctx *c)
 {
-    if (combine_prefix_forced()) return combine_prefix_forced();
+    if (const int forced = combine_prefix_forced(c)) return forced;
     return c->combine_prefix ? c->combine_prefix : COMBINE_PREFIX_DEFAULT;
 }
 static int combine_prefix_for(u64 max_pairs_per_task)
@@ -30,21 +28,18 @@ static int combine_prefix_for(u64 max_pairs_per_task)
     while (p < COMBINE_PREFIX_MAX && (max_pairs_per_task >> p) > 900) ++p;
     return p;
 }
-// more than one pair per combine_ratio() k-mers: the instance path (break-even measured at one per ~15); HSK_COMBINE_RATIO=1: never leave (measurements)
-static u64 combine_ratio()
+// more than one pair per combine_ratio() k-mers: the instance path (break-even measured at one per ~15); tuning "combine_ratio=1": never leave (measurements)
+static u64 combine_ratio(const hsk_ctx *c)
 {
-    return (u64)std::max<long long>(1, tune("combine_ratio", 16));
-}
-// combine_dedup=0: every item's k-mers are rolled (combine_kernel<K, false>); 1: equal items of a unit are rolled once
-static bool combine_dedup()
-{
-    return tune("combine_dedup", 1) != 0;
+    return (u64)std::max<long long>(1, c->tune.combine_ratio);
 }
 // words of ScatterBatch::d_nout / the pinned pair counts behind the tasks' pairs and the error word: items read, items rolled
 constexpr int COMBINE_STAT = XCD_BATCH + 2;
-static u64 combine_bucket_kmers()
+// k-mers per bucket the bucket order aims at (a table of CB_CAP slots takes the ~400 distinct k-mers of such a bucket at 32x coverage
+// with room to spare, and still most of them at 5x)
+static u64 combine_bucket_kmers(const hsk_ctx *c)
 {
-    return (u64)std::max<long long>(256, tune("combine_bucket", 12288));
+    return (u64)std::max<long long>(256, c->tune.combine_bucket);
 }
 
 static int bins_to_store(hsk_ctx *c, ScanBins &b, SupermerStore &st, u32 nvt, u32 vt_shift, hipStream_t stream)
@@ -83,7 +78,7 @@ static int bucket_order_tasks(hsk_ctx *c, u32 ntasks, const std::vector<TaskSegs
     bo.log2nb.assign(ntasks, 0); bo.out_base.assign(ntasks, 0); bo.unit_off.assign(ntasks, 0); bo.nitems.assign(ntasks, 0);
     std::vector<BucketItem> items;
     u64 run = 0, urun = 0; u32 maxlg = 0;
-    const u64 target = combine_bucket_kmers();
+    const u64 target = combine_bucket_kmers(c);
     for (u32 t : tasks) {
         if (t == ~0u) continue;
         u64 nsup = 0;
@@ -230,7 +225,8 @@ static int combine_batch(hsk_ctx *c, const u32 *tk, const BatchTask *bt, u64 *co
     }
     a.k = c->cfg.kmer_size; a.shift0 = plan[0].shift; a.shift1 = plan[1].shift; a.chunk = CH; a.err = c->d_err;
     ca.k = a.k; ca.shift0 = a.shift0; ca.bits0 = plan[0].bits; ca.shift1 = a.shift1; ca.err = c->d_err;
-    const bool dedup = NW == 1 && combine_dedup();       // (two-word keys: combine2_kernel has no such instance)
+    // tuning "combine_dedup=0": every item's k-mers are rolled (combine_kernel<K, false>); 1: equal items of a unit are rolled once
+    const bool dedup = NW == 1 && c->tune.combine_dedup != 0;       // (two-word keys: combine2_kernel has no such instance)
     ca.stat = sb.d_nout + COMBINE_STAT;
     if (!dedup) sb.items_host = nitems;
     static int occ_of[2] = {0, 0};                       // workgroups per CU of the instance that is launched

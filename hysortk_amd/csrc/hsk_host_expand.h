@@ -60,15 +60,13 @@ static int expand_batch(hsk_ctx *c, const ExpandJob *jobs, int njobs, int npass 
     ExpandScratch xown[EXP_BATCH];
     ExpandScratch *x = pre ? pre : xown;
     int nt = 0; u64 max_tiles = 0;
-    const bool reserve_enabled = tune("expand_reserve", 1) != 0;
-    bool reserve = true;
+    bool reserve = c->tune.expand_reserve != 0;
     {
         const TaskSegs *tsp[EXP_BATCH]; const u8 *lens[EXP_BATCH]; int m = 0;
         for (int i = 0; i < njobs; ++i) if (jobs[i].ts->ntiles) { tsp[m] = jobs[i].ts; lens[m] = jobs[i].sm_len; ++m; }
         // (ts.segs is host memory owned by the caller and stays alive until the next sync)
         // bases read in place (one GPU, one segment per task): no tile sums, a tile takes its output range with an atomic
         for (int i = 0; i < njobs; ++i) if (jobs[i].ts->ntiles && (!reads_in_place(jobs[i].src) || jobs[i].ts->segs.size() != 1)) reserve = false;
-        if (!reserve_enabled) reserve = false;
         int rc = expand_prepare_batch(c, m, tsp, lens, x, stream, pre != nullptr, !reserve); if (rc) return rc;
     }
     u64 *d_kcur = nullptr;

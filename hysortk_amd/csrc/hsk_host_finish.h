@@ -80,8 +80,8 @@ static void host_release(hsk_ctx *c, ResultPriv *rp, void *p)
     c->hpool.release(p);
 }
 
-static bool finish_enabled() { return !(g_plan_flags & HSK_FLAG_FULL_SORT); }
-static bool agg_enabled() { return !(g_plan_flags & (HSK_FLAG_NO_AGGREGATION | HSK_FLAG_FULL_SORT)); }
+static bool finish_enabled(const hsk_ctx *c) { return !(c->cfg.flags & HSK_FLAG_FULL_SORT); }
+static bool agg_enabled(const hsk_ctx *c) { return !(c->cfg.flags & (HSK_FLAG_NO_AGGREGATION | HSK_FLAG_FULL_SORT)); }
 static u32 auto_ntasks(hsk_ctx *c, u64 packed_bytes, int nranks)
 {
     // one task per ~2^28 k-mers (2 GB of 8-byte keys): large enough to saturate the chip, small
@@ -207,9 +207,9 @@ static void first_table_down(hsk_ctx *c, int first_cap, u64 ovf_bins, const u32 
 // More than half of all bins did not fit 2048 slots: this input has (nearly) as many distinct k-mers as k-mers -- reads with 5 % errors
 // and more -- and the aggregation is the wrong tool.  No further rungs: the listed bins' tasks take the long way now, the batches after
 // them (and later calls on this context) go without prefix passes + tables (off: hsk_ctx::agg_off or agg_off_wide).
-static bool ladder_hopeless(int cap, u64 listed, u64 all_bins, bool &off)
+static bool ladder_hopeless(const hsk_ctx *c, int cap, u64 listed, u64 all_bins, bool &off)
 {
-    if (tune("agg_adapt", 1) == 0 || cap < AG_LOG2CAP_MEDIUM || listed * 2 <= all_bins) return false;
+    if (c->tune.agg_adapt == 0 || cap < AG_LOG2CAP_MEDIUM || listed * 2 <= all_bins) return false;
     return off = true;
 }
 
@@ -249,6 +249,7 @@ static int long_way_batch(hsk_ctx *c, const BatchTask *bt, const bool *redo, int
 }
 
 constexpr int AG_LOG2CAP_HUGE = 13;                     // last rung for one-word keys: agg_big_kernel (8192 slots, 1024 threads) on the listed bins
+static_assert(Tuning().agg_maxrung == AG_LOG2CAP_HUGE, "the table's default of agg_maxrung (hsk_tuning.h) is the last rung");
 
 // The runtime table size as a compile-time constant: f(std::integral_constant<int, AG_LOG2CAP_*>) for the three tables of the finish kernels.
 template <typename F>
@@ -300,7 +301,7 @@ static int agg_large_setup(hsk_ctx *c, AggArgs &a, int slot, bool ext, char *&d_
 {
     d_large = nullptr;
     u64 nmax = 0; for (int i = 0; i < AG_BATCH; ++i) if (a.t[i].active) nmax = std::max(nmax, a.t[i].n);
-    if (tune("agg_large", 1) == 0 || nmax < AG_LARGE_BIN) return HSK_OK;
+    if (c->tune.agg_large == 0 || nmax < AG_LARGE_BIN) return HSK_OK;
     const u32 nbins = a.nbins;
     const size_t tab8 = (size_t)AGL_TABLES * AGL_TAB * 8, tab4 = (size_t)AGL_TABLES * AGL_TAB * 4;
     size_t off[AG_BATCH][8], total = (sizeof(AggLarge) * AG_BATCH + 255) / 256 * 256;
@@ -440,7 +441,7 @@ static int agg_stage2(hsk_ctx *c, AggPending &p, u64 *d_histo, u32 histo_len, Ta
         if (!first_table_up(c, p.first_cap, AG_LOG2CAP_LARGE, ovf_bins, all_bins)) first_table_down(c, p.first_cap, ovf_bins, NW == 1 ? &maxd : nullptr);
     }
     // (tests: as if this batch had been found hopeless, but finished normally)
-    if (tune("agg_adapt", 1) == 2 && !c->forbid_long_way && !p.weighted) agg_off = true;
+    if (c->tune.agg_adapt == 2 && !c->forbid_long_way && !p.weighted) agg_off = true;
     // ---- the ladder, bin by bin: the listed bins again one table size up, until no bin is left or the rungs are ----------------
     if (ovf_bins) {
         AggArgs keep = a;
@@ -449,13 +450,13 @@ static int agg_stage2(hsk_ctx *c, AggPending &p, u64 *d_histo, u32 histo_len, Ta
         for (;;) {
             u32 longest = 0; u64 nb = 0; for (int i = 0; i < AG_BATCH; ++i) { longest = std::max(longest, n_cur[i]); nb += n_cur[i]; }
             if (!longest) break;
-            const int max_rung = (int)tune("agg_maxrung", AG_LOG2CAP_HUGE);     // (tests: stop the ladder early, the listed bins' tasks take the long way)
+            const int max_rung = (int)c->tune.agg_maxrung;     // (tests: stop the ladder early, the listed bins' tasks take the long way)
             int next = (NW >= 2 || p.weighted) ? (cap < AG_LOG2CAP_LARGE ? cap + 1 : 0) : (cap < AG_LOG2CAP_HUGE ? cap + 1 : 0);
             if (next > max_rung) next = 0;
             if (!next) { for (int i = 0; i < AG_BATCH; ++i) if (n_cur[i]) done[i] = false; break; }   // a bin beyond the last rung: the task takes the long way
             // hopeless (one-word keys: four prefix passes + the tile finish from here on; multi-word keys have no tile finish to change
             // to: their tasks just stop climbing a ladder that ends in the long way anyway)
-            if (!c->forbid_long_way && !p.weighted && ladder_hopeless(cap, nb, all_bins, agg_off)) {
+            if (!c->forbid_long_way && !p.weighted && ladder_hopeless(c, cap, nb, all_bins, agg_off)) {
                 for (int i = 0; i < AG_BATCH; ++i) if (n_cur[i]) done[i] = false;
                 break;
             }
@@ -624,7 +625,7 @@ static int agg_ext_finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, const u
             if (first && nact && !first_table_up(c, first_cap, TOP - 1, listed, all_bins)) first_table_down(c, first_cap, listed, nullptr);
             if (!longest) break;
             // hopeless: the listed bins' tasks take the long way now instead of after the last table
-            if (ladder_hopeless(cap, listed, all_bins, c->agg_off_wide)) {
+            if (ladder_hopeless(c, cap, listed, all_bins, c->agg_off_wide)) {
                 for (int i = 0; i < AG_BATCH; ++i) if (keep.t[i].active && ovf.appended(i)) hopeless[i] = true;
                 break;
             }
@@ -634,7 +635,7 @@ static int agg_ext_finish_batch_device(hsk_ctx *c, BatchTask *bt, int K, const u
         a = keep;
     }
     if (d_large) hipLaunchKernelGGL((agg_ext_large_place_kernel<NW>), dim3(160, AG_BATCH), dim3(AG_THREADS), 0, c->stream, a);
-    if (tune("agg_adapt", 1) == 2) c->agg_off_wide = true;      // (tests: as in agg_stage2)
+    if (c->tune.agg_adapt == 2) c->agg_off_wide = true;      // (tests: as in agg_stage2)
     for (int i = 0; i < AG_BATCH; ++i) sa.t[i].active = a.t[i].active;
     hipLaunchKernelGGL(agg_scan_kernel, dim3(AG_BATCH), dim3(AG_THREADS), 0, c->stream, sa);
     HIPCHK(c, hipGetLastError());

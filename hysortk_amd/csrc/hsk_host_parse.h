@@ -67,11 +67,11 @@ static BaseSource source_from_store(const SupermerStore &st, const u8 *d_packed,
 // bound by its chain of dependent phases, not by bandwidth) while the placement pays for the extra stores (12.8 against
 // 8.4 ms).  With several GPUs the bytes must be produced anyway (they are what travels), and writing them here replaces
 // pack_kernel's scattered gather (~20 ms per rank and step).  So: byte store when the supermers travel, positions when
-// they stay; HSK_PLACE_BYTES=0/1 forces either.
-static bool place_bytes_enabled(bool supermers_travel)
+// they stay; tuning "place_bytes=0" / "=1" forces either.
+static bool place_bytes_enabled(const hsk_ctx *c, bool supermers_travel)
 {
-    const int env = (int)tune("place_bytes", -1);
-    return env < 0 ? supermers_travel : env != 0;
+    const int forced = (int)c->tune.place_bytes;
+    return forced < 0 ? supermers_travel : forced != 0;
 }
 
 // this call's tiling (hsk_parseplan.h); nslabs > 1: the slab ingest wants that many slabs
@@ -99,7 +99,7 @@ static ParseArgs make_parse_args(hsk_ctx *c, const ParseTiling &t, const u8 *d_p
 // task) chunk lists.  The chunk store is sized from the EXPECTED supermer count (a window of W k-mers starts a supermer every (W + 1) / 2
 // positions on random sequence, every 16 k-mers at least, once per read) with a quarter to spare; real genomes with long low-complexity
 // stretches make FEWER supermers, and an input that does overrun it (error bit 128; a bin beyond its map: 256) sends the call round again
-// without the combining extraction.  tuning "scan_place=1" selects it (default: tile records + the item placement, see scan_place_enabled).
+// without the combining extraction.  tuning "scan_place=1" selects it (default: tile records + the item placement, see below).
 struct ScanBins {
     u32 *cursor = nullptr, *map = nullptr, *ctl = nullptr, *chunk_bin = nullptr, *subs = nullptr; ulonglong2 *items = nullptr;
     BinTable *d_table = nullptr;                          // the table scan_kernel<.., true> reads (ParseArgs::bins)
@@ -109,7 +109,6 @@ struct ScanBins {
 // placement runs, 101.7 ms per step either way -- and from host memory the separate placement hides behind the ingest's DMA while the longer scan
 // does not (140 against 123 ms).  So the default stays the placement kernel; "scan_place=1" takes the fused form (no tile records: 13 GB less device
 // memory and 20 GB less traffic per 10 Gbp).
-static bool scan_place_enabled() { return tune("scan_place", 0) != 0; }
 static void bins_release(hsk_ctx *c, ScanBins &b)
 {
     c->pool.release(b.cursor); c->pool.release(b.map); c->pool.release(b.ctl); c->pool.release(b.chunk_bin); c->pool.release(b.subs); c->pool.release(b.items); c->pool.release(b.d_table);
@@ -123,11 +122,12 @@ static int bins_alloc(hsk_ctx *c, ScanBins &b, u32 nvt, u64 packed_bytes, u64 nr
     const double expect = positions * std::max(2.2 / (double)(W + 1), 1.2 / maxk) + 2.0 * (double)nreads + 65536.0;
     b.nbins = 8u * nvt;
     if (b.nbins > 8192) return fail(c, HSK_ERR_UNSUPPORTED, "more than 8192 bins");      // (a chunk's owner word: 13 bits of bin)
-    const u64 cap = (u64)(expect * (double)tune("bin_cap_pct", 125) / 100.0 / BIN_CHUNK) + (tune("bin_cap_pct", 125) >= 100 ? 2 * b.nbins + 64 : b.nbins + 1);      // (+ a first chunk and a chunk opened ahead per bin)      // (tests: a store that runs out)
+    const long long pct = c->tune.bin_cap_pct;
+    const u64 cap = (u64)(expect * (double)pct / 100.0 / BIN_CHUNK) + (pct >= 100 ? 2 * b.nbins + 64 : b.nbins + 1);      // (+ a first chunk and a chunk opened ahead per bin)      // (tests: a store that runs out)
     if (cap >= 0xFFFFFFF0ULL) return fail(c, HSK_ERR_UNSUPPORTED, "item store of %llu chunks", (unsigned long long)cap);
     b.cap = (u32)cap;
     b.vmax = (u32)std::min<u64>(std::max<u64>(cap / b.nbins * 64, 256), 1u << 16);
-    if (tune("bin_vmax", 0) > 0) b.vmax = (u32)tune("bin_vmax", 0);                                    // (tests: a bin beyond its map)
+    if (const long long vmax = c->tune.bin_vmax; vmax > 0) b.vmax = (u32)vmax;                               // (tests: a bin beyond its map)
     DALLOC(c, b.cursor, u32 *, (size_t)b.nbins * 4 * BIN_CUR_STRIDE);
     DALLOC(c, b.map, u32 *, (size_t)b.nbins * b.vmax * 4);
     DALLOC(c, b.ctl, u32 *, 256);
@@ -166,10 +166,10 @@ static void scan_release(hsk_ctx *c, ScanBufs &s)
 static int scan_setup(hsk_ctx *c, ScanBufs &s, ParseArgs &a, hipStream_t stream)
 {
     const int W = c->cfg.kmer_size - c->cfg.minimizer_size + 1;
-    a.rec_cap = parse_rec_cap(W, tune("parse_rec_cap", 0));
+    a.rec_cap = parse_rec_cap(W, c->tune.parse_rec_cap);
     a.place_group = place_group(PLACE_RECORDS, a.rec_cap);               // (launch_place: each kind's own)
     const bool items = c->call.combine_now && a.rec_cap <= PLACE_ITEM_REC;
-    const bool bins = items && c->call.item_mode_now && scan_place_enabled();
+    const bool bins = items && c->call.item_mode_now && c->tune.scan_place != 0;
     DALLOC(c, s.d_overflow, u32 *, 256);
     HIPCHK(c, hipMemsetAsync(s.d_overflow, 0, 4, stream));
     a.overflow = s.d_overflow;
@@ -236,11 +236,11 @@ static void prof_end(hsk_ctx *c, const EvPair &ep, hipStream_t stream)
 
 // The one place that names the instances of scan_kernel.  (k, m) = (31, 17) and (51, 17) have instances of their own;
 // "scan_generic=1" (tests) sends them through the generic one.
-static void launch_scan(hsk_ctx *, hipStream_t stream, u32 nblocks, u32 ntasks, const ParseArgs &a)
+static void launch_scan(const hsk_ctx *c, hipStream_t stream, u32 nblocks, u32 ntasks, const ParseArgs &a)
 {
     const dim3 grid(nblocks), block(PARSE_THREADS);
     const size_t lds = (size_t)ntasks * 16;
-    const bool generic = tune("scan_generic", 0) != 0;
+    const bool generic = c->tune.scan_generic != 0;
     const bool k31 = a.k == 31 && a.m == 17 && !generic, k51 = a.k == 51 && a.m == 17 && !generic;
     if (a.drop_mask) hipLaunchKernelGGL((scan_kernel<0, 0, false, true>), grid, block, lds, stream, a);
     else if (a.bins && k31) hipLaunchKernelGGL((scan_kernel<31, 17, true>), grid, block, lds, stream, a);
@@ -326,7 +326,6 @@ static int launch_parse_scan(hsk_ctx *c, hipStream_t st, const u64 *blk_cnt, u32
     if (!d_scratch) c->pool.release(d_part);              // (stream-ordered reuse: the caller's later work is enqueued on the same stream)
     return HSK_OK;
 }
-static bool parse_fast_enabled() { return tune("parse_fast", 1) != 0; }
 
 // parse_count, part 1 -- the fast scan: its buffers, scan_kernel over the whole input or slab by slab behind the DMA copies (h2d_src),
 // the task totals and the verdict words; returns when the host has them
@@ -449,7 +448,7 @@ static int parse_count(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u
     j.task_tot.assign((size_t)ntasks * 3, 0);
     if (nreads == 0 || packed_bytes == 0) return HSK_OK;            // nothing to parse on this rank
     j.empty = false;
-    j.fast = parse_fast_enabled() && c->cfg.minimizer_size <= SCAN_MAX_M;
+    j.fast = c->tune.parse_fast != 0 && c->cfg.minimizer_size <= SCAN_MAX_M;
     // slab ingest (hsk_count() from pinned memory): only the fast path hashes slab by slab, and only an input large enough for slabs;
     // everything else wants the reads in HBM first
     const u8 *h2d_src = c->call.h2d_src; c->call.h2d_src = nullptr;
@@ -527,7 +526,7 @@ static int parse_place(hsk_ctx *c, ParseJob &j, const std::vector<u32> &order, S
     if (!item_mode) DALLOC(c, st.sm_len, u8 *, st.tot_sup + 64);
     // byte-store mode (fast parse path): the supermers' bases are copied into per-task byte runs while the reads stream through
     // the byte placement once; positions are kept only where something still needs them (EXTENSION: pos / rid lookup)
-    bool bytes_mode = !item_mode && j.fast && place_bytes_enabled(supermers_travel) && a.rec_cap <= PLACE_BYTES_REC;
+    bool bytes_mode = !item_mode && j.fast && place_bytes_enabled(c, supermers_travel) && a.rec_cap <= PLACE_BYTES_REC;
     for (u32 t = 0; t < ntasks && bytes_mode; ++t) if (st.task_tot[3 * t + 1] >= (1ULL << 32)) bytes_mode = false;     // 32-bit offsets inside a task's run
     // several ranks with the combining extraction planned (c->call.combine_now): the supermers' minimizer bits go into the store as well
     const bool with_sub16 = bytes_mode && supermers_travel && c->call.combine_now && a.tile_sub && !ext;      // (heavy-hitter tasks are skipped by the kernel itself: their k-mers travel as lists)

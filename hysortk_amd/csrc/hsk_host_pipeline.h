@@ -8,7 +8,7 @@
 // between the virtual ranks of the loopback driver) while group g is expanded, sorted and counted on
 // the main stream.  The reference overlaps the same way with BATCH-sized MPI_Ialltoallv rounds
 // (src/kmerops.cpp:130-196, exchange_supermer's stage loop); here the unit is a task group so that a
-// sort batch never waits for bytes it does not need.  HSK_OVERLAP=0 selects one exchange up front.
+// sort batch never waits for bytes it does not need.  tuning "overlap=0" selects one exchange up front.
 // ------------------------------------------------------------------------------------------------
 static int estimate_plan(hsk_ctx *c, const u8 *d_packed, u64 packed_bytes, const u64 *d_roff, const u32 *d_rlen, u64 nreads, int nranks);      // hsk_api.hip
 static u32 certain_drop_mask(hsk_ctx *c);                                                                                                          // hsk_api.hip
@@ -168,8 +168,6 @@ struct GroupFeeder {
     }
 };
 
-static bool overlap_enabled() { return tune("overlap", 1) != 0; }
-
 // ---- heavy-hitter tasks (a8): the owner's side --------------------------------------------------------------
 // d_entries: the {k-mer, count} lists of all ranks for one task, concatenated (n entries, each list key-ordered,
 // a key at most once per list).  Orders them by key with the count as payload, sums equal keys, filters [L, U].
@@ -251,8 +249,8 @@ static RankPlan<NW> plan_rank(const hsk_ctx *c, u32 ntasks, const std::vector<in
     const bool ext = p.ext = c->cfg.extension != 0;
     const int K = p.K = c->cfg.kmer_size;
     // Tasks are sorted eight at a time, one per XCD (sort_batch_device); a remainder of fewer than eight
-    // tasks goes through the single-task kernel.  HSK_XCD_BATCH=0 forces the single-task path.
-    const bool batch_enabled = tune("xcd_batch", 1) != 0 && c->xcd_batch_ok;          // the one-task-per-XCD kernels need all eight XCDs (hsk_init's census)
+    // tasks goes through the single-task kernel.  tuning "xcd_batch=0" forces the single-task path.
+    const bool batch_enabled = c->tune.xcd_batch != 0 && c->xcd_batch_ok;          // the one-task-per-XCD kernels need all eight XCDs (hsk_init's census)
     std::vector<u32> &mine = p.mine;
     for (u32 t = 0; t < ntasks; ++t) if (owner[t] == rank && segs[t].nkmers) mine.push_back(t);
     // several ranks, the supermers arrived with their minimizer bits: the owner builds the items, batch by batch (hsk_combine.h, 1b)
@@ -269,29 +267,26 @@ static RankPlan<NW> plan_rank(const hsk_ctx *c, u32 ntasks, const std::vector<in
     const bool whole = mine.size() % XCD_BATCH == 0;
     p.batch = batch_enabled && mine.size() >= (size_t)XCD_BATCH;
     // fused finish: one-word keys (aggregating or tile finish), two-word keys with K >= 40 (aggregating finish only)
-    p.fused = !ext && finish_enabled() && (NW == 1 ? hybrid_enabled() : (NW <= 3 && agg_enabled() && prefix_plan_ok<NW>(K, true)));
-    p.agg = p.fused && agg_enabled();
+    p.fused = !ext && finish_enabled(c) && (NW == 1 ? hybrid_enabled(c) : (NW <= 3 && agg_enabled(c) && prefix_plan_ok<NW>(c, K, true)));
+    p.agg = p.fused && agg_enabled(c);
     // EXTENSION with one-word keys: two passes on the top 16 bits (payload carried) + grouping aggregation
-    p.fused_ext = ext && NW <= 3 && hybrid_enabled() && finish_enabled() && agg_enabled() && prefix_plan_ok<NW>(K, true);
+    p.fused_ext = ext && NW <= 3 && hybrid_enabled(c) && finish_enabled(c) && agg_enabled(c) && prefix_plan_ok<NW>(c, K, true);
     // Two batches in flight on ONE stream (two sets of sort buffers): the host enqueues expand / scatter / aggregation of
     // batch b + 1 BEFORE it waits for the aggregation totals of batch b, sizes batch b's outputs and enqueues its
-    // compaction.  The GPU therefore never runs dry while the host waits (HSK_LAG=0: one batch at a time, every wait drains
-    // the stream).  An earlier version expanded batch b + 1 on a second stream beside the sort of batch b (HSK_PIPELINE):
+    // compaction.  The GPU therefore never runs dry while the host waits (tuning "lag=0": one batch at a time, every wait drains
+    // the stream).  An earlier version expanded batch b + 1 on a second stream beside the sort of batch b:
     // every kernel of the path already fills the chip, the gain was 1 %, and it is gone.
     // Measured (10 Gbp, 5 batches): the batch interval is the same with and without the lag (18.7 / 18.8 ms: a drained
     // stream costs well under 0.1 ms against ~19 ms of kernels per batch), but the lag delays every batch's compaction,
     // and with it the batch's result copy, by one batch: host results take 214 ms with it and 197 ms without.  Default: on
-    // when the result stays in HBM (nothing to copy), off when it goes to the host; HSK_LAG=0/1 forces it.
+    // when the result stays in HBM (nothing to copy), off when it goes to the host; tuning "lag=0" / "=1" forces it.
     const bool keep_dev = (c->cfg.flags & HSK_FLAG_KEEP_DEVICE) != 0;
-    const int lag_env = (int)tune("lag", -1);
-    const bool lag_enabled = lag_env < 0 ? keep_dev : lag_env != 0;
+    const bool lag_enabled = c->tune.lag < 0 ? keep_dev : c->tune.lag != 0;
     p.lag = p.batch && p.agg && NW <= 2 && lag_enabled && mine.size() >= 2 * (size_t)XCD_BATCH;
     // expand fused with the first scatter pass (hsk_scatter.h): one-word keys, aggregating finish, whole batches
-    // (EXTENSION: payload chunks beside the key chunks, HSK_FUSED_SCATTER_EXT=0 turns that variant off)
-    const bool xs_ext_enabled = tune("fused_scatter_ext", 1) != 0;
-    const bool xs_wide_enabled = tune("fused_scatter_wide", 1) != 0;      // two-word keys
-    p.xs = p.batch && (NW == 1 ? (!ext || xs_ext_enabled) : (NW == 2 && !ext && xs_wide_enabled && prefix_top_bits(K, NW) == 16)) && scatter_enabled() &&
-           scatter_store_keys(max_task, p.XS_CH) < (1ULL << 32) && finish_enabled() && hybrid_enabled() && agg_enabled() && prefix_plan_ok<NW>(K, true);
+    // (EXTENSION: payload chunks beside the key chunks, tuning "fused_scatter_ext=0" turns that variant off; "fused_scatter_wide": two-word keys)
+    p.xs = p.batch && (NW == 1 ? (!ext || c->tune.fused_scatter_ext != 0) : (NW == 2 && !ext && c->tune.fused_scatter_wide != 0 && prefix_top_bits(K, NW) == 16)) && c->tune.fused_scatter != 0 &&
+           scatter_store_keys(max_task, p.XS_CH) < (1ULL << 32) && finish_enabled(c) && hybrid_enabled(c) && agg_enabled(c) && prefix_plan_ok<NW>(c, K, true);
     // the combining extraction (hsk_combine.h): the store carries the supermers' minimizer bits, whole batches, the aggregating finish
     // (an item-mode store holds nothing the instance path could read: every batch takes the combining extraction, or the call starts again
     //  without it)
@@ -309,13 +304,13 @@ static RankPlan<NW> plan_rank(const hsk_ctx *c, u32 ntasks, const std::vector<in
     // size (nobody starts again while peers wait).
     p.rec_cap = max_task;
     if (p.own_items() && !c->call.pair_cap_full) {
-        if (c->call.est.valid && tune("pair_cap", 1) != 0)
+        if (c->call.est.valid && c->tune.pair_cap != 0)
             p.rec_cap = std::min<u64>(max_task, std::max<u64>((u64)((double)max_task * std::min(1.0, 4.0 * c->call.est.distinct_per_kmer * c->est_bias + 0.02)), 1ULL << 22));
-        if (tune("pair_cap_records", 0) > 0) p.rec_cap = std::min<u64>(max_task, (u64)tune("pair_cap_records", 0));      // (tests: stores that run over; the attempt after an overrun is full size)
+        if (const long long forced_cap = c->tune.pair_cap_records; forced_cap > 0) p.rec_cap = std::min<u64>(max_task, (u64)forced_cap);      // (tests: stores that run over; the attempt after an overrun is full size)
     }
     // result copies that overlap the kernels: host result, no payload, tasks finished in ascending id (heavy tasks finish last, out of order)
-    p.early = p.batch && p.agg && NW <= 2 && !keep_dev && !ext && tune("early_d2h", 1) != 0 && !(ex && ex->heavy_in && !ex->heavy_in->empty());
-    p.compact_mode = (int)tune("compact_d2h", 2);
+    p.early = p.batch && p.agg && NW <= 2 && !keep_dev && !ext && c->tune.early_d2h != 0 && !(ex && ex->heavy_in && !ex->heavy_in->empty());
+    p.compact_mode = (int)c->tune.compact_d2h;
     return p;
 }
 
@@ -455,7 +450,7 @@ static int read_pair_counts(hsk_ctx *c, const RankPlan<NW> &P, BatchSlot &s)
     // one pair per 25.6 k-mers 102 against 126 ms, one per 6.6 -- reads with 0.3 % errors -- 171 against 138: the tables overflow inside
     // the buckets and the parse side's extra 20 ms buy nothing; at one per sixteen a bucket's table is already 37 % full); the batches of this
     // call finish on the pairs, the next calls take the instance path
-    if (bk && bp * combine_ratio() > bk && !c->combine_off) {
+    if (bk && bp * combine_ratio(c) > bk && !c->combine_off) {
         c->leave_combine();
         // (the estimate promised fewer pairs: later estimates on this context are scaled)
         if (c->call.est.valid) c->est_bias = std::min(8.0, std::max(1.0, ((double)bp / (double)bk) / c->call.est.distinct_per_kmer));
@@ -479,9 +474,9 @@ static int finish_slot(hsk_ctx *c, const RankPlan<NW> &P, BatchSlot &s, bool cov
             R.early = false;
             // a bin of pairs beyond the last table of the weighted finish: this call again, on the instance path (dispatch_pipeline)
             if (P.combine) {
-                if (!combine_prefix_forced() && s.prefix < COMBINE_PREFIX_MAX) c->combine_prefix = c->combine_prefix_floor = COMBINE_PREFIX_MAX;      // once more with the narrowest bins
+                if (!combine_prefix_forced(c) && s.prefix < COMBINE_PREFIX_MAX) c->combine_prefix = c->combine_prefix_floor = COMBINE_PREFIX_MAX;      // once more with the narrowest bins
                 else if (!c->combine_off) c->leave_combine();
-                c->distrust_estimate((double)combine_ratio());
+                c->distrust_estimate((double)combine_ratio(c));
                 return retry_plan("a bin beyond the weighted finish");
             }
         }
@@ -681,7 +676,7 @@ static int process_rank(hsk_ctx *c, u32 ntasks, const std::vector<int32_t> &owne
 // ---- what run_pipeline and run_loopback both say around process_rank ---------------------------------------------
 // May a call over `nranks` ranks with about `bytes` of packed reads per rank take the combining extraction?  The part both drivers share; what only
 // one of them knows (the attempt's history, the task count and bucket sizes of one GPU) stays there.
-// The combining extraction pays from a few hundred million k-mers on (a bucket order of the supermers comes first); HSK_COMBINE_MIN_BYTES moves
+// The combining extraction pays from a few hundred million k-mers on (a bucket order of the supermers comes first); tuning "combine_min_bytes" moves
 // the limit (tests: 0).  This call's own estimate of the input (estimate_plan) decides where there is one; the context's memory of earlier calls
 // (combine_off, agg_off) where there is none.
 // (two-word keys: 40 <= K <= 55 -- the prefix bits sit in the most significant word, an item of 64 bases holds six k-mers and more: shorter
@@ -692,10 +687,10 @@ template <int NW>
 static bool combine_allowed(const hsk_ctx *c, int nranks, u64 bytes)
 {
     const int K = c->cfg.kmer_size;
-    const bool pays = c->call.est.valid ? c->call.est.distinct_per_kmer * c->est_bias * (double)combine_ratio() <= 1.0 : !c->combine_off;
-    return (NW == 1 || (NW == 2 && K >= 40 && K <= 55)) && !c->cfg.extension && pays && !agg_is_off(c, NW) && combine_enabled() && parse_fast_enabled() &&
-           c->cfg.minimizer_size <= SCAN_MAX_M && bytes >= (u64)tune("combine_min_bytes", 64LL << 20) && c->xcd_batch_ok &&
-           (nranks == 1 || (overlap_enabled() && place_bytes_enabled(true)));
+    const bool pays = c->call.est.valid ? c->call.est.distinct_per_kmer * c->est_bias * (double)combine_ratio(c) <= 1.0 : !c->combine_off;
+    return (NW == 1 || (NW == 2 && K >= 40 && K <= 55)) && !c->cfg.extension && pays && !agg_is_off(c, NW) && combine_enabled(c) && c->tune.parse_fast != 0 &&
+           c->cfg.minimizer_size <= SCAN_MAX_M && bytes >= (u64)c->tune.combine_min_bytes && c->xcd_batch_ok &&
+           (nranks == 1 || (c->tune.overlap != 0 && place_bytes_enabled(c, true)));
 }
 static ResultPriv *begin_result(hsk_result *out, int nw) { memset(out, 0, sizeof *out); ResultPriv *rp = new ResultPriv(); out->priv = rp; out->nw = nw; return rp; }
 // virtual ranks: a rank's parse was timed on its own, its total is the sum of its phases
@@ -834,7 +829,7 @@ static int plan_call(hsk_ctx *c, int nranks, u64 packed_bytes, u32 &ntasks)
         // 2048-slot tables again and again (partial pairs: the detour stops paying) -- predicted from the estimate instead of found out by a batch
         const u32 lg = (u32)std::min<int>(CS_MAX_LOG2NB, CS_MAX_LOCAL + (int)c->call.vt_shift);
         const double per_bucket = (double)packed_bytes * 4.0 / (double)ntasks / (double)(1u << lg);
-        if (per_bucket > (double)combine_bucket_kmers() && c->call.est.distinct_per_kmer * per_bucket > 1400.0) { c->call.combine_now = false; c->call.vt_shift = 0; }
+        if (per_bucket > (double)combine_bucket_kmers(c) && c->call.est.distinct_per_kmer * per_bucket > 1400.0) { c->call.combine_now = false; c->call.vt_shift = 0; }
     }
     c->call.item_mode_now = c->call.combine_now && nranks == 1;      // one GPU: the store holds items (several ranks: byte runs + minimizer bits, the owners build the items)
     return HSK_OK;
@@ -845,9 +840,8 @@ static int plan_call(hsk_ctx *c, int nranks, u64 packed_bytes, u32 &ntasks)
 static int parse_pipelined(hsk_ctx *c, const CallInput &in, int nranks, u32 ntasks, SupermerStore &st, std::vector<TaskSegs> &segs, bool &done)
 {
     const u32 vts = c->call.vt_shift, nvt = ntasks << vts;       // what the parse calls tasks
-    const bool pipe_enabled = tune("ingest_pipeline", 1) != 0;
     done = false;
-    if (nranks != 1 || c->cfg.extension || !c->call.h2d_src || !pipe_enabled || !parse_fast_enabled() || c->cfg.minimizer_size > SCAN_MAX_M) return HSK_OK;
+    if (nranks != 1 || c->cfg.extension || !c->call.h2d_src || c->tune.ingest_pipeline == 0 || c->tune.parse_fast == 0 || c->cfg.minimizer_size > SCAN_MAX_M) return HSK_OK;
     const u8 *src = c->call.h2d_src; c->call.h2d_src = nullptr;
     std::vector<TaskSegs> segs_v;
     const int prc = parse_ingest_pipelined(c, src, in.d_packed, in.packed_bytes, in.d_roff, in.d_rlen, in.nreads, in.rid_base, nvt, st, vts ? segs_v : segs);
@@ -916,13 +910,13 @@ static int parse_two_steps(hsk_ctx *c, const CallInput &in, int nranks, u32 ntas
 }
 
 // Several ranks, after the placement: the byte runs are packed (src: the store's bases), then either the feeder is planned from the size matrix --
-// fed: the task groups travel while process_rank counts -- or, HSK_OVERLAP=0, everything travels now: `xb` holds the owned tasks' supermers and
+// fed: the task groups travel while process_rank counts -- or, tuning "overlap=0", everything travels now: `xb` holds the owned tasks' supermers and
 // the store is freed.  Afterwards segs[t] lists where the supermers of owned task t live.
 static int exchange_or_feed(hsk_ctx *c, int place_rc, u32 ntasks, const std::vector<int32_t> &owner, const std::vector<u32> &order, SupermerStore &st, const BaseSource &src, GroupFeeder &feeder, bool &fed, ExchangeBuffers &xb, std::vector<TaskSegs> &segs)
 {
     const int nranks = c->comm.nranks, rank = c->comm.rank;
-    const int local_rc = place_rc ? place_rc : pack_store_bytes(c, st, src, !overlap_enabled());
-    if (!overlap_enabled()) {
+    const int local_rc = place_rc ? place_rc : pack_store_bytes(c, st, src, c->tune.overlap == 0);
+    if (c->tune.overlap == 0) {
         const int rc = exchange_supermers(c->comm, c->stream, c->pool, c->cfg.extension != 0, c->cfg.kmer_size, ntasks, owner, order, st.task_tot, st.task_base, st.sm_len, st.sm_bytes, st.sm_pos, st.sm_rid, xb, segs, local_rc != 0);
         if (rc > 0 && local_rc) return local_rc;
         if (rc) return fail(c, HSK_ERR_COMM, "supermer exchange failed: %d (%s)", rc, c->comm.last_error.c_str());
@@ -1091,7 +1085,7 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
     std::vector<int64_t> rid_base(R, 0);
     for (int r = 1; r < R; ++r) rid_base[r] = rid_base[r - 1] + (int64_t)nreads[r - 1];      // MPI_Exscan of the read counts
     // the plan, as plan_call chooses it with several ranks: the sketch of a rank's reads (here: of the first virtual rank that has some)
-    const bool scan_ok = parse_fast_enabled() && c->cfg.minimizer_size <= SCAN_MAX_M;
+    const bool scan_ok = c->tune.parse_fast != 0 && c->cfg.minimizer_size <= SCAN_MAX_M;
     if (R > 1 && scan_ok && c->cfg.kmer_size <= 57) {          // (without a plan to choose, the sketch still says which k-mers are certain to be dropped)
         int r0 = 0; while (r0 + 1 < R && nreads[r0] == 0) ++r0;
         int erc = estimate_plan(c, in[r0].packed, packed_bytes[r0], in[r0].roff, in[r0].rlen, nreads[r0], R); if (erc) return erc;
@@ -1134,7 +1128,7 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
         int rc = parse_place(c, jobs[r], order, st[r], hv.any ? &hv.is_heavy : nullptr, R > 1);
         parse_release(c, jobs[r]);
         if (rc) return rc;
-        rc = pack_store_bytes(c, st[r], source_from_packed(in[r].packed, packed_bytes[r], st[r].sm_gpos), !overlap_enabled()); if (rc) return rc;
+        rc = pack_store_bytes(c, st[r], source_from_packed(in[r].packed, packed_bytes[r], st[r].sm_gpos), c->tune.overlap == 0); if (rc) return rc;
         (void)hipEventRecord(e3[r], c->stream);
         std::copy_n(st[r].task_tot.begin(), (size_t)ntasks * 3, M.begin() + (size_t)r * ntasks * 3);
     }
@@ -1156,7 +1150,7 @@ static int run_loopback(hsk_ctx *c, int R, const DevInput *in, const u64 *packed
     // 3. the exchange: same plans as the RCCL path (hsk_comm.h), device copies instead of send/recv
     std::vector<std::vector<TaskSegs>> segs(R);
     int rc_all = HSK_OK;
-    if (overlap_enabled()) {
+    if (c->tune.overlap != 0) {
         // grouped exchange overlapped with the sort, driven as run_pipeline drives it; 4. every rank finishes its own tasks while its groups travel
         std::vector<GroupFeeder> fd(R); std::vector<std::vector<ExchangePlan>> pl_all(R);
         bool all_sub = c->call.combine_now;

@@ -27,9 +27,9 @@ struct WidenPool {
     std::vector<std::thread> th;
     std::vector<hipEvent_t> evs;
     explicit WidenPool(hsk_ctx *c_) : c(c_) {}
-    static int nthreads()
+    int nthreads() const                                            // (asked by add(), on the thread of the call: the pool's threads read no setting)
     {
-        { const int v = (int)tune("widen_threads", 0); if (v > 0) return std::min(v, 64); }
+        { const int v = (int)c->tune.widen_threads; if (v > 0) return std::min(v, 64); }
         static const int n = []() { const unsigned hc = std::thread::hardware_concurrency(); return (int)std::min<unsigned>(32, std::max<unsigned>(2, hc / 2)); }();
         return n;
     }
@@ -83,7 +83,7 @@ struct WidenPool {
 template <int NW>
 struct ResultCopier {
     hsk_ctx *c; ResultPriv *rp; const std::vector<TaskSegs> &segs; const u32 ntasks; const u64 total_kmers; const bool ext, keep, profile_ev;
-    // compact copies: counts fit 16 bits whenever the filter's upper bound does.  HSK_COMPACT_D2H: 0 entries as they are (16 bytes), 1 k-mer
+    // compact copies: counts fit 16 bits whenever the filter's upper bound does.  tuning "compact_d2h": 0 entries as they are (16 bytes), 1 k-mer
     // words + 16-bit counts (10 bytes), 2 (default) the prefix form for one-word keys (7 bytes with U <= 255, else 8; + 256 KB of directory per task)
     const int compact_mode; const bool compact;
     std::vector<TaskOut> touts;                           // [task] what the finish left in HBM

@@ -18,10 +18,6 @@ struct ScatterBatch {
     bool tiles_done = false;                     // chunk_tiles_kernel has run already (combining extraction: the host reads the pair counts before the second pass is sized)
 };
 
-static bool scatter_enabled()
-{
-    return tune("fused_scatter", 1) != 0;
-}
 // keys the chunk store of a task of n k-mers must hold (less than one chunk is wasted per digit)
 static size_t scatter_store_keys(u64 n, int chunk) { return (size_t)(n / chunk + 257) * chunk; }
 // chunks of a store for n records (ChunkStore::cap_chunks: the combining extraction's pair stores have one more, which takes what does not fit)
@@ -101,9 +97,8 @@ static int scatter_expand_batch(hsk_ctx *c, const ExpandJob *jobs, const BatchTa
     a.k = c->cfg.kmer_size; a.shift0 = plan[0].shift; a.shift1 = plan[1].shift; a.chunk = XS_CHUNK; a.err = c->d_err;
     const bool ext = c->cfg.extension != 0;
     // expand_scatter2_kernel (two sweeps per flush, three workgroups per CU: 33.0 against 36.2 ms per step on the benchmark) takes
-    // one-word keys without payload whose bases are read in place, at most XS_MAXSEG segments per task; HSK_XS2=0: the one-sweep kernel
-    const bool xs2_env = tune("xs2", 1) != 0;
-    bool xs2 = xs2_env && NW == 1 && !ext;
+    // one-word keys without payload whose bases are read in place, at most XS_MAXSEG segments per task; tuning "xs2=0": the one-sweep kernel
+    bool xs2 = c->tune.xs2 != 0 && NW == 1 && !ext;
     for (int i = 0; i < XCD_BATCH && xs2; ++i) if (xi[i] >= 0 && !(reads_in_place(jobs[i].src) && jobs[i].ts->segs.size() <= (size_t)XS_MAXSEG)) xs2 = false;
     if constexpr (NW == 1) {
         if (xs2) {
@@ -131,7 +126,7 @@ static int scatter_expand_batch(hsk_ctx *c, const ExpandJob *jobs, const BatchTa
     }
     EvPair ep{}; if (profile) { ep.a = ev_get(c); ep.b = ev_get(c); ep.kind = 1; ep.keys = ntot; ep.bytes = ntot * (ext ? 16 : 8 * NW); (void)hipEventRecord(ep.a, stream); }
     const u32 grid = (u32)occ * 256u;
-    const bool xs_generic = tune("scatter_generic", 0) != 0;        // (tests: the default k through the generic instance)
+    const bool xs_generic = c->tune.scatter_generic != 0;        // (tests: the default k through the generic instance)
     if constexpr (NW == 1) {
         if (ext) hipLaunchKernelGGL((expand_scatter_kernel<1, true>), dim3(grid), dim3(XS_THREADS), 0, stream, a);
         else if (a.k == 31 && a.shift0 == 48 && a.shift1 == 56 && !xs_generic) hipLaunchKernelGGL((expand_scatter_kernel<1, false, 31>), dim3(grid), dim3(XS_THREADS), 0, stream, a);
@@ -158,7 +153,7 @@ static int sort_batch_prescattered(hsk_ctx *c, BatchTask *bt, const PassDesc *pl
     const bool has_val = bt[0].vA != nullptr;
     for (int i = 0; i < XCD_BATCH; ++i) { bt[i].out_k = bt[i].kA; bt[i].out_v = has_val ? bt[i].vA : nullptr; }
     if (!sb.active) return HSK_OK;
-    u64 tile_cap[XCD_BATCH], max_tiles = 0, ntot = 0; bool wide = force_wide_lookback();
+    u64 tile_cap[XCD_BATCH], max_tiles = 0, ntot = 0; bool wide = c->tune.wide_lookback != 0;
     size_t lb_off[XCD_BATCH + 1]; lb_off[0] = 0;
     for (int i = 0; i < XCD_BATCH; ++i) {
         tile_cap[i] = bt[i].n ? bt[i].n / XS_CHUNK + 256 : 0;
@@ -179,7 +174,7 @@ static int sort_batch_prescattered(hsk_ctx *c, BatchTask *bt, const PassDesc *pl
         a.keys_in = bt[i].kB; a.keys_out = bt[i].kA; a.vals_in = has_val ? bt[i].vB : nullptr; a.vals_out = has_val ? bt[i].vA : nullptr; a.n = bt[i].n;
         a.ntiles = tile_cap[i]; a.ntiles_dev = sb.d_ntiles + i;
         a.word = plan[1].word; a.shift = plan[1].shift; a.bits = plan[1].bits;
-        a.unstable = unstable_first_pass() ? 1 : 0;     // a tile is a chunk of ONE first-pass digit: the order inside it is free, the look-back keeps the tiles in order
+        a.unstable = c->tune.unstable_first != 0 ? 1 : 0;     // a tile is a chunk of ONE first-pass digit: the order inside it is free, the look-back keeps the tiles in order
         a.gbase = sb.d_gbase + (size_t)i * 256; a.lookback = (char *)d_lookback + lb_off[i];
         a.ticket = d_tickets + i; a.err = c->d_err; a.tile_src = sb.d_tile_src[i];
     }

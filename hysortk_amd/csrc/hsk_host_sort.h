@@ -11,29 +11,17 @@ static int plan_too_long(hsk_ctx *c, int K, int nw)
 {
     return fail(c, HSK_ERR_INTERNAL, "no digit plan of at most %d passes for K = %d, %d words, radix_bits = %d", MAX_PASSES, K, nw, c->cfg.radix_bits);
 }
-static bool hybrid_enabled()
-{
-    return !(g_plan_flags & HSK_FLAG_FULL_SORT);
-}
+static bool hybrid_enabled(const hsk_ctx *c) { return !(c->cfg.flags & HSK_FLAG_FULL_SORT); }
 // Two- and three-word keys take the prefix plan when the aggregating finish follows.  Where the most significant word carries
 // fewer than the 16 prefix bits (K - 32 (NW - 1) < 8 bases), the prefix continues in the top bits of the word below it
 // (make_split_prefix_plan).
-template <int NW> static bool prefix_plan_ok(int K, bool finish_follows)
+template <int NW> static bool prefix_plan_ok(const hsk_ctx *c, int K, bool finish_follows)
 {
-    return hybrid_enabled() && (NW == 1 || (NW <= 3 && finish_follows));
+    return hybrid_enabled(c) && (NW == 1 || (NW <= 3 && finish_follows));
 }
-// tasks of 2^30 keys and more use 64-bit look-back words; HSK_WIDE_LOOKBACK=1 forces them (tests: such tasks do not fit a test)
-static bool force_wide_lookback()
-{
-    return tune("wide_lookback", 0) != 0;
-}
-
+// Tasks of 2^30 keys and more use 64-bit look-back words; tuning "wide_lookback=1" forces them (tests: such tasks do not fit a test).
 // The first of several prefix passes need not be stable when an aggregation (which only needs the records GROUPED by the
-// prefix) follows: its ranking is then a single LDS atomic per key.  HSK_UNSTABLE_FIRST=0 keeps it stable.
-static bool unstable_first_pass()
-{
-    return tune("unstable_first", 1) != 0;
-}
+// prefix) follows: its ranking is then a single LDS atomic per key.  tuning "unstable_first=0" keeps it stable.
 
 // The profile bracket (HSK_FLAG_PROFILE): an event on the context's stream before and behind what `launch` enqueues, kept with the
 // kind of work and what it moved until the call's last wait (hsk_api.hip reads ev_pending).  Without the flag: just the launch.
@@ -74,7 +62,7 @@ static int sort_task_device(hsk_ctx *c, u64 *keysA, u64 *keysB, u64 *valsA, u64 
     if (scatter_passes) *scatter_passes = 0;
     if (n < 2) return HSK_OK;
     const bool has_val = valsA != nullptr;
-    const bool hybrid = allow_hybrid && NW == 1 && hybrid_enabled();
+    const bool hybrid = allow_hybrid && NW == 1 && hybrid_enabled(c);
     HistArgs h; memset(&h, 0, sizeof h);
     h.keys = keysA; h.n = n; h.npass = hybrid ? make_hybrid_plan(h.pass, MAX_PASSES) : make_pass_plan(K, NW, c->cfg.radix_bits, h.pass, MAX_PASSES); h.ghist = sc.ghist;
     if (h.npass < 0) return plan_too_long(c, K, NW);
@@ -98,7 +86,7 @@ static int sort_task_device(hsk_ctx *c, u64 *keysA, u64 *keysB, u64 *valsA, u64 
     HIPCHK(c, hipMemcpyAsync(sc.gbase, hb, (size_t)h.npass * 256 * 8, hipMemcpyHostToDevice, c->stream));
     constexpr int TILE = SortTile<NW>::TILE;
     const u32 ntiles = (u32)((n + TILE - 1) / TILE);
-    const bool wide = n >= (1ULL << 30) || force_wide_lookback();
+    const bool wide = n >= (1ULL << 30) || c->tune.wide_lookback != 0;
     const size_t lbw = wide ? 8 : 4;
     const size_t need = (size_t)todo.size() * ntiles * 256 * lbw;
     if (need > sc.lookback_bytes) {
@@ -185,7 +173,7 @@ static void launch_onesweep_multi(hsk_ctx *c, const MultiSortArgs &m, u32 grid)
 template <int NW>
 static int batch_pass_plan(hsk_ctx *c, int K, bool finish_follows, int prefix_bits, PassDesc *plan)
 {
-    const bool hybrid = prefix_plan_ok<NW>(K, finish_follows);
+    const bool hybrid = prefix_plan_ok<NW>(c, K, finish_follows);
     if (hybrid && finish_follows && NW >= 2 && prefix_top_bits(K, NW) < 16 && prefix_bits == 16) return make_split_prefix_plan(plan, MAX_PASSES, prefix_top_bits(K, NW), NW);
     return hybrid ? make_hybrid_plan(plan, MAX_PASSES, finish_follows ? prefix_bits : 64 - HYBRID_SHIFT, NW - 1) : make_pass_plan(K, NW, c->cfg.radix_bits, plan, MAX_PASSES);
 }
@@ -197,7 +185,7 @@ static int sort_batch_device(hsk_ctx *c, BatchTask *bt, int K, bool finish_follo
     const bool has_val = bt[0].vA != nullptr;
     constexpr int TILE = SortTile<NW>::TILE;
     PassDesc plan[MAX_PASSES];
-    const bool hybrid = prefix_plan_ok<NW>(K, finish_follows);
+    const bool hybrid = prefix_plan_ok<NW>(c, K, finish_follows);
     const int npass = batch_pass_plan<NW>(c, K, finish_follows, prefix_bits, plan);
     if (npass < 0) return plan_too_long(c, K, NW);
     u64 *d_ghist, *d_gbase; u32 *d_tickets;
@@ -209,7 +197,7 @@ static int sort_batch_device(hsk_ctx *c, BatchTask *bt, int K, bool finish_follo
     DALLOC(c, d_gbase, u64 *, (size_t)XCD_BATCH * MAX_PASSES * 256 * 8);
     DALLOC(c, d_tickets, u32 *, (size_t)XCD_BATCH * MAX_PASSES * 4 + 256);       // + 8 flag words behind the tickets
     HIPCHK(c, hipMemsetAsync(d_tickets, 0, (size_t)XCD_BATCH * MAX_PASSES * 4 + 64, c->stream));
-    u64 ntot = 0; bool wide = force_wide_lookback();
+    u64 ntot = 0; bool wide = c->tune.wide_lookback != 0;
     for (int i = 0; i < XCD_BATCH; ++i) {
         bt[i].out_k = bt[i].kA; bt[i].out_v = bt[i].vA;
         ntot += bt[i].n; if (bt[i].n >= (1ULL << 30)) wide = true;
@@ -260,7 +248,7 @@ static int sort_batch_device(hsk_ctx *c, BatchTask *bt, int K, bool finish_follo
                 SortArgs &a = m.t[i];
                 a.keys_in = kin[i]; a.keys_out = kout[i]; a.vals_in = vin[i]; a.vals_out = vout[i]; a.n = bt[i].n; a.ntiles = ntiles[i];
                 a.word = plan[p].word; a.shift = plan[p].shift; a.bits = plan[p].bits;
-                a.unstable = (hybrid && finish_follows && j == 0 && todo.size() > 1 && unstable_first_pass()) ? 1 : 0;
+                a.unstable = (hybrid && finish_follows && j == 0 && todo.size() > 1 && c->tune.unstable_first != 0) ? 1 : 0;
                 a.gbase = d_gbase + ((size_t)i * MAX_PASSES + p) * 256;
                 a.lookback = (char *)d_lookback + j * per_pass + lb_off[i];
                 a.ticket = d_tickets + (size_t)i * MAX_PASSES + j; a.err = c->d_err;

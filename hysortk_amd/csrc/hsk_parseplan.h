@@ -76,7 +76,7 @@ inline SlabBytes slab_bytes(const ParseTiling &t, u32 sl, u64 packed_bytes)
 
 // Record slots per 2048-position tile.  A window of W k-mers starts a supermer every (W + 1) / 2 positions on random
 // sequence (+ one per 128 positions and per read): 40 % head room, a power of two from SCAN_REC_CAP (W >= 12) to 2048
-// (tiny windows); a tile that still overflows sends the parse through the general kernels.  forced: tune("parse_rec_cap", 0), 0 = none
+// (tiny windows); a tile that still overflows sends the parse through the general kernels.  forced: tuning "parse_rec_cap", 0 = none
 inline u32 parse_rec_cap(int W, long long forced = 0)
 {
     if (forced) return (u32)std::min<long long>(std::max<long long>(forced, 1), (long long)PLACE_MAX_REC);

@@ -391,7 +391,7 @@ __global__ __launch_bounds__(TPB, 4) void expand_scatter_kernel(ScatterArgs a)
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Two-sweep variant (one-word keys, no payload, bases read in place -- positions in the packed reads on one GPU, offsets into the
-// received byte streams on several; HSK_XS2=0 takes expand_scatter_kernel instead, hsk_host_scatter.h).  expand_scatter_kernel keeps the
+// received byte streams on several; tuning "xs2=0" takes expand_scatter_kernel instead, hsk_host_scatter.h).  expand_scatter_kernel keeps the
 // 16 keys of a lane's item and their 16 ranks in registers from the roll to the permute: 48 of its 119 VGPRs, four waves per SIMD,
 // two workgroups per CU -- and no unit of the CU more than 55 % busy (VALU 54 %, LDS 34 %: the chain of phases waits for itself).
 // Here a flush rolls its k-mers TWICE: the first sweep only counts digits, the second -- after the digit scan, with the counts

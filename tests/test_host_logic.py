@@ -165,14 +165,23 @@ def test_paradis_order_rebuilds_the_reference_raw_vector_k51():
     assert r.cnt[perm].tolist() == [g[1] for g in gold]
 
 
-def test_every_tuning_name_the_library_reads_is_documented():
-    """hsk_config::tuning names (tune("...") in hysortk_amd/csrc) against INTEGRATION.md section 5: a switch nobody can find is a switch nobody can use."""
-    import glob
+def _tuning_table():
+    """the names of the tuning table, in the table's order: the X(name, default) rows of HSK_TUNING_TABLE in hysortk_amd/csrc/hsk_tuning.h"""
     import re
-    names = set()
-    for f in glob.glob(os.path.join(util.ROOT, "hysortk_amd", "csrc", "*")):
-        names |= set(re.findall(r'tune\("([a-z0-9_]+)"', open(f).read()))
+    text = open(os.path.join(util.ROOT, "hysortk_amd", "csrc", "hsk_tuning.h")).read()
+    table = text[text.index("#define HSK_TUNING_TABLE(X)"):text.index("struct Tuning {")]
+    names = re.findall(r'^\s*X\(([a-z0-9_]+),', table, re.M)
+    assert len(names) == len(set(names)) == table.count("X(")          # (every row was understood)
+    return names
+
+
+def test_every_tuning_name_the_library_reads_is_documented():
+    """hsk_config::tuning names (the table in hysortk_amd/csrc/hsk_tuning.h) against INTEGRATION.md section 5: a switch nobody can find is a
+    switch nobody can use."""
+    names = _tuning_table()
     doc = open(os.path.join(util.ROOT, "INTEGRATION.md")).read()
+    doc = doc[doc.index("## 5. Tuning names"):doc.index("## 6. ")]
+    assert "hsk_tuning.h" in doc
     assert len(names) > 30
     assert sorted(n for n in names if "`%s`" % n not in doc and "`%s=" % n not in doc) == []
 
@@ -180,12 +189,10 @@ def test_every_tuning_name_the_library_reads_is_documented():
 def test_every_tuning_name_the_tests_and_tools_set_is_read_by_the_library():
     """Tuning::parse ignores names it does not know: a misspelled pool_redzone or pair_cap_records would turn a boundary test into a plain run
     that passes.  Every name tests/ and tools/ set -- HSK_* dictionary keys and keywords folded by util.tune_env, and "name=value,..." strings
-    (tuning_extra, tuning=) -- must be one the library reads through tune("...") or tune.get("...") in hysortk_amd/csrc."""
+    (tuning_extra, tuning=) -- must be a row of the table in hysortk_amd/csrc/hsk_tuning.h."""
     import glob
     import re
-    read = set()
-    for f in glob.glob(os.path.join(util.ROOT, "hysortk_amd", "csrc", "*")):
-        read |= set(re.findall(r'tune(?:\.get)?\("([a-z0-9_]+)"', open(f).read()))
+    table = set(_tuning_table())
     files = glob.glob(os.path.join(util.ROOT, "tests", "*.py")) + glob.glob(os.path.join(util.ROOT, "tools", "**", "*.py"), recursive=True)
     used = {}
     for f in files:
@@ -197,7 +204,25 @@ def test_every_tuning_name_the_tests_and_tools_set_is_read_by_the_library():
         for n in names:
             used.setdefault(n, set()).add(os.path.relpath(f, util.ROOT))
     assert len(used) > 30 and {"pair_cap_records", "pool_redzone", "parse_rec_cap", "bin_cap_pct", "combine_min_bytes"} <= set(used)
-    assert {n: sorted(fs) for n, fs in used.items() if n not in read} == {}
+    assert {n: sorted(fs) for n, fs in used.items() if n not in table} == {}
+
+
+def test_every_tuning_name_of_the_table_is_read_and_only_as_a_member():
+    """No dead rows: every name of the table is read somewhere in hysortk_amd/csrc outside hsk_tuning.h, as a member of the context's table
+    (tune.<name>).  And the table is all there is: no string lookup (tune("...") or .get("...")) and no thread-local state is left in csrc --
+    whoever reads a setting is handed the context."""
+    import glob
+    import re
+    names = _tuning_table()
+    src = {}
+    for f in glob.glob(os.path.join(util.ROOT, "hysortk_amd", "csrc", "*")):
+        src[os.path.basename(f)] = open(f).read()
+    readers = "".join(text for name, text in src.items() if name != "hsk_tuning.h")
+    assert len(names) == 42
+    assert sorted(n for n in names if not re.search(r'\btune\.%s\b' % n, readers)) == []
+    for name, text in src.items():
+        for banned in ("thread_local", 'tune("', '.get("'):
+            assert banned not in text, (name, banned)
 
 
 def test_scripts_compile():
@@ -210,9 +235,10 @@ def test_scripts_compile():
 
 
 def test_every_entry_point_that_takes_a_context_opens_a_call_scope():
-    """hsk_api.hip: an extern "C" function that takes an hsk_ctx * opens an ApiCall (device, tuning and plan flags for the thread, a fresh
-    CallState, a pool mark; at its end the rollback of a failed call and the red-zone check) unless it only reads or releases.  Nothing else
-    selects the context's device or enters it: enter_ctx( and hipSetDevice(c->cfg.device) appear only inside ApiCall, hsk_init and hsk_destroy."""
+    """hsk_api.hip: an extern "C" function that takes an hsk_ctx * opens an ApiCall (device, a fresh CallState, a pool mark; at its end the
+    rollback of a failed call and the red-zone check) unless it only reads or releases.  Nothing else selects the context's device:
+    hipSetDevice(c->cfg.device) appears only inside ApiCall, hsk_init and hsk_destroy.  And nothing enters a context for a thread: enter_ctx
+    does not exist (the tuning table and the plan flags are read from the context that is passed along)."""
     import glob
     import re
     exempt = {"hsk_last_error", "hsk_get_stats", "hsk_result_free", "hsk_synth_free", "hsk_comm_destroy", "hsk_destroy"}
@@ -241,8 +267,8 @@ def test_every_entry_point_that_takes_a_context_opens_a_call_scope():
     allowed = [body(api, api.index("struct ApiCall {")), entries["hsk_init"], entries["hsk_destroy"]]
     for f in glob.glob(os.path.join(src_dir, "*")):
         text = open(f).read()
+        assert "enter_ctx" not in text, os.path.basename(f)
         for a in allowed:
             text = text.replace(a, "")
-        text = text.replace("static void enter_ctx(hsk_ctx *c)", "")
-        assert not re.search(r"\benter_ctx\(|hipSetDevice\(c->cfg\.device\)", text), os.path.basename(f)
+        assert not re.search(r"hipSetDevice\(c->cfg\.device\)", text), os.path.basename(f)
         assert not re.search(r"\b(snapshot|release_all_but|redzone_end_call)\(|PlanReset", text), os.path.basename(f)
