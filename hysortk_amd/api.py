@@ -588,16 +588,21 @@ class Context:
     """One hsk_ctx (one process, one GPU)."""
 
     def __init__(self, K=31, M=17, L=15, U=40, EXT=0, ntasks=0, device=0, plain_dispatcher=0, radix_bits=8, profile=False, keep_device=False,
-                 plan=None, tuning=None):
+                 plan=None, tuning=None, plain_classifier=False, unbalanced_ratio=None):
         """plan: None (two prefix passes + LDS aggregation, the library's choice), "no_aggregation" (HSK_FLAG_NO_AGGREGATION) or
-        "full_sort" (HSK_FLAG_FULL_SORT: the reference's algorithm, LSD over all key bytes + merge-count over the sorted array)."""
+        "full_sort" (HSK_FLAG_FULL_SORT: the reference's algorithm, LSD over all key bytes + merge-count over the sorted array).
+        plain_classifier (HSK_FLAG_PLAIN_CLASSIFIER): no task is a heavy hitter; unbalanced_ratio (hsk_config::unbalanced_ratio): a task
+        is one when its global k-mer count exceeds this many times the mean (the library's default when None)."""
         self.lib = _lib.load()
         cfg = _lib.Config()
         self.lib.hsk_config_default(C.byref(cfg))
         cfg.kmer_size, cfg.minimizer_size, cfg.lower_freq, cfg.upper_freq = K, M, L, U
         cfg.extension, cfg.ntasks, cfg.device, cfg.plain_dispatcher, cfg.radix_bits = EXT, ntasks, device, plain_dispatcher, radix_bits
         cfg.flags = (_lib.FLAG_PROFILE if profile else 0) | (_lib.FLAG_KEEP_DEVICE if keep_device else 0) | \
+            (_lib.FLAG_PLAIN_CLASSIFIER if plain_classifier else 0) | \
             {None: 0, "no_aggregation": _lib.FLAG_NO_AGGREGATION, "full_sort": _lib.FLAG_FULL_SORT, "no_combine": _lib.FLAG_NO_COMBINE}[plan]
+        if unbalanced_ratio is not None:
+            cfg.unbalanced_ratio = float(unbalanced_ratio)
         # tuning: dict or "name=value,..." (hsk_config::tuning): forced paths for tests and a few measured thresholds, per context
         if isinstance(tuning, dict):
             tuning = ",".join("%s=%d" % (k, int(v)) for k, v in tuning.items())

@@ -75,8 +75,10 @@ struct AggTask {
 // EXTENSION (agg_ext_kernel) owes the payloads grouped by key as well: the bin's workgroup takes the distinct keys and their counts from the
 // table, orders them, writes entries and payload offsets as always and leaves every table slot's group offset in tgoff; then the slices run
 // a second time (agg_ext_large_place_kernel): a record finds its group through the table, takes the group's next free place with an atomic
-// on tcur and stores its payload there.  A bin qualifies from AG_LARGE_BIN = 65536 records on and U <= 65535, so the k-mer that made the
-// bin large is never kept: groups of more than U records keep their range (the neighbours' payload offsets stay right) but are not written.
+// on tcur and stores its payload there.  A bin qualifies from AG_LARGE_BIN = 65536 records on.  With U <= 65535 -- every
+// call but the unfiltered pre-aggregation of a heavy-hitter task, which never has payloads -- the k-mer that made the bin large is never kept: groups
+// of more than U records keep their range (the neighbours' payload offsets stay right) but are not written.  The pre-aggregation (upper = INT32_MAX)
+// keeps it, with its 32-bit count from the table.
 constexpr u64 AG_LARGE_BIN = 1u << 16;
 constexpr u32 AGL_SLICE = 1u << 15;
 constexpr int AGL_LOG2TAB = 11;

@@ -54,7 +54,9 @@ __global__ __launch_bounds__(CNT_THREADS) void count_kernel(CountArgs a)
     __shared__ u64 s_keep[CNT_WORDS];
     __shared__ u32 s_pre[CNT_WORDS + 1];
     __shared__ u32 s_hist[EMIT ? CNT_LDS_HIST : 1];
-    __shared__ u16 s_ocnt[EMIT ? CNT_TILE : 2];     // count of the e-th kept run of the tile (U <= 65535)
+    __shared__ u16 s_ocnt[EMIT ? CNT_TILE : 2];     // count of the e-th kept run of the tile, when it fits 16 bits ...
+    __shared__ u32 s_olong;                         // ... else here: the tile's last run, the one that leaves the tile, is the only run of more than CNT_TILE records
+                                                    // (kept with 2^16 records and more only in the unfiltered pre-aggregation of a heavy-hitter task: upper = INT32_MAX)
     __shared__ u16 s_opos[EMIT ? CNT_TILE : 2];     // its first record
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const u64 ntiles = (a.n + CNT_TILE - 1) / CNT_TILE;
@@ -66,6 +68,7 @@ __global__ __launch_bounds__(CNT_THREADS) void count_kernel(CountArgs a)
     const u32 tn = (u32)((a.n - base) < (u64)CNT_TILE ? (a.n - base) : (u64)CNT_TILE);
     if (EMIT) __syncthreads();
     const u64 obase = EMIT ? a.tile_cnt[tile] : 0;             // issued early: not on the critical path at the end
+    if (EMIT && tid == 0) s_olong = 0;
     const u32 hn = (u32)((a.n - base - tn) < (u64)CNT_HALO ? (a.n - base - tn) : (u64)CNT_HALO);   // halo records available
     for (u32 i = tid; i < (tn + 1 + hn) * NW; i += CNT_THREADS) {     // records base-1 .. base+tn+hn-1
         const long long gi = (long long)(base * NW) + (long long)i - NW;
@@ -138,6 +141,7 @@ __global__ __launch_bounds__(CNT_THREADS) void count_kernel(CountArgs a)
             const u32 w = j * 4 + wave;
             const u32 slot = s_pre[w] + (u32)__popcll(s_keep[w] & ((1ULL << lane) - 1));
             s_opos[slot] = (u16)p; s_ocnt[slot] = (u16)c;
+            if (c > 0xFFFFu) s_olong = c;                     // (at most one run of a tile, and its last kept one)
             if (c < CNT_LDS_HIST) atomicAdd(&s_hist[c], 1u);
             else if (c < a.histo_len) atomicAdd((unsigned long long *)&a.histo[c], 1ULL);
         }
@@ -146,7 +150,7 @@ __global__ __launch_bounds__(CNT_THREADS) void count_kernel(CountArgs a)
         for (u32 i = tid; i < nkept * (NW + 1); i += CNT_THREADS) {      // one 8-byte word per lane, fully coalesced
             const u32 e = i / (NW + 1), x = i - e * (NW + 1);
             const u32 p = s_opos[e];
-            a.entries[(obase + e) * (NW + 1) + x] = (x < (u32)NW) ? s_k[(p + 1) * NW + x] : (u64)s_ocnt[e];
+            a.entries[(obase + e) * (NW + 1) + x] = (x < (u32)NW) ? s_k[(p + 1) * NW + x] : (u64)((e == nkept - 1 && s_olong) ? s_olong : s_ocnt[e]);
         }
         if (EXT) for (u32 e = tid; e < nkept; e += CNT_THREADS) a.run_start[obase + e] = a.payoff_add + base + s_opos[e];
     }

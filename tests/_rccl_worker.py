@@ -2,7 +2,8 @@
 communicator, or the stand-in transport named by HSK_RCCL_LIB when the ranks share one GPU; the id travels over a gloo
 group) and hsk_count on this rank's share of the reads -- and dumps the rank's list.  With spec["fail"] = "<rank>:<site>"
 the first count runs with that failure injected (HSK_TEST_FAIL) and must fail on EVERY rank; the count is then repeated on
-the same contexts and communicator without it.  Nothing here touches the oracle: the parent test compares."""
+the same contexts and communicator without it.  Optional spec keys: tuning, plan, plain_classifier, unbalanced_ratio go to the
+Context; counts gives the reads per rank in place of plan_partition_reads (rid_base stays the exscan).  Nothing here touches the oracle: the parent test compares."""
 import json
 import os
 import sys
@@ -23,13 +24,17 @@ def main():
     rank, size = comm.rank, comm.size
     seqs = json.load(open(spec["reads"]))
     counts = H.plan_partition_reads([len(s) for s in seqs], size)          # FastaIndex::getpartition
+    if spec.get("counts") is not None:                                     # the parent cuts the reads itself: reads per rank
+        counts = np.array(spec["counts"], dtype=np.int64)
+        assert counts.size == size and int(counts.sum()) == len(seqs)
     first = int(counts[:rank].sum())
     mine = seqs[first:first + int(counts[rank])]
     dna = H.DnaBuffer.from_sequences(mine)
     rid_base = comm.exscan_sum(dna.size())
     assert rid_base == first
     device = int(os.environ.get("HSK_FORCE_DEVICE", comm.local_rank))      # several ranks on one GPU (stand-in transport)
-    ctx = H.Context(K=spec["K"], M=spec["M"], L=spec["L"], U=spec["U"], EXT=spec["EXT"], ntasks=spec["ntasks"], device=device)
+    ctx = H.Context(K=spec["K"], M=spec["M"], L=spec["L"], U=spec["U"], EXT=spec["EXT"], ntasks=spec["ntasks"], device=device,
+                    tuning=spec.get("tuning"), plan=spec.get("plan"), plain_classifier=bool(spec.get("plain_classifier")), unbalanced_ratio=spec.get("unbalanced_ratio"))
     ctx.comm_init(comm)
     failure = None
     if spec.get("fail"):

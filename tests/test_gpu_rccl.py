@@ -20,9 +20,17 @@ from tests import util
 pytestmark = pytest.mark.gpu
 
 
+_NGPU = []
+
+
 def _ngpu():
-    import torch
-    return torch.cuda.device_count()
+    """Asked of a child process, once.  torch brings an RCCL and a HIP runtime of its own: imported here, they would be what a later dlopen of librccl in
+    THIS process finds (csrc/hsk_comm.h; test_gpu_multirank.py's test_rccl_binding_selftest), whichever file's tests ran first (tests/test_gpu_heavy.py
+    starts ranks through _run_ranks too)."""
+    if not _NGPU:
+        out = subprocess.check_output([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"], stderr=subprocess.DEVNULL)
+        _NGPU.append(int(out.decode().split()[-1]))
+    return _NGPU[0]
 
 
 def _transport_env():
