@@ -18,7 +18,8 @@
 //      writes keys (cursor / map / chunk protocol of hsk_chunks.h), the counts into the payload chunks; a table that fills up in
 //      the middle of a bucket is written out and started again, so a key may leave a bucket in several partial pairs: nothing
 //      downstream assumes otherwise; equal items of a bucket -- at c-fold coverage most of them -- are counted in an LDS item table first
-//      and rolled once, with their multiplicity as the weight (3a below; tuning combine_dedup);
+//      and rolled once, with their multiplicity as the weight, the k-mers of the distinct items handed to the lanes as one stream: equal
+//      work per lane whatever the items' lengths (3a below, hsk_lanes.h; tuning combine_dedup);
 //   4. the second radix pass carries the counts as the payload (onesweep_multi_kernel<1, true>), and the finish adds them up instead
 //      of counting records (agg_finish_kernel<cap, true>) over bins of the top 14 key bits: same order, same filter, same list.
 // At 32 instances per k-mer the pass and the finish move 1/26 of the records (a k-mer next to a read end misses some windows); what
@@ -32,6 +33,7 @@
 #include "hsk_expand.h"
 #include "hsk_scatter.h"
 #include "hsk_agg.h"
+#include "hsk_lanes.h"
 
 namespace hsk {
 
@@ -464,10 +466,16 @@ __device__ __forceinline__ void combine_dump(u64 *const (&kw)[NW], u32 *s_val, u
 //      at most 16, so it is never AG_EMPTY --, word 0 published behind it.  All-ones is that protocol's "not published yet": an item that
 //      starts with 32 T's never enters the table.  It, and an item whose probes ran out (a full table), stays with its lane as a DIRECT
 //      item, and the phase ends behind that step;
-//   B  the table's occupied slots are made a dense list (read to registers, block scan, written back: combine_dump's way) and handed out
-//      256 at a time to the first sweep and the probe loop, which add the item's multiplicity instead of 1; the direct items go first, with
-//      multiplicity 1.  A lane clears the entry it takes, so the table is empty again behind the last step.
-// A unit of more distinct items than the table holds takes several A/B rounds: the weights add up to the same counts.
+//   B  the table's occupied slots are made a dense list (read to registers, block scan, written back: combine_dump's way); the same scan
+//      gives every entry the offset of its first k-mer among the list's k-mers, kept beside the multiplicity in s_im (hsk_lanes.h).  The direct
+//      items go first, one item per lane with multiplicity 1 (roll).  The list is then ONE STREAM of k-mers, handed out by k-mer, not by
+//      item (`stream` below): a lane takes ceil(T / 256) consecutive k-mers, finds the entry of its first one by a binary search over the
+//      offsets and walks on across item ends, so the lanes of a wave work in step whatever the items' lengths (one item per lane left half
+//      the lanes idle: 7.6 k-mers per item on average, 16 steps for the longest).  The keys of a group of CB_GROUP k-mers stay in registers
+//      from the home reads to the probe loop, both add the item's multiplicity instead of 1, and a unit's first group -- nothing rolled
+//      since the k-mer table was written out -- skips the home reads, which could only miss.  The list is cleared in one sweep behind the
+//      last group, so the item table is empty again when phase A goes on.
+// A unit of more distinct items than the table holds takes several A/B rounds, each a stream of its own: the weights add up to the same counts.
 #ifndef CI_LOG2CAP
 #define CI_LOG2CAP 10
 #endif
@@ -478,6 +486,7 @@ constexpr int CI_PER = CI_CAP / CB_THREADS;
 #endif
 constexpr int CI_IPT = CI_IPT_N;                     // items a lane takes per step of phase A
 constexpr u32 CI_STEP = CI_IPT * CB_THREADS;
+static_assert(CB_THREADS == LN_LANES && CI_CAP <= LN_MAX_ITEMS && CB_UNIT < (1u << LN_MULT_BITS), "hsk_lanes.h: the workgroup's lanes, the list's entries, a multiplicity (at most a unit's items) beside the offset");
 
 // an item cut back to its own bases: cnt + k - 1 of them (cnt >= 1; at most 60 in all), the count byte kept
 __device__ __forceinline__ ulonglong2 item_own_bases(ulonglong2 itm, u32 cnt, int k)
@@ -494,25 +503,30 @@ __device__ __forceinline__ u32 item_slot(u64 w1, u64 w0)
 }
 // The item table as a dense list in its first `return value` slots, the slots behind them empty.  Called by the whole workgroup behind a
 // barrier (all inserts done); the barriers of the scan separate the reads from the writes, the caller's next barrier ends the writes.
-__device__ __forceinline__ u32 items_compact(u64 *s_i1, u64 *s_i0, u32 *s_im, u32 *s_scr)
+// The same scan carries the items' k-mer counts (hsk_lanes.h): an entry's s_im leaves as {multiplicity, offset of its first k-mer in the
+// list's k-mer stream}, nkmers as the stream's length.
+__device__ __forceinline__ u32 items_compact(u64 *s_i1, u64 *s_i0, u32 *s_im, u32 *s_scr, u32 &nkmers)
 {
     const int tid = threadIdx.x;
     u64 m1[CI_PER], m0[CI_PER]; u32 mc[CI_PER], c = 0;
 #pragma unroll
     for (int j = 0; j < CI_PER; ++j) {
         m1[j] = s_i1[j * CB_THREADS + tid]; m0[j] = s_i0[j * CB_THREADS + tid]; mc[j] = s_im[j * CB_THREADS + tid];
-        c += m1[j] != AG_EMPTY;
+        if (m1[j] != AG_EMPTY) c += lanes_scan_value(1u, (u32)(m1[j] & 0xFFULL));
     }
     u32 tot;
-    u32 o = block_excl_scan_xs<CB_WAVES>(c, s_scr, &tot);
+    const u32 ex = block_excl_scan_xs<CB_WAVES>(c, s_scr, &tot);
+    u32 o = lanes_scan_items(ex), p = lanes_scan_kmers(ex);
+    const u32 nd = lanes_scan_items(tot);
 #pragma unroll
     for (int j = 0; j < CI_PER; ++j) {
         const u32 sl = (u32)(j * CB_THREADS + tid);
         if (m1[j] == AG_EMPTY) continue;
-        if (sl >= tot) { s_i1[sl] = AG_EMPTY; s_i0[sl] = AG_EMPTY; s_im[sl] = 0; }      // (nobody's place in the list: the slot's owner empties it)
-        s_i1[o] = m1[j]; s_i0[o] = m0[j]; s_im[o] = mc[j]; ++o;
+        if (sl >= nd) { s_i1[sl] = AG_EMPTY; s_i0[sl] = AG_EMPTY; s_im[sl] = 0; }      // (nobody's place in the list: the slot's owner empties it)
+        s_i1[o] = m1[j]; s_i0[o] = m0[j]; s_im[o] = lanes_im(mc[j], p); ++o; p += (u32)(m1[j] & 0xFFULL);
     }
-    return tot;
+    nkmers = lanes_scan_kmers(tot);
+    return nd;
 }
 
 // CombineArgs::stat (DEDUP only): [0] items read, [1] items rolled (table entries + direct ones) -- added once per workgroup, like ghist
@@ -649,6 +663,112 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a)
 #pragma unroll
             for (int j = 0; j < CI_IPT; ++j) { const u32 i = at + (u32)(j * CB_THREADS + tid); x[j] = i < end ? t.recs[i] : make_ulonglong2(0, 0); }
         };
+        // ---- B: the list's nd entries as ONE STREAM of nkm k-mers (hsk_lanes.h).  Lane tid takes the k-mers [tid * n, (tid + 1) * n), n = ceil(nkm / 256):
+        //      it finds the entry of its first one by a binary search over the offsets in s_im and walks on from there -- inside an item the strands roll,
+        //      behind an item's last k-mer the next entry starts a fresh window, twin and multiplicity -- so every lane
+        //      has a k-mer in every step but the piece's last ones, whatever the items' lengths.  Per group of CB_GROUP k-mers the keys stay in registers:
+        //      the homes are read together, a k-mer found there adds its item's multiplicity, the others (a bit mask over the group) take the probe loop
+        //      with the keys they have, every lane its next one per round.  empty0 (uniform): nothing has been rolled into the k-mer table since it was
+        //      written out, so the first group's home reads would all miss: its k-mers go straight to the probe loop, position by position with all
+        //      their lanes.  Overflow as in roll: a lane keeps its remaining bits -- and its place in the piece -- across the dump.  The list is cleared
+        //      in one sweep behind the last group: the item table is empty again when phase A goes on. ----
+        auto stream = [&](const u32 nd, const u32 nkm, const bool empty0) {
+            if (nd == 0) return;
+            const u32 n = lanes_per(nkm);
+            u32 pos = lanes_begin((u32)tid, n);
+            const u32 end = lanes_end((u32)tid, n, nkm);
+            u32 e = 0, r = 0, cnt = 0, mult = 0;
+            u64 win0 = 0, win1 = 0;
+            Mer<1> fw, rc;
+            fw.w[0] = 0; rc.w[0] = 0;
+            // entry i becomes the lane's item; returns the offset of its first k-mer (behind the list's end: the last entry again, never used)
+            auto enter = [&](const u32 i) {
+                const u32 j = i < nd ? i : nd - 1u;
+                const u64 y = s_i1[j]; const u32 im = s_im[j];
+                win0 = s_i0[j]; win1 = y & ~0xFFULL; cnt = (u32)(y & 0xFFULL); mult = lanes_mult(im);
+                return lanes_off(im);
+            };
+            if (pos < end) {
+                e = lanes_find(s_im, nd, pos);
+                r = pos - enter(e);
+                fw.w[0] = (r ? funnel_left(win0, win1, 2 * (int)r) : win0) & lastmask;
+                rc = twin<1>(fw, k);
+            }
+            bool empty = empty0;
+#pragma unroll 1
+            for (u32 g0 = 0; g0 < n; g0 += CB_GROUP) {
+                u64 key[CB_GROUP]; u32 h[CB_GROUP], wq[CB_GROUP], mm = 0; ulonglong2 cur[CB_GROUP];
+                const u32 live = n - g0 < (u32)CB_GROUP ? n - g0 : (u32)CB_GROUP;      // steps of this group in which any lane has a k-mer (uniform)
+#pragma unroll
+                for (int q = 0; q < CB_GROUP; ++q) {
+                    key[q] = 0; h[q] = 0; wq[q] = 0; cur[q] = make_ulonglong2(0, 0);
+                    if ((u32)q >= live) continue;
+                    key[q] = rc.w[0] < fw.w[0] ? rc.w[0] : fw.w[0];
+                    h[q] = agg_slot<CB_LOG2CAP>(key[q]) & ~1u;
+                    wq[q] = mult;
+                    if (!empty) cur[q] = *reinterpret_cast<const ulonglong2 *>(&s_key[h[q]]);
+                    if (pos < end) {
+                        mm |= 1u << q; ++pos;
+                        if (lanes_step(e, r, cnt)) {
+                            enter(e);
+                            fw.w[0] = win0 & lastmask;
+                            rc = twin<1>(fw, k);
+                        } else {
+                            fw.w[0] = funnel_left(win0, win1, 2 * (int)r) & lastmask;
+                            const u64 nbase = (fw.w[0] >> low) & 3;
+                            rc.w[0] = ((rc.w[0] >> 2) | ((3 - nbase) << 62)) & lastmask;
+                        }
+                    }
+                }
+                if (!empty) {
+#pragma unroll
+                    for (int q = 0; q < CB_GROUP; ++q) {
+                        if ((mm >> q) & 1u) {
+                            if (cur[q].x == key[q]) { atomicAdd(&s_val[h[q]], wq[q]); mm &= ~(1u << q); }
+                            else if (cur[q].y == key[q]) { atomicAdd(&s_val[h[q] + 1u], wq[q]); mm &= ~(1u << q); }
+                        }
+                    }
+                }
+                bool dense = empty;
+                for (;;) {
+                    bool stuck = false;
+                    if (dense) {
+#pragma unroll
+                        for (int q = 0; q < CB_GROUP; ++q) {
+                            const bool mine = ((mm >> q) & 1u) != 0 && !stuck;
+                            const u64 act = __ballot(mine);
+                            if (act == 0) continue;
+                            u32 hh = h[q];
+                            const u64 left = agg_count_keys<(u32)CB_CAP - 1u>(act, key_lds, val_lds, hh, key[q], wq[q]);
+                            if (mine) { if ((left >> lane) & 1ULL) stuck = true; else mm &= ~(1u << q); }
+                        }
+                    } else {
+                        for (;;) {
+                            const bool mine = mm != 0 && !stuck;
+                            const u64 act = __ballot(mine);
+                            if (act == 0) break;
+                            const u32 qq = mine ? (u32)__builtin_ctz(mm) : 0u;
+                            u64 kk = key[0]; u32 hh = h[0], ww = wq[0];
+#pragma unroll
+                            for (int q = 1; q < CB_GROUP; ++q) if (qq == (u32)q) { kk = key[q]; hh = h[q]; ww = wq[q]; }
+                            const u64 left = agg_count_keys<(u32)CB_CAP - 1u>(act, key_lds, val_lds, hh, kk, ww);
+                            if (mine) { if ((left >> lane) & 1ULL) stuck = true; else mm &= mm - 1u; }
+                        }
+                    }
+                    const u32 fl = 1u + round % 3u;                    // (the rounds' flags, as in roll)
+                    if (tid == 0) s_flag[1u + (round + 1u) % 3u] = 0;
+                    if (mm) s_flag[fl] = 1;
+                    ++round;
+                    xs_barrier();
+                    if (s_flag[fl] == 0) break;
+                    dump();
+                    dense = false;
+                }
+                empty = false;
+            }
+            for (u32 i = (u32)tid; i < nd; i += CB_THREADS) { s_i1[i] = AG_EMPTY; s_i0[i] = AG_EMPTY; s_im[i] = 0; }
+            xs_barrier();
+        };
         for (;;) {
             xs_barrier();                                                 // (tables cleared / previous bucket dumped; the ticket word is free)
             if (tid == 0) s_flag[0] = __hip_atomic_fetch_add(&t.cs.ctl[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -658,6 +778,7 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a)
             const uint2 un = t.units[b];
             const u32 r0 = un.x, r1 = un.y;
             n_read += r1 - r0;
+            bool tbl_empty = true;                                        // nothing has been rolled since the k-mer table was written out (uniform)
             for (u32 base = r0; base < r1;) {
                 // ---- A: steps of CI_STEP items into the item table, until the unit ends or a lane has to keep an item ----
                 ulonglong2 cur[CI_IPT], ditm[CI_IPT];                 // ditm: this lane's direct items (count byte 0: none)
@@ -695,23 +816,25 @@ __global__ __launch_bounds__(CB_THREADS) void combine_kernel(CombineArgs a)
                     any_direct = s_flag[fl];
                 } while (base < r1 && !any_direct);
                 // ---- B: the distinct items with their multiplicities; the direct ones first ----
-                const u32 nd = items_compact(s_i1, s_i0, s_im, s_scr);
+                u32 nkm;
+                const u32 nd = items_compact(s_i1, s_i0, s_im, s_scr, nkm);
                 xs_barrier();
                 u32 ndir = 0;
 #pragma unroll
                 for (int j = 0; j < CI_IPT; ++j) ndir += (u32)__popcll(__ballot((ditm[j].y & 0xFFULL) != 0));
                 if (lane == 0) n_rolled += (tid == 0 ? nd : 0u) + ndir;
-                for (u32 i = any_direct ? 0u : (u32)CI_IPT; i < (u32)CI_IPT + (nd + CB_THREADS - 1u) / CB_THREADS; ++i) {
-                    ulonglong2 itm = make_ulonglong2(0, 0); u32 mult = 1u;
-                    if (i < (u32)CI_IPT) {
+                if (any_direct) {
+#pragma unroll 1
+                    for (u32 i = 0; i < (u32)CI_IPT; ++i) {
+                        ulonglong2 itm = make_ulonglong2(0, 0);
 #pragma unroll
                         for (int j = 0; j < CI_IPT; ++j) if (i == (u32)j) itm = ditm[j];
-                    } else {
-                        const u32 e = (i - (u32)CI_IPT) * CB_THREADS + (u32)tid;
-                        if (e < nd) { itm = make_ulonglong2(s_i0[e], s_i1[e]); mult = s_im[e]; s_i1[e] = AG_EMPTY; s_i0[e] = AG_EMPTY; s_im[e] = 0; }
+                        roll(itm, 1u);
                     }
-                    roll(itm, mult);
+                    tbl_empty = false;
                 }
+                stream(nd, nkm, tbl_empty);
+                tbl_empty = false;
             }
             dump();
         }
