@@ -35,6 +35,7 @@
 #include "hsk_count.h"
 #include "hsk_finish.h"
 #include "hsk_agg.h"
+#include "hsk_pairfinish.h"
 #include "hsk_combine.h"
 #include "hsk_heavy.h"
 #include "hsk_pairs.h"

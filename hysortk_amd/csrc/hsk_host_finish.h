@@ -260,14 +260,32 @@ static void with_cap(int log2cap, F &&f)
     else f(std::integral_constant<int, AG_LOG2CAP_LARGE>{});
 }
 
+// The first rung of the weighted finish of one-word keys is pair_finish_kernel (hsk_pairfinish.h: sort-merge of a bin's pairs, persistent
+// workgroups).  tuning "agg_adapt=3": the table finishes adapt as with 1, and that rung is a table too -- agg_finish_kernel<cap, true>
+// like every other finish, the form before 6.13 (the tests compare the two; the tuning table's rows are pinned, so the switch is a value of this row)
+constexpr long long AGG_ADAPT_TABLES_ONLY = 3;
+template <int NW>
+static bool pair_finish_first(const hsk_ctx *c, bool weighted) { return NW == 1 && weighted && c->tune.agg_adapt != AGG_ADAPT_TABLES_ONLY; }
+// its grid: as many workgroups as the device holds at once (the occupancy of the instance x 256 CUs, as combine_kernel's), shared among the
+// batch's active tasks; a workgroup walks a contiguous range of its task's bins
+static u32 pair_finish_grid(const AggArgs &a)
+{
+    static int occ = 0;
+    if (!occ) { int nb = 0; occ = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pair_finish_kernel, AG_THREADS, 0) == hipSuccess && nb > 0) ? nb : 4; }
+    u32 nact = 0; for (int i = 0; i < AG_BATCH; ++i) nact += a.t[i].active ? 1u : 0u;
+    return std::min<u32>(a.nbins, std::max<u32>(1u, (u32)occ * 256u / std::max<u32>(nact, 1u)));
+}
+
 // One rung of the ladder: the aggregation kernel with a 2^log2cap table over all bins (grid_x = nbins) or over the listed
 // bins (grid_x = the longest list).  Three-word keys have no weighted kernel, only one-word keys the 8192-slot one.
+// first: the rung over all bins (agg_stage1); that of the weighted finish of one-word keys is pair_finish_kernel.
 template <int NW>
-static int agg_launch_rung(hsk_ctx *c, AggPending &p, int log2cap, u32 grid_x, u64 records)
+static int agg_launch_rung(hsk_ctx *c, AggPending &p, int log2cap, u32 grid_x, u64 records, bool first = false)
 {
     const AggArgs &a = p.a; const dim3 grid(grid_x, AG_BATCH), block(AG_THREADS);
     // (record bytes READ: keys, and the counts of {k-mer, count} pairs)
     profiled(c, 2, records, records * (NW * 8 + (p.weighted ? 8 : 0)), [&] {
+        if constexpr (NW == 1) if (first && pair_finish_first<NW>(c, p.weighted)) { hipLaunchKernelGGL(pair_finish_kernel, dim3(pair_finish_grid(a), AG_BATCH), block, 0, c->stream, a); return; }
         if constexpr (NW == 1) if (log2cap == AG_LOG2CAP_HUGE && !p.weighted) { hipLaunchKernelGGL(agg_big_kernel, grid, dim3(AGB_THREADS), 0, c->stream, a); return; }
         with_cap(log2cap, [&](auto cap) {
             constexpr int CAP = decltype(cap)::value;
@@ -380,8 +398,12 @@ static int agg_stage1(hsk_ctx *c, const BatchTask *bt, int K, int prefix_bits, i
     if (weighted) {                                      // pairs are (nearly) all distinct: the table that takes the average bin twice over
         const u64 avg = nmax / nbins + 1;
         p.first_cap = avg * 2 <= 600 ? AG_LOG2CAP_SMALL : avg * 2 <= 1200 ? AG_LOG2CAP_MEDIUM : AG_LOG2CAP_LARGE;
+        // pair_finish_kernel has one size, and it is a number of PAIRS, not of distinct keys in a table: a bin of up to PF_CAP = 2^11 pairs
+        // whatever the average; the ladder goes on from there (the 4096-slot table takes the listed bins)
+        static_assert(PF_CAP == 1u << AG_LOG2CAP_MEDIUM, "the first rung of the weighted finish counts as the medium one");
+        if (pair_finish_first<NW>(c, weighted)) p.first_cap = AG_LOG2CAP_MEDIUM;
     }
-    int rc = agg_launch_rung<NW>(c, p, p.first_cap, nbins, p.ntot); if (rc) return rc;
+    int rc = agg_launch_rung<NW>(c, p, p.first_cap, nbins, p.ntot, true); if (rc) return rc;
     rc = agg_launch_scan(c, p); if (rc) return rc;
     p.ev = ev_get(c);
     HIPCHK(c, hipEventRecord(p.ev, c->stream));

@@ -48,7 +48,7 @@ namespace hsk {
     X(xs2, 1)                      /* 0: expand_scatter_kernel (one sweep per flush) where expand_scatter2_kernel would run */           \
     X(scatter_generic, 0)          /* 1: the generic fused-scatter instance for the default k too */                                     \
     /* table finishes (hsk_host_finish.h) */                                                                                             \
-    X(agg_adapt, 1)                /* 0: never leave the aggregation, 2: leave it after the first batch */                               \
+    X(agg_adapt, 1)                /* 0: never leave the aggregation, 2: leave it after the first batch, 3: as 1 with tables on every rung */ \
     X(agg_large, 1)                /* 0: a prefix bin of 65536 records and more is counted by one workgroup, not in slices */            \
     X(agg_maxrung, 13)             /* last rung of the table ladder (AG_LOG2CAP_HUGE; tests stop it early: the long way) */              \
     /* combining extraction (hsk_host_combine.h, hsk_host_pipeline.h) */                                                                 \
