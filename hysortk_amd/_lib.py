@@ -99,7 +99,7 @@ SYMBOLS = [
     "hsk_count", "hsk_count_device", "hsk_count_loopback", "hsk_count_loopback_device", "hsk_result_free", "hsk_result_device_task", "hsk_result_pairs", "hsk_pairs_free", "hsk_format_entries", "hsk_get_stats",
     "hsk_result_pairs_sliced", "hsk_pairs_merge",
     "hsk_result_strands", "hsk_strands_task", "hsk_strands_free", "hsk_result_pairs_oriented",
-    "hsk_result_pair_diagonals", "hsk_pair_diags_free",
+    "hsk_result_pair_diagonals", "hsk_pair_diags_free", "hsk_result_pair_diagonals_sliced", "hsk_pair_diags_merge",
     "hsk_stage_destinations", "hsk_stage_task_kmers", "hsk_stage_sort", "hsk_stage_count_sorted",
     "hsk_plan_tot_tasks", "hsk_plan_classify", "hsk_plan_dispatch", "hsk_plan_partition_reads", "hsk_plan_exchange",
     "hsk_comm_get_unique_id", "hsk_comm_init", "hsk_comm_destroy", "hsk_comm_selftest",
@@ -161,6 +161,9 @@ def load():
                                             C.POINTER(Pairs), C.POINTER(PairsSlices)]
     L.hsk_result_pair_diagonals.argtypes = [vp, C.POINTER(Result), C.POINTER(Strands), C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32,
                                             C.POINTER(PairDiags)]
+    L.hsk_result_pair_diagonals_sliced.argtypes = [vp, C.POINTER(Result), C.POINTER(Strands), C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, C.c_int32, C.c_int32,
+                                                   C.c_uint64, C.POINTER(PairDiags), C.POINTER(PairsSlices)]
+    L.hsk_pair_diags_merge.argtypes = [vp, C.POINTER(C.POINTER(PairDiags)), C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(PairDiags)]
     L.hsk_pair_diags_free.argtypes = [vp, C.POINTER(PairDiags)]
     L.hsk_pair_diags_free.restype = None
     L.hsk_pairs_free.argtypes = [vp, C.POINTER(Pairs)]

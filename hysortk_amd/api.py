@@ -326,7 +326,8 @@ class PairDiagonals:
     on opposite strands (o = 1), its bin D // diag_bin.  all_bins=False: one row per key -- the bin with the most records (the smallest such
     bin on a tie), `support` its records, `shared` the records of the key over all bins, first_pos_* / last_pos_* the smallest / largest
     (pos_a, pos_b) of that bin only.  all_bins=True: one row per (key, bin), ascending, shared == support.  With on_device the rows stay in
-    HBM (rows_dev: n rows of six uint64 words; close() gives them back).  select() and combine() work on all-bins lists, on the host."""
+    HBM (rows_dev: n rows of six uint64 words; close() gives them back).  select() and combine() work on all-bins lists, on the host or, with
+    a Context, on its GPU."""
 
     COLS = 6
 
@@ -365,12 +366,15 @@ class PairDiagonals:
         lo = self.bin.astype(np.int64) * w - np.where(self.opposite, 0, 1 << 32)
         return lo, lo + (w - 1)
 
-    def select(self, min_support=1):
-        """The selection property (include/hsk.h), on the host: the list by best bin of an all-bins list that was computed with
-        min_support=1 -- per key shared is the sum of support, the row with the largest support is kept (the smallest bin on a tie), and
-        min_support is applied afterwards."""
+    def select(self, min_support=1, ctx=None, on_device=False):
+        """The selection property (include/hsk.h): the list by best bin of an all-bins list that was computed with min_support=1 -- per
+        key shared is the sum of support, the row with the largest support is kept (the smallest bin on a tie), and min_support is
+        applied afterwards.  Without ctx: on the host, in numpy.  With a Context: hsk_pair_diags_merge of this one list on its GPU (rows
+        in HBM are read there; on_device=True leaves the result there)."""
         if not self.all_bins:
             raise ValueError("select() is for an all-bins list")
+        if ctx is not None:
+            return PairDiagonals._combine_device([self], ctx, False, min_support, on_device, self.diag_bin)
         r = self.rows()
         info = dict(self.info)
         if not r.shape[0]:
@@ -389,10 +393,13 @@ class PairDiagonals:
         return PairDiagonals.from_rows(out[out[:, 3] >= np.uint64(min_support)], diag_bin=self.diag_bin, all_bins=False, info=info)
 
     @staticmethod
-    def combine(parts):
-        """The several-list contract, on the host: the all-bins list of the union of disjoint task ranges, or of the ranks of a several-GPU
-        run, from their all-bins lists (computed with min_support=1, same diag_bin): rows with equal (key, bin) join -- support and shared
-        add up, first is the minimum, last the maximum.  Best-bin lists do not combine (ValueError): select() the joined list."""
+    def combine(parts, ctx=None, all_bins=True, min_support=1, on_device=False):
+        """The several-list contract: the all-bins list of the union of disjoint task ranges, or of the ranks of a several-GPU run, from
+        their all-bins lists (computed with min_support=1, same diag_bin): rows with equal (key, bin) join -- support and shared add up,
+        first is the minimum, last the maximum.  Best-bin lists do not combine (ValueError): select() the joined list.  Without ctx: on
+        the host, in numpy (the parts' rows must be on the host).  With a Context: hsk_pair_diags_merge on its GPU -- parts whose rows
+        are on the device are read there, host rows are uploaded, min_support is applied after the join, all_bins=False runs the
+        selection on the joined list, and on_device=True leaves the result in HBM."""
         parts = list(parts)
         if any(not p.all_bins for p in parts):
             raise ValueError("lists by best bin do not combine: combine the all-bins lists, then select()")
@@ -400,6 +407,10 @@ class PairDiagonals:
         if len(widths) > 1:
             raise ValueError("lists of different diag_bin do not combine")
         w = widths.pop() if widths else None
+        if ctx is not None:
+            return PairDiagonals._combine_device(parts, ctx, all_bins, min_support, on_device, w)
+        if not all_bins or min_support != 1 or on_device:
+            raise ValueError("all_bins=False, min_support and on_device are for the device join: give a ctx, or select() the joined list")
         info = {k: sum(int(p.info.get(k, 0)) for p in parts) for k in ("records", "self_records")}
         rows = [p.rows() for p in parts if len(p)]
         if not rows:
@@ -415,10 +426,30 @@ class PairDiagonals:
         return PairDiagonals.from_rows(out, diag_bin=w, all_bins=True, info=info)
 
     @staticmethod
-    def _wrap(ctx, pd, on_device, diag_bin, all_bins):
+    def _combine_device(parts, ctx, all_bins, min_support, on_device, diag_bin):
+        structs, keep = [], []
+        for p in parts:
+            s = _lib.PairDiags()
+            s.n = len(p)
+            s.records, s.self_records = int(p.info.get("records", 0)), int(p.info.get("self_records", 0))
+            if len(p) and p.rows_dev:
+                s.rows_dev = p.rows_dev
+            elif len(p):
+                r = np.ascontiguousarray(p.rows(), dtype=np.uint64)
+                keep.append(r)
+                s.rows = r.ctypes.data_as(C.POINTER(C.c_uint64))
+            structs.append(s)
+        arr = (C.POINTER(_lib.PairDiags) * max(len(structs), 1))(*[C.pointer(s) for s in structs])
+        pd = _lib.PairDiags()
+        ctx._check(ctx.lib.hsk_pair_diags_merge(ctx.h, arr, len(structs), int(min_support), 1 if all_bins else 0, 1 if on_device else 0, C.byref(pd)))
+        return PairDiagonals._wrap(ctx, pd, on_device, diag_bin, bool(all_bins))
+
+    @staticmethod
+    def _wrap(ctx, pd, on_device, diag_bin, all_bins, extra=None):
         """A PairDiagonals from a filled hsk_pair_diags: the rows copied to numpy and the struct freed, or (on_device) left in HBM and owned."""
         info = dict(records=int(pd.records), self_records=int(pd.self_records), keys=int(pd.keys), bins=int(pd.bins), sort_passes=int(pd.sort_passes),
                     ms_expand=pd.ms_expand, ms_sort=pd.ms_sort, ms_reduce=pd.ms_reduce, ms_d2h=pd.ms_d2h, ms_total=pd.ms_total)
+        info.update(extra or {})
         n = int(pd.n)
         if on_device:
             z = np.zeros(0, np.uint64)
@@ -561,13 +592,22 @@ class DeviceResult:
         extra = dict(slices=int(sl.slices), peak_records=int(sl.peak_records), merges=int(sl.merges), merged_rows=int(sl.merged_rows), ms_merge=sl.ms_merge)
         return ReadPairs._wrap(self.ctx, pr, on_device, extra)
 
-    def pair_diagonals(self, strands, diag_bin, task_lo=0, task_hi=None, min_support=1, all_bins=False, on_device=False):
+    def pair_diagonals(self, strands, diag_bin, task_lo=0, task_hi=None, min_support=1, all_bins=False, on_device=False, max_records=None):
         """hsk_result_pair_diagonals over tasks [task_lo, task_hi) (default: all): the records of pairs(strands=...) binned by diagonal
         (bins of diag_bin diagonals), as a PairDiagonals -- per oriented read pair the bin with the most records (all_bins=False), or every
         (pair, bin) (all_bins=True: what disjoint task ranges and ranks combine through, PairDiagonals.combine and .select).  strands: the
-        Strands of this result.  on_device=True leaves the rows in HBM (close() it before the context goes)."""
+        Strands of this result.  on_device=True leaves the rows in HBM (close() it before the context goes).  max_records=N:
+        hsk_result_pair_diagonals_sliced -- the same list, from at most N records expanded at a time (0: the library chooses from the
+        device memory that is left); info then has slices, peak_records, merges, merged_rows and ms_merge."""
         pd = _lib.PairDiags()
         hi = self.ntasks if task_hi is None else task_hi
+        if max_records is not None:
+            sl = _lib.PairsSlices()
+            self.ctx._check(self.ctx.lib.hsk_result_pair_diagonals_sliced(self.ctx.h, C.byref(self.res), C.byref(strands.st) if strands is not None else None, task_lo, hi,
+                                                                          int(diag_bin), int(min_support), 1 if all_bins else 0, 1 if on_device else 0, int(max_records),
+                                                                          C.byref(pd), C.byref(sl)))
+            extra = dict(slices=int(sl.slices), peak_records=int(sl.peak_records), merges=int(sl.merges), merged_rows=int(sl.merged_rows), ms_merge=sl.ms_merge)
+            return PairDiagonals._wrap(self.ctx, pd, on_device, int(diag_bin), bool(all_bins), extra)
         self.ctx._check(self.ctx.lib.hsk_result_pair_diagonals(self.ctx.h, C.byref(self.res), C.byref(strands.st) if strands is not None else None, task_lo, hi,
                                                                int(diag_bin), int(min_support), 1 if all_bins else 0, 1 if on_device else 0, C.byref(pd)))
         return PairDiagonals._wrap(self.ctx, pd, on_device, int(diag_bin), bool(all_bins))

@@ -41,6 +41,7 @@
 #include "hsk_pairs.h"
 #include "hsk_pairmerge.h"
 #include "hsk_pairdiag.h"
+#include "hsk_diagmerge.h"
 #include "hsk_strand.h"
 #include "hsk_estimate.h"
 #include "hsk_synth.h"

@@ -1,5 +1,6 @@
 // hsk_host_pairs.h -- host side of hsk_result_pairs, hsk_result_pairs_sliced, hsk_result_pairs_oriented and hsk_pairs_merge: read pairs that
-// share k-mers, from the resident EXTENSION list (kernels: hsk_pairs.h, hsk_pairmerge.h).
+// share k-mers, from the resident EXTENSION list (kernels: hsk_pairs.h, hsk_pairmerge.h).  The slice plan, the merge of two lists, the stack of
+// lists and the several-list call are templates over the rows: hsk_host_pairdiag.h uses them for the six-word rows of the diagonals.
 // Part of the single translation unit hsk_api.hip (included in this order; everything here is file-local).
 #pragma once
 
@@ -224,33 +225,47 @@ static int pairs_window(hsk_ctx *c, PairRange &r, const PairWindow &w, bool last
 
 // ---- merges ------------------------------------------------------------------------------------------------------------------------
 struct PairMergeStat { u64 merges = 0, merged_rows = 0; };
+struct PairMergeCounts { u64 keys = 0, bins = 0; };      // of a merged list before the filter: distinct keys; rows (the six-word lists only)
 
-// One merge (CountEmit: COUNT, the scans, EMIT) of two lists on the device into a block of its own; one wait, for the row count.  *keys: the
-// rows before min_shared.  The inputs are left to the caller.
-static int pairs_merge_two(hsk_ctx *c, const PairList &A, const PairList &B, u32 min_shared, PairClock &ck, PairMergeStat &ms, PairList *out, u64 *keys)
+// What a merge of two row lists needs to know about the rows: their width, the tile of the merge kernel, how many tile arrays its COUNT
+// pass fills (the kept rows first, then the counts before the filter) and the two launches.  The four-word rows of the pair lists are
+// PairRows; the six-word all-bins rows of the diagonals are DiagRows (hsk_host_pairdiag.h).
+struct PairRows {
+    static constexpr u64 ROW_BYTES = 32, TILE = PM_TILE;
+    static constexpr int NTILE = 2;                      // kept rows, keys
+    static constexpr bool COUNT_ONE = false;             // a single list's counts are known without a merge: keys = its rows
+    static void launch(hsk_ctx *c, bool emit, u32 tiles, const PairList &A, const PairList &B, u32 min_shared, u64 *const *tile, u64 *rows)
+    {
+        PairMergeArgs ma; memset(&ma, 0, sizeof ma);
+        ma.a = A.rows; ma.na = A.n; ma.b = B.rows; ma.nb = B.n; ma.min_shared = min_shared; ma.tile_cnt = tile[0]; ma.tile_keys = tile[1]; ma.rows = rows;
+        if (emit) hipLaunchKernelGGL(pair_merge_kernel<true>, dim3(tiles), dim3(PM_THREADS), 0, c->stream, ma);
+        else hipLaunchKernelGGL(pair_merge_kernel<false>, dim3(tiles), dim3(PM_THREADS), 0, c->stream, ma);
+    }
+    static void counts(const u64 *st, PairMergeCounts *n) { n->keys = st[1]; n->bins = 0; }
+};
+
+// One merge (CountEmit: COUNT, the scans, EMIT) of two lists on the device into a block of its own; one wait, for the row count.  *cnt: the
+// counts before the filter.  The inputs are left to the caller.
+template <typename R>
+static int pairs_merge_two(hsk_ctx *c, const PairList &A, const PairList &B, u32 min_shared, PairClock &ck, PairMergeStat &ms, PairList *out, PairMergeCounts *cnt)
 {
     out->rows = nullptr; out->n = 0; out->owned = true; out->level = std::max(A.level, B.level) + 1;
-    *keys = 0;
+    *cnt = PairMergeCounts();
     const u64 total = A.n + B.n;
     if (!total) return HSK_OK;
-    const u64 tiles = (total + PM_TILE - 1) / PM_TILE;
+    const u64 tiles = (total + R::TILE - 1) / R::TILE;
     if (tiles > 0x7fffffffULL) return fail(c, HSK_ERR_UNSUPPORTED, "%llu rows are more than one launch merges", (unsigned long long)total);
-    u64 *d_tot; DALLOC(c, d_tot, u64 *, 2 * 8);
-    PairMergeArgs ma; memset(&ma, 0, sizeof ma);
-    ma.a = A.rows; ma.na = A.n; ma.b = B.rows; ma.nb = B.n; ma.min_shared = min_shared;
-    CountEmit ce(c, ck, PT_MERGE, tiles, 2);
-    static const int word[2] = {0, 1};
+    u64 *d_tot; DALLOC(c, d_tot, u64 *, R::NTILE * 8);
+    CountEmit ce(c, ck, PT_MERGE, tiles, R::NTILE);
+    static const int word[3] = {0, 1, 2};
     const u64 *st;
-    int rc = ce.count(d_tot, 2, word, &st, [&] {
-        ma.tile_cnt = ce.tile[0]; ma.tile_keys = ce.tile[1];
-        hipLaunchKernelGGL(pair_merge_kernel<false>, dim3((u32)tiles), dim3(PM_THREADS), 0, c->stream, ma);
-    });
+    int rc = ce.count(d_tot, R::NTILE, word, &st, [&] { R::launch(c, false, (u32)tiles, A, B, min_shared, ce.tile, nullptr); });
     if (rc) return rc;
     const u64 nrows = st[0];
-    *keys = st[1];
-    if (nrows > total || st[1] > total) return fail(c, HSK_ERR_INTERNAL, "the merge of %llu rows counted %llu", (unsigned long long)total, (unsigned long long)std::max(nrows, st[1]));
-    if (nrows) { DALLOC(c, out->rows, u64 *, nrows * 32); ma.rows = out->rows; }
-    rc = ce.emit(nrows != 0, [&] { hipLaunchKernelGGL(pair_merge_kernel<true>, dim3((u32)tiles), dim3(PM_THREADS), 0, c->stream, ma); });
+    R::counts(st, cnt);
+    if (nrows > total || cnt->keys > total || cnt->bins > total) return fail(c, HSK_ERR_INTERNAL, "the merge of %llu rows counted %llu", (unsigned long long)total, (unsigned long long)std::max(nrows, std::max(cnt->keys, cnt->bins)));
+    if (nrows) DALLOC(c, out->rows, u64 *, nrows * R::ROW_BYTES);
+    rc = ce.emit(nrows != 0, [&] { R::launch(c, true, (u32)tiles, A, B, min_shared, ce.tile, out->rows); });
     if (rc) return rc;
     out->n = nrows;
     c->pool.release(d_tot);
@@ -260,12 +275,14 @@ static int pairs_merge_two(hsk_ctx *c, const PairList &A, const PairList &B, u32
 
 // The lists of the slices (or the caller's parts) in the order of a binary counter: a list enters at level 0, and while the two lists
 // on top have the same level they become one list of the next level.  A row is read by at most ceil(log2(lists)) + 1 merges, and no
-// list grows by one slice at a time.  finish() merges what is left, top first; the LAST merge applies min_shared and counts the keys.
+// list grows by one slice at a time.  finish() merges what is left, top first; the LAST merge applies the filter and counts the list
+// before it.  R: the rows (PairRows, DiagRows).
+template <typename R>
 struct PairStack {
     std::vector<PairList> v;
     PairMergeStat ms;
     static void drop(hsk_ctx *c, PairList &l) { if (l.owned) c->pool.release(l.rows); l.rows = nullptr; l.n = 0; }
-    int merge_top(hsk_ctx *c, u32 min_shared, bool final, PairClock &ck, u64 *keys)
+    int merge_top(hsk_ctx *c, u32 min_shared, bool final, PairClock &ck, PairMergeCounts *cnt)
     {
         PairList B = v.back(); v.pop_back();
         PairList A = v.back(); v.pop_back();
@@ -274,7 +291,7 @@ struct PairStack {
             o = A.n ? A : B; o.level = std::max(A.level, B.level) + 1;
             drop(c, A.n ? B : A);
         } else {
-            const int rc = pairs_merge_two(c, A, B, min_shared, ck, ms, &o, keys); if (rc) return rc;
+            const int rc = pairs_merge_two<R>(c, A, B, min_shared, ck, ms, &o, cnt); if (rc) return rc;
             drop(c, A); drop(c, B);                      // (behind the merge on the stream)
         }
         v.push_back(o);
@@ -284,19 +301,19 @@ struct PairStack {
     int push(hsk_ctx *c, const PairList &l, bool more, PairClock &ck)
     {
         v.push_back(l);
-        u64 keys;
-        while (more && v.size() >= 2 && v[v.size() - 1].level == v[v.size() - 2].level) { const int rc = merge_top(c, 1, false, ck, &keys); if (rc) return rc; }
+        PairMergeCounts cnt;
+        while (more && v.size() >= 2 && v[v.size() - 1].level == v[v.size() - 2].level) { const int rc = merge_top(c, 1, false, ck, &cnt); if (rc) return rc; }
         return HSK_OK;
     }
-    int finish(hsk_ctx *c, u32 min_shared, PairClock &ck, PairList *fin, u64 *keys)
+    int finish(hsk_ctx *c, u32 min_shared, PairClock &ck, PairList *fin, PairMergeCounts *cnt)
     {
-        *fin = PairList(); *keys = 0;
+        *fin = PairList(); *cnt = PairMergeCounts();
         if (v.empty()) return HSK_OK;
         if (v.size() == 1) {
-            if (min_shared > 1 && v[0].n) v.push_back(PairList());      // one list: the filter is a merge with nothing
-            else { *fin = v[0]; *keys = v[0].n; v.clear(); return HSK_OK; }
+            if ((min_shared > 1 || R::COUNT_ONE) && v[0].n) v.push_back(PairList());      // one list: the filter (and the count) is a merge with nothing
+            else { *fin = v[0]; cnt->keys = v[0].n; v.clear(); return HSK_OK; }
         }
-        while (v.size() > 1) { const int rc = merge_top(c, v.size() == 2 ? min_shared : 1, v.size() == 2, ck, keys); if (rc) return rc; }
+        while (v.size() > 1) { const int rc = merge_top(c, v.size() == 2 ? min_shared : 1, v.size() == 2, ck, cnt); if (rc) return rc; }
         *fin = v[0]; v.clear();
         return HSK_OK;
     }
@@ -338,12 +355,42 @@ static void pairs_store(Out *out, u64 nrows, const PairsPriv *pp, const PairCall
 // What hsk_result_pairs_sliced expands at a time when the caller leaves it to the library (include/hsk.h): 1/96 of the device memory the
 // context can still get -- what the runtime reports free plus what the context's pool holds unused -- in records: a third of it for the
 // 32 bytes a record takes, the rest for the row lists and the merges.
-static u64 pairs_auto_budget(hsk_ctx *c)
+// `bytes`: what a record takes while its slice is sorted (32 here; 48 for the two-word keys of hsk_result_pair_diagonals_sliced: 1/144).
+static u64 pairs_auto_budget(hsk_ctx *c, u64 bytes = 32)
 {
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); fr = 0; }
-    const u64 b = ((u64)fr + c->pool.bytes_cached) / 96;
+    const u64 b = ((u64)fr + c->pool.bytes_cached) / (3 * bytes);
     return b ? b : 1;
+}
+
+// The plan of a sliced call: every cut of the range's entries under the budget and the record offset at it, in one launch and one wait
+// (one lane cuts the whole range on the device, pair_plan_kernel: reading a cut back per slice would wait once per slice).  win: the
+// slices that hold records (a run of entries without any in front of a large entry is none), in the order of the entries.
+static int pairs_plan_windows(hsk_ctx *c, const PairRange &r, u64 budget, std::vector<PairWindow> &win)
+{
+    const u64 records = r.records;
+    const u64 cap = pair_plan_max_slices(r.nent, records, budget);
+    u64 *d_cut; DALLOC(c, d_cut, u64 *, (2 * cap + 1) * 8);
+    PairPlanArgs pa; memset(&pa, 0, sizeof pa);
+    pa.off = r.d_off; pa.nent = r.nent; pa.max_records = budget; pa.cut = d_cut; pa.cap = cap; pa.ncut = d_cut + 2 * cap;
+    hipLaunchKernelGGL(pair_plan_kernel, dim3(1), dim3(1), 0, c->stream, pa);
+    HIPCHK(c, hipGetLastError());
+    std::vector<u64> cut(2 * cap + 1);
+    HIPCHK(c, hipMemcpyAsync(cut.data(), d_cut, cut.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hsk_sync(c, c->stream));
+    c->pool.release(d_cut);
+    const u64 ncut = cut[2 * cap];
+    if (ncut == 0 || ncut > cap || cut[2 * (ncut - 1)] != r.nent || cut[2 * (ncut - 1) + 1] != records)
+        return fail(c, HSK_ERR_INTERNAL, "the slice plan of %llu entries does not end at the last one", (unsigned long long)r.nent);
+    u64 e0 = 0, r0 = 0;
+    for (u64 i = 0; i < ncut; ++i) {
+        const u64 e1 = cut[2 * i], r1 = cut[2 * i + 1];
+        if (e1 <= e0 || r1 < r0) return fail(c, HSK_ERR_INTERNAL, "the slice plan does not advance at entry %llu", (unsigned long long)e0);
+        if (r1 > r0) { const PairWindow w = {e0, e1, r0, r1 - r0}; win.push_back(w); }
+        e0 = e1; r0 = r1;
+    }
+    return HSK_OK;
 }
 
 // The tasks of the range go through ONE launch per kernel over a device table of task descriptors (at most HSK_MAX_TASKS of them).
@@ -369,29 +416,9 @@ static int pairs_impl(hsk_ctx *c, const ResultPriv *rp, const StrandsPriv *sp, i
         rc = pairs_window(c, r, w, true, oriented, min_shared, task_lo, task_hi, ck, out, &fin); if (rc) return rc;
         info->peak_records = records;
     } else {
-        // ---- the plan: every cut and the record offset at it, in one launch and one wait ---------------------------------------------
-        const u64 cap = pair_plan_max_slices(r.nent, records, budget);
-        u64 *d_cut; DALLOC(c, d_cut, u64 *, (2 * cap + 1) * 8);
-        PairPlanArgs pa; memset(&pa, 0, sizeof pa);
-        pa.off = r.d_off; pa.nent = r.nent; pa.max_records = budget; pa.cut = d_cut; pa.cap = cap; pa.ncut = d_cut + 2 * cap;
-        hipLaunchKernelGGL(pair_plan_kernel, dim3(1), dim3(1), 0, c->stream, pa);
-        HIPCHK(c, hipGetLastError());
-        std::vector<u64> cut(2 * cap + 1);
-        HIPCHK(c, hipMemcpyAsync(cut.data(), d_cut, cut.size() * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hsk_sync(c, c->stream));
-        c->pool.release(d_cut);
-        const u64 ncut = cut[2 * cap];
-        if (ncut == 0 || ncut > cap || cut[2 * (ncut - 1)] != r.nent || cut[2 * (ncut - 1) + 1] != records)
-            return fail(c, HSK_ERR_INTERNAL, "the slice plan of %llu entries does not end at the last one", (unsigned long long)r.nent);
-        std::vector<PairWindow> win;                     // the slices that hold records (a run of entries without any in front of a large entry is none)
-        u64 e0 = 0, r0 = 0;
-        for (u64 i = 0; i < ncut; ++i) {
-            const u64 e1 = cut[2 * i], r1 = cut[2 * i + 1];
-            if (e1 <= e0 || r1 < r0) return fail(c, HSK_ERR_INTERNAL, "the slice plan does not advance at entry %llu", (unsigned long long)e0);
-            if (r1 > r0) { const PairWindow w = {e0, e1, r0, r1 - r0}; win.push_back(w); }
-            e0 = e1; r0 = r1;
-        }
-        PairStack stk;
+        std::vector<PairWindow> win;
+        rc = pairs_plan_windows(c, r, budget, win); if (rc) return rc;
+        PairStack<PairRows> stk;
         hsk_pairs acc; memset(&acc, 0, sizeof acc);
         for (size_t i = 0; i < win.size(); ++i) {
             const bool last = i + 1 == win.size();
@@ -400,9 +427,9 @@ static int pairs_impl(hsk_ctx *c, const ResultPriv *rp, const StrandsPriv *sp, i
             info->peak_records = std::max<u64>(info->peak_records, win[i].records);
             rc = stk.push(c, l, !last, ck); if (rc) return rc;
         }
-        u64 keys = 0;
-        rc = stk.finish(c, min_shared, ck, &fin, &keys); if (rc) return rc;
-        out->self_records = acc.self_records; out->sort_passes = acc.sort_passes; out->keys = keys;
+        PairMergeCounts cnt;
+        rc = stk.finish(c, min_shared, ck, &fin, &cnt); if (rc) return rc;
+        out->self_records = acc.self_records; out->sort_passes = acc.sort_passes; out->keys = cnt.keys;
         info->slices = win.size(); info->merges = stk.ms.merges; info->merged_rows = stk.ms.merged_rows;
     }
     rc = pairs_egress(c, fin, 32, on_device, pc, pp); if (rc) return rc;
@@ -501,33 +528,57 @@ extern "C" int hsk_result_pairs_oriented(hsk_ctx *c, const hsk_result *res, cons
     return pairs_entry(c, res, strands, task_lo, task_hi, min_shared, on_device, true, max_records, out, info, "hsk_result_pairs_oriented");
 }
 
-// The several-list contract on the GPU: host lists go up, device lists are read where they are, and all meet on a PairStack.
+// The several-list contract on the GPU: host lists go up, device lists are read where they are, and all meet on a PairStack.  Part: the
+// ABI struct of the lists (hsk_pairs, hsk_pair_diags); out gets the sums of records and self_records.
+template <typename R, typename Part>
+static int pairs_stack_parts(hsk_ctx *c, const Part *const *parts, int32_t nparts, PairClock &ck, PairStack<R> &stk, Part *out)
+{
+    int32_t last = -1;
+    for (int32_t i = 0; i < nparts; ++i) { out->records += parts[i]->records; out->self_records += parts[i]->self_records; if (parts[i]->n) last = i; }
+    for (int32_t i = 0; i <= last; ++i) {
+        const Part *p = parts[i];
+        if (!p->n) continue;
+        PairList l; l.n = p->n;
+        if (p->rows_dev) { l.rows = (u64 *)p->rows_dev; l.owned = false; }
+        else {
+            DALLOC(c, l.rows, u64 *, p->n * R::ROW_BYTES);
+            HIPCHK(c, hipMemcpyAsync(l.rows, p->rows, p->n * R::ROW_BYTES, hipMemcpyHostToDevice, c->stream));      // (pageable or pinned: the part outlives the call's last wait)
+            c->stats.h2d_bytes += p->n * R::ROW_BYTES;
+        }
+        const int rc = stk.push(c, l, i != last, ck); if (rc) return rc;
+    }
+    return HSK_OK;
+}
+
 static int pairs_merge_impl(hsk_ctx *c, const hsk_pairs *const *parts, int32_t nparts, u32 min_shared, bool on_device, hsk_pairs *out, PairsPriv *pp)
 {
     PairCall pc(c);
     PairClock &ck = pc.ck;
     int rc = pc.start(c); if (rc) return rc;
-    int32_t last = -1;
-    for (int32_t i = 0; i < nparts; ++i) { out->records += parts[i]->records; out->self_records += parts[i]->self_records; if (parts[i]->n) last = i; }
-    PairStack stk;
-    for (int32_t i = 0; i <= last; ++i) {
-        const hsk_pairs *p = parts[i];
-        if (!p->n) continue;
-        PairList l; l.n = p->n;
-        if (p->rows_dev) { l.rows = (u64 *)p->rows_dev; l.owned = false; }
-        else {
-            DALLOC(c, l.rows, u64 *, p->n * 32);
-            HIPCHK(c, hipMemcpyAsync(l.rows, p->rows, p->n * 32, hipMemcpyHostToDevice, c->stream));      // (pageable or pinned: the part outlives the call's last wait)
-            c->stats.h2d_bytes += p->n * 32;
-        }
-        rc = stk.push(c, l, i != last, ck); if (rc) return rc;
-    }
-    PairList fin; u64 keys = 0;
-    rc = stk.finish(c, min_shared, ck, &fin, &keys); if (rc) return rc;
-    out->keys = keys;
+    PairStack<PairRows> stk;
+    rc = pairs_stack_parts(c, parts, nparts, ck, stk, out); if (rc) return rc;
+    PairList fin; PairMergeCounts cnt;
+    rc = stk.finish(c, min_shared, ck, &fin, &cnt); if (rc) return rc;
+    out->keys = cnt.keys;
     rc = pairs_egress(c, fin, 32, on_device, pc, pp); if (rc) return rc;
     pairs_store(out, fin.n, pp, pc);
     out->ms_reduce = ck.ms[PT_MERGE];                    // (the merges are this call's reduction)
+    return HSK_OK;
+}
+
+// what a merge call refuses about its parts (`min_name`: what the call names its filter)
+template <typename Part>
+static int pairs_merge_check(hsk_ctx *c, const char *name, const Part *const *parts, int32_t nparts, uint32_t min_rows, const char *min_name)
+{
+    if (nparts < 0) return fail(c, HSK_ERR_INVALID_ARG, "%s: %d parts", name, nparts);
+    if (nparts > 0 && !parts) return fail(c, HSK_ERR_INVALID_ARG, "%s: %d parts and no array of them", name, nparts);
+    if (min_rows == 0) return fail(c, HSK_ERR_INVALID_ARG, "%s must be at least 1", min_name);
+    for (int32_t i = 0; i < nparts; ++i) {
+        if (!parts[i]) return fail(c, HSK_ERR_INVALID_ARG, "%s: part %d is NULL", name, i);
+        if (parts[i]->n && !parts[i]->rows_dev && !parts[i]->rows) return fail(c, HSK_ERR_INVALID_ARG, "%s: part %d has %llu rows and neither rows nor rows_dev", name, i, (unsigned long long)parts[i]->n);
+        if (parts[i]->n && ((uintptr_t)parts[i]->rows_dev & 15)) return fail(c, HSK_ERR_INVALID_ARG, "%s: rows_dev of part %d is not 16-byte aligned", name, i);
+        if (parts[i]->n >> 58) return fail(c, HSK_ERR_INVALID_ARG, "%s: part %d claims %llu rows", name, i, (unsigned long long)parts[i]->n);
+    }
     return HSK_OK;
 }
 
@@ -535,15 +586,7 @@ extern "C" int hsk_pairs_merge(hsk_ctx *c, const hsk_pairs *const *parts, int32_
 {
     if (!c || !out) return HSK_ERR_INVALID_ARG;
     memset(out, 0, sizeof *out);
-    if (nparts < 0) return fail(c, HSK_ERR_INVALID_ARG, "hsk_pairs_merge: %d parts", nparts);
-    if (nparts > 0 && !parts) return fail(c, HSK_ERR_INVALID_ARG, "hsk_pairs_merge: %d parts and no array of them", nparts);
-    if (min_shared == 0) return fail(c, HSK_ERR_INVALID_ARG, "min_shared must be at least 1");
-    for (int32_t i = 0; i < nparts; ++i) {
-        if (!parts[i]) return fail(c, HSK_ERR_INVALID_ARG, "hsk_pairs_merge: part %d is NULL", i);
-        if (parts[i]->n && !parts[i]->rows_dev && !parts[i]->rows) return fail(c, HSK_ERR_INVALID_ARG, "hsk_pairs_merge: part %d has %llu rows and neither rows nor rows_dev", i, (unsigned long long)parts[i]->n);
-        if (parts[i]->n && ((uintptr_t)parts[i]->rows_dev & 15)) return fail(c, HSK_ERR_INVALID_ARG, "hsk_pairs_merge: rows_dev of part %d is not 16-byte aligned", i);
-        if (parts[i]->n >> 58) return fail(c, HSK_ERR_INVALID_ARG, "hsk_pairs_merge: part %d claims %llu rows", i, (unsigned long long)parts[i]->n);
-    }
+    const int chk = pairs_merge_check(c, "hsk_pairs_merge", parts, nparts, min_shared, "min_shared"); if (chk) return chk;
     return pairs_api_call(c, "hsk_pairs_merge", out, [&](PairsPriv *pp) { return pairs_merge_impl(c, parts, nparts, min_shared, on_device != 0, out, pp); });
 }
 

@@ -398,7 +398,8 @@ int  hsk_result_pairs_oriented(hsk_ctx *ctx, const hsk_result *res, const hsk_st
  * Several lists.  The ALL-BINS lists of disjoint task ranges, or of the ranks of a several-GPU run, join on (key, bin): support (and
  * shared) add up, first is the minimum, last the maximum; the selection then runs on the joined list.  Compute the parts with
  * min_support = 1.  The best-bin lists themselves DO NOT combine: the best bin of a part need not be the best bin of the union.
- * There is no slicing and no merge on the device for these lists yet: a narrower task range plus the join on the host is the way out.
+ * hsk_pair_diags_merge (below) is that join and selection on the GPU; hsk_result_pair_diagonals_sliced (below) computes either list of a
+ * task range from as many records at a time as the caller allows, through the same join.
  *
  *   diag_bin      the bin width W, 1 .. 2^31
  *   out           records, self_records as hsk_result_pairs_oriented; keys = distinct (read pair, orientation) before min_support; bins =
@@ -406,7 +407,8 @@ int  hsk_result_pairs_oriented(hsk_ctx *ctx, const hsk_result *res, const hsk_st
  *                 (-1: not known); ms_* HIP events (ms_expand includes the record count, ms_reduce both reducers).
  * Memory: 48 bytes per record while the sort runs (two buffers of two-word keys and two of values); then 48 bytes per distinct (key, bin)
  * for the bin rows, beside the record buffers while they are written, and 48 bytes per row of the result.  `records` is known after one
- * counting pass and before the record buffers are asked for: HSK_ERR_OOM then says how many records and bytes.  `bins` is known after
+ * counting pass and before the record buffers are asked for: HSK_ERR_OOM then says how many records and bytes, and
+ * hsk_result_pair_diagonals_sliced (below) is the way out: the same list from fewer records at a time.  `bins` is known after
  * the reducer's count pass, before the bin rows are asked for.
  * HSK_ERR_INVALID_ARG, with a hsk_last_error text, the context usable afterwards: everything hsk_result_pairs_oriented refuses (a NULL
  * pointer, `strands` NULL or not of `res`, a result that was not left on the device, a context without EXTENSION, a task range outside
@@ -431,6 +433,47 @@ int  hsk_result_pair_diagonals(hsk_ctx *ctx, const hsk_result *res, const hsk_st
                                int32_t task_lo, int32_t task_hi, uint64_t diag_bin, uint32_t min_support,
                                int32_t all_bins, int32_t on_device, hsk_pair_diags *out);
 void hsk_pair_diags_free(hsk_ctx *ctx, hsk_pair_diags *d);
+/*
+ * The same lists within a memory budget.  hsk_result_pair_diagonals_sliced has the definition, the row order, the refusals and the results
+ * of hsk_result_pair_diagonals, whatever the budget, and expands at most max_records records at a time: the record array of the task range
+ * is cut at entry boundaries into SLICES, as hsk_result_pairs_sliced cuts it; the bound of the positions is taken once for the range, so
+ * every slice sorts the same word; every slice is expanded, sorted and reduced to an all-bins list of its own with min_support 1 (48 bytes
+ * per record of the slice while that runs); and the lists are merged on the device on the two-word key (key, bin) -- rows with equal
+ * (key, bin) join, as in the several-list contract above.  all_bins != 0: the last merge applies min_support.  all_bins == 0: every merge
+ * keeps every row, and the selection runs over the joined list and applies min_support; best-bin lists of slices are never merged.
+ * The memory at the peak is 48 bytes x the largest slice plus the bin-row lists: up to three times 48 bytes x the joined list while the
+ * last merge runs.
+ *   max_records  the budget, with the meaning it has in hsk_result_pairs_sliced: a slice holds at least one entry, an entry above the
+ *                budget is a slice of its own, a budget of at least `records` runs hsk_result_pair_diagonals' single pass
+ *                (info->slices == 1).  0 = the library chooses: 1/144 of the device memory the context can still get when the record
+ *                count is known, in records -- a third of that memory at 48 bytes per record.
+ *   out          records and self_records are the sums over the slices, keys and bins those of the joined list before min_support,
+ *                sort_passes the most any slice's sort took, ms_expand / ms_sort / ms_reduce the sums over the slices, ms_total the call.
+ *   info         may be NULL; filled as hsk_result_pairs_sliced fills it.
+ * The limit of 2^31 expansion tiles holds per slice, not per range.
+ */
+int  hsk_result_pair_diagonals_sliced(hsk_ctx *ctx, const hsk_result *res, const hsk_strands *strands,
+                                      int32_t task_lo, int32_t task_hi, uint64_t diag_bin, uint32_t min_support,
+                                      int32_t all_bins, int32_t on_device, uint64_t max_records,
+                                      hsk_pair_diags *out, hsk_pairs_slices *info);
+/*
+ * The several-list contract of the diagonals on the GPU: the list of the union of `nparts` ALL-BINS lists that were computed with
+ * min_support = 1 and one diag_bin (disjoint task ranges, or the ranks of a several-GPU run).  Of each part the call reads n, rows_dev if
+ * set or else rows (host memory, pageable or pinned; uploaded), records and self_records; its priv may be NULL.  rows_dev must be 16-byte
+ * aligned (every list of this library is).  The lists -- ascending (key, bin), a (key, bin) at most once per list -- are merged two at a
+ * time on the device in the order of a binary counter, as hsk_pairs_merge merges its lists, and the last merge counts keys and bins of
+ * the joined list (a single list goes through one merge with nothing for these counts).
+ *   all_bins != 0   the joined list; min_support is applied by the last merge.
+ *   all_bins == 0   the selection runs on the joined list, min_support is applied after it: with nparts == 1 this is the selection
+ *                   property on the device.
+ * out is an ordinary hsk_pair_diags (host rows, or device rows with on_device), freed by hsk_pair_diags_free: n, rows, records and
+ * self_records (the sums), keys and bins (of the joined list, before min_support), ms_reduce (the merges and the selection), ms_d2h,
+ * ms_total.  The parts are left as they are.  Needs neither EXTENSION nor a resident result.  Memory: the uploaded parts, and up to three
+ * times 48 bytes x the joined list while the last merge runs.  HSK_ERR_INVALID_ARG: a NULL pointer, nparts < 0, min_support == 0, a part
+ * with n > 0 and no rows, a rows_dev that is not 16-byte aligned.  nparts == 0, or parts that are all empty, give an empty list.
+ */
+int  hsk_pair_diags_merge(hsk_ctx *ctx, const hsk_pair_diags *const *parts, int32_t nparts, uint32_t min_support,
+                          int32_t all_bins, int32_t on_device, hsk_pair_diags *out);
 /* Result egress (write_output_file, reference src/hysortk.cpp:138-164): the lines "KMERSTRING\tcount\n" of `n` entries
  * ((nw + 1)-word records: host memory, or device memory when `on_device`), formatted on the GPU into `text` (host, capacity
  * bytes); *nbytes = bytes needed (call with capacity 0 to size the buffer: K + 2 + up to 20 digits per entry). */

@@ -24,8 +24,15 @@ all bins, W diagonals per bin) on the same resident result, side by side: the ms
 oriented call, and the rows compared -- the selection of the all-bins list with the best-bin list, the all-bins list folded by key with the
 oriented list.  The oriented call is the yardstick: per record and scatter pass the sort moves 48 bytes (two key words and the value) where
 it moves 32.  Writes profiles/pairs_diagonals_8mbp.json unless --out says otherwise.
+--diagonals --max-records N (repeatable, N as above): hsk_result_pair_diagonals_sliced with that budget against the single pass of the same
+run -- best bin and all bins, the slices and merges, the merges' GB/s (48 B read per input row; the output rows are not counted: a lower
+bound) against hsk_copy_peak, the rows compared with the single pass -- and the device join of the all-bins lists of the two halves of the
+task range (hsk_pair_diags_merge, lists in HBM) against what it replaces: both lists copied to the host and PairDiagonals.combine there, with
+and without the selection.  Where the single pass is refused (HSK_ERR_OOM: --gbp 0.096), its error is recorded and the sliced runs with a
+budget that needs no record count (a number, or 0) stand alone, with what the device holds after them.  Writes
+profiles/pairs_diagonals_sliced_8mbp.json unless --out says otherwise.
 
-usage: python tools/time_pairs.py [--gbp 0.008] [--coverage 20] [--max-records N ...] [--merge-only] [--oriented [--strands-only]] [--diagonals [--diag-bin W]] [--out profiles/pairs_8mbp.json]"""
+usage: python tools/time_pairs.py [--gbp 0.008] [--coverage 20] [--max-records N ...] [--merge-only] [--oriented [--strands-only]] [--diagonals [--diag-bin W] [--max-records N ...]] [--out profiles/pairs_8mbp.json]"""
 import argparse, json, os, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -68,6 +75,32 @@ def budget(text, records):
     return int(text)
 
 
+def sliced_alone(H, ctx, dev, st, W, a):
+    """hsk_result_pair_diagonals_sliced where the single pass is refused: every budget that needs no record count (numbers, 0), both lists,
+    and what the device holds when the call is over (what the runtime reports used: the context's pool keeps its blocks, so this is the
+    high-water mark of the process, the resident result and the reads included)."""
+    res = []
+    for text in a.max_records:
+        if "/" in text:
+            continue
+        m, s = int(text), {"max_records": int(text), "asked": text}
+        for name, all_bins in (("best_bin", False), ("all_bins", True)):
+            runs = timed(lambda: dev.pair_diagonals(st, W, all_bins=all_bins, on_device=True, max_records=m), reps=a.reps)
+            last = runs[-1]
+            s[name] = {k: last[k] for k in ("records", "self_records", "rows", "keys", "bins", "slices", "peak_records", "merges", "merged_rows", "sort_passes")}
+            s[name].update({"ms_total": [r["ms_total"] for r in runs], "median_ms": median([r["ms_total"] for r in runs]),
+                            "ms_merge": [r["ms_merge"] for r in runs], "wall_ms": [r["wall_ms"] for r in runs]})
+        try:                                             # the HIP runtime the library has initialised in this process
+            import ctypes
+            fr, tot = ctypes.c_size_t(), ctypes.c_size_t()
+            rc = ctypes.CDLL("libamdhip64.so").hipMemGetInfo(ctypes.byref(fr), ctypes.byref(tot))
+            s["device_bytes_used_after"], s["device_bytes_total"] = (int(tot.value - fr.value), int(tot.value)) if rc == 0 else (None, None)
+        except OSError:
+            s["device_bytes_used_after"] = None
+        res.append(s)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gbp", type=float, default=0.008); ap.add_argument("--coverage", type=float, default=20.0)
@@ -78,7 +111,7 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "pairs_diagonals_8mbp.json" if a.diagonals else "pairs_8mbp.json")
+        a.out = os.path.join(ROOT, "profiles", ("pairs_diagonals_sliced_8mbp.json" if a.max_records else "pairs_diagonals_8mbp.json") if a.diagonals else "pairs_8mbp.json")
     sys.path.insert(0, ROOT)
     import numpy as np
     import hysortk_amd as H
@@ -96,13 +129,34 @@ def main():
            "workload": {"genome_bp": G, "read_len": RL, "reads": n, "K": 31, "M": 17, "L": 2, "U": 50, "ntasks": dev.ntasks, "entries": dev.n, "count_call_wall_ms": count_ms},
            "copy_peak_gbs": peak}
 
+    def finish(out):
+        dev.close()
+        ctx.synth_free(dp, do, dl)
+        ctx.close()
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+        print(json.dumps(out))
+
     if a.diagonals:
         # the oriented single pass and the diagonal call on the same resident result and strands: what the second key word and the second reducer cost
         W = a.diag_bin
-        with dev.strands(dna) as st:
+        st = dev.strands(dna)
+        try:
             ori = summary(timed(lambda: dev.pairs(on_device=True, strands=st), reps=a.reps))
             best = summary(timed(lambda: dev.pair_diagonals(st, W, on_device=True), reps=a.reps))
             allb = summary(timed(lambda: dev.pair_diagonals(st, W, all_bins=True, on_device=True), reps=a.reps))
+        except H.HskError as e:                          # the single pass does not fit the device: the sliced runs stand alone
+            if not a.max_records:
+                raise
+            out["what"] = "tools/time_pairs.py --diagonals --max-records: hsk_result_pair_diagonals_sliced where the single pass is refused"
+            out["diag_bin"] = W
+            out["single_pass"] = {"status": e.status, "error": str(e)}
+            out["sliced"] = sliced_alone(H, ctx, dev, st, W, a)
+            st.close()
+            finish(out)
+            return
+        with st:
             hb, ha, ho = dev.pair_diagonals(st, W), dev.pair_diagonals(st, W, all_bins=True), dev.pairs(strands=st)
             best["equals_selection_of_all_bins"] = bool(np.array_equal(ha.select().rows(), hb.rows()))
             k = ha.rows()
@@ -110,6 +164,63 @@ def main():
             folded = np.stack([k[start, 0], np.add.reduceat(k[:, 3], start), np.minimum.reduceat(k[:, 4], start), np.maximum.reduceat(k[:, 5], start)], axis=1) if k.shape[0] else np.zeros((0, 4), np.uint64)
             allb["folded_by_key_equals_oriented"] = bool(np.array_equal(folded, ho.rows()))
             best["rows_to_host"] = {"ms_d2h": hb.info["ms_d2h"], "ms_total": hb.info["ms_total"], "bytes": len(hb) * 48}
+            sliced = []
+            for text in a.max_records:
+                m = budget(text, best["records"])
+                s = {"max_records": m, "asked": text}
+                for name, all_bins, base, rows in (("best_bin", False, best, hb.rows()), ("all_bins", True, allb, ha.rows())):
+                    runs = timed(lambda: dev.pair_diagonals(st, W, all_bins=all_bins, on_device=True, max_records=m), reps=a.reps)
+                    last = runs[-1]
+                    tot, mrg = median([r["ms_total"] for r in runs]), median([r["ms_merge"] for r in runs])
+                    got = dev.pair_diagonals(st, W, all_bins=all_bins, max_records=m)
+                    s[name] = {"records": last["records"], "rows": last["rows"], "keys": last["keys"], "bins": last["bins"], "slices": last["slices"], "peak_records": last["peak_records"],
+                               "merges": last["merges"], "merged_rows": last["merged_rows"], "sort_passes": last["sort_passes"],
+                               "ms_total": [r["ms_total"] for r in runs], "median_ms": tot, "ms_merge": [r["ms_merge"] for r in runs], "median_ms_merge": mrg,
+                               "median_ms_expand": median([r["ms_expand"] for r in runs]), "median_ms_sort": median([r["ms_sort"] for r in runs]),
+                               "median_ms_reduce": median([r["ms_reduce"] for r in runs]),
+                               "merge_read_gbs": 48 * last["merged_rows"] / (mrg * 1e-3) / 1e9 if mrg > 0 else 0.0,
+                               "merge_read_of_copy_peak": 48 * last["merged_rows"] / (mrg * 1e-3) / 1e9 / peak if mrg > 0 and peak > 0 else 0.0,
+                               "ratio_to_single_pass": tot / base["median_ms"] if base["median_ms"] > 0 else None,
+                               "rows_equal_single_pass": bool(np.array_equal(got.rows(), rows)),
+                               "counts_equal_single_pass": all(got.info[k] == base[k] for k in ("records", "self_records", "keys", "bins"))}
+                    del got
+                sliced.append(s)
+            if sliced:
+                out["sliced"] = sliced
+                # the device join of two task-range lists against the host join and the copies it replaces
+                half = dev.ntasks // 2
+                join = {}
+                with dev.pair_diagonals(st, W, 0, half, all_bins=True, on_device=True) as pa, dev.pair_diagonals(st, W, half, dev.ntasks, all_bins=True, on_device=True) as pb:
+                    for name, all_bins in (("all_bins", True), ("best_bin", False)):
+                        runs = timed(lambda: H.PairDiagonals.combine([pa, pb], ctx=ctx, all_bins=all_bins, on_device=True), reps=a.reps)
+                        no = runs[-1]["rows"]
+                        nbytes = 48 * (pa.n + pb.n) + (48 * no if all_bins else 0)
+                        mm = median([r["ms_reduce"] for r in runs])
+                        join[name] = {"rows_a": pa.n, "rows_b": pb.n, "rows_out": no, "keys": runs[-1]["keys"], "bins": runs[-1]["bins"], "merge_bytes": nbytes,
+                                      "ms_reduce": [r["ms_reduce"] for r in runs], "median_ms_reduce": mm, "ms_total": [r["ms_total"] for r in runs],
+                                      "median_ms": median([r["ms_total"] for r in runs]), "wall_ms": [r["wall_ms"] for r in runs]}
+                        if all_bins:                     # (with the selection ms_reduce holds more than the merge: no GB/s for it)
+                            join[name]["gbs"] = nbytes / (mm * 1e-3) / 1e9 if mm > 0 else 0.0
+                            join[name]["of_copy_peak"] = nbytes / (mm * 1e-3) / 1e9 / peak if mm > 0 and peak > 0 else 0.0
+                    host_runs = []
+                    for i in range(WARMUP + a.reps):
+                        t0 = time.perf_counter()
+                        parts = [H.PairDiagonals.from_rows(ctx.d2h(p.rows_dev, p.n * 48).view(np.uint64).reshape(p.n, 6) if p.n else np.zeros((0, 6), np.uint64), diag_bin=W, all_bins=True, info=p.info) for p in (pa, pb)]
+                        t1 = time.perf_counter()
+                        comb = H.PairDiagonals.combine(parts)
+                        t2 = time.perf_counter()
+                        sel = comb.select()
+                        t3 = time.perf_counter()
+                        if i >= WARMUP:
+                            host_runs.append({"d2h_wall_ms": (t1 - t0) * 1e3, "combine_wall_ms": (t2 - t1) * 1e3, "select_wall_ms": (t3 - t2) * 1e3})
+                    join["host"] = {"d2h_bytes": 48 * (pa.n + pb.n), "runs": host_runs,
+                                    "median_wall_ms_all_bins": median([r["d2h_wall_ms"] + r["combine_wall_ms"] for r in host_runs]),
+                                    "median_wall_ms_best_bin": median([r["d2h_wall_ms"] + r["combine_wall_ms"] + r["select_wall_ms"] for r in host_runs])}
+                    dj, dsel = H.PairDiagonals.combine([pa, pb], ctx=ctx), H.PairDiagonals.combine([pa, pb], ctx=ctx, all_bins=False)
+                    join["device_rows_equal_host_join"] = bool(np.array_equal(dj.rows(), comb.rows()) and np.array_equal(dsel.rows(), sel.rows()))
+                    join["device_rows_equal_whole_range"] = bool(np.array_equal(dj.rows(), ha.rows()) and np.array_equal(dsel.rows(), hb.rows()))
+                    del dj, dsel, comb, sel, parts
+                out["join_two_task_ranges"] = join
             del hb, ha, ho
         out["what"] = "tools/time_pairs.py --diagonals: hsk_result_pairs_oriented (single pass) and hsk_result_pair_diagonals on the same resident EXTENSION result and strands"
         out["diag_bin"] = W
@@ -121,6 +232,10 @@ def main():
         print("%-28s %10s %10s %10s %10s %6s %10s" % ("call (median ms)", "total", "expand", "sort", "reduce", "passes", "rows"))
         for name, s in (("hsk_result_pairs_oriented", ori), ("hsk_result_pair_diagonals", best), ("  ... all_bins", allb)):
             print("%-28s %10.3f %10.3f %10.3f %10.3f %6d %10d" % (name, s["median_ms"], s["median_ms_expand"], s["median_ms_sort"], s["median_ms_reduce"], s["sort_passes"], s["rows"]))
+        for s in out.get("sliced", []):
+            for name in ("best_bin", "all_bins"):
+                print("max_records %-12d %-8s %10.3f ms, %d slices, %d merges in %.3f ms (%.1f GB/s read), x %.2f of the single pass" % (
+                    s["max_records"], name, s[name]["median_ms"], s[name]["slices"], s[name]["merges"], s[name]["median_ms_merge"], s[name]["merge_read_gbs"], s[name]["ratio_to_single_pass"] or 0.0))
     elif a.oriented:
         # the strand pass, then both pair calls on the same resident result: what the strand bit costs the sort (its top digit is no longer trivial)
         sruns = []
@@ -214,13 +329,7 @@ def main():
             sliced.append(s)
         if sliced:
             out["sliced"] = sliced
-    dev.close()
-    ctx.synth_free(dp, do, dl)
-    ctx.close()
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    finish(out)
 
 
 if __name__ == "__main__":
