@@ -444,6 +444,38 @@ class PairDiagonals:
         ctx._check(ctx.lib.hsk_pair_diags_merge(ctx.h, arr, len(structs), int(min_support), 1 if all_bins else 0, 1 if on_device else 0, C.byref(pd)))
         return PairDiagonals._wrap(ctx, pd, on_device, diag_bin, bool(all_bins))
 
+    def extend(self, ctx, reads, rid_base=None, match=1, mismatch=1, xdrop=7, min_score=0, min_length=0, wave_span=0, on_device=False):
+        """hsk_pair_diags_extend: the seed of every row (`first`) extended in both directions, ungapped, with an x-drop stop, over the reads
+        in HBM -- one overlap row per row of this list (best-bin or all-bins; rows in HBM are read there, host rows are uploaded).  reads: a
+        DeviceDna (read where it lies), a DnaBuffer or a (packed, off, lens) tuple of host arrays (uploaded for the call), as
+        DeviceResult.strands takes them; rid_base: the id of read 0 (default: the buffer's first_read_id, else 0).  match in 1 .. 2^15,
+        mismatch (a penalty) in 0 .. 2^15, xdrop in 0 .. 2^31 - 1; min_score / min_length drop rows after the extension; wave_span: rows
+        whose span is at least this many columns are extended by a whole wavefront (0: the library's default, 1: all, 0xFFFFFFFF: none; the
+        rows are the same).  Returns an Overlaps (on_device=True: its rows stay in HBM; close() it before the context goes)."""
+        pd = _lib.PairDiags()
+        pd.n = len(self)
+        keep = None
+        if len(self) and self.rows_dev:
+            pd.rows_dev = self.rows_dev
+        elif len(self):
+            keep = np.ascontiguousarray(self.rows(), dtype=np.uint64)
+            pd.rows = keep.ctypes.data_as(C.POINTER(C.c_uint64))
+        opts = _lib.ExtendOpts()
+        opts.match, opts.mismatch, opts.xdrop, opts.min_score, opts.min_length, opts.wave_span = int(match), int(mismatch), int(xdrop), int(min_score), int(min_length), int(wave_span)
+        ov = _lib.Overlaps()
+        if isinstance(reads, DeviceDna):
+            base = reads.first_read_id if rid_base is None else rid_base
+            rc = ctx.lib.hsk_pair_diags_extend(ctx.h, C.byref(pd), reads.dp, reads.nbytes, reads.do, reads.dl, reads.nreads, base, 1, C.byref(opts), 1 if on_device else 0, C.byref(ov))
+        else:
+            base = getattr(reads, "first_read_id", 0) if rid_base is None else rid_base
+            packed, off, lens = reads.arrays() if isinstance(reads, DnaBuffer) else reads
+            packed = np.ascontiguousarray(packed, dtype=np.uint8)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+            lens = np.ascontiguousarray(lens, dtype=np.uint32)
+            rc = ctx.lib.hsk_pair_diags_extend(ctx.h, C.byref(pd), _p(packed), packed.size, _p(off), _p(lens), lens.size, base, 0, C.byref(opts), 1 if on_device else 0, C.byref(ov))
+        ctx._check(rc)
+        return Overlaps._wrap(ctx, ov, on_device)
+
     @staticmethod
     def _wrap(ctx, pd, on_device, diag_bin, all_bins, extra=None):
         """A PairDiagonals from a filled hsk_pair_diags: the rows copied to numpy and the struct freed, or (on_device) left in HBM and owned."""
@@ -468,6 +500,88 @@ class PairDiagonals:
     def __del__(self):
         try:
             self.close()                 # (rows left on the device go back while the context is alive; after hsk_destroy there is nothing to free)
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Overlaps:
+    """The ungapped x-drop overlaps of a list of diagonal rows (hsk_pair_diags_extend, include/hsk.h): rows { key, score, a_lo << 32 | a_hi,
+    b_lo << 32 | b_hi, mismatches << 32 | ends, support } with key = o << 63 | rid_a << 32 | rid_b.  [a_lo, a_hi) and [b_lo, b_hi) are
+    forward read coordinates, half-open; ends has bit 0 a_lo == 0, bit 1 a_hi == len(a), bit 2 b_lo == 0, bit 3 b_hi == len(b).  info has
+    input_rows, dropped, columns, wave_rows and the ms_* of the call.  With on_device the rows stay in HBM (rows_dev: n rows of six uint64
+    words; close() gives them back)."""
+
+    COLS = 6
+    INTERNAL, DOVETAIL, A_CONTAINED, B_CONTAINED = 0, 1, 2, 3
+
+    def __init__(self, key, score, a, b, mm_ends, support, info=None, rows_dev=None, n=None, owner=None):
+        self.key, self.score, self._a, self._b, self._me, self.support = (np.ascontiguousarray(x, dtype=np.uint64) for x in (key, score, a, b, mm_ends, support))
+        lo = np.uint64(0xFFFFFFFF)
+        self.a_lo, self.a_hi = (self._a >> np.uint64(32)).astype(np.uint32), (self._a & lo).astype(np.uint32)
+        self.b_lo, self.b_hi = (self._b >> np.uint64(32)).astype(np.uint32), (self._b & lo).astype(np.uint32)
+        self.mismatches, self.ends = (self._me >> np.uint64(32)).astype(np.uint32), (self._me & lo).astype(np.uint32)
+        self.opposite = (self.key >> np.uint64(63)).astype(bool)
+        self.rid_a, self.rid_b = ((self.key >> np.uint64(32)) & np.uint64(0x7FFFFFFF)).astype(np.uint32), (self.key & lo).astype(np.uint32)
+        self.info = info or {}
+        self.rows_dev = rows_dev
+        self.n = int(self.key.size) if n is None else int(n)
+        self._owner = owner                      # (ctx, hsk_overlaps) of rows that live on the device
+
+    def __len__(self):
+        return self.n
+
+    def rows(self):
+        """[n, 6] uint64, the C ABI's layout."""
+        return np.stack([self.key, self.score, self._a, self._b, self._me, self.support], axis=1) if self.key.size else np.zeros((0, 6), np.uint64)
+
+    @classmethod
+    def from_rows(cls, rows, **kw):
+        rows = np.asarray(rows, dtype=np.uint64).reshape(-1, 6)
+        return cls(*(rows[:, i] for i in range(6)), **kw)
+
+    def kind(self):
+        """One small integer per row, what an overlapper asks next: A_CONTAINED -- the overlap is all of read A (ends has bits 0 and 1);
+        B_CONTAINED -- all of read B (bits 2 and 3) and not the former; DOVETAIL -- the side of the low columns reached a read's end and so did
+        the side of the high columns (same strand: bit 0 or 2, and bit 1 or 3; opposite strands, where B runs backwards: bit 0 or 3, and
+        bit 1 or 2); INTERNAL -- a local match that stops inside both reads on some side."""
+        e = self.ends
+        b = [(e >> np.uint32(i)) & np.uint32(1) != 0 for i in range(4)]
+        low = np.where(self.opposite, b[0] | b[3], b[0] | b[2])
+        high = np.where(self.opposite, b[1] | b[2], b[1] | b[3])
+        k = np.where(low & high, self.DOVETAIL, self.INTERNAL)
+        k = np.where(b[2] & b[3], self.B_CONTAINED, k)
+        k = np.where(b[0] & b[1], self.A_CONTAINED, k)
+        return k.astype(np.uint8)
+
+    @staticmethod
+    def _wrap(ctx, ov, on_device):
+        """An Overlaps from a filled hsk_overlaps: the rows copied to numpy and the struct freed, or (on_device) left in HBM and owned."""
+        info = dict(input_rows=int(ov.input_rows), dropped=int(ov.dropped), columns=int(ov.columns), wave_rows=int(ov.wave_rows),
+                    ms_extend=ov.ms_extend, ms_d2h=ov.ms_d2h, ms_total=ov.ms_total)
+        n = int(ov.n)
+        if on_device:
+            z = np.zeros(0, np.uint64)
+            return Overlaps(z, z, z, z, z, z, info=info, rows_dev=ov.rows_dev, n=n, owner=(ctx, ov))
+        rows = np.ctypeslib.as_array(ov.rows, shape=(n * 6,)).reshape(n, 6).copy() if n else np.zeros((0, 6), np.uint64)
+        ctx.lib.hsk_overlaps_free(ctx.h, C.byref(ov))
+        return Overlaps.from_rows(rows, info=info)
+
+    def close(self):
+        if self._owner is not None:
+            ctx, ov = self._owner
+            if getattr(ctx, "h", None):
+                ctx.lib.hsk_overlaps_free(ctx.h, C.byref(ov))
+            self._owner, self.rows_dev = None, None
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 

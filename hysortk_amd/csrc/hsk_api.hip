@@ -42,6 +42,7 @@
 #include "hsk_pairmerge.h"
 #include "hsk_pairdiag.h"
 #include "hsk_diagmerge.h"
+#include "hsk_extend.h"
 #include "hsk_strand.h"
 #include "hsk_estimate.h"
 #include "hsk_synth.h"
@@ -458,6 +459,8 @@ extern "C" int hsk_result_device_task(const hsk_result *r, int32_t task, const v
 #include "hsk_host_strand.h"
 // the oriented pairs by diagonal, and the best-supported bin of each: hsk_result_pair_diagonals, hsk_pair_diags_free
 #include "hsk_host_pairdiag.h"
+// the ungapped x-drop overlap of every diagonal row's seed: hsk_pair_diags_extend, hsk_overlaps_free
+#include "hsk_host_extend.h"
 
 // Uploads the DnaBuffer description; returns device arrays with nreads+1 offsets.
 

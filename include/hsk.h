@@ -474,6 +474,75 @@ int  hsk_result_pair_diagonals_sliced(hsk_ctx *ctx, const hsk_result *res, const
  */
 int  hsk_pair_diags_merge(hsk_ctx *ctx, const hsk_pair_diags *const *parts, int32_t nparts, uint32_t min_support,
                           int32_t all_bins, int32_t on_device, hsk_pair_diags *out);
+/*
+ * Ungapped x-drop overlaps: the seed of every diagonal row, extended in both directions over the reads in HBM.  One overlap row per
+ * input row; exact integer work, held to this definition word for word (csrc/hsk_xdrop.h is the one implementation the kernels, the
+ * host and the CPU tests share; tests/extend_ref.py spells it base by base).
+ *
+ * Input.  A list of hsk_pair_diags rows, best-bin or all-bins: of `in` the call reads n, rows_dev if set, else rows (host memory,
+ * pageable or pinned; uploaded as hsk_pair_diags_merge uploads its parts); its priv may be NULL, so a list the caller filled in by hand is
+ * valid.  The reads as hsk_result_strands takes them (packed, packed_bytes, read_byte_off, read_len, nreads, rid_base, reads_on_device).
+ * K is the context's.  Needs neither EXTENSION nor a resident result.
+ *
+ * Seed.  For each row: pa = first >> 32, pb = first & 0xffffffff, o = key >> 63; the reads a = rid_a - rid_base, b = rid_b - rid_base with
+ * lengths la, lb; base codes as the packed bytes hold them (N is A; base i of a read in byte i / 4 at shift 6 - 2 (i % 4)).
+ *
+ * Columns.  Column t (t = 0: the seed's first base in A's forward direction) pairs
+ *     o = 0:  A[pa + t] with B[pb + t];                valid t in [-min(pa, pb), min(la - pa, lb - pb))
+ *     o = 1:  A[pa + t] with 3 - B[pb + K - 1 - t];    valid t in [max(-pa, pb + K - lb), min(la - pa, pb + K))
+ * [t_lo, t_hi) is the valid range, span = t_hi - t_lo.  A column matches iff the two codes are equal.  Columns 0 .. K - 1 must be valid and
+ * must all match; else the row is no seed of these reads and the call refuses.
+ *
+ * Extension.  match in 1 .. 2^15, mismatch (a penalty) in 0 .. 2^15, xdrop in 0 .. 2^31 - 1.  Right side, for t = K, K + 1, ... < t_hi,
+ * from s = best = 0, end = K:  (1) s += match or s -= mismatch;  (2) if s > best: best = s, end = t + 1;  (3) if best - s > xdrop: stop.
+ * The left side is the same over t = -1, -2, ... >= t_lo and gives `begin`.  score = K * match + best_right + best_left (64 bits); the
+ * overlap is the columns [begin, end); mismatches counts the mismatching columns inside it.
+ *
+ * Row.  Six uint64 words (48 bytes; the lists are 16-byte aligned):
+ *     { key, score, a_lo << 32 | a_hi, b_lo << 32 | b_hi, mismatches << 32 | ends, support }
+ * in forward read coordinates, half-open: a_lo = pa + begin, a_hi = pa + end; o = 0: b_lo = pb + begin, b_hi = pb + end; o = 1:
+ * b_lo = pb + K - end, b_hi = pb + K - begin.  ends: bit 0 a_lo == 0, bit 1 a_hi == la, bit 2 b_lo == 0, bit 3 b_hi == lb.  support is
+ * word 3 of the input row.
+ *
+ * Filter.  Rows with score < min_score or a_hi - a_lo < min_length are dropped after the extension; the survivors keep the input's order.
+ * With both 0 the output has the input's n rows, one to one.
+ *
+ *   opts       match, mismatch, xdrop, min_score, min_length; wave_span: a row whose span is at least wave_span is extended by a whole
+ *              wavefront (64 windows of 32 columns per step), any other row by one lane.  0 = the library's default, 1 = every row by
+ *              a wavefront, UINT32_MAX = none.  Both give the same rows.
+ *   out        n, rows (host, pinned) or rows_dev (on_device); input_rows; dropped (by the filter); columns = the sum of a_hi - a_lo over
+ *              all rows before the filter; wave_rows = rows a wavefront took; ms_* HIP events.  hsk_overlaps_free before hsk_destroy.
+ * Memory: 48 + 8 bytes per input row, 1 + 48 per row more with a filter, and the uploaded rows and reads.
+ * HSK_ERR_INVALID_ARG, with a hsk_last_error text that names the case and how many rows, the context usable afterwards, no partial result:
+ * a NULL pointer; n > 0 without rows; a rows_dev that is not 16-byte aligned; match, mismatch or xdrop outside their ranges;
+ * rid_base + nreads > 2^31; a row whose rid_a or rid_b lies outside [rid_base, rid_base + nreads); a read of a row that does not lie
+ * inside packed_bytes; a seed that does not fit its reads (pa + K > la or pb + K > lb); a seed whose K columns do not all match ("these
+ * are not the reads the rows were computed from").  No byte at or beyond packed_bytes is read.  n == 0 is an empty list, no error.
+ */
+typedef struct {
+    int32_t  match, mismatch;
+    uint32_t xdrop;
+    uint64_t min_score;
+    uint32_t min_length;
+    uint32_t wave_span;
+    int64_t  reserved[4];
+} hsk_extend_opts;
+
+typedef struct {
+    uint64_t n;             /* rows */
+    uint64_t *rows;         /* host (pinned), n * 6 words; NULL when left on the device */
+    void     *rows_dev;     /* device copy when asked for */
+    uint64_t input_rows, dropped, columns, wave_rows;
+    double   ms_extend, ms_d2h, ms_total;   /* HIP events */
+    int64_t  reserved[4];
+    void    *priv;
+} hsk_overlaps;
+
+int  hsk_pair_diags_extend(hsk_ctx *ctx, const hsk_pair_diags *in,
+                           const void *packed, uint64_t packed_bytes, const void *read_byte_off, const void *read_len,
+                           uint64_t nreads, int64_t rid_base, int32_t reads_on_device,
+                           const hsk_extend_opts *opts, int32_t on_device, hsk_overlaps *out);
+void hsk_overlaps_free(hsk_ctx *ctx, hsk_overlaps *o);
 /* Result egress (write_output_file, reference src/hysortk.cpp:138-164): the lines "KMERSTRING\tcount\n" of `n` entries
  * ((nw + 1)-word records: host memory, or device memory when `on_device`), formatted on the GPU into `text` (host, capacity
  * bytes); *nbytes = bytes needed (call with capacity 0 to size the buffer: K + 2 + up to 20 digits per entry). */

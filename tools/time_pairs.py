@@ -32,7 +32,15 @@ and without the selection.  Where the single pass is refused (HSK_ERR_OOM: --gbp
 budget that needs no record count (a number, or 0) stand alone, with what the device holds after them.  Writes
 profiles/pairs_diagonals_sliced_8mbp.json unless --out says otherwise.
 
-usage: python tools/time_pairs.py [--gbp 0.008] [--coverage 20] [--max-records N ...] [--merge-only] [--oriented [--strands-only]] [--diagonals [--diag-bin W] [--max-records N ...]] [--out profiles/pairs_8mbp.json]"""
+--extend [--error-rate R]: on the input of --diagonals, with reads generated with substitution errors (default 0.01) so that the extension
+has something to stop at: hsk_result_pair_diagonals (best bin, rows left in HBM) and hsk_pair_diags_extend of those rows (reads and result in
+HBM) side by side -- the ms of each and their ratio, columns, wave_rows, and the bytes of reads the overlaps cover (two bits per base and
+read: columns / 2) per ms against hsk_copy_peak of the same run.  The host route it replaces, as a SAMPLE: the rows copied to the host, the
+packed reads copied to the host, and tests/extend_ref.py (numpy, one column per step) on --sample rows, which are also compared with the
+device's rows.  Then a wave_span sweep (1, 512, 4096, none) on a long-read input (--long-reads reads of --long-len bases).  Writes
+profiles/pairs_extend_8mbp.json unless --out says otherwise.
+
+usage: python tools/time_pairs.py [--gbp 0.008] [--coverage 20] [--max-records N ...] [--merge-only] [--oriented [--strands-only]] [--diagonals [--diag-bin W] [--max-records N ...]] [--extend [--error-rate R]] [--out profiles/pairs_8mbp.json]"""
 import argparse, json, os, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -101,8 +109,49 @@ def sliced_alone(H, ctx, dev, st, W, a):
     return res
 
 
+def unpack_reads(np, packed, off, lens, ids):
+    """(code matrix, lengths) of the reads `ids` of a packed buffer, as tests/extend_ref.code_matrix gives them for strings"""
+    lens = lens[ids].astype(np.int64)
+    m = np.zeros((ids.size, max(1, int(lens.max()) if ids.size else 1)), dtype=np.int64)
+    for i, (o, n) in enumerate(zip(off[ids].tolist(), lens.tolist())):
+        b = packed[o:o + (n + 3) // 4]
+        m[i, :n] = np.stack([(b >> 6) & 3, (b >> 4) & 3, (b >> 2) & 3, b & 3], axis=1).reshape(-1)[:n]
+    return m, lens
+
+
+def extend_summary(runs, peak):
+    last = runs[-1]
+    ms = median([r["ms_extend"] for r in runs])
+    gbs = last["columns"] / 2 / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
+    return {"rows": last["rows"], "input_rows": last["input_rows"], "columns": last["columns"], "wave_rows": last["wave_rows"], "dropped": last["dropped"],
+            "ms_extend": [r["ms_extend"] for r in runs], "median_ms_extend": ms, "ms_total": [r["ms_total"] for r in runs], "median_ms": median([r["ms_total"] for r in runs]),
+            "wall_ms": [r["wall_ms"] for r in runs], "read_bytes_covered": last["columns"] // 2, "read_gbs": gbs, "read_of_copy_peak": gbs / peak if peak > 0 else 0.0}
+
+
+def extend_sweep(H, a, peak):
+    """the wave_span sweep on long reads, in a context of its own: (workload, {wave_span: summary}, rows equal over the sweep)"""
+    import numpy as np
+    G, RL, n = a.long_len * a.long_reads // 8, a.long_len, a.long_reads      # 8x
+    ctx = H.Context(K=31, M=17, L=2, U=50, EXT=1, ntasks=0, keep_device=True)
+    dp, nb, do, dl = ctx.synth_reads(G, RL, n, 13, error_rate=a.error_rate)
+    dna = H.DeviceDna(ctx, dp, nb, do, dl, n)
+    res, base, same = {}, None, True
+    with dna.count_resident_device() as dev, dev.strands(dna) as st, dev.pair_diagonals(st, a.diag_bin, on_device=True) as pd:
+        for span in (1, 512, 4096, 0xFFFFFFFF):
+            res[str(span)] = extend_summary(timed(lambda: pd.extend(ctx, dna, wave_span=span, on_device=True), reps=a.reps), peak)
+            rows = pd.extend(ctx, dna, wave_span=span).rows()
+            same = same and (base is None or bool(np.array_equal(rows, base)))
+            base = rows
+        work = {"genome_bp": G, "read_len": RL, "reads": n, "error_rate": a.error_rate, "diagonal_rows": pd.n, "records": pd.info["records"]}
+    ctx.synth_free(dp, do, dl)
+    ctx.close()
+    return work, res, same
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--extend", action="store_true"); ap.add_argument("--error-rate", type=float, default=0.01); ap.add_argument("--sample", type=int, default=20000)
+    ap.add_argument("--long-reads", type=int, default=2000); ap.add_argument("--long-len", type=int, default=12000)
     ap.add_argument("--gbp", type=float, default=0.008); ap.add_argument("--coverage", type=float, default=20.0)
     ap.add_argument("--max-records", action="append", default=[]); ap.add_argument("--merge-only", action="store_true")
     ap.add_argument("--oriented", action="store_true"); ap.add_argument("--strands-only", action="store_true")
@@ -110,6 +159,8 @@ def main():
     ap.add_argument("--reps", type=int, default=REPS)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None and a.extend:
+        a.out = os.path.join(ROOT, "profiles", "pairs_extend_8mbp.json")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", ("pairs_diagonals_sliced_8mbp.json" if a.max_records else "pairs_diagonals_8mbp.json") if a.diagonals else "pairs_8mbp.json")
     sys.path.insert(0, ROOT)
@@ -120,7 +171,7 @@ def main():
     n = int(G * a.coverage / RL)
     ctx = H.Context(K=31, M=17, L=2, U=50, EXT=1, ntasks=0, keep_device=True)
     peak = ctx.copy_peak(1 << 30, 3)
-    dp, nb, do, dl = ctx.synth_reads(G, RL, n, 11)
+    dp, nb, do, dl = ctx.synth_reads(G, RL, n, 11, error_rate=a.error_rate if a.extend else 0.0)
     dna = H.DeviceDna(ctx, dp, nb, do, dl, n)
     t0 = time.perf_counter()
     dev = dna.count_resident_device()
@@ -138,6 +189,56 @@ def main():
             json.dump(out, f, indent=1)
         print(json.dumps(out))
 
+    if a.extend:
+        # the diagonal call (unchanged code: the yardstick) and the extension of its rows, both with rows and reads in HBM
+        from tests import extend_ref as X
+        W = a.diag_bin
+        with dev.strands(dna) as st:
+            diag = summary(timed(lambda: dev.pair_diagonals(st, W, on_device=True), reps=a.reps))
+            with dev.pair_diagonals(st, W, on_device=True) as pd:
+                ext = extend_summary(timed(lambda: pd.extend(ctx, dna, on_device=True), reps=a.reps), peak)
+                lane = extend_summary(timed(lambda: pd.extend(ctx, dna, wave_span=0xFFFFFFFF, on_device=True), reps=a.reps), peak)
+                t0 = time.perf_counter()
+                hrows = ctx.d2h(pd.rows_dev, pd.n * 48).view(np.uint64).reshape(pd.n, 6)
+                t1 = time.perf_counter()
+                packed, off, lens = dna.packed(), ctx.d2h(do, n * 8).view(np.uint64), ctx.d2h(dl, n * 4).view(np.uint32)
+                t2 = time.perf_counter()
+                pick = np.sort(np.random.default_rng(1).choice(pd.n, min(a.sample, pd.n), replace=False))
+                srows = hrows[pick].copy()
+                ids = np.concatenate([(srows[:, 0] >> np.uint64(32)) & np.uint64(0x7FFFFFFF), srows[:, 0] & np.uint64(0xFFFFFFFF)]).astype(np.int64)
+                uniq, inv = np.unique(ids, return_inverse=True)
+                top = srows[:, 0] & (np.uint64(1) << np.uint64(63))
+                srows[:, 0] = top | (inv[:pick.size].astype(np.uint64) << np.uint64(32)) | inv[pick.size:].astype(np.uint64)      # the sample's reads renumbered
+                mat = unpack_reads(np, packed, off.astype(np.int64), lens, uniq)
+                t3 = time.perf_counter()
+                want, _ = X.extend_rows_bulk(srows, mat, 31)
+                t4 = time.perf_counter()
+                got = pd.extend(ctx, dna).rows()[pick]
+                ext["host_route_sample"] = {"note": "a sample: the rows and the packed reads copied to the host (all of them), then the numpy reference on `rows` rows only",
+                                            "rows_d2h_bytes": pd.n * 48, "rows_d2h_wall_ms": (t1 - t0) * 1e3, "reads_d2h_bytes": int(packed.size) + n * 12, "reads_d2h_wall_ms": (t2 - t1) * 1e3,
+                                            "rows": int(pick.size), "unpack_wall_ms": (t3 - t2) * 1e3, "reference_wall_ms": (t4 - t3) * 1e3,
+                                            "reference_us_per_row": (t4 - t3) * 1e6 / max(1, pick.size),
+                                            "device_rows_equal_reference": bool(np.array_equal(got[:, 1:], want[:, 1:]) and np.array_equal(got[:, 0], hrows[pick, 0]))}
+        out["what"] = "tools/time_pairs.py --extend: hsk_result_pair_diagonals (best bin) and hsk_pair_diags_extend of its rows, rows and reads in HBM"
+        out["workload"]["error_rate"] = a.error_rate
+        out["diag_bin"] = W
+        out["pair_diagonals"], out["extend"], out["extend_lane_path_only"] = diag, ext, lane
+        out["extend_over_pair_diagonals"] = ext["median_ms"] / diag["median_ms"] if diag["median_ms"] > 0 else None
+        print("%-32s %10.3f ms, %d rows" % ("hsk_result_pair_diagonals", diag["median_ms"], diag["rows"]))
+        print("%-32s %10.3f ms (kernels %.3f), %d columns, %d wave rows, %.1f GB/s of reads covered (%.3f of the copy peak), x %.3f of the diagonal call" % (
+            "hsk_pair_diags_extend", ext["median_ms"], ext["median_ms_extend"], ext["columns"], ext["wave_rows"], ext["read_gbs"], ext["read_of_copy_peak"], out["extend_over_pair_diagonals"] or 0.0))
+        dev.close()
+        ctx.synth_free(dp, do, dl)
+        ctx.close()
+        work, sweep, same = extend_sweep(H, a, peak)
+        out["wave_span_sweep"] = {"workload": work, "default_wave_span": 512, "by_wave_span": sweep, "rows_equal_over_the_sweep": same}
+        for span, s in sweep.items():
+            print("long reads, wave_span %-10s %10.3f ms (kernels %.3f), %d wave rows of %d, %d columns" % (span, s["median_ms"], s["median_ms_extend"], s["wave_rows"], s["input_rows"], s["columns"]))
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+        print(json.dumps(out))
+        return
     if a.diagonals:
         # the oriented single pass and the diagonal call on the same resident result and strands: what the second key word and the second reducer cost
         W = a.diag_bin
