@@ -39,9 +39,9 @@
 #include "hsk_combine.h"
 #include "hsk_heavy.h"
 #include "hsk_pairs.h"
-#include "hsk_pairmerge.h"
+#include "hsk_pairplan.h"
 #include "hsk_pairdiag.h"
-#include "hsk_diagmerge.h"
+#include "hsk_rowmerge.h"
 #include "hsk_extend.h"
 #include "hsk_strand.h"
 #include "hsk_estimate.h"

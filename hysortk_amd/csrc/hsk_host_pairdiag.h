@@ -1,24 +1,8 @@
 // hsk_host_pairdiag.h -- host side of hsk_result_pair_diagonals, hsk_result_pair_diagonals_sliced and hsk_pair_diags_merge: the seed bins of
-// every oriented read pair, and the best-supported one (kernels: hsk_pairdiag.h, hsk_diagmerge.h, and the expansion of hsk_pairs.h).  The
+// every oriented read pair, and the best-supported one (kernels: hsk_pairdiag.h, hsk_rowmerge.h, and the expansion of hsk_pairs.h).  The
 // range, the record pass, the count-and-emit driver, the slice plan, the stack of lists and its merges, the egress and the argument checks
 // are those of hsk_host_pairs.h.  Part of the single translation unit hsk_api.hip (included in this order; everything here is file-local).
 #pragma once
-
-// the six-word all-bins rows on a PairStack (hsk_host_pairs.h: PairRows has the members' meaning)
-struct DiagRows {
-    static constexpr u64 ROW_BYTES = DIAG_ROW_WORDS * 8, TILE = DM_TILE;
-    static constexpr int NTILE = 3;                      // kept rows, keys, bins
-    static constexpr bool COUNT_ONE = true;              // the keys of a single list are not its rows: the merge with nothing counts them
-    static void launch(hsk_ctx *c, bool emit, u32 tiles, const PairList &A, const PairList &B, u32 min_support, u64 *const *tile, u64 *rows)
-    {
-        DiagMergeArgs ma; memset(&ma, 0, sizeof ma);
-        ma.a = A.rows; ma.na = A.n; ma.b = B.rows; ma.nb = B.n; ma.min_support = min_support; ma.tile_cnt = tile[0]; ma.tile_keys = tile[1]; ma.tile_bins = tile[2]; ma.rows = rows;
-        if (emit) hipLaunchKernelGGL(diag_merge_kernel<true>, dim3(tiles), dim3(DM_THREADS), 0, c->stream, ma);
-        else hipLaunchKernelGGL(diag_merge_kernel<false>, dim3(tiles), dim3(DM_THREADS), 0, c->stream, ma);
-    }
-    static void counts(const u64 *st, PairMergeCounts *n) { n->keys = st[1]; n->bins = st[2]; }
-};
-static_assert(DM_ROW_WORDS == DIAG_ROW_WORDS, "the merge and the reducers agree on the row");
 
 static const PassTexts diag_texts = {"read pair diagonals", "(two buffers of two-word keys and two value buffers) and the bin rows on top; ask for a narrower task range and join the all-bins lists",
                                      " and join the all-bins lists"};
@@ -126,7 +110,7 @@ static int pair_diags_impl(hsk_ctx *c, const ResultPriv *rp, const StrandsPriv *
         rc = diag_window(c, r, w, true, nw, diag_w, all_bins ? min_support : 1, task_lo, task_hi, ck, out, &allb); if (rc) return rc;
         info->peak_records = records;
     } else {
-        PairStack<DiagRows> stk;
+        PairStack<DiagRow> stk;
         hsk_pair_diags acc; memset(&acc, 0, sizeof acc);
         for (size_t i = 0; i < win.size(); ++i) {
             const bool last = i + 1 == win.size();
@@ -188,7 +172,7 @@ static int pair_diags_merge_impl(hsk_ctx *c, const hsk_pair_diags *const *parts,
     PairCall pc(c);
     PairClock &ck = pc.ck;
     int rc = pc.start(c); if (rc) return rc;
-    PairStack<DiagRows> stk;
+    PairStack<DiagRow> stk;
     rc = pairs_stack_parts(c, parts, nparts, ck, stk, out); if (rc) return rc;
     PairList allb, fin; PairMergeCounts cnt;
     rc = stk.finish(c, all_bins ? min_support : 1, ck, &allb, &cnt); if (rc) return rc;

@@ -1,5 +1,5 @@
 // hsk_host_pairs.h -- host side of hsk_result_pairs, hsk_result_pairs_sliced, hsk_result_pairs_oriented and hsk_pairs_merge: read pairs that
-// share k-mers, from the resident EXTENSION list (kernels: hsk_pairs.h, hsk_pairmerge.h).  The slice plan, the merge of two lists, the stack of
+// share k-mers, from the resident EXTENSION list (kernels: hsk_pairs.h, hsk_pairplan.h, hsk_rowmerge.h).  The slice plan, the merge of two lists, the stack of
 // lists and the several-list call are templates over the rows: hsk_host_pairdiag.h uses them for the six-word rows of the diagonals.
 // Part of the single translation unit hsk_api.hip (included in this order; everything here is file-local).
 #pragma once
@@ -227,22 +227,20 @@ static int pairs_window(hsk_ctx *c, PairRange &r, const PairWindow &w, bool last
 struct PairMergeStat { u64 merges = 0, merged_rows = 0; };
 struct PairMergeCounts { u64 keys = 0, bins = 0; };      // of a merged list before the filter: distinct keys; rows (the six-word lists only)
 
-// What a merge of two row lists needs to know about the rows: their width, the tile of the merge kernel, how many tile arrays its COUNT
-// pass fills (the kept rows first, then the counts before the filter) and the two launches.  The four-word rows of the pair lists are
-// PairRows; the six-word all-bins rows of the diagonals are DiagRows (hsk_host_pairdiag.h).
-struct PairRows {
-    static constexpr u64 ROW_BYTES = 32, TILE = PM_TILE;
-    static constexpr int NTILE = 2;                      // kept rows, keys
-    static constexpr bool COUNT_ONE = false;             // a single list's counts are known without a merge: keys = its rows
-    static void launch(hsk_ctx *c, bool emit, u32 tiles, const PairList &A, const PairList &B, u32 min_shared, u64 *const *tile, u64 *rows)
-    {
-        PairMergeArgs ma; memset(&ma, 0, sizeof ma);
-        ma.a = A.rows; ma.na = A.n; ma.b = B.rows; ma.nb = B.n; ma.min_shared = min_shared; ma.tile_cnt = tile[0]; ma.tile_keys = tile[1]; ma.rows = rows;
-        if (emit) hipLaunchKernelGGL(pair_merge_kernel<true>, dim3(tiles), dim3(PM_THREADS), 0, c->stream, ma);
-        else hipLaunchKernelGGL(pair_merge_kernel<false>, dim3(tiles), dim3(PM_THREADS), 0, c->stream, ma);
-    }
-    static void counts(const u64 *st, PairMergeCounts *n) { n->keys = st[1]; n->bins = 0; }
-};
+// What a merge of two row lists needs to know about the rows -- their width, the tile of the merge kernel, how many tile arrays its COUNT
+// pass fills (the kept rows first, then the counts before the filter) -- is the row's shape in hsk_rowmerge.h: PairRow, the four-word rows
+// of the pair lists, and DiagRow, the six-word all-bins rows of the diagonals.
+static_assert(PairRow::WORDS == PAIR_ROW_WORDS && DiagRow::WORDS == DIAG_ROW_WORDS, "the merge and the reducers agree on the rows");
+
+template <typename R>
+static void row_merge_launch(hsk_ctx *c, bool emit, u32 tiles, const PairList &A, const PairList &B, u32 min_count, u64 *const *tile, u64 *rows)
+{
+    RowMergeArgs<R> ma; memset(&ma, 0, sizeof ma);
+    ma.a = A.rows; ma.na = A.n; ma.b = B.rows; ma.nb = B.n; ma.min_count = min_count; ma.rows = rows;
+    for (int i = 0; i < R::NTILE; ++i) ma.tile[i] = tile[i];
+    if (emit) hipLaunchKernelGGL((row_merge_kernel<R, true>), dim3(tiles), dim3(MP_THREADS), 0, c->stream, ma);
+    else hipLaunchKernelGGL((row_merge_kernel<R, false>), dim3(tiles), dim3(MP_THREADS), 0, c->stream, ma);
+}
 
 // One merge (CountEmit: COUNT, the scans, EMIT) of two lists on the device into a block of its own; one wait, for the row count.  *cnt: the
 // counts before the filter.  The inputs are left to the caller.
@@ -259,13 +257,13 @@ static int pairs_merge_two(hsk_ctx *c, const PairList &A, const PairList &B, u32
     CountEmit ce(c, ck, PT_MERGE, tiles, R::NTILE);
     static const int word[3] = {0, 1, 2};
     const u64 *st;
-    int rc = ce.count(d_tot, R::NTILE, word, &st, [&] { R::launch(c, false, (u32)tiles, A, B, min_shared, ce.tile, nullptr); });
+    int rc = ce.count(d_tot, R::NTILE, word, &st, [&] { row_merge_launch<R>(c, false, (u32)tiles, A, B, min_shared, ce.tile, nullptr); });
     if (rc) return rc;
     const u64 nrows = st[0];
-    R::counts(st, cnt);
+    cnt->keys = st[1]; cnt->bins = R::NTILE > 2 ? st[2] : 0;       // (PairRow: the rows before the filter are its keys)
     if (nrows > total || cnt->keys > total || cnt->bins > total) return fail(c, HSK_ERR_INTERNAL, "the merge of %llu rows counted %llu", (unsigned long long)total, (unsigned long long)std::max(nrows, std::max(cnt->keys, cnt->bins)));
-    if (nrows) DALLOC(c, out->rows, u64 *, nrows * R::ROW_BYTES);
-    rc = ce.emit(nrows != 0, [&] { R::launch(c, true, (u32)tiles, A, B, min_shared, ce.tile, out->rows); });
+    if (nrows) DALLOC(c, out->rows, u64 *, nrows * R::WORDS * 8);
+    rc = ce.emit(nrows != 0, [&] { row_merge_launch<R>(c, true, (u32)tiles, A, B, min_shared, ce.tile, out->rows); });
     if (rc) return rc;
     out->n = nrows;
     c->pool.release(d_tot);
@@ -276,7 +274,7 @@ static int pairs_merge_two(hsk_ctx *c, const PairList &A, const PairList &B, u32
 // The lists of the slices (or the caller's parts) in the order of a binary counter: a list enters at level 0, and while the two lists
 // on top have the same level they become one list of the next level.  A row is read by at most ceil(log2(lists)) + 1 merges, and no
 // list grows by one slice at a time.  finish() merges what is left, top first; the LAST merge applies the filter and counts the list
-// before it.  R: the rows (PairRows, DiagRows).
+// before it.  R: the rows (PairRow, DiagRow).  A single PairRow list's counts are known without a merge: keys = its rows.
 template <typename R>
 struct PairStack {
     std::vector<PairList> v;
@@ -418,7 +416,7 @@ static int pairs_impl(hsk_ctx *c, const ResultPriv *rp, const StrandsPriv *sp, i
     } else {
         std::vector<PairWindow> win;
         rc = pairs_plan_windows(c, r, budget, win); if (rc) return rc;
-        PairStack<PairRows> stk;
+        PairStack<PairRow> stk;
         hsk_pairs acc; memset(&acc, 0, sizeof acc);
         for (size_t i = 0; i < win.size(); ++i) {
             const bool last = i + 1 == win.size();
@@ -541,9 +539,9 @@ static int pairs_stack_parts(hsk_ctx *c, const Part *const *parts, int32_t npart
         PairList l; l.n = p->n;
         if (p->rows_dev) { l.rows = (u64 *)p->rows_dev; l.owned = false; }
         else {
-            DALLOC(c, l.rows, u64 *, p->n * R::ROW_BYTES);
-            HIPCHK(c, hipMemcpyAsync(l.rows, p->rows, p->n * R::ROW_BYTES, hipMemcpyHostToDevice, c->stream));      // (pageable or pinned: the part outlives the call's last wait)
-            c->stats.h2d_bytes += p->n * R::ROW_BYTES;
+            DALLOC(c, l.rows, u64 *, p->n * R::WORDS * 8);
+            HIPCHK(c, hipMemcpyAsync(l.rows, p->rows, p->n * R::WORDS * 8, hipMemcpyHostToDevice, c->stream));      // (pageable or pinned: the part outlives the call's last wait)
+            c->stats.h2d_bytes += p->n * R::WORDS * 8;
         }
         const int rc = stk.push(c, l, i != last, ck); if (rc) return rc;
     }
@@ -555,7 +553,7 @@ static int pairs_merge_impl(hsk_ctx *c, const hsk_pairs *const *parts, int32_t n
     PairCall pc(c);
     PairClock &ck = pc.ck;
     int rc = pc.start(c); if (rc) return rc;
-    PairStack<PairRows> stk;
+    PairStack<PairRow> stk;
     rc = pairs_stack_parts(c, parts, nparts, ck, stk, out); if (rc) return rc;
     PairList fin; PairMergeCounts cnt;
     rc = stk.finish(c, min_shared, ck, &fin, &cnt); if (rc) return rc;

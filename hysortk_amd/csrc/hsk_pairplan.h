@@ -1,4 +1,4 @@
-// hsk_pairplan.h -- slices of a task range's records for hsk_result_pairs_sliced (host: hsk_host_pairs.h; kernel: hsk_pairmerge.h).
+// hsk_pairplan.h -- slices of a task range's records for hsk_result_pairs_sliced (host: hsk_host_pairs.h; the kernel is at the end).
 //
 // pair_tsum_kernel gives entry e of the range its exclusive record offset off[e] (off[0] = 0, off[nent] = records).  A SLICE is a run
 // of entries [from, e): its records are the window [off[from], off[e]) of the range's record array, expanded, sorted and reduced on its
@@ -10,7 +10,7 @@
 // wherever the run lies, so a run of any length costs no slice and no step.  The differences are taken, never off[from] + max_records:
 // a budget near 2^64 does not wrap.
 //
-// No HIP in here: the planner runs on the CPU under the sanitizers (tests/pairplan_test.cpp).
+// No HIP in the planner: it runs on the CPU under the sanitizers (tests/pairplan_test.cpp).
 #pragma once
 #include <cstdint>
 
@@ -60,3 +60,31 @@ HSK_PP_FN uint64_t pair_plan_max_slices(uint64_t nent, uint64_t records, uint64_
 }
 
 } // namespace hsk
+
+#if defined(__HIPCC__)
+#include "hsk_device.h"
+
+namespace hsk {
+
+// one lane: every cut of the range's entries under the budget, and the record offset at each cut
+struct PairPlanArgs {
+    const u64 *off; u64 nent, max_records;
+    u64 *cut;                // cap pairs { cut, off[cut] }
+    u64 cap;
+    u64 *ncut;
+};
+
+__global__ void pair_plan_kernel(PairPlanArgs p)
+{
+    if (blockIdx.x || threadIdx.x) return;
+    u64 n = 0, from = 0;
+    while (from < p.nent && n < p.cap) {
+        from = pair_plan_next(p.off, p.nent, from, p.max_records);
+        p.cut[2 * n] = from; p.cut[2 * n + 1] = p.off[from];
+        ++n;
+    }
+    p.ncut[0] = from < p.nent ? ~0ULL : n;               // (the bound of the cuts did not hold: never, by the argument above)
+}
+
+} // namespace hsk
+#endif

@@ -192,6 +192,7 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_expand_kernel(PairExpandArg
 
 constexpr int PR_PPT = 8, PR_TILE = PAIR_THREADS * PR_PPT, PR_WORDS = PR_TILE / 64;
 constexpr int PR_AHEAD = 4;                              // records per lane and step of the read-ahead
+constexpr int PAIR_ROW_WORDS = 4;                        // { key, shared, first, last }
 enum { PAIR_STAT_RECORDS = 0, PAIR_STAT_ROWS, PAIR_STAT_SELF, PAIR_STAT_KEYS, PAIR_STAT_ERR, PAIR_STAT_WORDS = 8 };
 
 struct PairReduceArgs {
@@ -276,7 +277,7 @@ __global__ __launch_bounds__(PAIR_THREADS) void pair_reduce_kernel(PairReduceArg
         RunAcc r = L;
         if (p != (u32)p_last) r.span(s_v, p, (u32)c);
         typedef unsigned long long v2u64r __attribute__((ext_vector_type(2)));
-        v2u64r *row = (v2u64r *)(a.rows + (obase + rm_slot(s_keep, s_pre, j)) * 4);
+        v2u64r *row = (v2u64r *)(a.rows + (obase + rm_slot(s_keep, s_pre, j)) * PAIR_ROW_WORDS);
         const v2u64r r0 = {s_k[p + 1], c}, r1 = {r.mn, r.mx};
         row[0] = r0; row[1] = r1;
     }

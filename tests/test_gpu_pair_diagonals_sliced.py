@@ -1,6 +1,6 @@
 """hsk_result_pair_diagonals_sliced (include/hsk.h): the read pairs by diagonal of a resident EXTENSION result from at most max_records
 records expanded at a time -- the slice planner, the window arguments of the expansion with the two-word key, one bound of the positions
-for all slices, and the merges of the slices' all-bins lists on (key, bin) (hsk_diagmerge.h) with the selection behind them -- against
+for all slices, and the merges of the slices' all-bins lists on (key, bin) (hsk_rowmerge.h) with the selection behind them -- against
 the definition applied in numpy to the CPU oracle's result (tests/diagonal_ref.py).  Everything is integer work and compared exactly,
 whatever the budget.  The inputs are those of tests/test_gpu_pair_diagonals.py."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """hsk_pair_diags_merge (include/hsk.h): the several-list contract of the read pairs by diagonal on the GPU -- the merge kernel of
-hysortk_amd/csrc/hsk_diagmerge.h on the two-word key (key, bin), and the selection behind it -- against PairDiagonals.combine(parts) and
+hysortk_amd/csrc/hsk_rowmerge.h on six-word rows and the two-word key (key, bin), and the selection behind it -- against PairDiagonals.combine(parts) and
 .select(), the host code in numpy, on synthetic all-bins lists.  A list is ascending by (key, bin) with every (key, bin) at most once;
 first and last are arbitrary 64-bit numbers (the minimum and maximum are held to the unsigned order everywhere).  All comparisons are exact:
 rows, keys, bins, records, self_records."""
@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 SIZES = [0, 1, 2, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 2049, 4097, 20011]      # around the tile of the merge (512) and of the selection (1024), and many tiles
 BIT63 = np.uint64(1) << np.uint64(63)
-MERGE_TILE, SELECT_TILE = 512, 1024                      # hsk_diagmerge.h: DM_TILE; hsk_pairdiag.h: DS_TILE
+MERGE_TILE, SELECT_TILE = 512, 1024                      # hsk_rowmerge.h: DiagRow::TILE; hsk_pairdiag.h: DS_TILE
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
-"""hsk_pairs_merge (include/hsk.h): the several-list contract of the read pairs on the GPU -- the merge kernels of
-hysortk_amd/csrc/hsk_pairmerge.h -- against ReadPairs.combine(parts), the host code in numpy, on synthetic row lists.  A list is ascending
+"""hsk_pairs_merge (include/hsk.h): the several-list contract of the read pairs on the GPU -- the merge kernel of
+hysortk_amd/csrc/hsk_rowmerge.h on four-word rows -- against ReadPairs.combine(parts), the host code in numpy, on synthetic row lists.  A list is ascending
 by key with every key at most once; the words behind the key are arbitrary 64-bit numbers here (first and last use all 64 bits throughout,
 so the minimum and maximum are held to the unsigned order everywhere).  All comparisons are exact: rows, keys, records, self_records."""
 import ctypes as C
@@ -10,7 +10,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-SIZES = [0, 1, 2, 255, 256, 257, 2047, 2048, 2049, 4095, 4096, 4097, 20011]      # around every tile size the kernel may have (2^8 .. 2^12), and many tiles
+# around the tile the kernel has (hsk_rowmerge.h: PairRow::TILE = 1024; 0 + 1024 and 1 + 1023 are one full tile with no look-ahead), around
+# every other tile size it may have (2^8 .. 2^12), and many tiles
+SIZES = [0, 1, 2, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4096, 4097, 20011]
 BIT63 = np.uint64(1) << np.uint64(63)
 
 

@@ -1,6 +1,6 @@
 """hsk_result_pairs_sliced (include/hsk.h): the read pairs of a resident EXTENSION result from at most max_records records expanded at a
 time -- the slice planner (hsk_pairplan.h), the window arguments of the expansion and the merges of the slices' row lists
-(hsk_pairmerge.h) -- against the definition applied in numpy to the CPU oracle's result (tests/test_gpu_pairs.py: reference).  Everything
+(hsk_rowmerge.h) -- against the definition applied in numpy to the CPU oracle's result (tests/test_gpu_pairs.py: reference).  Everything
 is integer work and compared exactly, whatever the budget."""
 import numpy as np
 import pytest
