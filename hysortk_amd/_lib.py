@@ -99,7 +99,15 @@ class Overlaps(C.Structure):
         ("n", C.c_uint64), ("rows", C.POINTER(C.c_uint64)), ("rows_dev", C.c_void_p),
         ("input_rows", C.c_uint64), ("dropped", C.c_uint64), ("columns", C.c_uint64), ("wave_rows", C.c_uint64),
         ("ms_extend", C.c_double), ("ms_d2h", C.c_double), ("ms_total", C.c_double),
-        ("reserved", C.c_int64 * 4), ("priv", C.c_void_p),
+        ("cells", C.c_uint64), ("reserved", C.c_int64 * 3), ("priv", C.c_void_p),
+    ]
+
+
+class GappedOpts(C.Structure):
+    """hsk_gapped_opts: the scores, the band, the filter and the group width of hsk_pair_diags_extend_gapped."""
+    _fields_ = [
+        ("match", C.c_int32), ("mismatch", C.c_int32), ("gap", C.c_int32), ("xdrop", C.c_uint32), ("band", C.c_uint32), ("min_score", C.c_uint64),
+        ("min_length", C.c_uint32), ("group", C.c_uint32), ("reserved", C.c_int64 * 4),
     ]
 
 
@@ -118,7 +126,7 @@ SYMBOLS = [
     "hsk_result_pairs_sliced", "hsk_pairs_merge",
     "hsk_result_strands", "hsk_strands_task", "hsk_strands_free", "hsk_result_pairs_oriented",
     "hsk_result_pair_diagonals", "hsk_pair_diags_free", "hsk_result_pair_diagonals_sliced", "hsk_pair_diags_merge",
-    "hsk_pair_diags_extend", "hsk_overlaps_free",
+    "hsk_pair_diags_extend", "hsk_overlaps_free", "hsk_pair_diags_extend_gapped",
     "hsk_stage_destinations", "hsk_stage_task_kmers", "hsk_stage_sort", "hsk_stage_count_sorted",
     "hsk_plan_tot_tasks", "hsk_plan_classify", "hsk_plan_dispatch", "hsk_plan_partition_reads", "hsk_plan_exchange",
     "hsk_comm_get_unique_id", "hsk_comm_init", "hsk_comm_destroy", "hsk_comm_selftest",
@@ -187,6 +195,8 @@ def load():
     L.hsk_pair_diags_free.restype = None
     L.hsk_pair_diags_extend.argtypes = [vp, C.POINTER(PairDiags), vp, C.c_uint64, vp, vp, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(ExtendOpts), C.c_int32,
                                         C.POINTER(Overlaps)]
+    L.hsk_pair_diags_extend_gapped.argtypes = [vp, C.POINTER(PairDiags), vp, C.c_uint64, vp, vp, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(GappedOpts), C.c_int32,
+                                               C.POINTER(Overlaps)]
     L.hsk_overlaps_free.argtypes = [vp, C.POINTER(Overlaps)]
     L.hsk_overlaps_free.restype = None
     L.hsk_pairs_free.argtypes = [vp, C.POINTER(Pairs)]

@@ -452,6 +452,25 @@ class PairDiagonals:
         mismatch (a penalty) in 0 .. 2^15, xdrop in 0 .. 2^31 - 1; min_score / min_length drop rows after the extension; wave_span: rows
         whose span is at least this many columns are extended by a whole wavefront (0: the library's default, 1: all, 0xFFFFFFFF: none; the
         rows are the same).  Returns an Overlaps (on_device=True: its rows stay in HBM; close() it before the context goes)."""
+        opts = _lib.ExtendOpts()
+        opts.match, opts.mismatch, opts.xdrop, opts.min_score, opts.min_length, opts.wave_span = int(match), int(mismatch), int(xdrop), int(min_score), int(min_length), int(wave_span)
+        return self._extend_call(ctx, ctx.lib.hsk_pair_diags_extend, reads, rid_base, opts, on_device)
+
+    def extend_gapped(self, ctx, reads, rid_base=None, match=1, mismatch=1, gap=1, xdrop=7, band=15, min_score=0, min_length=0, group=0, on_device=False):
+        """hsk_pair_diags_extend_gapped: the seed of every row extended in both directions inside a band of diagonals -- cell by cell over
+        the antidiagonals, with match / mismatch / gap scores and an x-drop stop (include/hsk.h has the definition) --, so that the overlap
+        follows the reads across insertions and deletions.  Rows, reads, rid_base, min_score, min_length and on_device as in extend().
+        match in 1 .. 255, mismatch and gap (penalties) in 0 .. 255, xdrop in 0 .. 2^31 - 1, band in 0 .. 63 (band 0 gives extend()'s rows);
+        group: the lanes that take one row, 0 (the smallest that holds the band) or 8, 16, 32, 64 with band <= group - 1 -- the rows are the
+        same.  Reads with la + lb >= 2^22 are refused.  Returns an Overlaps: `edits` counts substitutions and gap bases, info["cells"] the
+        live cells of all rows."""
+        opts = _lib.GappedOpts()
+        opts.match, opts.mismatch, opts.gap, opts.xdrop, opts.band = int(match), int(mismatch), int(gap), int(xdrop), int(band)
+        opts.min_score, opts.min_length, opts.group = int(min_score), int(min_length), int(group)
+        return self._extend_call(ctx, ctx.lib.hsk_pair_diags_extend_gapped, reads, rid_base, opts, on_device)
+
+    def _extend_call(self, ctx, fn, reads, rid_base, opts, on_device):
+        """what extend() and extend_gapped() share: the rows where they lie, the reads where they lie, the call, the Overlaps"""
         pd = _lib.PairDiags()
         pd.n = len(self)
         keep = None
@@ -460,19 +479,17 @@ class PairDiagonals:
         elif len(self):
             keep = np.ascontiguousarray(self.rows(), dtype=np.uint64)
             pd.rows = keep.ctypes.data_as(C.POINTER(C.c_uint64))
-        opts = _lib.ExtendOpts()
-        opts.match, opts.mismatch, opts.xdrop, opts.min_score, opts.min_length, opts.wave_span = int(match), int(mismatch), int(xdrop), int(min_score), int(min_length), int(wave_span)
         ov = _lib.Overlaps()
         if isinstance(reads, DeviceDna):
             base = reads.first_read_id if rid_base is None else rid_base
-            rc = ctx.lib.hsk_pair_diags_extend(ctx.h, C.byref(pd), reads.dp, reads.nbytes, reads.do, reads.dl, reads.nreads, base, 1, C.byref(opts), 1 if on_device else 0, C.byref(ov))
+            rc = fn(ctx.h, C.byref(pd), reads.dp, reads.nbytes, reads.do, reads.dl, reads.nreads, base, 1, C.byref(opts), 1 if on_device else 0, C.byref(ov))
         else:
             base = getattr(reads, "first_read_id", 0) if rid_base is None else rid_base
             packed, off, lens = reads.arrays() if isinstance(reads, DnaBuffer) else reads
             packed = np.ascontiguousarray(packed, dtype=np.uint8)
             off = np.ascontiguousarray(off, dtype=np.uint64)
             lens = np.ascontiguousarray(lens, dtype=np.uint32)
-            rc = ctx.lib.hsk_pair_diags_extend(ctx.h, C.byref(pd), _p(packed), packed.size, _p(off), _p(lens), lens.size, base, 0, C.byref(opts), 1 if on_device else 0, C.byref(ov))
+            rc = fn(ctx.h, C.byref(pd), _p(packed), packed.size, _p(off), _p(lens), lens.size, base, 0, C.byref(opts), 1 if on_device else 0, C.byref(ov))
         ctx._check(rc)
         return Overlaps._wrap(ctx, ov, on_device)
 
@@ -511,7 +528,8 @@ class PairDiagonals:
 
 
 class Overlaps:
-    """The ungapped x-drop overlaps of a list of diagonal rows (hsk_pair_diags_extend, include/hsk.h): rows { key, score, a_lo << 32 | a_hi,
+    """The x-drop overlaps of a list of diagonal rows, ungapped (hsk_pair_diags_extend, include/hsk.h) or banded and gapped
+    (hsk_pair_diags_extend_gapped: `edits` is `mismatches`, info["cells"] the live cells): rows { key, score, a_lo << 32 | a_hi,
     b_lo << 32 | b_hi, mismatches << 32 | ends, support } with key = o << 63 | rid_a << 32 | rid_b.  [a_lo, a_hi) and [b_lo, b_hi) are
     forward read coordinates, half-open; ends has bit 0 a_lo == 0, bit 1 a_hi == len(a), bit 2 b_lo == 0, bit 3 b_hi == len(b).  info has
     input_rows, dropped, columns, wave_rows and the ms_* of the call.  With on_device the rows stay in HBM (rows_dev: n rows of six uint64
@@ -526,6 +544,7 @@ class Overlaps:
         self.a_lo, self.a_hi = (self._a >> np.uint64(32)).astype(np.uint32), (self._a & lo).astype(np.uint32)
         self.b_lo, self.b_hi = (self._b >> np.uint64(32)).astype(np.uint32), (self._b & lo).astype(np.uint32)
         self.mismatches, self.ends = (self._me >> np.uint64(32)).astype(np.uint32), (self._me & lo).astype(np.uint32)
+        self.edits = self.mismatches             # (the gapped call's name for the same word: substitutions and gap bases)
         self.opposite = (self.key >> np.uint64(63)).astype(bool)
         self.rid_a, self.rid_b = ((self.key >> np.uint64(32)) & np.uint64(0x7FFFFFFF)).astype(np.uint32), (self.key & lo).astype(np.uint32)
         self.info = info or {}
@@ -562,7 +581,7 @@ class Overlaps:
     @staticmethod
     def _wrap(ctx, ov, on_device):
         """An Overlaps from a filled hsk_overlaps: the rows copied to numpy and the struct freed, or (on_device) left in HBM and owned."""
-        info = dict(input_rows=int(ov.input_rows), dropped=int(ov.dropped), columns=int(ov.columns), wave_rows=int(ov.wave_rows),
+        info = dict(input_rows=int(ov.input_rows), dropped=int(ov.dropped), columns=int(ov.columns), wave_rows=int(ov.wave_rows), cells=int(ov.cells),
                     ms_extend=ov.ms_extend, ms_d2h=ov.ms_d2h, ms_total=ov.ms_total)
         n = int(ov.n)
         if on_device:

@@ -43,6 +43,7 @@
 #include "hsk_pairdiag.h"
 #include "hsk_rowmerge.h"
 #include "hsk_extend.h"
+#include "hsk_extend_gapped.h"
 #include "hsk_strand.h"
 #include "hsk_estimate.h"
 #include "hsk_synth.h"

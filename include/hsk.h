@@ -534,7 +534,8 @@ typedef struct {
     void     *rows_dev;     /* device copy when asked for */
     uint64_t input_rows, dropped, columns, wave_rows;
     double   ms_extend, ms_d2h, ms_total;   /* HIP events */
-    int64_t  reserved[4];
+    uint64_t cells;         /* hsk_pair_diags_extend_gapped: live cells (below); 0 from the ungapped call.  The first word of what was reserved[4] */
+    int64_t  reserved[3];
     void    *priv;
 } hsk_overlaps;
 
@@ -543,6 +544,67 @@ int  hsk_pair_diags_extend(hsk_ctx *ctx, const hsk_pair_diags *in,
                            uint64_t nreads, int64_t rid_base, int32_t reads_on_device,
                            const hsk_extend_opts *opts, int32_t on_device, hsk_overlaps *out);
 void hsk_overlaps_free(hsk_ctx *ctx, hsk_overlaps *o);
+/*
+ * Gapped x-drop overlaps: the seed of every diagonal row, extended in both directions inside a band of diagonals, so that the overlap
+ * follows the reads across insertions and deletions.  One overlap row per input row; exact integer work, held to this definition word
+ * for word (csrc/hsk_gapped.h is the one implementation the kernel and the CPU tests share; tests/gapped_ref.py spells it base by base).
+ *
+ * Input.  Input, seed checks and refusals are exactly those of hsk_pair_diags_extend: the rows come from host memory or from HBM; the
+ * reads are given as hsk_result_strands takes them; K is the context's; the seed's K columns must fit their reads and all match.
+ *
+ * Sides.  For a row with seed (pa, pb), orientation o and reads A, B of lengths la, lb, each side walks two base sequences x (from A) and
+ * y (from B) away from the seed.  Indices start at 1.
+ *     side   x_i                 na            o   y_j                      nb
+ *     right  A[pa + K - 1 + i]   la - pa - K   0   B[pb + K - 1 + j]        lb - pb - K
+ *     right  A[pa + K - 1 + i]   la - pa - K   1   3 - B[pb - j]            pb
+ *     left   A[pa - i]           pa            0   B[pb - j]                pb
+ *     left   A[pa - i]           pa            1   3 - B[pb + K - 1 + j]    lb - pb - K
+ *
+ * Cells.  Cell (i, j) exists for 0 <= i <= na, 0 <= j <= nb and |i - j| <= band.  It lies on antidiagonal d = i + j.  A live cell holds a
+ * pair (s, e): score and edits.  Pairs compare by larger s first, then smaller e.  Cell (0, 0) is live with (0, 0).  For d = 1, 2, ...,
+ * the candidates of a cell come from its live predecessors:
+ *     from (i-1, j-1): (s + match, e) if x_i == y_j, else (s - mismatch, e + 1);
+ *     from (i-1, j) and from (i, j-1): (s - gap, e + 1).
+ * The cell takes the best candidate.  A cell with no candidate is dead.  It is also dead if best - s > xdrop.  Here `best` is the side's
+ * best score over antidiagonals 0 .. d - 1.
+ * After antidiagonal d: if its best live cell has s > best (strictly), then best, (i*, j*) and e* become that cell's.  The best live cell is
+ * the one with the largest (s, e) pair, and the smallest i on a tie.
+ * The side ends after two consecutive antidiagonals without a live cell, or after d = na + nb.  Nothing beyond that can be live, so the
+ * stop is exact.
+ *
+ * Row.  { key, score, a_lo << 32 | a_hi, b_lo << 32 | b_hi, edits << 32 | ends, support }
+ *     score = K * match + best_right + best_left.      edits = e*_right + e*_left.
+ *     a_lo = pa - i*_left, a_hi = pa + K + i*_right.
+ *     o = 0: b_lo = pb - j*_left, b_hi = pb + K + j*_right.      o = 1: b_lo = pb - j*_right, b_hi = pb + K + j*_left.
+ * `ends`, `support` and the order-keeping min_score / min_length filter are as in the ungapped call.
+ *
+ * Consequence.  With band = 0 the row equals hsk_pair_diags_extend's row word for word, for every match, mismatch and xdrop.
+ *
+ * Ranges.  match 1 .. 255; mismatch and gap 0 .. 255; xdrop 0 .. 2^31 - 1; band 0 .. 63.  A row with la + lb >= 2^22 is refused.  A 32-bit
+ * score is then exact.
+ *
+ *   opts       match, mismatch, gap, xdrop, band, min_score, min_length; group: the lanes that take one row.  0 = the smallest group that
+ *              holds the band; 8, 16, 32 or 64 force a width; a width with band > group - 1, or any other value, is
+ *              HSK_ERR_INVALID_ARG.  All legal widths give the same rows.
+ *   out        an hsk_overlaps as the ungapped call fills it; cells = the number of live cells on antidiagonals d >= 1 of both sides,
+ *              summed over all rows before the filter; columns as before; wave_rows = 0.
+ * Memory: 48 bytes per input row, 1 + 48 per row more with a filter, and the uploaded rows and reads.
+ * HSK_ERR_INVALID_ARG: every case of hsk_pair_diags_extend, with the same texts; match, mismatch, gap, xdrop, band or group outside
+ * their ranges; a row with la + lb >= 2^22 (no row is written).  The texts name the case and the number of rows.
+ */
+typedef struct {
+    int32_t  match, mismatch, gap;
+    uint32_t xdrop, band;
+    uint64_t min_score;
+    uint32_t min_length;
+    uint32_t group;
+    int64_t  reserved[4];
+} hsk_gapped_opts;
+
+int  hsk_pair_diags_extend_gapped(hsk_ctx *ctx, const hsk_pair_diags *in,
+                                  const void *packed, uint64_t packed_bytes, const void *read_byte_off, const void *read_len,
+                                  uint64_t nreads, int64_t rid_base, int32_t reads_on_device,
+                                  const hsk_gapped_opts *opts, int32_t on_device, hsk_overlaps *out);
 /* Result egress (write_output_file, reference src/hysortk.cpp:138-164): the lines "KMERSTRING\tcount\n" of `n` entries
  * ((nw + 1)-word records: host memory, or device memory when `on_device`), formatted on the GPU into `text` (host, capacity
  * bytes); *nbytes = bytes needed (call with capacity 0 to size the buffer: K + 2 + up to 20 digits per entry). */

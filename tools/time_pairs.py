@@ -40,7 +40,16 @@ packed reads copied to the host, and tests/extend_ref.py (numpy, one column per 
 device's rows.  Then a wave_span sweep (1, 512, 4096, none) on a long-read input (--long-reads reads of --long-len bases).  Writes
 profiles/pairs_extend_8mbp.json unless --out says otherwise.
 
-usage: python tools/time_pairs.py [--gbp 0.008] [--coverage 20] [--max-records N ...] [--merge-only] [--oriented [--strands-only]] [--diagonals [--diag-bin W] [--max-records N ...]] [--extend [--error-rate R]] [--out profiles/pairs_8mbp.json]"""
+--gapped [--band B ...] [--indel-rate R] [--error-rate R]: the gapped call beside the ungapped one.  The reads are made on the HOST -- fixed
+spans of a random genome, both strands, substitutions (--error-rate, default 0.01) and indels (--indel-rate, default 0.005: half
+insertions, half deletions), so their lengths differ; the device generator has substitutions only and stays as it is --, written as FASTA
+and packed on the GPU (hsk_pack_fasta).  The diagonal rows come from the pipeline (count, strands, hsk_result_pair_diagonals, best bin, left
+in HBM).  Timed in one run: hsk_result_pair_diagonals, hsk_pair_diags_extend, and hsk_pair_diags_extend_gapped for every --band (default 7,
+15, 31; the library's group width), with ms, live cells and live cells per second; a sample of --gapped-sample rows of every band is
+compared with tests/gapped_ref.py, and how many overlaps are longer than the ungapped ones is counted.  Writes
+profiles/pairs_gapped_8mbp.json unless --out says otherwise.
+
+usage: python tools/time_pairs.py [--gbp 0.008] [--coverage 20] [--max-records N ...] [--merge-only] [--oriented [--strands-only]] [--diagonals [--diag-bin W] [--max-records N ...]] [--extend [--error-rate R]] [--gapped [--band B ...] [--indel-rate R]] [--out profiles/pairs_8mbp.json]"""
 import argparse, json, os, sys, time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -148,8 +157,112 @@ def extend_sweep(H, a, peak):
     return work, res, same
 
 
+def host_reads_fasta(np, path, G, RL, n, sub, indel, seed):
+    """n reads as a FASTA file with its .fai: spans of RL bases of a random genome of G bases, half of them reverse-complemented, with
+    substitutions and indels (an insertion in front of a base, or the base deleted).  One line per record."""
+    rng = np.random.default_rng(seed)
+    genome = rng.integers(0, 4, G, dtype=np.uint8)
+    lens = np.zeros(n, np.int64)
+    parts = []
+    for lo in range(0, n, 1 << 17):                      # in blocks: the per-base random numbers of all reads at once are large
+        m = min(1 << 17, n - lo)
+        start = rng.integers(0, G - RL, m)
+        base = genome[start[:, None] + np.arange(RL)[None, :]]
+        rev = rng.integers(0, 2, m).astype(bool)
+        base[rev] = 3 - base[rev][:, ::-1]
+        u = rng.random((m, RL))
+        hit = (u >= indel) & (u < indel + sub)
+        base[hit] = (base[hit] + rng.integers(1, 4, int(hit.sum()), dtype=np.uint8)) & 3
+        emit = np.stack([rng.integers(0, 4, (m, RL), dtype=np.uint8), base], axis=2)                # (an inserted base, the base)
+        valid = np.stack([(u >= indel / 2) & (u < indel), u >= indel / 2], axis=2)
+        parts.append(emit[valid])                        # row-major: every read's bases in order
+        lens[lo:lo + m] = valid.sum(axis=(1, 2))
+    codes = np.concatenate(parts)
+    rec = np.concatenate([[0], np.cumsum(lens + 4)])     # ">r\n" + bases + "\n"
+    text = np.full(int(rec[-1]), 10, np.uint8)
+    text[rec[:-1]], text[rec[:-1] + 1] = ord(">"), ord("r")
+    flat = np.concatenate([[0], np.cumsum(lens)])
+    text[np.repeat(rec[:-1] + 3 - flat[:-1], lens) + np.arange(codes.size)] = np.frombuffer(b"ACGT", np.uint8)[codes]
+    text.tofile(path)
+    with open(path + ".fai", "w") as f:
+        f.write("".join("r\t%d\t%d\t%d\t%d\n" % (L, o + 3, L, L + 1) for L, o in zip(lens.tolist(), rec[:-1].tolist())))
+    return lens
+
+
+def gapped_run(H, a):
+    """--gapped: see the module's text"""
+    import shutil, tempfile
+    import numpy as np
+    from tests import gapped_ref as GR
+    RL, G = 150, int(a.gbp * 1e9)
+    n = int(G * a.coverage / RL)
+    bands = a.band or [7, 15, 31]
+    ctx = H.Context(K=31, M=17, L=2, U=50, EXT=1, ntasks=0, keep_device=True)
+    peak = ctx.copy_peak(1 << 30, 3)
+    tmp = tempfile.mkdtemp()
+    try:
+        t0 = time.perf_counter()
+        lens = host_reads_fasta(np, os.path.join(tmp, "reads.fa"), G, RL, n, a.error_rate, a.indel_rate, 11)
+        make_ms = (time.perf_counter() - t0) * 1e3
+        dna = H.read_dna_buffer_device(ctx, os.path.join(tmp, "reads.fa"))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    dev = dna.count_resident_device()
+    out = {"what": "tools/time_pairs.py --gapped: hsk_result_pair_diagonals (best bin), hsk_pair_diags_extend and hsk_pair_diags_extend_gapped of its rows, rows and reads in HBM; one run on one card",
+           "workload": {"genome_bp": G, "read_span": RL, "reads": n, "read_len_min": int(lens.min()), "read_len_max": int(lens.max()), "bases": int(lens.sum()), "error_rate": a.error_rate,
+                        "indel_rate": a.indel_rate, "K": 31, "M": 17, "L": 2, "U": 50, "ntasks": dev.ntasks, "entries": dev.n, "host_reads_wall_ms": make_ms},
+           "scores": {"match": 1, "mismatch": 1, "gap": 1, "xdrop": 7}, "diag_bin": a.diag_bin, "copy_peak_gbs": peak, "reps": a.reps}
+    with dev.strands(dna) as st:
+        diag = summary(timed(lambda: dev.pair_diagonals(st, a.diag_bin, on_device=True), reps=a.reps))
+        with dev.pair_diagonals(st, a.diag_bin, on_device=True) as pd:
+            ung = extend_summary(timed(lambda: pd.extend(ctx, dna, on_device=True), reps=a.reps), peak)
+            hrows = ctx.d2h(pd.rows_dev, pd.n * 48).view(np.uint64).reshape(pd.n, 6)
+            packed, off = dna.packed(), ctx.d2h(dna.do, n * 8).view(np.uint64)
+            pick = np.sort(np.random.default_rng(1).choice(pd.n, min(a.gapped_sample, pd.n), replace=False))
+            srows = hrows[pick].copy()
+            ids = np.concatenate([(srows[:, 0] >> np.uint64(32)) & np.uint64(0x7FFFFFFF), srows[:, 0] & np.uint64(0xFFFFFFFF)]).astype(np.int64)
+            uniq, inv = np.unique(ids, return_inverse=True)
+            srows[:, 0] = (srows[:, 0] & (np.uint64(1) << np.uint64(63))) | (inv[:pick.size].astype(np.uint64) << np.uint64(32)) | inv[pick.size:].astype(np.uint64)
+            mat = unpack_reads(np, packed, off.astype(np.int64), lens.astype(np.uint32), uniq)
+            urows = pd.extend(ctx, dna).rows()
+            lo = np.uint64(0xFFFFFFFF)
+            ulen = (urows[:, 2] & lo) - (urows[:, 2] >> np.uint64(32))
+            by_band = {}
+            for b in bands:
+                runs = timed(lambda: pd.extend_gapped(ctx, dna, band=b, on_device=True), reps=a.reps)
+                s = extend_summary(runs, peak)
+                s["cells"] = runs[-1]["cells"]
+                s["cells_per_s"] = s["cells"] / (s["median_ms_extend"] * 1e-3) if s["median_ms_extend"] > 0 else 0.0
+                s["group"] = 8 if b < 8 else 16 if b < 16 else 32 if b < 32 else 64
+                grows = pd.extend_gapped(ctx, dna, band=b).rows()
+                glen, gblen = (grows[:, 2] & lo) - (grows[:, 2] >> np.uint64(32)), (grows[:, 3] & lo) - (grows[:, 3] >> np.uint64(32))
+                s["rows_longer_than_ungapped"], s["rows_shorter_than_ungapped"], s["rows_whose_spans_differ"] = int((glen > ulen).sum()), int((glen < ulen).sum()), int((glen != gblen).sum())
+                s["edits"] = int((grows[:, 4] >> np.uint64(32)).sum())
+                t0 = time.perf_counter()
+                want, _, _ = GR.extend_rows_bulk(srows, mat, 31, band=b)
+                s["sample"] = {"rows": int(pick.size), "reference_wall_ms": (time.perf_counter() - t0) * 1e3,
+                               "device_rows_equal_reference": bool(np.array_equal(grows[pick][:, 1:], want[:, 1:]) and np.array_equal(grows[pick][:, 0], hrows[pick, 0]))}
+                s["over_ungapped"] = s["median_ms_extend"] / ung["median_ms_extend"] if ung["median_ms_extend"] > 0 else None
+                s["over_pair_diagonals"] = s["median_ms"] / diag["median_ms"] if diag["median_ms"] > 0 else None
+                by_band[str(b)] = s
+                print("%-40s %10.3f ms (kernels %.3f), %d cells, %.3g cells/s, %d of %d rows longer than ungapped, sample equal: %s" % (
+                    "hsk_pair_diags_extend_gapped band %d" % b, s["median_ms"], s["median_ms_extend"], s["cells"], s["cells_per_s"], s["rows_longer_than_ungapped"], pd.n, s["sample"]["device_rows_equal_reference"]))
+    out["pair_diagonals"], out["extend"], out["extend_gapped"] = diag, ung, by_band
+    print("%-40s %10.3f ms, %d rows" % ("hsk_result_pair_diagonals", diag["median_ms"], diag["rows"]))
+    print("%-40s %10.3f ms (kernels %.3f), %d columns" % ("hsk_pair_diags_extend", ung["median_ms"], ung["median_ms_extend"], ung["columns"]))
+    dev.close()
+    dna.free()
+    ctx.close()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gapped", action="store_true"); ap.add_argument("--band", type=int, action="append", default=[]); ap.add_argument("--indel-rate", type=float, default=0.005)
+    ap.add_argument("--gapped-sample", type=int, default=2000)
     ap.add_argument("--extend", action="store_true"); ap.add_argument("--error-rate", type=float, default=0.01); ap.add_argument("--sample", type=int, default=20000)
     ap.add_argument("--long-reads", type=int, default=2000); ap.add_argument("--long-len", type=int, default=12000)
     ap.add_argument("--gbp", type=float, default=0.008); ap.add_argument("--coverage", type=float, default=20.0)
@@ -159,6 +272,8 @@ def main():
     ap.add_argument("--reps", type=int, default=REPS)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None and a.gapped:
+        a.out = os.path.join(ROOT, "profiles", "pairs_gapped_8mbp.json")
     if a.out is None and a.extend:
         a.out = os.path.join(ROOT, "profiles", "pairs_extend_8mbp.json")
     if a.out is None:
@@ -166,6 +281,8 @@ def main():
     sys.path.insert(0, ROOT)
     import numpy as np
     import hysortk_amd as H
+    if a.gapped:
+        return gapped_run(H, a)
     RL = 150
     G = int(a.gbp * 1e9)
     n = int(G * a.coverage / RL)
