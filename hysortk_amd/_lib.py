@@ -111,6 +111,24 @@ class GappedOpts(C.Structure):
     ]
 
 
+class ReduceOpts(C.Structure):
+    """hsk_reduce_opts: the slack of the transitive test and the path threshold of hsk_overlaps_reduce."""
+    _fields_ = [("fuzz", C.c_uint32), ("wave_degree", C.c_uint32), ("reserved", C.c_int64 * 4)]
+
+
+class Reduced(C.Structure):
+    """hsk_reduced: the string graph of a list of overlap rows (hsk_overlaps_reduce)."""
+    _fields_ = [
+        ("n", C.c_uint64), ("rows", C.POINTER(C.c_uint64)), ("rows_dev", C.c_void_p),
+        ("row_class", C.POINTER(C.c_uint8)), ("row_class_dev", C.c_void_p), ("contained", C.POINTER(C.c_uint32)), ("contained_dev", C.c_void_p),
+        ("input_rows", C.c_uint64), ("nreads", C.c_uint64), ("class_rows", C.c_uint64 * 8),
+        ("contained_reads", C.c_uint64), ("arcs", C.c_uint64), ("wave_vertices", C.c_uint64), ("max_degree", C.c_uint64),
+        ("wave_degree", C.c_uint32), ("pad_", C.c_uint32),
+        ("ms_classify", C.c_double), ("ms_sort", C.c_double), ("ms_reduce", C.c_double), ("ms_d2h", C.c_double), ("ms_total", C.c_double),
+        ("reserved", C.c_int64 * 4), ("priv", C.c_void_p),
+    ]
+
+
 FLAG_PROFILE = 1
 FLAG_KEEP_DEVICE = 2
 FLAG_PLAIN_CLASSIFIER = 4
@@ -127,6 +145,7 @@ SYMBOLS = [
     "hsk_result_strands", "hsk_strands_task", "hsk_strands_free", "hsk_result_pairs_oriented",
     "hsk_result_pair_diagonals", "hsk_pair_diags_free", "hsk_result_pair_diagonals_sliced", "hsk_pair_diags_merge",
     "hsk_pair_diags_extend", "hsk_overlaps_free", "hsk_pair_diags_extend_gapped",
+    "hsk_overlaps_reduce", "hsk_reduced_free",
     "hsk_stage_destinations", "hsk_stage_task_kmers", "hsk_stage_sort", "hsk_stage_count_sorted",
     "hsk_plan_tot_tasks", "hsk_plan_classify", "hsk_plan_dispatch", "hsk_plan_partition_reads", "hsk_plan_exchange",
     "hsk_comm_get_unique_id", "hsk_comm_init", "hsk_comm_destroy", "hsk_comm_selftest",
@@ -199,6 +218,9 @@ def load():
                                                C.POINTER(Overlaps)]
     L.hsk_overlaps_free.argtypes = [vp, C.POINTER(Overlaps)]
     L.hsk_overlaps_free.restype = None
+    L.hsk_overlaps_reduce.argtypes = [vp, C.POINTER(Overlaps), vp, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(ReduceOpts), C.c_int32, C.POINTER(Reduced)]
+    L.hsk_reduced_free.argtypes = [vp, C.POINTER(Reduced)]
+    L.hsk_reduced_free.restype = None
     L.hsk_pairs_free.argtypes = [vp, C.POINTER(Pairs)]
     L.hsk_pairs_free.restype = None
     L.hsk_get_stats.argtypes = [vp, C.POINTER(Stats), C.c_int]

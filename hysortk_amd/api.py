@@ -578,6 +578,36 @@ class Overlaps:
         k = np.where(b[0] & b[1], self.A_CONTAINED, k)
         return k.astype(np.uint8)
 
+    def reduce(self, ctx, reads, rid_base=None, fuzz=10, wave_degree=0, on_device=False):
+        """hsk_overlaps_reduce: the string graph of this list (include/hsk.h has the definition) -- the reads that lie inside another read
+        go out, the dovetails become arcs between read ends, every arc that two shorter arcs explain is marked; what is left are the
+        edges.  Rows in HBM are read there, host rows are uploaded.  reads: only the lengths are used -- a DeviceDna (read where they lie), a
+        DnaBuffer, a (packed, off, lens) tuple or a bare array of lengths; rid_base: the id of read 0 (default: the buffer's first_read_id,
+        else 0).  fuzz: the bases by which the two short arcs may exceed the long one -- what it has to cover is the indel drift along one
+        overlap; wave_degree: vertices with at least this many out-arcs are reduced by a whole workgroup (0: the library's default, 1: all,
+        0xFFFFFFFF: none; the result is the same).  Returns an OverlapGraph (on_device=True: everything stays in HBM; close() it before the
+        context goes)."""
+        ov = _lib.Overlaps()
+        ov.n = len(self)
+        keep = None
+        if len(self) and self.rows_dev:
+            ov.rows_dev = self.rows_dev
+        elif len(self):
+            keep = np.ascontiguousarray(self.rows(), dtype=np.uint64)
+            ov.rows = keep.ctypes.data_as(C.POINTER(C.c_uint64))
+        opts = _lib.ReduceOpts(fuzz=int(fuzz), wave_degree=int(wave_degree))
+        rd = _lib.Reduced()
+        if isinstance(reads, DeviceDna):
+            base = reads.first_read_id if rid_base is None else rid_base
+            rc = ctx.lib.hsk_overlaps_reduce(ctx.h, C.byref(ov), reads.dl, reads.nreads, base, 1, C.byref(opts), 1 if on_device else 0, C.byref(rd))
+        else:
+            base = getattr(reads, "first_read_id", 0) if rid_base is None else rid_base
+            lens = reads.arrays()[2] if isinstance(reads, DnaBuffer) else (reads[2] if isinstance(reads, tuple) else reads)
+            lens = np.ascontiguousarray(lens, dtype=np.uint32)
+            rc = ctx.lib.hsk_overlaps_reduce(ctx.h, C.byref(ov), _p(lens), lens.size, base, 0, C.byref(opts), 1 if on_device else 0, C.byref(rd))
+        ctx._check(rc)
+        return OverlapGraph._wrap(ctx, rd, on_device, int(base))
+
     @staticmethod
     def _wrap(ctx, ov, on_device):
         """An Overlaps from a filled hsk_overlaps: the rows copied to numpy and the struct freed, or (on_device) left in HBM and owned."""
@@ -597,6 +627,101 @@ class Overlaps:
             if getattr(ctx, "h", None):
                 ctx.lib.hsk_overlaps_free(ctx.h, C.byref(ov))
             self._owner, self.rows_dev = None, None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class OverlapGraph:
+    """The string graph of a list of overlap rows (hsk_overlaps_reduce, include/hsk.h): `edges` -- an Overlaps with the KEPT rows in the
+    input's order --, `row_class` -- one of the class constants per input row --, `contained` -- one bool per read --, and info:
+    input_rows, rows per class under the classes' names in lower case, contained_reads, arcs, wave_vertices, max_degree, wave_degree (the
+    threshold that was used) and the ms_* of the call.  With on_device all three stay in HBM: edges.rows_dev, row_class_dev (input_rows
+    bytes) and contained_dev ((nreads + 31) // 32 uint32 words, read r is bit r % 32 of word r // 32); row_class and contained are then
+    None, host_copy() fetches them, close() gives everything back."""
+
+    KEPT, REDUCED, INTERNAL, A_CONTAINED, B_CONTAINED, DROPPED_READ, DUPLICATE, SELF = range(8)
+    CLASS_NAMES = ("kept", "reduced", "internal", "a_contained", "b_contained", "dropped_read", "duplicate", "self")
+
+    def __init__(self, edges, row_class, contained, info, rid_base=0, nreads=0, row_class_dev=None, contained_dev=None, owner=None):
+        self.edges, self.row_class, self.contained, self.info = edges, row_class, contained, info
+        self.rid_base, self.nreads = int(rid_base), int(nreads)
+        self.row_class_dev, self.contained_dev = row_class_dev, contained_dev
+        self._owner = owner                      # (ctx, hsk_reduced) of a graph that lives on the device
+
+    def __len__(self):
+        return len(self.edges)
+
+    @staticmethod
+    def unpack_contained(words, nreads):
+        """one bool per read from the bit words of the C ABI"""
+        return np.unpackbits(np.ascontiguousarray(words, dtype="<u4").view(np.uint8), bitorder="little")[:nreads].astype(bool)
+
+    @staticmethod
+    def _wrap(ctx, rd, on_device, rid_base):
+        info = dict(input_rows=int(rd.input_rows), contained_reads=int(rd.contained_reads), arcs=int(rd.arcs), wave_vertices=int(rd.wave_vertices), max_degree=int(rd.max_degree),
+                    wave_degree=int(rd.wave_degree), ms_classify=rd.ms_classify, ms_sort=rd.ms_sort, ms_reduce=rd.ms_reduce, ms_d2h=rd.ms_d2h, ms_total=rd.ms_total)
+        info.update({name: int(rd.class_rows[i]) for i, name in enumerate(OverlapGraph.CLASS_NAMES)})
+        n, rows_in, nreads = int(rd.n), int(rd.input_rows), int(rd.nreads)
+        if on_device:
+            z = np.zeros(0, np.uint64)
+            edges = Overlaps(z, z, z, z, z, z, rows_dev=rd.rows_dev, n=n)      # (the rows belong to the graph)
+            return OverlapGraph(edges, None, None, info, rid_base, nreads, row_class_dev=rd.row_class_dev, contained_dev=rd.contained_dev, owner=(ctx, rd))
+        rows = np.ctypeslib.as_array(rd.rows, shape=(n * 6,)).reshape(n, 6).copy() if n else np.zeros((0, 6), np.uint64)
+        cls = np.ctypeslib.as_array(rd.row_class, shape=(rows_in,)).copy() if rows_in else np.zeros(0, np.uint8)
+        words = np.ctypeslib.as_array(rd.contained, shape=((nreads + 31) // 32,)).copy() if nreads else np.zeros(0, np.uint32)
+        ctx.lib.hsk_reduced_free(ctx.h, C.byref(rd))
+        return OverlapGraph(Overlaps.from_rows(rows), cls, OverlapGraph.unpack_contained(words, nreads), info, rid_base, nreads)
+
+    def host_copy(self):
+        """(row_class, contained) of a graph in HBM, fetched"""
+        if self._owner is None:
+            return self.row_class, self.contained
+        ctx = self._owner[0]
+        n = self.info["input_rows"]
+        cls = ctx.d2h(self.row_class_dev, n) if n else np.zeros(0, np.uint8)
+        words = ctx.d2h(self.contained_dev, 4 * ((self.nreads + 31) // 32)).view(np.uint32) if self.nreads else np.zeros(0, np.uint32)
+        return cls, OverlapGraph.unpack_contained(words, self.nreads)
+
+    def arcs(self, lens, rid_base=None):
+        """(v, w, len, row) of the kept edges on the host, two arcs per edge (the table of include/hsk.h; numpy, needs no GPU): v = 2 r + s
+        with r counted from rid_base (default: the call's), s = 1 the reverse complement; an arc v -> w says that a suffix of v overlaps
+        a prefix of w, len is the number of bases of v in front of the overlap; row is the edge's index.  What a client walks."""
+        e = self.edges
+        base = self.rid_base if rid_base is None else int(rid_base)
+        lens = np.asarray(lens, dtype=np.int64)
+        a, b = e.rid_a.astype(np.int64) - base, e.rid_b.astype(np.int64) - base
+        la, lb = lens[a], lens[b]
+        a_lo, a_hi, b_lo, b_hi = (x.astype(np.int64) for x in (e.a_lo, e.a_hi, e.b_lo, e.b_hi))
+        o, en = e.opposite.astype(np.int64), (e.ends & np.uint32(15)).astype(np.int64)
+        good = np.where(o == 0, (en == 6) | (en == 9), (en == 10) | (en == 5))
+        if not good.all():
+            raise ValueError("row %d of the edges is no dovetail" % int(np.flatnonzero(~good)[0]))
+        first = (en == 6) | (en == 10)           # a_hi == la: a is in front
+        sb = o                                   # the orientation of b next to a forward a
+        v1 = np.where(first, 2 * a, 2 * b + sb)
+        w1 = np.where(first, 2 * b + sb, 2 * a)
+        l1 = np.where(first, a_lo, np.where(o == 0, b_lo, lb - b_hi))
+        l2 = np.where(first, np.where(o == 0, lb - b_hi, b_lo), la - a_hi)
+        row = np.arange(len(a), dtype=np.int64)
+        return np.concatenate([v1, w1 ^ 1]), np.concatenate([w1, v1 ^ 1]), np.concatenate([l1, l2]), np.concatenate([row, row])
+
+    def close(self):
+        if self._owner is not None:
+            ctx, rd = self._owner
+            if getattr(ctx, "h", None):
+                ctx.lib.hsk_reduced_free(ctx.h, C.byref(rd))
+            self._owner, self.row_class_dev, self.contained_dev = None, None, None
+            self.edges.rows_dev = None
 
     def __del__(self):
         try:

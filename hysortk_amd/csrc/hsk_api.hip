@@ -44,6 +44,7 @@
 #include "hsk_rowmerge.h"
 #include "hsk_extend.h"
 #include "hsk_extend_gapped.h"
+#include "hsk_reduce.h"
 #include "hsk_strand.h"
 #include "hsk_estimate.h"
 #include "hsk_synth.h"
@@ -462,6 +463,8 @@ extern "C" int hsk_result_device_task(const hsk_result *r, int32_t task, const v
 #include "hsk_host_pairdiag.h"
 // the ungapped x-drop overlap of every diagonal row's seed: hsk_pair_diags_extend, hsk_overlaps_free
 #include "hsk_host_extend.h"
+// the string graph of a list of overlap rows: hsk_overlaps_reduce, hsk_reduced_free
+#include "hsk_host_reduce.h"
 
 // Uploads the DnaBuffer description; returns device arrays with nreads+1 offsets.
 

@@ -193,7 +193,8 @@ __global__ __launch_bounds__(EW_THREADS) void extend_wave_kernel(ExtendArgs a)
 struct ExtendCompactArgs { const u64 *in; const u8 *keep; u64 n; u64 *tile_cnt; u64 *rows; };
 
 // COUNT (EMIT == false): tile_cnt[tile] = kept rows of the tile.  EMIT: tile_cnt holds the exclusive scan; the kept rows leave in order.
-template <bool EMIT>
+// KEEP_ZERO: the rows whose byte is 0 stay (hsk_overlaps_reduce: the byte is the row's class, and 0 is KEPT).
+template <bool EMIT, bool KEEP_ZERO = false>
 __global__ __launch_bounds__(RM_THREADS) void extend_compact_kernel(ExtendCompactArgs a)
 {
     __shared__ u64 s_keep[EC_WORDS];
@@ -203,7 +204,7 @@ __global__ __launch_bounds__(RM_THREADS) void extend_compact_kernel(ExtendCompac
 #pragma unroll
     for (int j = 0; j < EC_ROUNDS; ++j) {
         const u64 g = t0 + (u64)j * RM_THREADS + threadIdx.x;
-        kp[j] = g < a.n && a.keep[g] != 0;
+        kp[j] = g < a.n && (a.keep[g] != 0) != KEEP_ZERO;
         rm_publish(s_keep, j, __ballot(kp[j]));
     }
     __syncthreads();

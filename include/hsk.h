@@ -605,6 +605,88 @@ int  hsk_pair_diags_extend_gapped(hsk_ctx *ctx, const hsk_pair_diags *in,
                                   const void *packed, uint64_t packed_bytes, const void *read_byte_off, const void *read_len,
                                   uint64_t nreads, int64_t rid_base, int32_t reads_on_device,
                                   const hsk_gapped_opts *opts, int32_t on_device, hsk_overlaps *out);
+/*
+ * String graph: the reads that lie inside another read go out, the dovetails become arcs between read ends, and every arc that two
+ * shorter arcs explain is marked.  What is left are the edges of the string graph.  Integer work on the whole list at once, held to this
+ * definition word for word (csrc/hsk_strgraph.h is the one implementation the kernels and the CPU tests share; tests/strgraph_ref.py
+ * spells it with dictionaries).
+ *
+ * Input.  A list of hsk_overlaps rows: of `in` the call reads n, rows_dev if set, else rows (host memory, uploaded as the extend calls
+ * upload theirs); its priv may be NULL.  The reads' lengths read_len[nreads] (uint32; on the device with lens_on_device) and rid_base.
+ * No bases are read.  For a row: o = key >> 63; a, b are the reads rid_a - rid_base, rid_b - rid_base with lengths la, lb;
+ * e = word4 & 15 (the ends bits).
+ *
+ * Vertices.  Two per read: v = 2 r + s; s = 0 is the read as stored, s = 1 its reverse complement; the complement of v is v ^ 1.  An arc
+ * v -> w says that a suffix of oriented read v overlaps a prefix of oriented read w; len(v -> w) is the number of bases of v, in v's
+ * orientation, in front of the overlap.
+ *
+ * Row class (one byte per input row; the first rule that applies wins):
+ *     7 SELF          rid_a == rid_b
+ *     3 A_CONTAINED   e & 3 == 3: marks read a contained (also e == 15: of two reads that cover each other, a goes)
+ *     4 B_CONTAINED   e & 12 == 12: marks read b contained
+ *     2 INTERNAL      not a dovetail: o = 0 and e not in {6, 9}, or o = 1 and e not in {10, 5}
+ *     5 DROPPED_READ  a dovetail with a or b marked contained by ANY row of the list
+ *     6 DUPLICATE     among dovetails with equal (key, e) all but the one with the largest score; on a tie the smallest row index stays
+ *     1 REDUCED       a surviving dovetail with at least one transitive arc
+ *     0 KEPT          an edge of the string graph
+ *
+ * Arcs of a surviving dovetail: two, complements of each other.
+ *     o, e                              arc 1 (len)                  arc 2 (len)
+ *     0, 6   a_hi == la, b_lo == 0      2a   -> 2b   (a_lo)          2b+1 -> 2a+1 (lb - b_hi)
+ *     0, 9   a_lo == 0,  b_hi == lb     2b   -> 2a   (b_lo)          2a+1 -> 2b+1 (la - a_hi)
+ *     1, 10  a_hi == la, b_hi == lb     2a   -> 2b+1 (a_lo)          2b   -> 2a+1 (b_lo)
+ *     1, 5   a_lo == 0,  b_lo == 0      2b+1 -> 2a   (lb - b_hi)     2a+1 -> 2b   (la - a_hi)
+ *
+ * Transitive.  G is all arcs of surviving dovetails, duplicates out; arcs that are themselves transitive stay in G.  An arc v -> x of
+ * length L is transitive iff G has arcs v -> w and w -> x with w's read different from both v's read and x's read and
+ * len(v -> w) + len(w -> x) <= L + fuzz (64-bit sums).  One round on the unreduced graph: the result does not depend on the order of
+ * evaluation, and a second round would find nothing new.  A row is REDUCED iff either of its two arcs is transitive.  (Two rows with a
+ * and b exchanged can give the same arc twice; they are no duplicates, both arcs are in G.)
+ *
+ *   opts       fuzz; wave_degree: a vertex with at least this many out-arcs (arc records, duplicates included) is reduced by a whole
+ *              workgroup, any other arc by one lane.  0 = the library's default, 1 = every vertex by a workgroup, UINT32_MAX = none.
+ *              The result is the same for every value.
+ *   out        n, rows / rows_dev: the KEPT rows, six words unchanged, in the input's order -- again a valid hsk_overlaps list;
+ *              row_class / row_class_dev: input_rows bytes; contained / contained_dev: (nreads + 31) / 32 uint32 words, read r is
+ *              bit r % 32 of word r / 32.  With on_device all three stay in HBM, else all three are pinned host memory.
+ *              class_rows[c] = rows of class c; contained_reads; arcs = arcs of G; wave_vertices = vertices a workgroup took;
+ *              max_degree = the most arc records of one vertex; wave_degree = the threshold that was used; ms_classify (classes,
+ *              contained bits, arc records), ms_sort, ms_reduce (duplicates, offsets, the reduction, the kept rows), ms_d2h, ms_total
+ *              (HIP events).  hsk_reduced_free before hsk_destroy.
+ * Memory: the uploaded rows and lengths; 1 byte per row; 64 bytes per dovetail row between live reads (two arc records, sorted in two
+ * buffers) and the sort's tables; 8 bytes x (2 nreads + 1); 48 bytes per kept row.  HSK_ERR_OOM names the bytes that were asked for.
+ * HSK_ERR_INVALID_ARG, with a hsk_last_error text that names the case and how many rows, the context usable afterwards, no partial result:
+ * a NULL pointer; n > 0 without rows; a rows_dev that is not 16-byte aligned; rid_base + nreads > 2^31; n >= 2^32 (the row index travels
+ * in 32 bits); a row that names a read outside [rid_base, rid_base + nreads); a row whose coordinates and ends bits do not agree with the
+ * lengths ("these are not the lengths of the reads the rows were computed from"): a_lo < a_hi <= la and b_lo < b_hi <= lb must hold, and
+ * bit 0 <=> a_lo == 0, bit 1 <=> a_hi == la, bit 2 <=> b_lo == 0, bit 3 <=> b_hi == lb.  n == 0 is an empty graph, no error.
+ */
+typedef struct {
+    uint32_t fuzz;
+    uint32_t wave_degree;
+    int64_t  reserved[4];
+} hsk_reduce_opts;
+
+typedef struct {
+    uint64_t n;             /* kept rows */
+    uint64_t *rows;         /* host (pinned), n * 6 words; NULL when left on the device */
+    void     *rows_dev;
+    uint8_t  *row_class;    /* host (pinned), input_rows bytes */
+    void     *row_class_dev;
+    uint32_t *contained;    /* host (pinned), (nreads + 31) / 32 words */
+    void     *contained_dev;
+    uint64_t input_rows, nreads;
+    uint64_t class_rows[8];
+    uint64_t contained_reads, arcs, wave_vertices, max_degree;
+    uint32_t wave_degree, pad_;
+    double   ms_classify, ms_sort, ms_reduce, ms_d2h, ms_total;   /* HIP events */
+    int64_t  reserved[4];
+    void    *priv;
+} hsk_reduced;
+
+int  hsk_overlaps_reduce(hsk_ctx *ctx, const hsk_overlaps *in, const void *read_len, uint64_t nreads, int64_t rid_base,
+                         int32_t lens_on_device, const hsk_reduce_opts *opts, int32_t on_device, hsk_reduced *out);
+void hsk_reduced_free(hsk_ctx *ctx, hsk_reduced *r);
 /* Result egress (write_output_file, reference src/hysortk.cpp:138-164): the lines "KMERSTRING\tcount\n" of `n` entries
  * ((nw + 1)-word records: host memory, or device memory when `on_device`), formatted on the GPU into `text` (host, capacity
  * bytes); *nbytes = bytes needed (call with capacity 0 to size the buffer: K + 2 + up to 20 digits per entry). */

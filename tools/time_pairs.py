@@ -49,6 +49,14 @@ in HBM).  Timed in one run: hsk_result_pair_diagonals, hsk_pair_diags_extend, an
 compared with tests/gapped_ref.py, and how many overlaps are longer than the ungapped ones is counted.  Writes
 profiles/pairs_gapped_8mbp.json unless --out says otherwise.
 
+--reduce [--band B] [--pile P] [--pile-lane-only]: the string graph (hsk_overlaps_reduce) of the overlap rows of the --gapped workload (band B,
+default 15), rows and lengths in HBM.  Timed in one run: hsk_result_pair_diagonals, hsk_pair_diags_extend_gapped, the reduction with its
+phases and counts (rows per class, arcs, largest degree, the kept rows' bytes against the input's), the copy of the input rows alone to the
+host (what the host route pays before it starts), a wave_degree sweep (1, 64, 256, 1024, none), the rows kept at fuzz 0 / 10 / 100, and the
+same sweep with a staggered pile of --pile reads (default 3000) of one length behind the reads, whose rows are fabricated
+(tests/strgraph_ref.py: every pair of the pile is a dovetail, so its vertices have up to P - 1 out-arcs); `none` on the pile only with
+--pile-lane-only (its deg^2 walk takes long).  Writes profiles/overlaps_reduce_8mbp.json unless --out says otherwise.
+
 usage: python tools/time_pairs.py [--gbp 0.008] [--coverage 20] [--max-records N ...] [--merge-only] [--oriented [--strands-only]] [--diagonals [--diag-bin W] [--max-records N ...]] [--extend [--error-rate R]] [--gapped [--band B ...] [--indel-rate R]] [--out profiles/pairs_8mbp.json]"""
 import argparse, json, os, sys, time
 
@@ -259,8 +267,84 @@ def gapped_run(H, a):
     print(json.dumps(out))
 
 
+def reduce_run(H, a):
+    """--reduce: see the module's text"""
+    import shutil, tempfile
+    import numpy as np
+    from tests import strgraph_ref as SR
+    RL, G, NONE = 150, int(a.gbp * 1e9), 0xFFFFFFFF
+    n = int(G * a.coverage / RL)
+    band = (a.band or [15])[0]
+    ctx = H.Context(K=31, M=17, L=2, U=50, EXT=1, ntasks=0, keep_device=True)
+    peak = ctx.copy_peak(1 << 30, 3)
+    tmp = tempfile.mkdtemp()
+    try:
+        lens = host_reads_fasta(np, os.path.join(tmp, "reads.fa"), G, RL, n, a.error_rate, a.indel_rate, 11)
+        dna = H.read_dna_buffer_device(ctx, os.path.join(tmp, "reads.fa"))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    dev = dna.count_resident_device()
+    out = {"what": "tools/time_pairs.py --reduce: hsk_overlaps_reduce of the rows of hsk_pair_diags_extend_gapped (band %d), rows and lengths in HBM, beside the calls that make the rows; one run on one card" % band,
+           "workload": {"genome_bp": G, "read_span": RL, "reads": n, "read_len_min": int(lens.min()), "read_len_max": int(lens.max()), "error_rate": a.error_rate, "indel_rate": a.indel_rate,
+                        "K": 31, "M": 17, "L": 2, "U": 50, "band": band}, "copy_peak_gbs": peak, "reps": a.reps}
+    phases = ("ms_total", "ms_classify", "ms_sort", "ms_reduce", "ms_d2h")
+
+    def run(src, reads, **kw):
+        """the counts of the last of `reps` calls after the warm-up, and the median of every phase"""
+        infos = []
+        for i in range(WARMUP + a.reps):
+            with src.reduce(ctx, reads, on_device=True, **kw) as g:
+                infos.append(dict(g.info, rows=len(g)))
+        s = {k: v for k, v in infos[-1].items() if not k.startswith("ms_")}
+        s.update({"median_" + ph: median([r[ph] for r in infos[WARMUP:]]) for ph in phases})
+        s["median_ms_kernels"] = median([r["ms_classify"] + r["ms_sort"] + r["ms_reduce"] for r in infos[WARMUP:]])
+        return s
+
+    with dev.strands(dna) as st:
+        diag = summary(timed(lambda: dev.pair_diagonals(st, a.diag_bin, on_device=True), reps=a.reps))
+        with dev.pair_diagonals(st, a.diag_bin, on_device=True) as pd:
+            gap = extend_summary(timed(lambda: pd.extend_gapped(ctx, dna, band=band, on_device=True), reps=a.reps), peak)
+            with pd.extend_gapped(ctx, dna, band=band, on_device=True) as ov:
+                walls = []
+                for i in range(WARMUP + a.reps):          # what the host route pays before it starts: the rows over PCIe
+                    t0 = time.perf_counter()
+                    hrows = ctx.d2h(ov.rows_dev, ov.n * 48)
+                    walls.append((time.perf_counter() - t0) * 1e3)
+                hrows = hrows.view(np.uint64).reshape(ov.n, 6)
+                out["input_rows_d2h"] = {"bytes": ov.n * 48, "median_wall_ms": median(walls[WARMUP:]), "note": "into pageable host memory"}
+                red = run(ov, dna)
+                red["kept_bytes"], red["input_bytes"] = red["rows"] * 48, ov.n * 48
+                out["sweep_wave_degree"] = {str(wd): run(ov, dna, wave_degree=wd) for wd in (1, 64, 256, 1024, NONE)}
+                out["kept_by_fuzz"] = {str(f): run(ov, dna, fuzz=f)["kept"] for f in (0, 10, 100)}
+        # a staggered pile of reads of one length behind the reads -- what a tandem repeat shorter than the reads does: every pair of the
+        # pile is a dovetail, its vertices have up to pile - 1 out-arcs.  The rows are fabricated (no bases are read) and uploaded per call.
+        P = a.pile
+        pile = SR.layout_rows(np.arange(P), np.full(P, P + RL), np.random.default_rng(5).integers(0, 2, P), 31, rid_base=n)
+        both = H.Overlaps.from_rows(np.concatenate([hrows, pile]))
+        lens2 = np.concatenate([lens, np.full(P, P + RL)]).astype(np.uint32)
+        out["sweep_wave_degree_with_pile"] = {"pile_reads": P, "pile_rows": int(pile.shape[0]), "note": "host rows, uploaded by every call: compare median_ms_kernels",
+                                              "runs": {str(wd): run(both, lens2, wave_degree=wd) for wd in (1, 64, 256, 1024, NONE)[:None if a.pile_lane_only else -1]}}
+    out["pair_diagonals"], out["extend_gapped"], out["overlaps_reduce"] = diag, gap, red
+    print("%-40s %10.3f ms, %d rows" % ("hsk_result_pair_diagonals", diag["median_ms"], diag["rows"]))
+    print("%-40s %10.3f ms (kernels %.3f)" % ("hsk_pair_diags_extend_gapped", gap["median_ms"], gap["median_ms_extend"]))
+    print("%-40s %10.3f ms (classify %.3f, sort %.3f, reduce %.3f), %d of %d rows kept, %d arcs, max degree %d; the rows alone to the host: %.3f ms" % (
+        "hsk_overlaps_reduce", red["median_ms_total"], red["median_ms_classify"], red["median_ms_sort"], red["median_ms_reduce"], red["rows"], red["input_rows"], red["arcs"], red["max_degree"],
+        out["input_rows_d2h"]["median_wall_ms"]))
+    for name in ("sweep_wave_degree", "sweep_wave_degree_with_pile"):
+        runs = out[name].get("runs", out[name])
+        print(name + ": " + ", ".join("%s: %.3f ms" % (wd, s["median_ms_kernels"]) for wd, s in runs.items()))
+    dev.close()
+    dna.free()
+    ctx.close()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--reduce", action="store_true"); ap.add_argument("--pile", type=int, default=3000); ap.add_argument("--pile-lane-only", action="store_true")
     ap.add_argument("--gapped", action="store_true"); ap.add_argument("--band", type=int, action="append", default=[]); ap.add_argument("--indel-rate", type=float, default=0.005)
     ap.add_argument("--gapped-sample", type=int, default=2000)
     ap.add_argument("--extend", action="store_true"); ap.add_argument("--error-rate", type=float, default=0.01); ap.add_argument("--sample", type=int, default=20000)
@@ -272,6 +356,8 @@ def main():
     ap.add_argument("--reps", type=int, default=REPS)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None and a.reduce:
+        a.out = os.path.join(ROOT, "profiles", "overlaps_reduce_8mbp.json")
     if a.out is None and a.gapped:
         a.out = os.path.join(ROOT, "profiles", "pairs_gapped_8mbp.json")
     if a.out is None and a.extend:
@@ -281,6 +367,8 @@ def main():
     sys.path.insert(0, ROOT)
     import numpy as np
     import hysortk_amd as H
+    if a.reduce:
+        return reduce_run(H, a)
     if a.gapped:
         return gapped_run(H, a)
     RL = 150
