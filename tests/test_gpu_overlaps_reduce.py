@@ -3,7 +3,8 @@ transitive arcs marked -- against the definition in plain Python (tests/strgraph
 tests/test_strgraph_ref.py).  The rows are fabricated from layouts of reads on a line (strgraph_ref.layout_rows): only lengths are needed.
 Everything is integer work and compared for equality: the class of every row, the kept rows, the contained bits and every count.  Every case
 runs with wave_degree 0 (the library's default), 1 (every vertex by a workgroup) and 0xFFFFFFFF (none), unless it says otherwise, and must
-give the same result."""
+give the same result.  tests/test_gpu_overlaps_reduce_hubs.py holds the wave path's length rule, dead records, narrowing and grid-stride loop
+to the same reference on vertices of several chunks, and has the tile edges, the 33-bit sums and the top of the read-id range."""
 import ctypes as C
 
 import numpy as np
@@ -206,7 +207,10 @@ def test_doubled_rows(H, ctx, layouts):
 def test_staggered_pile(H, ctx, d):
     """Read j starts at base j, all reads have one length and share at least 20 bases: none is contained, every pair is a dovetail and
     vertex 0 has d out-arcs.  In closed form: a row is KEPT iff its reads are neighbours, every other row is REDUCED.  The run without the
-    wave path is limited to d <= 65: its walk of deg^2 searches per vertex is the reason the wave path exists."""
+    wave path is limited to d <= 65: its walk of deg^2 searches per vertex is the reason the wave path exists.  This pins the mechanics of
+    the chunks (63 to 1025 records, one chunk and two), not the length rule: every arc that is not between neighbours has hundreds of
+    witnesses far below L, fuzz is 0 and no record is dead, so a wave path with a wrong comparison or a wrong range of out(w) gives the
+    same classes here.  The hubs of tests/test_gpu_overlaps_reduce_hubs.py are what pins those."""
     n = d + 1
     rng = np.random.default_rng(d)
     lens = np.full(n, d + 50)
