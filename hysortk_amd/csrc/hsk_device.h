@@ -22,9 +22,11 @@ __host__ __device__ __forceinline__ u64 fmix64(u64 k)
     k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
     return k;
 }
-__host__ __device__ __forceinline__ u64 murmur64_8(u64 key)
+constexpr u64 MURMUR_C1 = 0x87c37b91114253d5ULL;
+// murmur64_8(key << s) with the shift folded into the first multiply: c1s = MURMUR_C1 << s (scan_kernel keeps its m-mers right-aligned)
+__host__ __device__ __forceinline__ u64 murmur64_8_c1(u64 key, u64 c1s)
 {
-    u64 k1 = key * 0x87c37b91114253d5ULL;
+    u64 k1 = key * c1s;
     k1 = rotl64(k1, 31);
     k1 *= 0x4cf5ad432745937fULL;
     u64 h1 = 313ULL ^ k1, h2 = 313ULL;
@@ -33,6 +35,7 @@ __host__ __device__ __forceinline__ u64 murmur64_8(u64 key)
     h1 = fmix64(h1); h2 = fmix64(h2);
     return h1 + h2;
 }
+__host__ __device__ __forceinline__ u64 murmur64_8(u64 key) { return murmur64_8_c1(key, MURMUR_C1); }
 
 // The same hash over NW 64-bit words (16 / 24 bytes: Mmer<2> / Mmer<3>, minimizers of 33..63 / 65..94 bases): one body
 // block of 16 bytes, and for 24 bytes an 8-byte tail (reference src/hashfuncs.cpp:42-114 with len = 8 * NW).

@@ -25,6 +25,7 @@
 // the supermers of a task that go to one destination rank are contiguous for the all-to-all.
 #pragma once
 #include "hsk_device.h"
+#include "hsk_fmin.h"           // 64-bit minima as v_min_f64: the clamp, the sentinel, what makes a result exact
 #include "hsk_parseplan.h"      // the tiling, PARSE_TILE, the record capacities: what host and kernels must agree on
 
 namespace hsk {
@@ -603,6 +604,45 @@ __device__ __forceinline__ void bin_store(const BinTable &a, u64 slot, u64 w0, u
 constexpr int SCAN_HSTRIDE = PARSE_THREADS + 16;      // 256 lanes + 12 lanes' worth of positions behind the tile
 __device__ __forceinline__ int scan_hidx(int p) { return (p & 7) * SCAN_HSTRIDE + (p >> 3); }
 
+// Builds of profiles/scan_issue_ab.json: 0 gives the integer compares back, part by part
+#ifndef HSK_SCAN_FMIN
+#define HSK_SCAN_FMIN 1                               // the window minima of step 3 through v_min_f64 (hsk_fmin.h)
+#endif
+#ifndef HSK_SCAN_RKEY
+#define HSK_SCAN_RKEY 1                               // step 2 keeps the m-mers right-aligned: the canonical one is a v_min_f64, the alignment is in the first multiply's constant
+#endif
+
+// scan_kernel's step 3 for windows of at least PARSE_PPT m-mers: the window minima of a lane's eight positions from its own hashes h[] and the
+// W - 1 hashes behind them in LDS (shared middle: the eight windows have all but 14 elements in common).  FAST: every hash is clamped as it is
+// read (hsk_fmin.h; what is in LDS stays exact) and the 35 minima are one v_min_f64 each; a minimum whose top word comes out at FMIN_SENTINEL
+// is not known -- the caller looks at all eight and runs the wave through the integer compares (FAST = false) when a lane has one.
+template <bool FAST>
+__device__ __forceinline__ void scan_window_minima(const u64 (&h)[PARSE_PPT], const u64 *s_hash, const u64 *s_bmin, int tid, int W, u64 (&mn)[PARSE_PPT])
+{
+    auto in = [](u64 v) -> u64 { return FAST ? fmin_clamp(v) : v; };
+    auto lower = [](u64 x, u64 y) -> u64 { return FAST ? fmin_u64(x, y) : (y < x ? y : x); };
+    const int p0 = tid * PARSE_PPT;
+    u64 c = in(h[PARSE_PPT - 1]);
+    // the shared middle [p0 + 8, p0 + W - 1]: whole lanes from their block minima (K = 51: 3 + 3 reads instead of 27), the rest position by position
+    const int nfull = (W - PARSE_PPT) / PARSE_PPT;
+    int j = PARSE_PPT;
+    if (nfull > 0 && tid + nfull < PARSE_THREADS) {
+        for (int b = 1; b <= nfull; ++b) c = lower(c, in(s_bmin[tid + b]));
+        j = PARSE_PPT * (nfull + 1);
+    }
+#pragma unroll 8
+    for (; j <= W - 1; ++j) c = lower(c, in(s_hash[scan_hidx(p0 + j)]));
+    mn[PARSE_PPT - 1] = c;
+    u64 suf = in(h[PARSE_PPT - 2]);
+    mn[PARSE_PPT - 2] = lower(suf, c);
+#pragma unroll
+    for (int i = PARSE_PPT - 3; i >= 0; --i) { suf = lower(suf, in(h[i])); mn[i] = lower(suf, c); }
+    u64 run = in(s_hash[scan_hidx(p0 + W)]);
+    mn[1] = lower(run, mn[1]);
+#pragma unroll
+    for (int i = 2; i < PARSE_PPT; ++i) { run = lower(run, in(s_hash[scan_hidx(p0 + W + i - 1)])); mn[i] = lower(run, mn[i]); }
+}
+
 #ifdef HSK_DIAG
 __device__ unsigned long long g_scan_diag[16];
 #endif
@@ -627,6 +667,8 @@ __global__ __launch_bounds__(PARSE_THREADS, 4) void scan_kernel(ParseArgs a)
 
     const int tid = threadIdx.x;
     const int K = KT ? KT : a.k, M = MT ? MT : a.m, W = K - M + 1;
+    // the v_min_f64 forms of steps 2 and 3 are for the instances with k and m fixed: <0, 0> has no registers left for them (128 VGPRs and scratch)
+    constexpr bool FIXED_KM = KT != 0 && MT != 0;
     const u64 mmask = ~0ULL << (64 - 2 * M);
     for (u32 i = tid; i < 2 * a.ntasks; i += PARSE_THREADS) s_cur[i] = 0;
     // (scan-placed items: nobody needs the supermers' byte totals -- a task's second word is the workgroup's memory of the bin's last chunk instead:
@@ -737,11 +779,23 @@ __global__ __launch_bounds__(PARSE_THREADS, 4) void scan_kernel(ParseArgs a)
             // reverse complement of the whole window: the twin of the m-mer at offset i is its bases [32 - M - i, 32 - i)
             // (i + M <= 32: SCAN_MAX_M), one shift per position instead of a rolled state
             const u64 rw = ~rev2(w0);
+            if constexpr (HSK_SCAN_RKEY && FIXED_KM) {
+                // both strands RIGHT-aligned: 2 M <= 50 bits are sign-free doubles far below the sentinel class, the smaller one is one exact v_min_f64
+                // (hsk_fmin.h), and the hash of the left-aligned key is the hash chain with the alignment shifted into its first constant
+                const u64 kmask = ~0ULL >> (64 - 2 * M), c1s = MURMUR_C1 << (64 - 2 * M);
 #pragma unroll
-            for (int i = 0; i < PARSE_PPT; ++i) {
-                const u64 fw = (w0 << (2 * i)) & mmask;
-                const u64 rc = (rw << (2 * (32 - M - i))) & mmask;
-                h[i] = murmur64_8(rc < fw ? rc : fw);
+                for (int i = 0; i < PARSE_PPT; ++i) {
+                    const u64 fw = (w0 >> (64 - 2 * M - 2 * i)) & kmask;
+                    const u64 rc = (rw >> (2 * i)) & kmask;
+                    h[i] = murmur64_8_c1(fmin_u64(rc, fw), c1s);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < PARSE_PPT; ++i) {
+                    const u64 fw = (w0 << (2 * i)) & mmask;
+                    const u64 rc = (rw << (2 * (32 - M - i))) & mmask;
+                    h[i] = murmur64_8(rc < fw ? rc : fw);
+                }
             }
 #pragma unroll
             for (int i = 0; i < PARSE_PPT; ++i) s_hash[i * SCAN_HSTRIDE + tid] = h[i];
@@ -767,23 +821,15 @@ __global__ __launch_bounds__(PARSE_THREADS, 4) void scan_kernel(ParseArgs a)
         // ---- 3. window minima (shared middle), validity --------------------------------------------------
         u64 mn[PARSE_PPT];
         if (W >= PARSE_PPT) {
-            u64 c = h[PARSE_PPT - 1];
-            // the shared middle [p0 + 8, p0 + W - 1]: whole lanes from their block minima (K = 51: 3 + 3 reads instead of 27), the rest position by position
-            const int nfull = (W - PARSE_PPT) / PARSE_PPT;
-            int j = PARSE_PPT;
-            if (nfull > 0 && tid + nfull < PARSE_THREADS) {
-                for (int b = 1; b <= nfull; ++b) { const u64 v = s_bmin[tid + b]; c = v < c ? v : c; }
-                j = PARSE_PPT * (nfull + 1);
-            }
-#pragma unroll 8
-            for (; j <= W - 1; ++j) { const u64 v = s_hash[scan_hidx(p0 + j)]; c = v < c ? v : c; }
-            mn[PARSE_PPT - 1] = c;
-            u64 suf = ~0ULL;
+            if constexpr (HSK_SCAN_FMIN && FIXED_KM) {
+                scan_window_minima<true>(h, s_hash, s_bmin, tid, W, mn);
+                // all of a window in the sentinel class (half of the hashes are: 2^-15 of the windows of 15, one wave and tile in ~60): the wave takes
+                // the integer compares, before anybody reads s_last
+                u32 top = (u32)(mn[0] >> 32);
 #pragma unroll
-            for (int i = PARSE_PPT - 2; i >= 0; --i) { suf = h[i] < suf ? h[i] : suf; mn[i] = suf < c ? suf : c; }
-            u64 run = ~0ULL;
-#pragma unroll
-            for (int i = 1; i < PARSE_PPT; ++i) { const u64 v = s_hash[scan_hidx(p0 + W + i - 1)]; run = v < run ? v : run; mn[i] = run < mn[i] ? run : mn[i]; }
+                for (int i = 1; i < PARSE_PPT; ++i) { const u32 t = (u32)(mn[i] >> 32); top = t > top ? t : top; }
+                if (__ballot(top >= FMIN_SENTINEL)) scan_window_minima<false>(h, s_hash, s_bmin, tid, W, mn);
+            } else scan_window_minima<false>(h, s_hash, s_bmin, tid, W, mn);
         } else {
 #pragma unroll
             for (int i = 0; i < PARSE_PPT; ++i) {

@@ -28,7 +28,7 @@ CLASS = {
     "v_add_lshl_u32": "lshl_add32", "v_or3_b32": "or3", "v_ffbl_b32": "ffbl", "v_ffbh_u32": "ffbl", "v_mbcnt_lo_u32_b32": "mbcnt", "v_mbcnt_hi_u32_b32": "mbcnt",
     "v_readlane_b32": "lane", "v_writelane_b32": "lane", "v_readfirstlane_b32": "lane", "v_mov_b64": "mov64", "v_pk_mov_b32": "mov64",
     "v_add_co_u32": "addc64", "v_addc_co_u32": "addc64", "v_sub_co_u32": "addc64", "v_subb_co_u32": "addc64", "v_subrev_co_u32": "addc64", "v_subbrev_co_u32": "addc64",
-    "v_cndmask_b32": "cmp32_cnd",
+    "v_cndmask_b32": "cmp32_cnd", "v_min_f64": "min_f64",          # (min_f64: scan_kernel's 64-bit minima, hsk_fmin.h; a rates file without the key prices it as DEFAULT)
 }
 DEFAULT = "alignbit"          # anything unlisted: priced like the other three-operand / special integer instructions (4.2 - 4.4 cycles)
 
