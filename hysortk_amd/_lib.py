@@ -129,6 +129,24 @@ class Reduced(C.Structure):
     ]
 
 
+class UnitigOpts(C.Structure):
+    """hsk_unitig_opts: a reserved block."""
+    _fields_ = [("reserved", C.c_int64 * 4)]
+
+
+class Unitigs(C.Structure):
+    """hsk_unitigs: the unitigs of a list of string graph edges (hsk_overlaps_unitigs)."""
+    _fields_ = [
+        ("members", C.c_uint64), ("rows", C.POINTER(C.c_uint64)), ("rows_dev", C.c_void_p),
+        ("unitigs", C.c_uint64), ("table", C.POINTER(C.c_uint64)), ("table_dev", C.c_void_p),
+        ("input_rows", C.c_uint64), ("nreads", C.c_uint64),
+        ("singletons", C.c_uint64), ("circular", C.c_uint64), ("longest", C.c_uint64), ("links", C.c_uint64), ("branch_vertices", C.c_uint64),
+        ("live_reads", C.c_uint64), ("arcs", C.c_uint64), ("rounds", C.c_uint64),
+        ("ms_arcs", C.c_double), ("ms_sort", C.c_double), ("ms_rank", C.c_double), ("ms_emit", C.c_double), ("ms_d2h", C.c_double), ("ms_total", C.c_double),
+        ("reserved", C.c_int64 * 4), ("priv", C.c_void_p),
+    ]
+
+
 FLAG_PROFILE = 1
 FLAG_KEEP_DEVICE = 2
 FLAG_PLAIN_CLASSIFIER = 4
@@ -145,7 +163,7 @@ SYMBOLS = [
     "hsk_result_strands", "hsk_strands_task", "hsk_strands_free", "hsk_result_pairs_oriented",
     "hsk_result_pair_diagonals", "hsk_pair_diags_free", "hsk_result_pair_diagonals_sliced", "hsk_pair_diags_merge",
     "hsk_pair_diags_extend", "hsk_overlaps_free", "hsk_pair_diags_extend_gapped",
-    "hsk_overlaps_reduce", "hsk_reduced_free",
+    "hsk_overlaps_reduce", "hsk_reduced_free", "hsk_overlaps_unitigs", "hsk_unitigs_free",
     "hsk_stage_destinations", "hsk_stage_task_kmers", "hsk_stage_sort", "hsk_stage_count_sorted",
     "hsk_plan_tot_tasks", "hsk_plan_classify", "hsk_plan_dispatch", "hsk_plan_partition_reads", "hsk_plan_exchange",
     "hsk_comm_get_unique_id", "hsk_comm_init", "hsk_comm_destroy", "hsk_comm_selftest",
@@ -221,6 +239,9 @@ def load():
     L.hsk_overlaps_reduce.argtypes = [vp, C.POINTER(Overlaps), vp, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(ReduceOpts), C.c_int32, C.POINTER(Reduced)]
     L.hsk_reduced_free.argtypes = [vp, C.POINTER(Reduced)]
     L.hsk_reduced_free.restype = None
+    L.hsk_overlaps_unitigs.argtypes = [vp, C.POINTER(Overlaps), vp, C.c_int32, vp, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(UnitigOpts), C.c_int32, C.POINTER(Unitigs)]
+    L.hsk_unitigs_free.argtypes = [vp, C.POINTER(Unitigs)]
+    L.hsk_unitigs_free.restype = None
     L.hsk_pairs_free.argtypes = [vp, C.POINTER(Pairs)]
     L.hsk_pairs_free.restype = None
     L.hsk_get_stats.argtypes = [vp, C.POINTER(Stats), C.c_int]

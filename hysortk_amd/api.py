@@ -715,6 +715,47 @@ class OverlapGraph:
         row = np.arange(len(a), dtype=np.int64)
         return np.concatenate([v1, w1 ^ 1]), np.concatenate([w1, v1 ^ 1]), np.concatenate([l1, l2]), np.concatenate([row, row])
 
+    @staticmethod
+    def pack_contained(contained):
+        """the bit words of the C ABI from one bool per read"""
+        bits = np.packbits(np.asarray(contained, dtype=bool), bitorder="little")
+        return np.concatenate([bits, np.zeros(-bits.size % 4, np.uint8)]).view("<u4").astype(np.uint32)
+
+    def unitigs(self, ctx, reads, rid_base=None, on_device=False):
+        """hsk_overlaps_unitigs: the maximal non-branching paths of this graph's edges (include/hsk.h has the definition), one of each
+        complement pair, with every member read's orientation and position -- list ranking in HBM, not a walk.  A graph in HBM gives its
+        rows and its contained bits where they lie, a host graph uploads its rows and its packed bits.  reads: as Overlaps.reduce takes
+        them (only the lengths are used); rid_base: default the graph's.  Returns a Unitigs (on_device=True: both row lists stay in HBM;
+        close() it before the context goes)."""
+        e = self.edges
+        ov = _lib.Overlaps()
+        ov.n = len(e)
+        keep = bits = None
+        if len(e) and e.rows_dev:
+            ov.rows_dev = e.rows_dev
+        elif len(e):
+            keep = np.ascontiguousarray(e.rows(), dtype=np.uint64)
+            ov.rows = keep.ctypes.data_as(C.POINTER(C.c_uint64))
+        if isinstance(reads, DeviceDna):
+            lens, plens, nreads, lens_dev = None, reads.dl, int(reads.nreads), 1
+        else:
+            lens = reads.arrays()[2] if isinstance(reads, DnaBuffer) else (reads[2] if isinstance(reads, tuple) else reads)
+            lens = np.ascontiguousarray(lens, dtype=np.uint32)
+            plens, nreads, lens_dev = _p(lens), int(lens.size), 0
+        if nreads != self.nreads:
+            raise ValueError("the graph was reduced over %d reads, lengths of %d were given" % (self.nreads, nreads))
+        if self.contained_dev:
+            con, con_dev = self.contained_dev, 1
+        else:                                    # (no bits at all: no read is contained)
+            bits = np.ascontiguousarray(OverlapGraph.pack_contained(np.zeros(nreads, bool) if self.contained is None else self.contained))
+            con, con_dev = (_p(bits) if bits.size else None), 0
+        base = self.rid_base if rid_base is None else rid_base
+        opts = _lib.UnitigOpts()
+        ut = _lib.Unitigs()
+        rc = ctx.lib.hsk_overlaps_unitigs(ctx.h, C.byref(ov), con, con_dev, plens, nreads, base, lens_dev, C.byref(opts), 1 if on_device else 0, C.byref(ut))
+        ctx._check(rc)
+        return Unitigs._wrap(ctx, ut, on_device)
+
     def close(self):
         if self._owner is not None:
             ctx, rd = self._owner
@@ -722,6 +763,88 @@ class OverlapGraph:
                 ctx.lib.hsk_reduced_free(ctx.h, C.byref(rd))
             self._owner, self.row_class_dev, self.contained_dev = None, None, None
             self.edges.rows_dev = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Unitigs:
+    """The unitigs of a string graph (hsk_overlaps_unitigs, include/hsk.h).  Per member, ordered by (unitig, rank): unitig, rank, rid (the
+    absolute read id), reverse (bool: the member is the read's reverse complement), offset (the unitig coordinate of the oriented read's
+    first base), link_len and link_row (the link to the next member: its len and the index of its row in the graph's edges; NO_LINK in
+    both for the last member of a path; the last member of a cycle links back to rank 0).  Per unitig: first (its first layout row),
+    reads, bases, circular.  info: unitigs, members, singletons, circular, longest, links, branch_vertices, live_reads, input_rows, arcs,
+    rounds and the ms_* of the call.  With on_device the two row lists stay in HBM (rows_dev: members rows, table_dev: unitigs rows, four
+    uint64 words each; the per-member and per-unitig arrays are then empty; close() gives them back)."""
+
+    NO_LINK = 0xFFFFFFFF
+
+    def __init__(self, rows, table, info, rows_dev=None, table_dev=None, owner=None):
+        rows, table = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4) for x in (rows, table))
+        lo, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+        self._rows, self._table = rows, table
+        self.unitig, self.rank = (rows[:, 0] >> s32).astype(np.uint32), (rows[:, 0] & lo).astype(np.uint32)
+        self.rid, self.reverse = (rows[:, 1] >> np.uint64(1)).astype(np.uint32), (rows[:, 1] & np.uint64(1)).astype(bool)
+        self.offset = rows[:, 2].copy()
+        self.link_len, self.link_row = (rows[:, 3] >> s32).astype(np.uint32), (rows[:, 3] & lo).astype(np.uint32)
+        self.first, self.reads, self.bases, self.circular = table[:, 0].copy(), table[:, 1].copy(), table[:, 2].copy(), table[:, 3] != 0
+        self.info = info
+        self.rows_dev, self.table_dev = rows_dev, table_dev
+        self._owner = owner                      # (ctx, hsk_unitigs) of lists that live on the device
+
+    def __len__(self):
+        return int(self.info["unitigs"])
+
+    def rows(self):
+        """[members, 4] uint64, the layout rows in the C ABI's layout"""
+        return self._rows
+
+    def table(self):
+        """[unitigs, 4] uint64, the unitig rows in the C ABI's layout"""
+        return self._table
+
+    def members(self, u):
+        """(rid, reverse, offset) of unitig u's members in the order of their ranks"""
+        s = slice(int(self.first[u]), int(self.first[u]) + int(self.reads[u]))
+        return self.rid[s], self.reverse[s], self.offset[s]
+
+    @staticmethod
+    def _wrap(ctx, ut, on_device):
+        info = {k: int(getattr(ut, k)) for k in ("unitigs", "members", "singletons", "circular", "longest", "links", "branch_vertices", "live_reads", "input_rows", "arcs", "rounds")}
+        info.update({k: getattr(ut, k) for k in ("ms_arcs", "ms_sort", "ms_rank", "ms_emit", "ms_d2h", "ms_total")})
+        m, u = int(ut.members), int(ut.unitigs)
+        z = np.zeros((0, 4), np.uint64)
+        if on_device:
+            return Unitigs(z, z, info, rows_dev=ut.rows_dev, table_dev=ut.table_dev, owner=(ctx, ut))
+        rows = np.ctypeslib.as_array(ut.rows, shape=(m * 4,)).reshape(m, 4).copy() if m else z
+        table = np.ctypeslib.as_array(ut.table, shape=(u * 4,)).reshape(u, 4).copy() if u else z
+        ctx.lib.hsk_unitigs_free(ctx.h, C.byref(ut))
+        return Unitigs(rows, table, info)
+
+    def host_copy(self):
+        """(layout rows, unitig rows) of lists in HBM, fetched"""
+        if self._owner is None:
+            return self._rows, self._table
+        ctx = self._owner[0]
+        m, u = self.info["members"], self.info["unitigs"]
+        z = np.zeros((0, 4), np.uint64)
+        return (ctx.d2h(self.rows_dev, m * 32).view(np.uint64).reshape(m, 4) if m else z), (ctx.d2h(self.table_dev, u * 32).view(np.uint64).reshape(u, 4) if u else z)
+
+    def close(self):
+        if self._owner is not None:
+            ctx, ut = self._owner
+            if getattr(ctx, "h", None):
+                ctx.lib.hsk_unitigs_free(ctx.h, C.byref(ut))
+            self._owner, self.rows_dev, self.table_dev = None, None, None
 
     def __del__(self):
         try:

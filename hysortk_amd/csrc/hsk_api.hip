@@ -45,6 +45,7 @@
 #include "hsk_extend.h"
 #include "hsk_extend_gapped.h"
 #include "hsk_reduce.h"
+#include "hsk_unitig_kernels.h"
 #include "hsk_strand.h"
 #include "hsk_estimate.h"
 #include "hsk_synth.h"
@@ -465,6 +466,8 @@ extern "C" int hsk_result_device_task(const hsk_result *r, int32_t task, const v
 #include "hsk_host_extend.h"
 // the string graph of a list of overlap rows: hsk_overlaps_reduce, hsk_reduced_free
 #include "hsk_host_reduce.h"
+// the unitigs of a list of string graph edges: hsk_overlaps_unitigs, hsk_unitigs_free
+#include "hsk_host_unitig.h"
 
 // Uploads the DnaBuffer description; returns device arrays with nreads+1 offsets.
 

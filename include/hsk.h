@@ -687,6 +687,78 @@ typedef struct {
 int  hsk_overlaps_reduce(hsk_ctx *ctx, const hsk_overlaps *in, const void *read_len, uint64_t nreads, int64_t rid_base,
                          int32_t lens_on_device, const hsk_reduce_opts *opts, int32_t on_device, hsk_reduced *out);
 void hsk_reduced_free(hsk_ctx *ctx, hsk_reduced *r);
+/*
+ * Unitigs: the maximal non-branching paths of a list of string graph edges, one of each complement pair, with every member read's
+ * orientation and position in the unitig.  Integer work in HBM, held to this definition word for word (csrc/hsk_unitig.h is the one
+ * implementation the kernels and the CPU tests share; tests/unitig_ref.py spells it with dictionaries and a sequential walk).
+ *
+ * Input.  A list of hsk_overlaps rows: of `edges` the call reads n, rows_dev if set, else rows (host memory, uploaded as
+ * hsk_overlaps_reduce uploads its own); its priv may be NULL.  The contained bits: (nreads + 31) / 32 uint32 words laid out as
+ * hsk_reduced.contained, on the host or (contained_on_device) on the device; NULL: no read is contained.  The reads' lengths
+ * read_len[nreads] (uint32; on the device with lens_on_device) and rid_base.  No bases are read.  The vertices, the two arcs of a row and
+ * their len are those of hsk_overlaps_reduce.
+ *
+ * Out-arcs.  out(v) is the set of distinct w with an arc v -> w.  Two rows with a and b exchanged can give the same arc twice: the arc
+ * is then represented by the record with the smallest len, then the smallest row index.  deg(v) = |out(v)|.  Every row gives an arc and
+ * its complement, so the in-arcs of v are the complements of out(v ^ 1).
+ *
+ * Links.  An arc v -> w is a link iff deg(v) == 1 and deg(w ^ 1) == 1; then succ(v) = w and pred(w) = v.  Links form vertex-disjoint
+ * paths and cycles over the live vertices -- the two vertices of every read that is not contained; a live vertex without a link is a
+ * path of one.  No chain holds both v and v ^ 1 (its middle would be an arc between the two vertices of one read, and SELF rows are
+ * refused), so chains come in disjoint complement pairs over the same reads.
+ *
+ * Unitigs.  Of each complement pair, the unitig is the chain in which the smallest read id is forward: whose smallest vertex is even.
+ * A path starts at its head; a cycle starts at its smallest vertex and is marked circular.  Unitigs are numbered in increasing order of
+ * their first vertex.  Every live read is therefore a member of exactly one unitig, exactly once.
+ *
+ * Layout rows: one row of four words per (unitig, member), ordered by (unitig, rank):
+ *     { unitig << 32 | rank, rid << 1 | s, offset, link }
+ * rid is the absolute read id, s = 1 the reverse complement; offset is the sum of the len of the links in front of the member, in 64
+ * bits: the unitig coordinate of the oriented read's first base; link = len << 32 | row of the link to the next member (row: the index
+ * of the representative's row in `edges`); ~0 for the last member of a path; for the last member of a cycle the link back to rank 0.
+ * Unitig rows: one row of four words per unitig:
+ *     { first layout row, reads, bases, circular }
+ * bases of a path = offset(last) + len(last read); of a cycle = the sum of all its links' len.
+ *
+ *   opts       nothing yet: a reserved block, zero.
+ *   out        members, rows / rows_dev: the layout rows; unitigs, table / table_dev: the unitig rows.  With on_device both stay in HBM,
+ *              else both are pinned host memory.  singletons = unitigs of one read; circular; longest = the most reads in one unitig;
+ *              links (both orientations are counted); branch_vertices = live v with deg(v) > 1; live_reads; input_rows; arcs = the sum
+ *              of deg(v) (distinct arcs, both orientations); rounds = the ranking launches: the ranking is pointer doubling, and the
+ *              number of its rounds is fixed before the first launch, 2 ceil(log2(min(nreads, n + 1))) -- one phase brings every
+ *              path's prefix sums to its head and every cycle's smallest vertex around it, the second ranks the cycles cut there;
+ *              ms_arcs (checks, arc records), ms_sort, ms_rank (degrees, links, rounds), ms_emit (unitig ids, the two row lists, the
+ *              counts), ms_d2h, ms_total (HIP events).  hsk_unitigs_free before hsk_destroy.
+ * Memory: the uploaded rows, bits and lengths; 1 byte per row; 64 bytes per row (two arc records, sorted in two buffers) and the sort's
+ * tables; 104 bytes per vertex, two vertices per read; 32 bytes per unitig and per member.  HSK_ERR_OOM names the bytes asked for.
+ * HSK_ERR_INVALID_ARG, with a hsk_last_error text that names the call, the case and how many rows, the context usable afterwards, no
+ * partial result: every pointer, alignment, 2^31, 2^32, read-range and lengths-disagree case of hsk_overlaps_reduce, with the same
+ * texts; a row that is not a dovetail between two different reads -- its own class is SELF, A_CONTAINED, B_CONTAINED or INTERNAL -- ("k of
+ * n rows are no dovetails: this is not a list of string graph edges"); a row that names a read whose contained bit is set.  Of a row
+ * with several faults the first of this order counts.  n == 0 is no error: every live read is then a unitig of its own.
+ */
+typedef struct {
+    int64_t  reserved[4];
+} hsk_unitig_opts;
+
+typedef struct {
+    uint64_t members;       /* layout rows */
+    uint64_t *rows;         /* host (pinned), members * 4 words; NULL when left on the device */
+    void     *rows_dev;
+    uint64_t unitigs;       /* unitig rows */
+    uint64_t *table;        /* host (pinned), unitigs * 4 words */
+    void     *table_dev;
+    uint64_t input_rows, nreads;
+    uint64_t singletons, circular, longest, links, branch_vertices, live_reads, arcs, rounds;
+    double   ms_arcs, ms_sort, ms_rank, ms_emit, ms_d2h, ms_total;   /* HIP events */
+    int64_t  reserved[4];
+    void    *priv;
+} hsk_unitigs;
+
+int  hsk_overlaps_unitigs(hsk_ctx *ctx, const hsk_overlaps *edges, const void *contained, int32_t contained_on_device,
+                          const void *read_len, uint64_t nreads, int64_t rid_base, int32_t lens_on_device,
+                          const hsk_unitig_opts *opts, int32_t on_device, hsk_unitigs *out);
+void hsk_unitigs_free(hsk_ctx *ctx, hsk_unitigs *u);
 /* Result egress (write_output_file, reference src/hysortk.cpp:138-164): the lines "KMERSTRING\tcount\n" of `n` entries
  * ((nw + 1)-word records: host memory, or device memory when `on_device`), formatted on the GPU into `text` (host, capacity
  * bytes); *nbytes = bytes needed (call with capacity 0 to size the buffer: K + 2 + up to 20 digits per entry). */

@@ -57,6 +57,14 @@ same sweep with a staggered pile of --pile reads (default 3000) of one length be
 (tests/strgraph_ref.py: every pair of the pile is a dovetail, so its vertices have up to P - 1 out-arcs); `none` on the pile only with
 --pile-lane-only (its deg^2 walk takes long).  Writes profiles/overlaps_reduce_8mbp.json unless --out says otherwise.
 
+--unitigs [--band B] [--synthetic-reads N]: the unitigs (hsk_overlaps_unitigs) of the --reduce workload's string graph, everything resident:
+gapped overlaps, hsk_overlaps_reduce with on_device, then the unitigs of that graph.  Timed in one run, --reps repetitions after the warm-up,
+every time with its median, smallest and largest: the unitigs call and its phases, the reduce call and its phases, and the host route the
+call replaces -- the kept rows and the contained bits over PCIe plus OverlapGraph.arcs (wall clock) --, with the walk a client would then
+do timed once behind it (numpy and one Python step per link).  Then a synthetic line and a ring of N reads (default 10^6) on random strands:
+one chain through every read, where a sequential walk is one chase of N steps.  Writes profiles/overlaps_unitigs_8mbp.json unless --out
+says otherwise.
+
 usage: python tools/time_pairs.py [--gbp 0.008] [--coverage 20] [--max-records N ...] [--merge-only] [--oriented [--strands-only]] [--diagonals [--diag-bin W] [--max-records N ...]] [--extend [--error-rate R]] [--gapped [--band B ...] [--indel-rate R]] [--out profiles/pairs_8mbp.json]"""
 import argparse, json, os, sys, time
 
@@ -342,8 +350,131 @@ def reduce_run(H, a):
     print(json.dumps(out))
 
 
+def spread(v):
+    """the median, the smallest and the largest of the timed repetitions"""
+    return {"median": median(v), "min": min(v), "max": max(v), "all": list(v)}
+
+
+def host_walk(np, v, w, nv):
+    """what a client does with OverlapGraph.arcs: degrees, links, and one pointer chase per chain (numpy, then a Python loop per link);
+    returns (chains, the longest chain's vertices)"""
+    pair = np.unique(v.astype(np.int64) << 32 | w.astype(np.int64))
+    pv, pw = pair >> 32, pair & 0xFFFFFFFF
+    deg = np.bincount(pv, minlength=nv)
+    link = (deg[pv] == 1) & (deg[pw ^ 1] == 1)
+    succ = np.full(nv, -1, np.int64)
+    succ[pv[link]] = pw[link]
+    has_pred = np.zeros(nv, bool)
+    has_pred[pw[link]] = True
+    succ_l, seen = succ.tolist(), np.zeros(nv, bool)
+    chains = longest = 0
+    for h in np.flatnonzero(~has_pred).tolist() + np.flatnonzero(has_pred).tolist():      # the paths from their heads, then what is left: the cycles
+        if seen[h]:
+            continue
+        x, k = h, 0
+        while x >= 0 and not seen[x]:
+            seen[x] = True
+            x, k = succ_l[x], k + 1
+        chains, longest = chains + 1, max(longest, k)
+    return chains, longest
+
+
+def unitigs_run(H, a):
+    """--unitigs: see the module's text"""
+    import shutil, tempfile
+    import numpy as np
+    from tests import strgraph_ref as SR
+    RL, G = 150, int(a.gbp * 1e9)
+    n = int(G * a.coverage / RL)
+    band = (a.band or [15])[0]
+    ctx = H.Context(K=31, M=17, L=2, U=50, EXT=1, ntasks=0, keep_device=True)
+    tmp = tempfile.mkdtemp()
+    try:
+        lens = host_reads_fasta(np, os.path.join(tmp, "reads.fa"), G, RL, n, a.error_rate, a.indel_rate, 11)
+        dna = H.read_dna_buffer_device(ctx, os.path.join(tmp, "reads.fa"))
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    dev = dna.count_resident_device()
+    out = {"what": "tools/time_pairs.py --unitigs: hsk_overlaps_unitigs on the resident graph of hsk_overlaps_reduce (rows of hsk_pair_diags_extend_gapped, band %d), beside the reduce call and the host route "
+                   "it replaces, and on a synthetic line and ring; %d repetitions after %d warm-up calls, one run on one card" % (band, a.reps, WARMUP),
+           "workload": {"genome_bp": G, "read_span": RL, "reads": n, "error_rate": a.error_rate, "indel_rate": a.indel_rate, "K": 31, "M": 17, "L": 2, "U": 50, "band": band}, "reps": a.reps}
+    UPH = ("ms_total", "ms_arcs", "ms_sort", "ms_rank", "ms_emit", "ms_d2h")
+
+    def unitigs_of(g, reads):
+        infos = []
+        for i in range(WARMUP + a.reps):
+            with g.unitigs(ctx, reads, on_device=True) as ut:
+                infos.append(dict(ut.info))
+        s = {k: v for k, v in infos[-1].items() if not k.startswith("ms_")}
+        s.update({ph: spread([r[ph] for r in infos[WARMUP:]]) for ph in UPH})
+        return s
+
+    with dev.strands(dna) as st, dev.pair_diagonals(st, a.diag_bin, on_device=True) as pd, pd.extend_gapped(ctx, dna, band=band, on_device=True) as ov:
+        infos = []
+        for i in range(WARMUP + a.reps):
+            with ov.reduce(ctx, dna, on_device=True) as g:
+                infos.append(dict(g.info, rows=len(g)))
+        red = {k: v for k, v in infos[-1].items() if not k.startswith("ms_")}
+        red.update({ph: spread([r[ph] for r in infos[WARMUP:]]) for ph in ("ms_total", "ms_classify", "ms_sort", "ms_reduce", "ms_d2h")})
+        with ov.reduce(ctx, dna, on_device=True) as g:
+            uni = unitigs_of(g, dna)
+            # the host route the call replaces: the kept rows and the bits over PCIe, then OverlapGraph.arcs -- and only then the walk
+            walls, walks = [], []
+            for i in range(WARMUP + a.reps):
+                t0 = time.perf_counter()
+                kept = ctx.d2h(g.edges.rows_dev, len(g) * 48).view(np.uint64).reshape(len(g), 6)
+                contained = g.host_copy()[1]
+                av, aw, al, ar = H.OverlapGraph(H.Overlaps.from_rows(kept), None, contained, {}, g.rid_base, g.nreads).arcs(lens)
+                walls.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            chains, longest = host_walk(np, av, aw, 2 * g.nreads)
+            out["host_route"] = {"bytes": len(g) * 48 + 4 * ((g.nreads + 31) // 32), "wall_ms_rows_bits_arcs": spread(walls[WARMUP:]), "wall_ms_walk_once": (time.perf_counter() - t0) * 1e3,
+                                 "chains_of_both_orientations": chains, "longest": longest, "note": "pageable host memory; the walk is numpy and one Python step per link, timed once, not repeated"}
+            with g.unitigs(ctx, dna) as ut:               # every live read once, and the walk's chains are the unitigs and their complements
+                out["checks"] = {"every_live_read_once": bool(np.array_equal(np.sort(ut.rid.astype(np.int64) - g.rid_base), np.flatnonzero(~contained))),
+                                 "chains_are_twice_the_unitigs": chains - int(contained.sum()) * 2 == 2 * len(ut), "longest_equal": longest == ut.info["longest"]}
+    out["overlaps_reduce"], out["overlaps_unitigs"] = red, uni
+    # a line and a ring of a million reads on random strands: one chain through every read, where a walk is one chase of a million steps
+    N = a.synthetic_reads
+    strands = np.random.default_rng(9).integers(0, 2, N)
+    slens = np.full(N, 100, np.uint32)
+    line = SR.layout_rows(np.arange(N) * 40, slens, strands, 41)
+    back = SR.layout_rows([40, 0], [100, 100], [strands[0], strands[N - 1]], 1)[0].copy()
+    back[0] = np.uint64((int(back[0]) >> 63) << 63 | (N - 1))
+    for name, rows, want in (("line", line, [0, N, 40 * (N - 1) + 100, 0]), ("ring", np.concatenate([line, back[None, :]]), [0, N, 40 * N, 1])):
+        with H.Overlaps.from_rows(rows).reduce(ctx, slens, fuzz=0, on_device=True) as g:
+            s = unitigs_of(g, slens)
+            with g.unitigs(ctx, slens) as ut:
+                s["one_unitig_as_expected"] = bool(len(g) == rows.shape[0] and ut.table().tolist() == [want])
+                t0 = time.perf_counter()
+                kept = ctx.d2h(g.edges.rows_dev, len(g) * 48).view(np.uint64).reshape(len(g), 6)
+                av, aw, al, ar = H.OverlapGraph(H.Overlaps.from_rows(kept), None, np.zeros(N, bool), {}, 0, N).arcs(slens)
+                s["host_wall_ms_rows_arcs_once"] = (time.perf_counter() - t0) * 1e3
+                t0 = time.perf_counter()
+                s["host_walk"] = host_walk(np, av, aw, 2 * N)
+                s["host_wall_ms_walk_once"] = (time.perf_counter() - t0) * 1e3
+        out["synthetic_" + name] = s
+    for name in ("overlaps_unitigs", "synthetic_line", "synthetic_ring"):
+        s = out[name]
+        print("%-40s %10.3f ms [%.3f, %.3f] (arcs %.3f, sort %.3f, rank %.3f, emit %.3f), %d rows, %d unitigs, longest %d, %d rounds" % (
+            "hsk_overlaps_unitigs " + name, s["ms_total"]["median"], s["ms_total"]["min"], s["ms_total"]["max"], s["ms_arcs"]["median"], s["ms_sort"]["median"], s["ms_rank"]["median"], s["ms_emit"]["median"],
+            s["input_rows"], s["unitigs"], s["longest"], s["rounds"]))
+    print("%-40s %10.3f ms [%.3f, %.3f] (classify %.3f, sort %.3f, reduce %.3f), %d of %d rows kept" % (
+        "hsk_overlaps_reduce", red["ms_total"]["median"], red["ms_total"]["min"], red["ms_total"]["max"], red["ms_classify"]["median"], red["ms_sort"]["median"], red["ms_reduce"]["median"], red["rows"], red["input_rows"]))
+    print("%-40s %10.3f ms [%.3f, %.3f] rows, bits and arcs on the host; the walk behind it once: %.3f ms" % (
+        "the host route", out["host_route"]["wall_ms_rows_bits_arcs"]["median"], out["host_route"]["wall_ms_rows_bits_arcs"]["min"], out["host_route"]["wall_ms_rows_bits_arcs"]["max"], out["host_route"]["wall_ms_walk_once"]))
+    dev.close()
+    dna.free()
+    ctx.close()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--unitigs", action="store_true"); ap.add_argument("--synthetic-reads", type=int, default=1000000)
     ap.add_argument("--reduce", action="store_true"); ap.add_argument("--pile", type=int, default=3000); ap.add_argument("--pile-lane-only", action="store_true")
     ap.add_argument("--gapped", action="store_true"); ap.add_argument("--band", type=int, action="append", default=[]); ap.add_argument("--indel-rate", type=float, default=0.005)
     ap.add_argument("--gapped-sample", type=int, default=2000)
@@ -356,6 +487,8 @@ def main():
     ap.add_argument("--reps", type=int, default=REPS)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None and a.unitigs:
+        a.out = os.path.join(ROOT, "profiles", "overlaps_unitigs_8mbp.json")
     if a.out is None and a.reduce:
         a.out = os.path.join(ROOT, "profiles", "overlaps_reduce_8mbp.json")
     if a.out is None and a.gapped:
@@ -367,6 +500,8 @@ def main():
     sys.path.insert(0, ROOT)
     import numpy as np
     import hysortk_amd as H
+    if a.unitigs:
+        return unitigs_run(H, a)
     if a.reduce:
         return reduce_run(H, a)
     if a.gapped:
